@@ -8,7 +8,13 @@ already resident in HBM: pack → RCCL reduce-scatter → fused Adam → RCCL al
 (N=1: one fused Adam launch).  value = params/s = 3,075,098,624 / step time (whole job; total work
 is fixed as N grows → "strong" scaling).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain N=1 run does what the headline needs and no more: set-up, W warm-up steps, the K timed
+steps, the line.  ``--full`` adds the other legs of the N=1 line — the other gradient hand-off and
+the fp32-master step beside the headline, and the CPU baselines (each still has its ``--no-...``
+switch).  An N>1 run does not look at ``--full``: it runs its checks, calibration, sweep and
+layout ablation as before.  ``--dump-outputs DIR`` writes what the last timed step left its caller (the parameters
+and Adam's exp_avg / exp_avg_sq; a fixed seeded sample of a large set) as DIR/<name>.npy.
 N>1 runs one rank per GPU: under torch.distributed.run (WORLD_SIZE must equal N, else exit 2), or,
 with no launcher, bench.py starts ``torch.distributed.run --nproc-per-node N`` itself as a child
 process and relays rank 0's line.  A product communicator that cannot be created or fails its
@@ -56,6 +62,65 @@ METRIC = "ZeRO step time & params/sec at 1/2/4/8 GPU; Adam HBM GB/s vs peak"
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: every .npy file together stays below this
+
+
+def dump_outputs(out_dir, arrays: dict, seed: int = 0) -> dict:
+    """--dump-outputs: write ``arrays`` (name -> list of tensors, in parameter order) as
+    ``out_dir/<name>.npy``, one 1-D array per name: the tensors' elements concatenated, float32
+    (float64 tensors stay float64).  A set too large for ``DUMP_BUDGET_BYTES`` is sampled: of every
+    tensor its first and last element and seeded random positions between them, in proportion to
+    its size — the positions depend only on ``seed``, the tensor's index and its size, so two
+    builds run with the same arguments write the same elements.  Returns name -> elements kept."""
+    import numpy as np
+    import torch
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {k: [t for t in v if t is not None] for k, v in arrays.items()}
+    arrays = {k: v for k, v in arrays.items() if v}
+    kept = {}
+    for name, tensors in arrays.items():
+        # 8 bytes per element whatever the dtype, minus one element per tensor for the rounding
+        # up below and 4 KiB for the file's header
+        cap = (DUMP_BUDGET_BYTES // len(arrays) - 4096) // 8 - len(tensors)
+        total = sum(t.numel() for t in tensors)
+        parts = []
+        for i, t in enumerate(tensors):
+            flat = t.detach().reshape(-1)
+            n = flat.numel()
+            if total > cap:
+                k = max(1, n * cap // total)
+                idx = np.sort(np.random.default_rng([seed, i]).integers(0, n, size=k))
+                idx[0], idx[-1] = 0, n - 1
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            parts.append(flat.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+                         .cpu().numpy())
+        a = np.concatenate(parts)
+        np.save(out / f"{name}.npy", a)
+        kept[name] = int(a.size)
+    return kept
+
+
+def _dump_step_outputs(args, rank, params, opt=None, extra=None) -> None:
+    """After the timed steps (rank 0, --dump-outputs): what the last step left its caller — the
+    parameters (at N>1 as this rank holds them) and, where the optimizer exposes them,
+    optimizer.state[p]'s exp_avg / exp_avg_sq of the parameters this rank owns."""
+    if not args.dump_outputs or rank != 0:
+        return
+    import torch
+
+    torch.cuda.synchronize()
+    arrays = {"params": list(params)}
+    state = getattr(getattr(opt, "optimizer", None), "state", None)
+    if state is not None:
+        for key in ("exp_avg", "exp_avg_sq"):
+            arrays[key] = [state[p].get(key) for p in params if p in state]
+    arrays.update(extra or {})
+    kept = dump_outputs(args.dump_outputs, arrays)
+    log(f"[bench] --dump-outputs {args.dump_outputs}: {kept}")
 
 
 def _cpu_sample(shapes, sample_elems: int, per_layer: int = 9, min_tensors: int = 30):
@@ -1331,6 +1396,7 @@ def bench_zero3(args, world, rank, dev, use_nccl):
         del ref
     _phase("warmup")
     el = _zero3_timed(args, opt, step, dev, world)
+    _dump_step_outputs(args, rank, list(model.parameters()), opt)
     _zero3_report(args, opt, world, rank, red_dev, el, total,
                   f"{args.config} ZeRO-3 training iteration of the reference MLP 6xLinear({D},{D})+ReLU "
                   f"(hooked all-gathers, backward reduce-scatters, update-mode step), batch {batch}",
@@ -1402,6 +1468,7 @@ def bench_zero3_paramset(args, world, rank, dev, use_nccl):
 
     _phase("warmup")
     el = _zero3_timed(args, opt, step, dev, world)
+    _dump_step_outputs(args, rank, params, opt)
     if args.simulate_ws > 1:
         ev, opt.timing_events = opt.timing_events, None
         adam_ms = sum(a.elapsed_time(b) for a, b, _ in ev)
@@ -1507,6 +1574,8 @@ def bench_train_smollm3(args, world, rank, dev, use_nccl):
     torch.cuda.synchronize()
     dist.barrier()
     el = time.perf_counter() - t0
+    _dump_step_outputs(args, rank, list(model.parameters()), opt,
+                       extra={"loss": [loss.detach()]} if args.steps > 0 else None)
     red_dev = dev if use_nccl else "cpu"
     t = torch.tensor([el], dtype=torch.float64, device=red_dev)
     if world > 1:
@@ -1587,6 +1656,14 @@ def main(argv=None):
                          "sampler sees the timed region), 300 at N>1 (exchange-bound steps are "
                          "longer); --train: 4")
     ap.add_argument("--warmup", type=int, default=None, help="default 5 (--train: 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also run every leg beside the headline: the other gradient hand-off, "
+                         "the fp32-master step, the CPU baselines (a plain N=1 run times the "
+                         "headline only; an N>1 run is the same with or without it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one left its caller (the "
+                         "parameters and Adam's exp_avg / exp_avg_sq; a fixed seeded sample of a "
+                         "set above 64 MB) as DIR/<name>.npy, float32")
     ap.add_argument("--config", default="C4", choices=["C2", "C3", "C4", "C5"])
     ap.add_argument("--zero", type=int, default=2, choices=[1, 2, 3],
                     help="3 on C2/C3 = a ZeRO-3 training iteration (hooked forward/backward + "
@@ -1679,6 +1756,8 @@ def main(argv=None):
                          f"{WATCHDOG_BUDGET_S:.0f} s since process start, inside the driver's 600 s; "
                          "0 disables it")
     args = ap.parse_args(argv)
+    if not args.full and args.gpus == 1:  # a plain N=1 run: the headline alone, no leg beside it
+        args.no_cpu_baseline = args.no_fp32_master_line = args.no_default_leg = True
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks here, one process per
@@ -1979,6 +2058,7 @@ def _main(args):
     ms = el / args.steps * 1e3
     _PARTIAL["timed_before_failure"] = {"ms_per_step": ms, "value": total / (ms / 1e3),
                                         "steps": args.steps, "arena": getattr(eng, "arena_kind", None)}
+    _dump_step_outputs(args, rank, params, opt)  # (before any other leg steps the set further)
 
     # Adam roofline: algorithmic bytes / kernel time, per launch, from HIP events on the launch stream
     adam_ms = sum(a.elapsed_time(b) for a, b, _ in eng_events)

@@ -341,3 +341,32 @@ def test_optional_legs_yield_to_the_watchdog(monkeypatch):
     assert not bench.leg_fits("other hand-off", 90.0)           # 2 x 90 + 30 > 200
     assert set(bench._SKIPPED) == {"other hand-off"}
     assert bench._SKIPPED["other hand-off"]["estimated_s"] == 90.0
+
+
+def test_dump_outputs_whole_when_small_sampled_and_repeatable_when_large(tmp_path, monkeypatch):
+    """--dump-outputs: a set within the budget is written whole, element for element (bf16 as
+    float32, float64 kept); a larger one is sampled per tensor in proportion to its size, first and
+    last element included, at positions that a second call repeats, and every file together stays
+    within the budget."""
+    ts = [torch.arange(7, dtype=torch.float32).reshape(7, 1), torch.tensor([0.5, -2.0]).bfloat16()]
+    kept = bench.dump_outputs(tmp_path / "a", {"params": ts, "loss": [torch.tensor(1.25).double()],
+                                               "absent": [None]})
+    assert kept == {"params": 9, "loss": 1}
+    p = np.load(tmp_path / "a" / "params.npy")
+    assert p.dtype == np.float32 and p.tolist() == [0, 1, 2, 3, 4, 5, 6, 0.5, -2.0]
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64
+    assert not (tmp_path / "a" / "absent.npy").exists()
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * (4096 + 8 * 300))
+    big = [torch.arange(9000, dtype=torch.float32), torch.arange(1000, dtype=torch.float32) - 5000,
+           torch.tensor([7.0])]
+    for d in ("b", "c"):
+        kept = bench.dump_outputs(tmp_path / d, {"params": big, "exp_avg": big})
+    b, c = np.load(tmp_path / "b" / "params.npy"), np.load(tmp_path / "c" / "params.npy")
+    assert np.array_equal(b, c) and np.array_equal(b, np.load(tmp_path / "b" / "exp_avg.npy"))
+    first = b[b >= 0][:-1]
+    second = b[b < 0]
+    assert b[-1] == 7.0 and first[0] == 0 and first[-1] == 8999 and second[0] == -5000 and second[-1] == -4001
+    assert 8 <= first.size / second.size <= 10 and np.all(np.diff(first) >= 0)
+    assert kept["params"] == b.size <= 300
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 2 * (4096 + 8 * 300)

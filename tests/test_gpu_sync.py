@@ -63,10 +63,13 @@ def test_flag_created_while_null_stream_is_busy(gpu):
     a wait whose epoch was overwritten by a late zero fill)."""
     from zero_amd.comm import StreamEvent
 
+    # (x is zeroed on the null stream: done before that stream is kept busy, so the producer's
+    # non-blocking stream cannot add to it ahead of the fill)
+    x = torch.zeros(16, device=gpu)
+    torch.cuda.synchronize()
     torch.cuda._sleep(SLEEP_CYCLES)  # on the null (default) stream
     prod, cons = torch.cuda.Stream(gpu), torch.cuda.Stream(gpu)
     evs = [StreamEvent("flag") for _ in range(5000)]  # more than one slab of 4096 words
-    x = torch.zeros(16, device=gpu)
     for k, ev in enumerate(evs[-3:]):
         with torch.cuda.stream(prod):
             x.add_(1.0)
