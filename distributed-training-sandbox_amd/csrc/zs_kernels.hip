@@ -2,9 +2,12 @@
 //
 // Both kernels are HBM-bound streaming kernels (no MFMA, no LDS): 64-wide waves, 256-thread
 // workgroups, 16-byte-per-lane coalesced accesses, a grid of 128 workgroups per CU (16x the 8
-// resident) that strides over fixed-size chunks of a segment table.  A workgroup finds the segment of its chunk with a forward
-// scan from the previous one (chunks are visited in increasing order), so the lookup is a couple of
-// scalar loads, not a per-chunk binary search.
+// resident; 1024 per CU for the split-master Adam) that strides over fixed-size chunks of a
+// segment table.  A workgroup finds the segment of its chunk with a forward scan from the previous
+// one (chunks are visited in increasing order), so the lookup is a couple of scalar loads, not a
+// per-chunk binary search (the Adam bisects once, for its first chunk).  The Adam issues all of a
+// full chunk's loads (20 for the split master) before its first wait and addresses them from
+// scalar bases, which keeps its headline instance at 79 VGPRs (6 waves per SIMD), no scratch.
 //
 // Tables (segment pointers + chunk prefix sums) are uploaded once per set and reused every step:
 // the step itself only launches kernels (no host sync), so it can be captured into a hipGraph.
@@ -28,7 +31,9 @@ constexpr int kThreads = 256;
 constexpr int kCopyUnrollDefault = 4;
 constexpr int64_t copy_chunk_bytes(int u) { return int64_t(kThreads) * 16 * u; }
 // float4 groups per thread: 2 (2048-element chunks); 4 (4096) for the split master, whose 26 B/elem
-// stream has one fp32 array fewer in flight per group (+1 % measured, profiles/r01_adam_split_master.log)
+// stream has one fp32 array fewer per group (+1 % measured with the predicated body, which has one
+// group's loads in flight at a time: profiles/r01_adam_split_master.log).  adam_full_chunk has all
+// G groups' loads in flight at once: 5 G loads, 14 G raw registers per lane for the split master.
 constexpr int adam_groups(bool split) { return split ? 4 : 2; }
 constexpr int64_t adam_chunk(bool split) { return int64_t(kThreads) * 4 * adam_groups(split); }
 
@@ -325,83 +330,266 @@ __device__ __forceinline__ float4 load_g4(const void* g, int64_t i) {
   }
 }
 
+// A stream of a full chunk is addressed as a uniform base in scalar registers, one 32-bit per-lane
+// byte offset shared by all streams of that width, and an immediate: no access has a 64-bit
+// address pair of its own in vector registers.  The immediate reaches -4096..4095 bytes, so a
+// stream gets the base chunk start + 4096 B (groups at -4096 and 0 for fp32, -4096 .. 2048 for
+// bf16) and, for fp32 groups 2 and 3, a second one 8192 B on.
+template <typename T>
+__device__ __forceinline__ T* lane_ptr(T* base, uint32_t lane_off, int imm) {
+  return (T*)((gptr<char>)(char*)base + lane_off + imm);
+}
+// a pointer the compiler keeps as it is, in scalar registers (or it would fold the bases of a
+// stream into one and carry the difference in per-access vector adds)
+template <typename T>
+__device__ __forceinline__ T* scalar_base(T* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+s"(p));
+#endif
+  return p;
+}
+// the bases of one stream of a chunk that starts at p, and group u's access through them
+template <typename T, int G>
+struct ChunkStream {
+  static constexpr int kBytes = int(kThreads * 4 * sizeof(T));  // per group
+  static constexpr int kPer = 8192 / kBytes;                    // groups per base
+  T* base[(G + kPer - 1) / kPer];
+  __device__ __forceinline__ explicit ChunkStream(T* p) {
+#pragma unroll
+    for (int k = 0; k < (G + kPer - 1) / kPer; ++k)
+      base[k] = scalar_base(reinterpret_cast<T*>((char*)p + 4096 + 8192 * k));
+  }
+  __device__ __forceinline__ T* at(int u, uint32_t lane_off) const {
+    return lane_ptr(base[u / kPer], lane_off, (u % kPer) * kBytes - 4096);
+  }
+};
+
+// One full chunk [e0, e0 + adam_chunk) of a segment, no per-lane predicate; HASG (the segment has a
+// gradient) is resolved by the caller, once per chunk.  First loop: every load of the chunk (g,
+// hi/lo or master, m, v, vmax, carry; 20 for the split master's G = 4) goes into raw registers
+// before anything depends on one.  Second loop: unpack, adam_elem and the stores, group by group.
+template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool HASG>
+__device__ __forceinline__ void adam_full_chunk(const AdamSeg& s, int64_t e0, const HP& hp) {
+  constexpr int G = adam_groups(SPLIT);
+  constexpr bool G32 = sizeof(GT) == 4;
+  uint32_t o4 = threadIdx.x * 16u;                   // lane byte offset in an fp32 stream
+  uint32_t o2 = threadIdx.x * 8u;                    // ... in a bf16 stream
+#if defined(__HIP_DEVICE_COMPILE__)
+  // Opaque per chunk: hoisted out of the chunk loop, the offsets' zero-extensions would end up in
+  // another block than the accesses, which then fall back to a 64-bit vector address each.
+  asm volatile("" : "+v"(o4), "+v"(o2));
+#endif
+  typedef ChunkStream<float, G> S4;
+  typedef ChunkStream<unsigned short, G> S2;
+  const S4 gf(HASG && G32 ? (float*)s.g + e0 : nullptr), pm(SPLIT ? nullptr : (float*)s.master + e0);
+  const S4 po(SPLIT ? nullptr : s.master_out + e0), sm(s.m + e0), sv(s.v + e0);
+  const S4 sx(AMS ? s.vmax + e0 : nullptr), sc(CARRY ? s.carry + e0 : nullptr);
+  const S2 gh(HASG && !G32 ? (unsigned short*)s.g + e0 : nullptr);
+  const S2 hi(SPLIT ? (unsigned short*)s.master + e0 : nullptr);
+  const S2 lo(SPLIT ? (unsigned short*)s.master_out + e0 : nullptr), pb(s.p_out + e0);
+  uint4 gq[G], pq[G], mq[G], vq[G], xq[G], cq[G];
+  uint2 gd[G], hd[G], ld[G];
+#pragma unroll
+  for (int u = 0; u < G; ++u) {
+    if constexpr (HASG) {
+      if constexpr (G32) gq[u] = nt_ld16(gf.at(u, o4));
+      else gd[u] = nt_ld8(gh.at(u, o2));
+    }
+    if constexpr (SPLIT) {
+      hd[u] = nt_ld8(hi.at(u, o2));
+      ld[u] = nt_ld8(lo.at(u, o2));
+    } else {
+      pq[u] = nt_ld16(pm.at(u, o4));
+    }
+    mq[u] = nt_ld16(sm.at(u, o4));
+    vq[u] = nt_ld16(sv.at(u, o4));
+    if constexpr (AMS) xq[u] = nt_ld16(sx.at(u, o4));
+    if constexpr (CARRY) cq[u] = nt_ld16(sc.at(u, o4));
+  }
+#pragma unroll
+  for (int u = 0; u < G; ++u) {
+    float gp[4] = {0.f, 0.f, 0.f, 0.f}, pp[4];
+    if constexpr (HASG && G32) {
+      gp[0] = __uint_as_float(gq[u].x), gp[1] = __uint_as_float(gq[u].y);
+      gp[2] = __uint_as_float(gq[u].z), gp[3] = __uint_as_float(gq[u].w);
+    } else if constexpr (HASG) {
+      gp[0] = __uint_as_float(gd[u].x << 16), gp[1] = __uint_as_float(gd[u].x & 0xffff0000u);
+      gp[2] = __uint_as_float(gd[u].y << 16), gp[3] = __uint_as_float(gd[u].y & 0xffff0000u);
+    }
+    if constexpr (SPLIT) {
+      pp[0] = join_master(hd[u].x & 0xFFFFu, ld[u].x), pp[1] = join_master(hd[u].x >> 16, ld[u].x >> 16);
+      pp[2] = join_master(hd[u].y & 0xFFFFu, ld[u].y), pp[3] = join_master(hd[u].y >> 16, ld[u].y >> 16);
+    } else {
+      pp[0] = __uint_as_float(pq[u].x), pp[1] = __uint_as_float(pq[u].y);
+      pp[2] = __uint_as_float(pq[u].z), pp[3] = __uint_as_float(pq[u].w);
+    }
+    float mp[4] = {__uint_as_float(mq[u].x), __uint_as_float(mq[u].y), __uint_as_float(mq[u].z),
+                   __uint_as_float(mq[u].w)};
+    float vp[4] = {__uint_as_float(vq[u].x), __uint_as_float(vq[u].y), __uint_as_float(vq[u].z),
+                   __uint_as_float(vq[u].w)};
+    float xp[4] = {0.f, 0.f, 0.f, 0.f}, cp[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (AMS) {
+      xp[0] = __uint_as_float(xq[u].x), xp[1] = __uint_as_float(xq[u].y);
+      xp[2] = __uint_as_float(xq[u].z), xp[3] = __uint_as_float(xq[u].w);
+    }
+    if constexpr (CARRY) {
+      cp[0] = __uint_as_float(cq[u].x), cp[1] = __uint_as_float(cq[u].y);
+      cp[2] = __uint_as_float(cq[u].z), cp[3] = __uint_as_float(cq[u].w);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) adam_elem<AMS, CARRY>(gp[j], pp[j], mp[j], vp[j], xp[j], cp[j], hp);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(o4), "+v"(o2));  // as above, for the block the stores are in
+#endif
+    if constexpr (SPLIT) {
+      uint32_t h[4], l[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        h[j] = f32_to_bf16(pp[j]);
+        l[j] = master_residual(pp[j], h[j]);
+      }
+      nt_st8(pb.at(u, o2),
+             make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16)));
+      nt_st8(lo.at(u, o2), make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16)));
+    } else {
+      if (s.master_out)
+        nt_st16(po.at(u, o4),
+                make_uint4(__float_as_uint(pp[0]), __float_as_uint(pp[1]), __float_as_uint(pp[2]),
+                           __float_as_uint(pp[3])));
+      if (s.p_out) {
+        uint2 r;
+        r.x = uint32_t(f32_to_bf16(pp[0])) | (uint32_t(f32_to_bf16(pp[1])) << 16);
+        r.y = uint32_t(f32_to_bf16(pp[2])) | (uint32_t(f32_to_bf16(pp[3])) << 16);
+        nt_st8(pb.at(u, o2), r);
+      }
+    }
+    nt_st16(sm.at(u, o4),
+            make_uint4(__float_as_uint(mp[0]), __float_as_uint(mp[1]), __float_as_uint(mp[2]),
+                       __float_as_uint(mp[3])));
+    nt_st16(sv.at(u, o4),
+            make_uint4(__float_as_uint(vp[0]), __float_as_uint(vp[1]), __float_as_uint(vp[2]),
+                       __float_as_uint(vp[3])));
+    if constexpr (AMS)
+      nt_st16(sx.at(u, o4),
+              make_uint4(__float_as_uint(xp[0]), __float_as_uint(xp[1]), __float_as_uint(xp[2]),
+                         __float_as_uint(xp[3])));
+    if constexpr (CARRY)
+      nt_st16(sc.at(u, o4),
+              make_uint4(__float_as_uint(cp[0]), __float_as_uint(cp[1]), __float_as_uint(cp[2]),
+                         __float_as_uint(cp[3])));
+  }
+}
+
+// The per-lane predicated body: G float4 groups from element e0 of a segment, each group under its
+// own `i < s.n`.  The branches keep each group's loads and their waits in a block of their own, so
+// a wave has one group's loads in flight at a time.
+template <typename GT, bool AMS, bool CARRY, bool SPLIT, int G>
+__device__ __forceinline__ void adam_pred_groups(const AdamSeg& s, int64_t e0, const HP& hp) {
+  float4 g4[G], p4[G], m4[G], v4[G];
+  float4 x4[G], c4[G];
+#pragma unroll
+  for (int u = 0; u < G; ++u) {
+    const int64_t i = e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
+    if (i < s.n) {
+      g4[u] = s.g ? load_g4<GT>(s.g, i) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (SPLIT) {
+        const uint2 h = nt_ld8(reinterpret_cast<const unsigned short*>(s.master) + i);
+        const uint2 l = nt_ld8(reinterpret_cast<const unsigned short*>(s.master_out) + i);
+        p4[u] = make_float4(join_master(h.x & 0xFFFFu, l.x), join_master(h.x >> 16, l.x >> 16),
+                            join_master(h.y & 0xFFFFu, l.y), join_master(h.y >> 16, l.y >> 16));
+      } else {
+        p4[u] = ld4(s.master, i);
+      }
+      m4[u] = ld4(s.m, i);
+      v4[u] = ld4(s.v, i);
+      if constexpr (AMS) x4[u] = ld4(s.vmax, i);
+      if constexpr (CARRY) c4[u] = ld4(s.carry, i);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < G; ++u) {
+    const int64_t i = e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
+    if (i < s.n) {
+      float* gp = reinterpret_cast<float*>(&g4[u]);
+      float* pp = reinterpret_cast<float*>(&p4[u]);
+      float* mp = reinterpret_cast<float*>(&m4[u]);
+      float* vp = reinterpret_cast<float*>(&v4[u]);
+      float* xp = reinterpret_cast<float*>(&x4[u]);
+      float* cp = reinterpret_cast<float*>(&c4[u]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float xv = AMS ? xp[j] : 0.0f;
+        float cv = CARRY ? cp[j] : 0.0f;
+        adam_elem<AMS, CARRY>(gp[j], pp[j], mp[j], vp[j], xv, cv, hp);
+        if constexpr (AMS) xp[j] = xv;
+        if constexpr (CARRY) cp[j] = cv;
+      }
+      if constexpr (SPLIT) {
+        uint32_t h[4], l[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          h[j] = f32_to_bf16(pp[j]);
+          l[j] = master_residual(pp[j], h[j]);
+        }
+        nt_st8(s.p_out + i, make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16)));
+        nt_st8(reinterpret_cast<unsigned short*>(s.master_out) + i,
+               make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16)));
+      } else {
+        if (s.master_out) st4(s.master_out, i, p4[u]);
+        if (s.p_out) {
+          uint2 r;
+          r.x = uint32_t(f32_to_bf16(pp[0])) | (uint32_t(f32_to_bf16(pp[1])) << 16);
+          r.y = uint32_t(f32_to_bf16(pp[2])) | (uint32_t(f32_to_bf16(pp[3])) << 16);
+          nt_st8(s.p_out + i, r);
+        }
+      }
+      st4(s.m, i, m4[u]);
+      st4(s.v, i, v4[u]);
+      if constexpr (AMS) st4(s.vmax, i, x4[u]);
+      if constexpr (CARRY) st4(s.carry, i, c4[u]);
+    }
+  }
+}
+
 // Vector kernel: every segment 16-B aligned (8-B for bf16 arrays) with n % 4 == 0 (the host
 // splits tails off into the scalar table).  adam_groups() float4 groups per thread, lane-contiguous
 // (16 B per lane per access), so each wave instruction touches one contiguous 1 KiB (f32) /
-// 512 B (bf16) run; every group's loads are issued before any math.
-template <typename GT, bool AMS, bool CARRY, bool SPLIT>
+// 512 B (bf16) run.  LOADS_FIRST (the default): a full chunk, all but the last of a segment, goes
+// through adam_full_chunk and the partial one through the predicated body a group at a time (it
+// is one chunk per segment, and a group at a time it stays out of the kernel's register budget).
+// !LOADS_FIRST (`zs_tune("adam_loads_first", 0)`): every chunk through the predicated body, all
+// groups unrolled -- the kernel as it was before adam_full_chunk, kept for A/B runs.
+template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool LOADS_FIRST>
 __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
     const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
     int64_t total_chunks, HP hp) {
   int64_t seg = 0;
+  if constexpr (LOADS_FIRST) {
+    // The segment of the first chunk by bisection: with a grid near one workgroup per chunk a
+    // forward scan from 0 would cost a workgroup more than its chunks do.
+    int64_t hi = nseg;
+    while (hi - seg > 1) {
+      const int64_t mid = (seg + hi) >> 1;
+      if (chunk_prefix[mid] <= int64_t(blockIdx.x)) seg = mid;
+      else hi = mid;
+    }
+  }
   for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
     while (chunk_prefix[seg + 1] <= c) ++seg;
     const AdamSeg s = segs[seg];
     constexpr int G = adam_groups(SPLIT);
     const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT);
-    float4 g4[G], p4[G], m4[G], v4[G];
-    float4 x4[G], c4[G];
-#pragma unroll
-    for (int u = 0; u < G; ++u) {
-      const int64_t i = e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
-      if (i < s.n) {
-        g4[u] = s.g ? load_g4<GT>(s.g, i) : make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (SPLIT) {
-          const uint2 h = nt_ld8(reinterpret_cast<const unsigned short*>(s.master) + i);
-          const uint2 l = nt_ld8(reinterpret_cast<const unsigned short*>(s.master_out) + i);
-          p4[u] = make_float4(join_master(h.x & 0xFFFFu, l.x), join_master(h.x >> 16, l.x >> 16),
-                              join_master(h.y & 0xFFFFu, l.y), join_master(h.y >> 16, l.y >> 16));
-        } else {
-          p4[u] = ld4(s.master, i);
-        }
-        m4[u] = ld4(s.m, i);
-        v4[u] = ld4(s.v, i);
-        if constexpr (AMS) x4[u] = ld4(s.vmax, i);
-        if constexpr (CARRY) c4[u] = ld4(s.carry, i);
+    if constexpr (LOADS_FIRST) {
+      if (e0 + adam_chunk(SPLIT) <= s.n) {  // uniform per workgroup
+        if (s.g) adam_full_chunk<GT, AMS, CARRY, SPLIT, true>(s, e0, hp);
+        else adam_full_chunk<GT, AMS, CARRY, SPLIT, false>(s, e0, hp);
+      } else {
+#pragma unroll 1
+        for (int u = 0; u < G && e0 + int64_t(u) * kThreads * 4 < s.n; ++u)
+          adam_pred_groups<GT, AMS, CARRY, SPLIT, 1>(s, e0 + int64_t(u) * kThreads * 4, hp);
       }
-    }
-#pragma unroll
-    for (int u = 0; u < G; ++u) {
-      const int64_t i = e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
-      if (i < s.n) {
-        float* gp = reinterpret_cast<float*>(&g4[u]);
-        float* pp = reinterpret_cast<float*>(&p4[u]);
-        float* mp = reinterpret_cast<float*>(&m4[u]);
-        float* vp = reinterpret_cast<float*>(&v4[u]);
-        float* xp = reinterpret_cast<float*>(&x4[u]);
-        float* cp = reinterpret_cast<float*>(&c4[u]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float xv = AMS ? xp[j] : 0.0f;
-          float cv = CARRY ? cp[j] : 0.0f;
-          adam_elem<AMS, CARRY>(gp[j], pp[j], mp[j], vp[j], xv, cv, hp);
-          if constexpr (AMS) xp[j] = xv;
-          if constexpr (CARRY) cp[j] = cv;
-        }
-        if constexpr (SPLIT) {
-          uint32_t h[4], l[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            h[j] = f32_to_bf16(pp[j]);
-            l[j] = master_residual(pp[j], h[j]);
-          }
-          nt_st8(s.p_out + i, make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16)));
-          nt_st8(reinterpret_cast<unsigned short*>(s.master_out) + i,
-                 make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16)));
-        } else {
-          if (s.master_out) st4(s.master_out, i, p4[u]);
-          if (s.p_out) {
-            uint2 r;
-            r.x = uint32_t(f32_to_bf16(pp[0])) | (uint32_t(f32_to_bf16(pp[1])) << 16);
-            r.y = uint32_t(f32_to_bf16(pp[2])) | (uint32_t(f32_to_bf16(pp[3])) << 16);
-            nt_st8(s.p_out + i, r);
-          }
-        }
-        st4(s.m, i, m4[u]);
-        st4(s.v, i, v4[u]);
-        if constexpr (AMS) st4(s.vmax, i, x4[u]);
-        if constexpr (CARRY) st4(s.carry, i, c4[u]);
-      }
+    } else {
+      adam_pred_groups<GT, AMS, CARRY, SPLIT, G>(s, e0, hp);
     }
   }
 }
@@ -866,15 +1054,28 @@ DqTune& dq_tune() {
   return t;
 }
 
-// Adam grid (zs_tune "adam_wg_per_cu", diagnostic A/B): 0 = grid_cap() (128 workgroups per CU),
-// k = at most k workgroups per CU striding over the chunks
+// Adam grid (zs_tune "adam_wg_per_cu", diagnostic A/B): 0 = the kernel's default, k = at most k
+// workgroups per CU striding over the chunks.  The default is grid_cap()'s 128 per CU, and 1024
+// per CU for the loads-first vector kernel of the split master: at C4 size 1024-2048 per CU
+// measured 2.5 % under 128 and 2.2 % under one workgroup per chunk
+// (profiles/r07_adam_ab_grid.json); the predicated kernel gains half of that from the grid, and
+// the fp32-master instance 0.4 %, short of the 1 % that tells a gain from noise
+// (profiles/r07_adam_ab_fp32_master.json), so both keep 128
+constexpr int kAdamWgPerCu = 128, kAdamLoadsFirstWgPerCu = 1024;
 int& adam_wg_per_cu() {
   static int v = 0;
   return v;
 }
-int64_t adam_grid_cap() {
+// Full chunks' issue order (zs_tune "adam_loads_first", diagnostic A/B): 1 = adam_full_chunk (all
+// of a chunk's loads before its first wait), 0 = every chunk through the predicated body that
+// partial chunks take
+int& adam_loads_first() {
+  static int v = 1;
+  return v;
+}
+int64_t adam_grid_cap(int default_per_cu) {
   const int k = adam_wg_per_cu();
-  return k > 0 ? int64_t(grid_cap() / 128) * k : int64_t(grid_cap());
+  return int64_t(grid_cap() / 128) * (k > 0 ? k : default_per_cu);
 }
 
 // zs_scale's / zs_convert's / zs_copyset_run's cache policy: -1 by size (kMallBytes), 0 default
@@ -1057,7 +1258,7 @@ static int launch_adam_tables(const AdamSeg* vec, const int64_t* vpre, int64_t n
                               int g_dtype, bool split, bool ams, bool carry, const HP& hp,
                               hipStream_t st) {
 #define ZS_LAUNCH(KERNEL, GT, A, C, S, TAB, PRE, NS, NCH)                                     \
-  hipLaunchKernelGGL((KERNEL<GT, A, C, S>), dim3(int(std::min<int64_t>(NCH, adam_grid_cap()))), \
+  hipLaunchKernelGGL((KERNEL<GT, A, C, S LF>), dim3(int(std::min<int64_t>(NCH, cap))),        \
                      dim3(kThreads), 0, st, TAB, PRE, NS, NCH, hp)
 #define ZS_DISPATCH_AC(KERNEL, GT, S, TAB, PRE, NS, NCH)                                      \
   do {                                                                                        \
@@ -1073,11 +1274,22 @@ static int launch_adam_tables(const AdamSeg* vec, const int64_t* vpre, int64_t n
     else ZS_DISPATCH_AC(KERNEL, unsigned short, false, TAB, PRE, NS, NCH);                   \
   } while (0)
   if (vch) {
-    ZS_DISPATCH(adam_segments_kernel, vec, vpre, nvec, vch);
+    const bool lf = adam_loads_first() != 0;
+    const int64_t cap =
+        adam_grid_cap(lf && split ? kAdamLoadsFirstWgPerCu : kAdamWgPerCu);
+#define LF , true
+    if (lf) ZS_DISPATCH(adam_segments_kernel, vec, vpre, nvec, vch);
+#undef LF
+#define LF , false
+    else ZS_DISPATCH(adam_segments_kernel, vec, vpre, nvec, vch);
+#undef LF
     ZS_HIP(hipGetLastError());
   }
   if (sch) {
+    const int64_t cap = adam_grid_cap(kAdamWgPerCu);
+#define LF
     ZS_DISPATCH(adam_scalar_kernel, sca, spre, nsca, sch);
+#undef LF
     ZS_HIP(hipGetLastError());
   }
 #undef ZS_DISPATCH
@@ -1856,6 +2068,9 @@ int zs_tune(const char* key, int64_t value, int64_t* previous) {
   } else if (std::strcmp(key, "adam_wg_per_cu") == 0) {
     slot = &adam_wg_per_cu();
     ok = value >= 0 && value <= 1024;
+  } else if (std::strcmp(key, "adam_loads_first") == 0) {
+    slot = &adam_loads_first();
+    ok = value == 0 || value == 1;
   } else if (std::strcmp(key, "sync_host_flags") == 0) {
     slot = &zs::sync_host_flags();
     ok = value == 0 || value == 1;

@@ -325,8 +325,11 @@ int zs_device_alloc_chunked(int64_t bytes, int64_t chunk_bytes, void** out);
  * workgroups per CU walking several rows each), "scale_nt" (zs_scale's cache policy: -1 by size,
  * non-temporal above 256 MiB; 0 default policy; 1 non-temporal), "convert_nt" (zs_convert's, the
  * same by source + destination bytes), "copy_nt" (zs_copyset_run's, by 2 x the set's bytes),
- * "adam_wg_per_cu" (0 = 128 workgroups per CU, the default grid of the fused Adam; k = at most k
- * per CU), "sync_host_flags" (1: flag syncs created from now on take words in pinned host
+ * "adam_wg_per_cu" (0 = the default grid of the fused Adam: 128 workgroups per CU, 1024 for the
+ * loads-first kernel of a split master; k = at most k per CU), "adam_loads_first" (1: a full chunk
+ * of the vector Adam issues all its loads before its first wait; 0: every chunk through the
+ * per-lane predicated body that partial chunks take, one group's loads in flight at a time — the
+ * kernel before the loads-first body, kept for A/B runs, tools/adam_ab.py), "sync_host_flags" (1: flag syncs created from now on take words in pinned host
  * memory, whose satisfied waits the host skips; 0: device words, every wait enqueued — the
  * fallback the library takes by itself when pinned memory is refused), "sync_write_kernel" (1: a
  * flag sync's record is a one-wave kernel storing the epoch with a system-scope release; 0:
