@@ -1,4 +1,4 @@
-// CDNA4 (gfx950) kernels of the ZeRO step: segment copy (pack / unpack) and the fused Adam.
+// CDNA4 (gfx950) kernels of the ZeRO step: segment copy (pack / unpack), the fused Adam, its clip.
 //
 // Both kernels are HBM-bound streaming kernels (no MFMA, no LDS): 64-wide waves, 256-thread
 // workgroups, 16-byte-per-lane coalesced accesses, a grid of 128 workgroups per CU (16x the 8
@@ -246,15 +246,20 @@ __device__ __forceinline__ uint32_t master_residual(float p, uint32_t hi) {
 // exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2) = fma((1-b2)*g, g, v*b2), denom = sqrt(v)/bc2_sqrt + eps,
 // param.addcdiv_(m, denom, -step_size) = p + (-step_size*m)/denom.  Only explicit fmaf() fuse;
 // sqrt and '/' are IEEE correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt).
-template <bool AMS, bool CARRY>
+//
+// CLIP (zs_adamset_run_clipped): the averaged gradient times the global-norm clip coefficient
+// (clip_grad_norm_'s `g.mul_(clip_coef_clamped)`), one IEEE multiply before maximize / weight decay;
+// `coef` is uniform (a scalar register) and unused otherwise.
+template <bool AMS, bool CARRY, bool CLIP>
 __device__ __forceinline__ void adam_elem(float gsum, float& p, float& m, float& v, float& vmax,
-                                          float& carry, const HP& hp) {
+                                          float& carry, const HP& hp, float coef) {
 #pragma clang fp contract(off)
   float s = gsum;
   if constexpr (CARRY) s = s + hp.carry_mul * carry;  // ZeRO-1: Σ G + (ws-1)·A_{t-1}
   // zero1.py:84 / zero2.py:111 `grad / ws`; a power-of-two divisor is an exact reciprocal multiply
   float g = hp.div_pow2 ? s * hp.inv_div : s / hp.grad_div;
   if constexpr (CARRY) carry = g;
+  if constexpr (CLIP) g = g * coef;
   if (hp.maximize) g = -g;
   if (hp.wd != 0.0f) g = fmaf(hp.wd, p, g);  // grad.add(param, alpha=wd)
   p = p * hp.decay_mul;                       // AdamW: param.mul_(1 - lr*wd); 1.0 otherwise
@@ -275,11 +280,28 @@ __device__ __forceinline__ float load_g1(const void* g, int64_t i) {
   else return bf16_to_f32(glob(static_cast<const unsigned short*>(g))[i]);
 }
 
+// The clip coefficient of a CLIP instance: one uniform load per workgroup (the pointer is a kernel
+// argument, the load a scalar one), kept in a scalar register; 1 (unused) otherwise.
+template <bool CLIP>
+__device__ __forceinline__ float clip_coef(const float* __restrict__ coef_ptr) {
+  if constexpr (CLIP) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(*coef_ptr)));
+#else
+    return *coef_ptr;
+#endif
+  } else {
+    return 1.0f;
+  }
+}
+
 // Scalar kernel: any alignment, any length (segment tails and unaligned segments; tiny).
-template <typename GT, bool AMS, bool CARRY, bool SPLIT>
+template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool CLIP>
 __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
-    int64_t total_chunks, HP hp) {
+    int64_t total_chunks, HP hp, const float* __restrict__ coef_ptr) {
+  static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
+  const float coef = clip_coef<CLIP>(coef_ptr);
   int64_t seg = 0;
   for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
     while (chunk_prefix[seg + 1] <= c) ++seg;
@@ -293,7 +315,7 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     float m = glob(s.m)[i], v = glob(s.v)[i];
     float vm = AMS ? glob(s.vmax)[i] : 0.0f;
     float cr = CARRY ? glob(s.carry)[i] : 0.0f;
-    adam_elem<AMS, CARRY>(gs, p, m, v, vm, cr, hp);
+    adam_elem<AMS, CARRY, CLIP>(gs, p, m, v, vm, cr, hp, coef);
     if constexpr (SPLIT) {
       const unsigned short h = f32_to_bf16(p);
       glob(s.p_out)[i] = h;
@@ -368,8 +390,9 @@ struct ChunkStream {
 // gradient) is resolved by the caller, once per chunk.  First loop: every load of the chunk (g,
 // hi/lo or master, m, v, vmax, carry; 20 for the split master's G = 4) goes into raw registers
 // before anything depends on one.  Second loop: unpack, adam_elem and the stores, group by group.
-template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool HASG>
-__device__ __forceinline__ void adam_full_chunk(const AdamSeg& s, int64_t e0, const HP& hp) {
+template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool HASG, bool CLIP>
+__device__ __forceinline__ void adam_full_chunk(const AdamSeg& s, int64_t e0, const HP& hp,
+                                                float coef) {
   constexpr int G = adam_groups(SPLIT);
   constexpr bool G32 = sizeof(GT) == 4;
   uint32_t o4 = threadIdx.x * 16u;                   // lane byte offset in an fp32 stream
@@ -437,7 +460,8 @@ __device__ __forceinline__ void adam_full_chunk(const AdamSeg& s, int64_t e0, co
       cp[2] = __uint_as_float(cq[u].z), cp[3] = __uint_as_float(cq[u].w);
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) adam_elem<AMS, CARRY>(gp[j], pp[j], mp[j], vp[j], xp[j], cp[j], hp);
+    for (int j = 0; j < 4; ++j)
+      adam_elem<AMS, CARRY, CLIP>(gp[j], pp[j], mp[j], vp[j], xp[j], cp[j], hp, coef);
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(o4), "+v"(o2));  // as above, for the block the stores are in
 #endif
@@ -483,8 +507,9 @@ __device__ __forceinline__ void adam_full_chunk(const AdamSeg& s, int64_t e0, co
 // The per-lane predicated body: G float4 groups from element e0 of a segment, each group under its
 // own `i < s.n`.  The branches keep each group's loads and their waits in a block of their own, so
 // a wave has one group's loads in flight at a time.
-template <typename GT, bool AMS, bool CARRY, bool SPLIT, int G>
-__device__ __forceinline__ void adam_pred_groups(const AdamSeg& s, int64_t e0, const HP& hp) {
+template <typename GT, bool AMS, bool CARRY, bool SPLIT, int G, bool CLIP>
+__device__ __forceinline__ void adam_pred_groups(const AdamSeg& s, int64_t e0, const HP& hp,
+                                                 float coef) {
   float4 g4[G], p4[G], m4[G], v4[G];
   float4 x4[G], c4[G];
 #pragma unroll
@@ -520,7 +545,7 @@ __device__ __forceinline__ void adam_pred_groups(const AdamSeg& s, int64_t e0, c
       for (int j = 0; j < 4; ++j) {
         float xv = AMS ? xp[j] : 0.0f;
         float cv = CARRY ? cp[j] : 0.0f;
-        adam_elem<AMS, CARRY>(gp[j], pp[j], mp[j], vp[j], xv, cv, hp);
+        adam_elem<AMS, CARRY, CLIP>(gp[j], pp[j], mp[j], vp[j], xv, cv, hp, coef);
         if constexpr (AMS) xp[j] = xv;
         if constexpr (CARRY) cp[j] = cv;
       }
@@ -559,10 +584,12 @@ __device__ __forceinline__ void adam_pred_groups(const AdamSeg& s, int64_t e0, c
 // is one chunk per segment, and a group at a time it stays out of the kernel's register budget).
 // !LOADS_FIRST (`zs_tune("adam_loads_first", 0)`): every chunk through the predicated body, all
 // groups unrolled -- the kernel as it was before adam_full_chunk, kept for A/B runs.
-template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool LOADS_FIRST>
+template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP>
 __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
     const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
-    int64_t total_chunks, HP hp) {
+    int64_t total_chunks, HP hp, const float* __restrict__ coef_ptr) {
+  static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
+  const float coef = clip_coef<CLIP>(coef_ptr);
   int64_t seg = 0;
   if constexpr (LOADS_FIRST) {
     // The segment of the first chunk by bisection: with a grid near one workgroup per chunk a
@@ -581,17 +608,154 @@ __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
     const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT);
     if constexpr (LOADS_FIRST) {
       if (e0 + adam_chunk(SPLIT) <= s.n) {  // uniform per workgroup
-        if (s.g) adam_full_chunk<GT, AMS, CARRY, SPLIT, true>(s, e0, hp);
-        else adam_full_chunk<GT, AMS, CARRY, SPLIT, false>(s, e0, hp);
+        if (s.g) adam_full_chunk<GT, AMS, CARRY, SPLIT, true, CLIP>(s, e0, hp, coef);
+        else adam_full_chunk<GT, AMS, CARRY, SPLIT, false, CLIP>(s, e0, hp, coef);
       } else {
 #pragma unroll 1
         for (int u = 0; u < G && e0 + int64_t(u) * kThreads * 4 < s.n; ++u)
-          adam_pred_groups<GT, AMS, CARRY, SPLIT, 1>(s, e0 + int64_t(u) * kThreads * 4, hp);
+          adam_pred_groups<GT, AMS, CARRY, SPLIT, 1, CLIP>(s, e0 + int64_t(u) * kThreads * 4, hp,
+                                                           coef);
       }
     } else {
-      adam_pred_groups<GT, AMS, CARRY, SPLIT, G>(s, e0, hp);
+      adam_pred_groups<GT, AMS, CARRY, SPLIT, G, CLIP>(s, e0, hp, coef);
     }
   }
+}
+
+// ----------------------------------------------------------------------------------------------
+// gradient sum of squares over an Adam set (global-norm clipping, clip_grad_norm_'s norm)
+// ----------------------------------------------------------------------------------------------
+// One read-only pass over the gradients a set is bound to, driven by the set's own tables: the
+// vector table in the Adam's chunks (16 B fp32 / 8 B bf16 per lane per access, all of a chunk's
+// loads before its first use), the scalar table in 256-element chunks.  fp32 arithmetic covers one
+// lane's terms of one chunk (fmaf(g, g, acc): 4 * adam_groups() terms, 16 for a split-master set
+// and 8 otherwise; 1 in the scalar table); everything above is double: a lane's total over its
+// chunks, the wave (shuffles), the 4 waves (LDS) and one partial per workgroup, a plain store.  No
+// atomics.  The grid is the number of partials, fixed when the set is created: min(chunks, cap)
+// per table, workgroup b summing chunks b, b + grid, ... — neither zs_tune nor the device enters,
+// so the sum has the same bits on every run.
+constexpr int64_t kSqnormVecPartials = 8192, kSqnormScaPartials = 1024;
+
+// Sum over the workgroup in a fixed order; the result is valid in every thread.
+__device__ __forceinline__ double block_sum(double x) {
+  __shared__ double wave_sum[kThreads / 64];
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+}
+
+// NT: the loads' cache policy (zs_tune "sqnorm_nt")
+template <typename GT, bool SPLIT, bool NT>
+__global__ __launch_bounds__(kThreads) void grad_sqnorm_kernel(
+    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
+    int64_t total_chunks, double* __restrict__ partials) {
+  constexpr int G = adam_groups(SPLIT);
+  constexpr bool G32 = sizeof(GT) == 4;
+  int64_t seg = 0, hi = nseg;
+  while (hi - seg > 1) {  // the segment of the first chunk, as adam_segments_kernel
+    const int64_t mid = (seg + hi) >> 1;
+    if (chunk_prefix[mid] <= int64_t(blockIdx.x)) seg = mid;
+    else hi = mid;
+  }
+  double total = 0.0;
+  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
+    while (chunk_prefix[seg + 1] <= c) ++seg;
+    const GT* g = static_cast<const GT*>(segs[seg].g);
+    const int64_t n = segs[seg].n;
+    if (!g) continue;  // no gradient: nothing read (uniform per workgroup)
+    const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT);
+    uint4 r[G];  // bf16: x, y hold the four elements
+    if (e0 + adam_chunk(SPLIT) <= n) {
+#pragma unroll
+      for (int u = 0; u < G; ++u) {
+        const GT* p = g + e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
+        if constexpr (G32) {
+          r[u] = ld16<NT>(p);
+        } else {
+          const uint2 d = ld8<NT>(p);
+          r[u] = make_uint4(d.x, d.y, 0u, 0u);
+        }
+      }
+    } else {  // the segment's last chunk: groups past n contribute +0
+#pragma unroll
+      for (int u = 0; u < G; ++u) {
+        const int64_t i = e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
+        r[u] = make_uint4(0u, 0u, 0u, 0u);
+        if (i < n) {
+          if constexpr (G32) {
+            r[u] = ld16<NT>(g + i);
+          } else {
+            const uint2 d = ld8<NT>(g + i);
+            r[u] = make_uint4(d.x, d.y, 0u, 0u);
+          }
+        }
+      }
+    }
+    float acc = 0.0f;
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      float x[4];
+      if constexpr (G32) {
+        x[0] = __uint_as_float(r[u].x), x[1] = __uint_as_float(r[u].y);
+        x[2] = __uint_as_float(r[u].z), x[3] = __uint_as_float(r[u].w);
+      } else {
+        x[0] = __uint_as_float(r[u].x << 16), x[1] = __uint_as_float(r[u].x & 0xffff0000u);
+        x[2] = __uint_as_float(r[u].y << 16), x[3] = __uint_as_float(r[u].y & 0xffff0000u);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc = fmaf(x[j], x[j], acc);
+    }
+    total += double(acc);
+  }
+  const double b = block_sum(total);
+  if (threadIdx.x == 0) partials[blockIdx.x] = b;
+}
+
+template <typename GT>
+__global__ __launch_bounds__(kThreads) void grad_sqnorm_scalar_kernel(
+    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
+    int64_t total_chunks, double* __restrict__ partials) {
+  int64_t seg = 0;
+  double total = 0.0;
+  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
+    while (chunk_prefix[seg + 1] <= c) ++seg;
+    const void* g = segs[seg].g;
+    const int64_t n = segs[seg].n;
+    if (!g) continue;
+    const int64_t i = (c - chunk_prefix[seg]) * kThreads + threadIdx.x;
+    if (i < n) {
+      const float x = load_g1<GT>(g, i);
+      total += double(fmaf(x, x, 0.0f));
+    }
+  }
+  const double b = block_sum(total);
+  if (threadIdx.x == 0) partials[blockIdx.x] = b;
+}
+
+// n double partials -> the fp32 rounding of their double sum: one workgroup, thread t summing
+// partials t, t + 256, ... in order, then block_sum.
+__global__ __launch_bounds__(kThreads) void sqnorm_reduce_kernel(
+    const double* __restrict__ partials, int64_t n, float* __restrict__ sumsq) {
+  double t = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += kThreads) t += partials[i];
+  const double b = block_sum(t);
+  if (threadIdx.x == 0) *sumsq = float(b);
+}
+
+// clip_grad_norm_'s coefficient (error_if_nonfinite=False): norm = sqrt(sumsq) / grad_div in
+// double, rounded once; coef = min(1, max_norm / (norm + 1e-6)) in fp32, a NaN norm giving a NaN
+// coefficient as torch's clamp does.  One lane.
+__global__ __launch_bounds__(64) void clip_coef_kernel(const float* __restrict__ sumsq,
+                                                       double grad_div, float max_norm,
+                                                       float* __restrict__ out2) {
+#pragma clang fp contract(off)
+  if (threadIdx.x != 0) return;
+  const float norm = float(sqrt(double(*sumsq)) / grad_div);
+  const float c = max_norm / (norm + 1e-6f);
+  out2[0] = norm;
+  out2[1] = c > 1.0f ? 1.0f : c;
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1073,6 +1237,12 @@ int& adam_loads_first() {
   static int v = 1;
   return v;
 }
+// Cache policy of the gradient sum-of-squares pass (zs_tune "sqnorm_nt", diagnostic A/B): 1 =
+// non-temporal loads, 0 = the default policy.  The sum's bits do not depend on it.
+int& sqnorm_nt() {
+  static int v = 1;
+  return v;
+}
 int64_t adam_grid_cap(int default_per_cu) {
   const int k = adam_wg_per_cu();
   return int64_t(grid_cap() / 128) * (k > 0 ? k : default_per_cu);
@@ -1145,6 +1315,8 @@ struct zs_adamset {
   AdamSeg* d_sca = nullptr;
   int64_t* d_sca_prefix = nullptr;
   int64_t nvec = 0, vec_chunks = 0, nsca = 0, sca_chunks = 0, elems = 0, bytes = 0;
+  // zs_adamset_grad_sqnorm: partials (= workgroups) of the vector and of the scalar table
+  int64_t sq_vec = 0, sq_sca = 0;
   int g_dtype = ZS_F32, p_dtype = ZS_BF16, has_carry = 0, has_vmax = 0;
   // zs_adamset_set_grads: which input segment each table entry came from (the scalar entries with
   // their byte offset into that input's gradient), the gradient each input is bound to now, its
@@ -1253,19 +1425,26 @@ static HP make_hp(const zs_adam_hparams* h) {
 // Vector table (aligned, n % 4 == 0) then scalar table (tails, unaligned), each a segment array
 // with its chunk prefix; the template instance is picked by grad dtype, split master, amsgrad
 // and carry.
+template <bool CLIP>
 static int launch_adam_tables(const AdamSeg* vec, const int64_t* vpre, int64_t nvec, int64_t vch,
                               const AdamSeg* sca, const int64_t* spre, int64_t nsca, int64_t sch,
                               int g_dtype, bool split, bool ams, bool carry, const HP& hp,
-                              hipStream_t st) {
+                              const float* coef, hipStream_t st) {
+  // CLIP instances exist without the carry only (zs_adamset_run_clipped refuses a set with one)
 #define ZS_LAUNCH(KERNEL, GT, A, C, S, TAB, PRE, NS, NCH)                                     \
-  hipLaunchKernelGGL((KERNEL<GT, A, C, S LF>), dim3(int(std::min<int64_t>(NCH, cap))),        \
-                     dim3(kThreads), 0, st, TAB, PRE, NS, NCH, hp)
+  hipLaunchKernelGGL((KERNEL<GT, A, C, S LF, CLIP>), dim3(int(std::min<int64_t>(NCH, cap))),  \
+                     dim3(kThreads), 0, st, TAB, PRE, NS, NCH, hp, coef)
 #define ZS_DISPATCH_AC(KERNEL, GT, S, TAB, PRE, NS, NCH)                                      \
   do {                                                                                        \
-    if (ams && carry) ZS_LAUNCH(KERNEL, GT, true, true, S, TAB, PRE, NS, NCH);                \
-    else if (ams) ZS_LAUNCH(KERNEL, GT, true, false, S, TAB, PRE, NS, NCH);                   \
-    else if (carry) ZS_LAUNCH(KERNEL, GT, false, true, S, TAB, PRE, NS, NCH);                 \
-    else ZS_LAUNCH(KERNEL, GT, false, false, S, TAB, PRE, NS, NCH);                           \
+    if constexpr (CLIP) {                                                                     \
+      if (ams) ZS_LAUNCH(KERNEL, GT, true, false, S, TAB, PRE, NS, NCH);                      \
+      else ZS_LAUNCH(KERNEL, GT, false, false, S, TAB, PRE, NS, NCH);                         \
+    } else {                                                                                  \
+      if (ams && carry) ZS_LAUNCH(KERNEL, GT, true, true, S, TAB, PRE, NS, NCH);              \
+      else if (ams) ZS_LAUNCH(KERNEL, GT, true, false, S, TAB, PRE, NS, NCH);                 \
+      else if (carry) ZS_LAUNCH(KERNEL, GT, false, true, S, TAB, PRE, NS, NCH);               \
+      else ZS_LAUNCH(KERNEL, GT, false, false, S, TAB, PRE, NS, NCH);                         \
+    }                                                                                         \
   } while (0)
 #define ZS_DISPATCH(KERNEL, TAB, PRE, NS, NCH)                                                \
   do {                                                                                        \
@@ -1773,6 +1952,8 @@ int zs_adamset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype
   as->vec_chunks = vpre.back();
   as->nsca = int64_t(sca.size());
   as->sca_chunks = spre.back();
+  as->sq_vec = std::min(as->vec_chunks, kSqnormVecPartials);
+  as->sq_sca = std::min(as->sca_chunks, kSqnormScaPartials);
   as->elems = elems;
   as->bytes = bytes;
   as->g_dtype = g_dtype;
@@ -1808,10 +1989,87 @@ int zs_adamset_run(const zs_adamset* as, const zs_adam_hparams* h, uintptr_t str
   const bool ams = h->amsgrad != 0;
   ZS_REQUIRE(!ams || as->has_vmax || (as->nvec + as->nsca) == 0,
              "zs_adamset_run: amsgrad needs vmax segments");
-  return launch_adam_tables(as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks, as->d_sca,
-                            as->d_sca_prefix, as->nsca, as->sca_chunks, as->g_dtype,
-                            as->p_dtype == ZS_BF16_SPLIT, ams, as->has_carry != 0, make_hp(h),
-                            reinterpret_cast<hipStream_t>(stream));
+  return launch_adam_tables<false>(as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks, as->d_sca,
+                                   as->d_sca_prefix, as->nsca, as->sca_chunks, as->g_dtype,
+                                   as->p_dtype == ZS_BF16_SPLIT, ams, as->has_carry != 0,
+                                   make_hp(h), nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+int zs_adamset_run_clipped(const zs_adamset* as, const zs_adam_hparams* h, const float* coef,
+                           uintptr_t stream) {
+  ZS_REQUIRE(as && h && coef, "zs_adamset_run_clipped: NULL argument");
+  ZS_REQUIRE(!as->has_carry,
+             "zs_adamset_run_clipped: a set with the ZeRO-1 carry cannot be clipped");
+  const bool ams = h->amsgrad != 0;
+  ZS_REQUIRE(!ams || as->has_vmax || (as->nvec + as->nsca) == 0,
+             "zs_adamset_run_clipped: amsgrad needs vmax segments");
+  return launch_adam_tables<true>(as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks, as->d_sca,
+                                  as->d_sca_prefix, as->nsca, as->sca_chunks, as->g_dtype,
+                                  as->p_dtype == ZS_BF16_SPLIT, ams, false, make_hp(h), coef,
+                                  reinterpret_cast<hipStream_t>(stream));
+}
+
+int zs_adamset_sqnorm_partials(const zs_adamset* as, int64_t* n) {
+  ZS_REQUIRE(as && n, "zs_adamset_sqnorm_partials: NULL argument");
+  *n = as->sq_vec + as->sq_sca;
+  return ZS_OK;
+}
+
+int zs_adamset_grad_sqnorm(const zs_adamset* as, double* partials, uintptr_t stream) {
+  ZS_REQUIRE(as != nullptr, "zs_adamset_grad_sqnorm: NULL set");
+  ZS_REQUIRE(partials != nullptr || as->sq_vec + as->sq_sca == 0,
+             "zs_adamset_grad_sqnorm: partials is NULL");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool f32 = as->g_dtype == ZS_F32, split = as->p_dtype == ZS_BF16_SPLIT;
+  if (as->sq_vec) {
+#define ZS_SQ(GT, S, NT)                                                                      \
+  hipLaunchKernelGGL((grad_sqnorm_kernel<GT, S, NT>), dim3(int(as->sq_vec)), dim3(kThreads), 0, \
+                     st, as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks, partials)
+    if (sqnorm_nt()) {
+      if (f32) ZS_SQ(float, false, true);
+      else if (split) ZS_SQ(unsigned short, true, true);
+      else ZS_SQ(unsigned short, false, true);
+    } else {
+      if (f32) ZS_SQ(float, false, false);
+      else if (split) ZS_SQ(unsigned short, true, false);
+      else ZS_SQ(unsigned short, false, false);
+    }
+#undef ZS_SQ
+    ZS_HIP(hipGetLastError());
+  }
+  if (as->sq_sca) {
+    if (f32)
+      hipLaunchKernelGGL(grad_sqnorm_scalar_kernel<float>, dim3(int(as->sq_sca)), dim3(kThreads),
+                         0, st, as->d_sca, as->d_sca_prefix, as->nsca, as->sca_chunks,
+                         partials + as->sq_vec);
+    else
+      hipLaunchKernelGGL(grad_sqnorm_scalar_kernel<unsigned short>, dim3(int(as->sq_sca)),
+                         dim3(kThreads), 0, st, as->d_sca, as->d_sca_prefix, as->nsca,
+                         as->sca_chunks, partials + as->sq_vec);
+    ZS_HIP(hipGetLastError());
+  }
+  return ZS_OK;
+}
+
+int zs_sqnorm_reduce(const double* partials, int64_t n, float* sumsq, uintptr_t stream) {
+  ZS_REQUIRE(sumsq != nullptr, "zs_sqnorm_reduce: sumsq is NULL");
+  ZS_REQUIRE(n >= 0 && (n == 0 || partials), "zs_sqnorm_reduce: %lld partials at NULL",
+             (long long)n);
+  hipLaunchKernelGGL(sqnorm_reduce_kernel, dim3(1), dim3(kThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), partials, n, sumsq);
+  ZS_HIP(hipGetLastError());
+  return ZS_OK;
+}
+
+int zs_clip_coef(const float* sumsq, double grad_div, double max_norm, float* out2,
+                 uintptr_t stream) {
+  ZS_REQUIRE(sumsq && out2, "zs_clip_coef: NULL argument");
+  ZS_REQUIRE(grad_div > 0.0, "zs_clip_coef: grad_div must be > 0");
+  ZS_REQUIRE(max_norm >= 0.0, "zs_clip_coef: max_norm must be >= 0 (infinity allowed), not NaN");
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(64), 0,
+                     reinterpret_cast<hipStream_t>(stream), sumsq, grad_div, float(max_norm), out2);
+  ZS_HIP(hipGetLastError());
+  return ZS_OK;
 }
 
 // zs_adam_step: one contiguous range through the same kernels.  Its two one-entry tables
@@ -1869,8 +2127,9 @@ int zs_adam_step_ex(float* p, uint16_t* p_bf16, const void* g, int g_dtype, floa
   hipLaunchKernelGGL(write_tables_kernel, dim3(1), dim3(1), 0, st, d, t);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) {
-    rc = launch_adam_tables(d->seg, d->prefix, 1, vch, d->seg + 1, d->prefix + 2, 1, sch, g_dtype,
-                            false, false, carry != nullptr, make_hp(&h), st);
+    rc = launch_adam_tables<false>(d->seg, d->prefix, 1, vch, d->seg + 1, d->prefix + 2, 1, sch,
+                                   g_dtype, false, false, carry != nullptr, make_hp(&h), nullptr,
+                                   st);
   }
   const hipError_t ef = hipFreeAsync(d, st);  // after the launches, in stream order
   if (e != hipSuccess)
@@ -2070,6 +2329,9 @@ int zs_tune(const char* key, int64_t value, int64_t* previous) {
     ok = value >= 0 && value <= 1024;
   } else if (std::strcmp(key, "adam_loads_first") == 0) {
     slot = &adam_loads_first();
+    ok = value == 0 || value == 1;
+  } else if (std::strcmp(key, "sqnorm_nt") == 0) {
+    slot = &sqnorm_nt();
     ok = value == 0 || value == 1;
   } else if (std::strcmp(key, "sync_host_flags") == 0) {
     slot = &zs::sync_host_flags();

@@ -36,6 +36,8 @@ EXPORTED = (
     "zs_fp8_dequantize_gathered",
     "zs_adam_hparams_init", "zs_adamset_create", "zs_adamset_run", "zs_adamset_set_grads", "zs_adamset_destroy",
     "zs_adamset_stats", "zs_adam_step", "zs_adam_step_ex",
+    "zs_adamset_sqnorm_partials", "zs_adamset_grad_sqnorm", "zs_sqnorm_reduce", "zs_clip_coef",
+    "zs_adamset_run_clipped",
     "zs_comm_unique_id", "zs_comm_init", "zs_comm_destroy", "zs_reduce_scatter", "zs_all_gather",
     "zs_all_reduce", "zs_reduce", "zs_broadcast", "zs_reduce_group", "zs_broadcast_group", "zs_all_gather_group", "zs_reduce_scatter_group",
     "zs_all_gather_group_ordered", "zs_reduce_scatter_group_ordered", "zs_stream_wait_event",
@@ -120,6 +122,11 @@ _SIGS = {
     "zs_adamset_set_grads": ([_P, _I64, _P, _U], ctypes.c_int),
     "zs_adamset_destroy": ([_P], ctypes.c_int),
     "zs_adamset_stats": ([_P, _PI64, _PI64], ctypes.c_int),
+    "zs_adamset_sqnorm_partials": ([_P, _PI64], ctypes.c_int),
+    "zs_adamset_grad_sqnorm": ([_P, _P, _U], ctypes.c_int),
+    "zs_sqnorm_reduce": ([_P, _I64, _P, _U], ctypes.c_int),
+    "zs_clip_coef": ([_P, ctypes.c_double, ctypes.c_double, _P, _U], ctypes.c_int),
+    "zs_adamset_run_clipped": ([_P, ctypes.POINTER(AdamHParams), _P, _U], ctypes.c_int),
     "zs_adam_step": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_float] * 5 +
                      [ctypes.c_int, _I64, ctypes.c_float, _P, ctypes.c_float, _U], ctypes.c_int),
     "zs_adam_step_ex": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_double] * 5 +

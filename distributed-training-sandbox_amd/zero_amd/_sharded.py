@@ -45,9 +45,26 @@ class ShardedOptimizerBase:
     def __init__(self, optimizer: Optimizer, *, layout: str = "reference",
                  bucket_mb: float | None = None, comm=None, sync: bool = True, buckets: str = "ragged",
                  overlap: bool = False, overlap_bucket_mb: float = 64.0, master: str = "split",
-                 arena: str = "flat", grad_comm: str | None = None):
+                 arena: str = "flat", grad_comm: str | None = None,
+                 max_grad_norm: float | None = None):
         if arena not in ("flat", "buckets", "auto"):
             raise ValueError(f"arena must be 'flat', 'buckets' or 'auto' (got {arena!r})")
+        # global gradient-norm clipping inside step() (None = off); a plain attribute, it may be
+        # changed between steps.  What it cannot be combined with is refused here, on every rank
+        # and before anything collective
+        self.max_grad_norm = max_grad_norm
+        self.engine = None
+        self._clip_unsupported = None
+        if self._carry and get("ws") > 1:
+            self._clip_unsupported = ("ZeRO-1 at world size > 1 (what the gradient carry should "
+                                      "hold under clipping is undecided)")
+        elif overlap:
+            self._clip_unsupported = "overlap=True (the backward-overlapped reduction)"
+        elif arena == "buckets":
+            self._clip_unsupported = "arena='buckets' (the bucket arena)"
+        elif layout != "reference" and (layout != "flat" or self._carry):
+            self._clip_unsupported = f"layout={layout!r} (it runs on the bucket arena)"
+        self._check_clip()
         if not isinstance(optimizer, torch.optim.Adam):
             raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW "
                             f"(got {type(optimizer).__name__})")
@@ -88,6 +105,9 @@ class ShardedOptimizerBase:
             if world_size > 1 and layout == "reference" and grad_comm is None:
                 self.arena_calibration = calibrate_arena(self)
                 arena = self.arena_calibration["chosen"]
+                if arena == "buckets":  # (rank 0's choice, broadcast: every rank raises alike)
+                    self._clip_unsupported = "arena='auto' that resolved to the bucket arena"
+                    self._check_clip()
         # bytes per bucket (bucket arena) / per round (flat arena, all owners' windows together);
         # default 256 MiB / 1 GiB: a flat round has no pack to pipeline, so fewer, larger rounds
         # cost only the last round's Adam as exposed tail and cut the launches per step
@@ -122,6 +142,37 @@ class ShardedOptimizerBase:
             # before the first step (every rank builds it: the communicator is a collective)
             self._build_engine()
             self._overlap_hooks = self.engine.register_marks()
+
+    def _check_clip(self):
+        """``max_grad_norm`` is None or a limit >= 0 (infinity: report the norm, clip nothing) on
+        a configuration that supports clipping; ValueError otherwise."""
+        m = self.max_grad_norm
+        if m is None:
+            return
+        if isinstance(m, bool) or not isinstance(m, (int, float)) or not m >= 0:
+            raise ValueError(f"max_grad_norm must be None or a number >= 0 (got {m!r})")
+        if self._clip_unsupported is not None:
+            raise ValueError("zero_amd: max_grad_norm is not supported with "
+                             + self._clip_unsupported)
+
+    @property
+    def last_grad_norm(self):
+        """0-d fp32 device tensor: the L2 norm of the averaged gradient the last clipped step
+        saw (clip_grad_norm_'s return value); valid in stream order after step(), overwritten by
+        the next step; None before the first clipped step."""
+        out = None if self.engine is None else self.engine.clip_out
+        return None if out is None else out[0]
+
+    @property
+    def last_clip_coef(self):
+        """0-d fp32 device tensor: min(1, max_grad_norm / (last_grad_norm + 1e-6)), as above."""
+        out = None if self.engine is None else self.engine.clip_out
+        return None if out is None else out[1]
+
+    @property
+    def last_norm_bytes(self) -> int:
+        """Gradient bytes the last step's norm pass read (0 without clipping)."""
+        return 0 if self.engine is None else self.engine.last_norm_bytes
 
     def _flat(self) -> bool:
         """The flat parameter arena: the reference layout (the drop-in), or the balanced Layout F
@@ -201,6 +252,8 @@ class ShardedOptimizerBase:
         step_start = time.perf_counter()
         if self.engine is None:
             self._build_engine()
+        self._check_clip()
+        self.engine.max_grad_norm = self.max_grad_norm
         had_vmax = self.engine.vmax is not None
         grads = [p.grad for p in self.params]
         seen = self._validated

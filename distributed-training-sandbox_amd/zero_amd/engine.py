@@ -368,6 +368,11 @@ class ShardEngine:
         self.copy_events = None    # optional list of (kind, start, end, bytes) per pack / unpack
         self.capture_reduced = None  # optional tensor (stream-long): the reduced grads, for checks
         self.last_adam_bytes = 0
+        # global gradient-norm clipping (flat arena only; flat.py _clip_*): the limit of this step
+        # (None = off), bytes the last step's norm pass read, and the device results
+        self.max_grad_norm = None
+        self.last_norm_bytes = 0
+        self.clip_out = None  # fp32 {norm, coef}, allocated by the first clipped step
 
     # ------------------------------------------------------------------------------------------
     def _piece_cols(self):
@@ -453,11 +458,14 @@ class ShardEngine:
         mst = np.uint64(self.master.data_ptr()) + so64 * np.uint64(4)
         return self._adam_rows(idx, g, mst, mst, p_out, so, n)
 
-    def _run_adam(self, tag, rows, param_idx, hparams_of, stream, carry_mul=None, gptr=None):
+    def _run_adam(self, tag, rows, param_idx, hparams_of, stream, carry_mul=None, gptr=None,
+                  defer=None):
         """Partition rows by (group, step, carry multiplier) — torch's bias correction is per param,
         and the ZeRO-1 carry weight depends on which grads survived since the last step — and
         launch one fused-Adam set per part.  ``gptr`` (per row): gradient addresses bound into the
-        sets before they run (AdamSet.set_grads; the rows then carry g = 0)."""
+        sets before they run (AdamSet.set_grads; the rows then carry g = 0).  ``defer`` (a list;
+        gradient clipping): nothing is launched, every part is appended as ``(aset, hp, gptr of
+        its rows or None)`` for the caller to run once the clip coefficient exists."""
         if len(rows) == 0:
             return
         if carry_mul is None:
@@ -471,7 +479,7 @@ class ShardEngine:
             gz = getattr(self, "czdtype", self.zdtype)  # dtype of the reduced grad Adam reads
             aset = self._cached(("adam", tag, gidx, len(sel), int(sel[0])), sub.tobytes(),
                                 lambda: AdamSet(sub, gz, self.p_dtype))
-            if gptr is not None:
+            if gptr is not None and defer is None:
                 aset.set_grads(np.asarray(gptr, np.uint64)[sel], stream)
             hpd = hparams_of(gidx)
             if hpd["amsgrad"] and self.vmax is None:
@@ -481,6 +489,9 @@ class ShardEngine:
                               amsgrad=hpd["amsgrad"], maximize=hpd["maximize"],
                               grad_div=float(self.ws),
                               carry_mul=float(cmul) if self.carry is not None else 0.0)
+            if defer is not None:
+                defer.append((aset, hp, None if gptr is None else np.asarray(gptr, np.uint64)[sel]))
+                continue
             if self.timing_events is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
@@ -495,6 +506,8 @@ class ShardEngine:
     def step(self, grads, hparams_of, stream=None):
         """One optimizer step.  ``grads[i]`` is param i's local gradient (or None);
         ``hparams_of(group_index)`` returns that group's Adam hyper-parameters."""
+        if self.max_grad_norm is not None:
+            raise ValueError("zero_amd: max_grad_norm needs the flat arena")
         stream = torch.cuda.current_stream(self.device) if stream is None else stream
         n = len(self.params)
         has = np.fromiter((g is not None for g in grads), bool, n)

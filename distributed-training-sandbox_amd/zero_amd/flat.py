@@ -34,6 +34,12 @@ which in the reference clears owned grads only) and by 0 when the caller replace
 ``model.zero_grad()`` → None → a fresh tensor from backward), per parameter, on the assumption
 that every rank treats its grads alike.  Zeroing a view in place
 (``model.zero_grad(set_to_none=False)``) cannot be told apart from ``opt.zero_grad()``.
+
+Global gradient-norm clipping (``max_grad_norm``; ``_clip_*`` below) sits between the reduction
+and the update, where ``clip_grad_norm_`` would if the reduced gradient were visible to it: the
+step's Adam launches are collected, a read-only pass sums the squares of the reduced gradients
+they are bound to, the one-element sum is all-reduced, and the update reads the coefficient from
+device memory.  Without the ZeRO-1 carry and without backward overlap only.
 """
 from __future__ import annotations
 
@@ -155,6 +161,7 @@ class FlatEngine(ShardEngine):
         mk = lambda: [StreamEvent() for _ in range(self.K)]  # noqa: E731
         self.ev_red, self.ev_adam, self.ev_bc = mk(), mk(), mk()
         self.ev_grads = StreamEvent()
+        self.norm_events = None  # optional list of (start, end, bytes) per norm pass
         self.ev_c0 = torch.cuda.Event(enable_timing=True)
         self.ev_c1 = torch.cuda.Event(enable_timing=True)
         self.capture_reduced = None  # optional tensor: a copy of R after the reduces (checks)
@@ -299,15 +306,20 @@ class FlatEngine(ShardEngine):
             rd.sets = sets
         return sets
 
-    def _adam_round_fast(self, rd: _Round, hps, stream, gptr=None) -> bool:
+    def _adam_round_fast(self, rd: _Round, hps, stream, gptr=None, defer=None) -> bool:
         """Launch the round's static sets if every param in them shares its group's (step,
         carry) key this step; returns False to fall back to the general partitioning.  ``gptr``
-        (in place, ws == 1): every parameter's gradient address, bound into the sets first."""
+        (in place, ws == 1): every parameter's gradient address, bound into the sets first.
+        ``defer`` (gradient clipping): collect ``(aset, hp, gptr of its rows)`` instead."""
         sets = self._static_sets(rd)
         for gi, idx, aset in sets:
             hp = hps.get(gi)
             if hp is None:
                 return False
+        if defer is not None:
+            defer.extend((aset, hps[gi], None if gptr is None else gptr[idx])
+                         for gi, idx, aset in sets)
+            return True
         for gi, idx, aset in sets:
             if gptr is not None:
                 aset.set_grads(gptr[idx], stream)
@@ -321,6 +333,90 @@ class FlatEngine(ShardEngine):
                 aset.run(hps[gi], stream)
             self.last_adam_bytes += aset.bytes
         return True
+
+    def _adam_round(self, rd: _Round, has, cmul, hps, hparams_of, stream, gptr=None, defer=None):
+        """Round ``rd``'s Adam: the static sets, or the general partitioning when a parameter has
+        no gradient or a (step, carry) key of its own."""
+        if not len(rd.idx) or (hps and self._adam_round_fast(rd, hps, stream, gptr, defer)):
+            return
+        live = has[rd.idx]
+        rows, idx = (rd.rows, rd.idx) if live.all() else (rd.rows[live], rd.idx[live])
+        self._run_adam(("flat", rd.j), rows, idx, hparams_of, stream, carry_mul=cmul[idx],
+                       gptr=None if gptr is None else gptr[idx], defer=defer)
+
+    # ------------------------------------------------------------------------------------------
+    # Global gradient-norm clipping (clip_grad_norm_ between the reduction and the update): one
+    # read-only pass over the reduced gradients the collected Adam sets are bound to, a scalar
+    # all-reduce, and the coefficient read from device memory by the update.  The gradient is
+    # never rewritten and the host never waits.
+    def _clip_prepare(self, deferred):
+        """Each collected set's slice of the partials tensor (sized on first use, regrown only
+        when the list of sets changes) and the device scalars."""
+        key = tuple((id(aset), aset.sqnorm_partials) for aset, _, _ in deferred)
+        if getattr(self, "_clip_key", None) != key:
+            counts = [n for _, n in key]
+            self._clip_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            total = int(self._clip_off[-1])
+            buf = getattr(self, "clip_partials", None)
+            if buf is None or buf.numel() < total:
+                if buf is not None:  # queued kernels may still write it
+                    self.retired.append(buf)
+                self.clip_partials = torch.zeros(max(total, 1), dtype=torch.float64,
+                                                 device=self.device)
+            self._clip_key = key
+        if self.clip_out is None:
+            self.clip_sumsq = torch.zeros(1, dtype=torch.float32, device=self.device)
+            self.clip_out = torch.zeros(2, dtype=torch.float32, device=self.device)
+            self.ev_clip = (StreamEvent(), StreamEvent())  # around the norm's scalar all-reduce
+
+    def _clip_norm(self, deferred, first, stream):
+        """Stage 1 for ``deferred[first:]``: bind the gradients where needed, then the sum of
+        squares into the set's slice."""
+        base = self.clip_partials.data_ptr()
+        for k in range(first, len(deferred)):
+            aset, _, g = deferred[k]
+            if g is not None:
+                aset.set_grads(g, stream)
+            ev = None
+            if self.norm_events is not None:
+                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                ev[0].record(stream)
+            aset.grad_sqnorm(base + int(self._clip_off[k]) * 8, stream)
+            nb = aset.grad_bytes  # what the pass reads
+            if ev is not None:
+                ev[1].record(stream)
+                self.norm_events.append((ev[0], ev[1], nb))
+            self.last_norm_bytes += nb
+
+    def _clip_coef(self, deferred, stream):
+        """Stages 2 and 3: one fixed-order reduction of all partials, the scalar all-reduce on the
+        communication stream (ordered by events on both sides; a rank that owns nothing
+        contributes 0 and still takes part), the coefficient."""
+        from .kernels import clip_coef, sqnorm_reduce
+
+        sqnorm_reduce(self.clip_partials, int(self._clip_off[-1]), self.clip_sumsq, stream)
+        if self.ws > 1:
+            cs = self.comm_stream
+            self.ev_clip[0].record(stream)
+            cs.wait_event(self.ev_clip[0])
+            self.comm.all_reduce(self.clip_sumsq, cs)
+            self.ev_clip[1].record(cs)
+            stream.wait_event(self.ev_clip[1])
+        clip_coef(self.clip_sumsq, float(self.ws), float(self.max_grad_norm), self.clip_out, stream)
+
+    def _clip_run(self, deferred, first, last, stream):
+        """Stage 4 for ``deferred[first:last]``: the update with the coefficient."""
+        coef = self.clip_out.data_ptr() + 4
+        for aset, hp, _ in deferred[first:last]:
+            if self.timing_events is not None:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                aset.run_clipped(hp, coef, stream)
+                e1.record(stream)
+                self.timing_events.append((e0, e1, aset.bytes))
+            else:
+                aset.run_clipped(hp, coef, stream)
+            self.last_adam_bytes += aset.bytes
 
     # ------------------------------------------------------------------------------------------
     def _reduce_round(self, rd: _Round, cs):
@@ -673,15 +769,28 @@ class FlatEngine(ShardEngine):
             from .kernels import convert  # of bytes: read 4 + write 2 B per element)
 
             convert(self.G, self.Gc, stream)
+        clip = self.max_grad_norm is not None
+        self.last_norm_bytes = 0
+        if clip:
+            if self.overlap or self.carry is not None:
+                raise ValueError("zero_amd: max_grad_norm is not supported with backward overlap "
+                                 "or the ZeRO-1 gradient carry")
+            # every Adam launch of the step is collected first (host only): the sets' slices of
+            # the partials tensor must be known before the first norm pass
+            deferred, ends = [], []
+            for rd in self.rounds:
+                self._adam_round(rd, has, cmul, hps, hparams_of, stream, gptr, deferred)
+                ends.append(len(deferred))
+            self._clip_prepare(deferred)
         if self.ws == 1:  # zero1.py:107-108 / zero2.py:120 at ws=1: Adam on the local grads
             with _lib.phase_range("optimizer_step"):
-                for rd in self.rounds:
-                    if len(rd.idx) and not (hps and self._adam_round_fast(rd, hps, stream, gptr)):
-                        live = has[rd.idx]
-                        rows, idx = (rd.rows, rd.idx) if live.all() else (rd.rows[live], rd.idx[live])
-                        self._run_adam(("flat", rd.j), rows, idx, hparams_of, stream,
-                                       carry_mul=cmul[idx],
-                                       gptr=None if gptr is None else gptr[idx])
+                if clip:
+                    self._clip_norm(deferred, 0, stream)
+                    self._clip_coef(deferred, stream)
+                    self._clip_run(deferred, 0, len(deferred), stream)
+                else:
+                    for rd in self.rounds:
+                        self._adam_round(rd, has, cmul, hps, hparams_of, stream, gptr)
             if self.inplace:
                 if self.overlap:
                     self.launched_in_backward = self.ov_launched
@@ -703,13 +812,19 @@ class FlatEngine(ShardEngine):
                 with torch.cuda.stream(cs):
                     self.capture_reduced.copy_(self.R[:self.capture_reduced.numel()])
         with _lib.phase_range("optimizer_step"):  # zero1.py:88
-            for rd in self.rounds:
-                stream.wait_event(self.ev_red[rd.j])
-                if len(rd.idx) and not (hps and self._adam_round_fast(rd, hps, stream)):
-                    live = has[rd.idx]
-                    rows, idx = (rd.rows, rd.idx) if live.all() else (rd.rows[live], rd.idx[live])
-                    self._run_adam(("flat", rd.j), rows, idx, hparams_of, stream,
-                                   carry_mul=cmul[idx])
+            if clip:
+                # the norm of round j waits for its reduction only, so it runs while later rounds
+                # still reduce; Adam starts once the coefficient exists
+                for rd, a, b in zip(self.rounds, [0] + ends[:-1], ends):
+                    stream.wait_event(self.ev_red[rd.j])
+                    self._clip_norm(deferred[:b], a, stream)
+                self._clip_coef(deferred, stream)
+            for k, rd in enumerate(self.rounds):
+                if clip:
+                    self._clip_run(deferred, ends[k - 1] if k else 0, ends[k], stream)
+                else:
+                    stream.wait_event(self.ev_red[rd.j])
+                    self._adam_round(rd, has, cmul, hps, hparams_of, stream)
                 self.ev_adam[rd.j].record(stream)
         with _lib.phase_range("broadcast_parameters"):  # zero1.py:91-102
             for rd in self.rounds:

@@ -2,7 +2,8 @@
 
 ``CopySet``  — one launch of the descriptor-driven gather/scatter copy (pack / unpack).
 ``copy_direct`` — the same copy with the segments in the kernel arguments (no table to keep).
-``AdamSet``  — one launch of the fused Adam/AdamW update over a list of segments.
+``AdamSet``  — one launch of the fused Adam/AdamW update over a list of segments; its
+``grad_sqnorm`` / ``run_clipped`` with ``sqnorm_reduce`` and ``clip_coef`` are global-norm clipping.
 ``adam_step`` — the same update over one contiguous range (zs_adam_step_ex; no table to keep).
 
 Both upload their segment table once; ``run(stream)`` only enqueues a kernel on ``stream``.
@@ -141,6 +142,8 @@ class AdamSet:
         self._h = h
         self.nseg = len(segs)
         self._g = np.ascontiguousarray(segs[:, 0])  # the gradients bound now, per input row
+        self._n = segs[:, 8].astype(np.int64)
+        self._gsz = 4 if int(g_dtype) == _lib.ZS_F32 else 2
         self._stats()
 
     def _stats(self):
@@ -162,6 +165,35 @@ class AdamSet:
     def run(self, hp: AdamHParams, stream) -> None:
         _lib.call("zs_adamset_run", self._h, ctypes.byref(hp), stream_handle(stream))
 
+    @property
+    def grad_bytes(self) -> int:
+        """Bytes of the gradients bound now (what ``grad_sqnorm`` reads)."""
+        return int(self._n[self._g != 0].sum()) * self._gsz
+
+    @property
+    def sqnorm_partials(self) -> int:
+        """Double partials ``grad_sqnorm`` writes for this set (fixed when the set was created)."""
+        n = getattr(self, "_sq_partials", None)
+        if n is None:
+            c = ctypes.c_int64()
+            _lib.call("zs_adamset_sqnorm_partials", self._h, ctypes.byref(c))
+            n = self._sq_partials = c.value
+        return n
+
+    def grad_sqnorm(self, partials, stream) -> None:
+        """Sum of squares of the gradients bound now into ``partials`` (a float64 device tensor of
+        at least ``sqnorm_partials`` elements, or its address): zs_adamset_grad_sqnorm."""
+        if not isinstance(partials, int):
+            assert partials.dtype.itemsize == 8 and partials.numel() >= self.sqnorm_partials
+            partials = partials.data_ptr()
+        _lib.call("zs_adamset_grad_sqnorm", self._h, partials, stream_handle(stream))
+
+    def run_clipped(self, hp: AdamHParams, coef, stream) -> None:
+        """``run`` with every averaged gradient times the fp32 device scalar ``coef`` (a tensor or
+        its address), read when the kernel runs: zs_adamset_run_clipped."""
+        ptr = coef if isinstance(coef, int) else coef.data_ptr()
+        _lib.call("zs_adamset_run_clipped", self._h, ctypes.byref(hp), ptr, stream_handle(stream))
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib is not None:
@@ -170,6 +202,23 @@ class AdamSet:
             except Exception:  # interpreter teardown
                 pass
             self._h = None
+
+
+def sqnorm_reduce(partials, n: int, sumsq, stream) -> None:
+    """``sumsq`` (one fp32 device element) = the fp32 rounding of the double sum of the first ``n``
+    float64 ``partials``, added in a fixed order (zs_sqnorm_reduce)."""
+    assert n == 0 or (partials.dtype.itemsize == 8 and partials.numel() >= n)
+    _lib.call("zs_sqnorm_reduce", partials.data_ptr() if n else None, int(n), sumsq.data_ptr(),
+              stream_handle(stream))
+
+
+def clip_coef(sumsq, grad_div: float, max_norm: float, out2, stream) -> None:
+    """``out2`` (two fp32 device elements) = {norm, coef}: the L2 norm of the averaged gradient
+    from the raw sum of squares ``sumsq`` and clip_grad_norm_'s clamped coefficient
+    (zs_clip_coef)."""
+    assert out2.numel() >= 2 and out2.dtype.itemsize == 4 and sumsq.dtype.itemsize == 4
+    _lib.call("zs_clip_coef", sumsq.data_ptr(), float(grad_div), float(max_norm), out2.data_ptr(),
+              stream_handle(stream))
 
 
 def adam_step(p, g, m, v, *, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,

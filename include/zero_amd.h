@@ -278,6 +278,41 @@ int zs_adamset_destroy(zs_adamset* as);
  * bound now) */
 int zs_adamset_stats(const zs_adamset* as, int64_t* elems, int64_t* bytes);
 
+/* Global gradient-norm clipping fused into the update (additive in ABI v13).  Together these
+ * replace torch.nn.utils.clip_grad_norm_(params, max_norm) between zero2.py's reduce-scatter
+ * (zero2.py:94-113) and its optimizer.step() (zero2.py:120): the reduced gradient is read once
+ * more, never rewritten, and the host never waits for the norm.  All buffers are the caller's.
+ *
+ * zs_adamset_sqnorm_partials: how many double partials zs_adamset_grad_sqnorm writes for this set;
+ * fixed when the set is created (it depends on the segment table alone, not on zs_tune or the
+ * device), 0 for an empty set. */
+int zs_adamset_sqnorm_partials(const zs_adamset* as, int64_t* n);
+/* The squares of the gradients the set is bound to now (so after zs_adamset_set_grads), summed
+ * into partials[0 .. n): the `torch.linalg.vector_norm(g, 2)` pass of clip_grad_norm_ over every
+ * segment of the set, on the raw reduced sums (before the division by the world size).  A segment
+ * with g == 0 contributes nothing and is not read.  fp32 only inside one lane's 8 (16: split
+ * master) terms of a chunk, double above, no atomics: the partials have the same bits on every
+ * run.  Every partial is written (plain stores); nothing else is. */
+int zs_adamset_grad_sqnorm(const zs_adamset* as, double* partials, uintptr_t stream);
+/* *sumsq = (float) of the double sum of partials[0 .. n), added in a fixed order by one workgroup
+ * (n == 0: 0).  The partials of several sets laid side by side reduce in one call; at world size
+ * > 1 the caller all-reduces the one float before zs_clip_coef. */
+int zs_sqnorm_reduce(const double* partials, int64_t n, float* sumsq, uintptr_t stream);
+/* out2[0] = norm = (float)(sqrt((double)*sumsq) / grad_div): the L2 norm of the averaged gradient
+ * (clip_grad_norm_'s return value); out2[1] = coef = min(1, (float)max_norm / (norm + 1e-6f)) in
+ * fp32 (its clip_coef_clamped, error_if_nonfinite=False: a NaN norm gives a NaN coefficient, a
+ * zero norm 1; max_norm = infinity reports the norm and clips nothing).  ZS_ERR_INVALID for
+ * max_norm < 0 or NaN, or grad_div <= 0. */
+int zs_clip_coef(const float* sumsq, double grad_div, double max_norm, float* out2,
+                 uintptr_t stream);
+/* zs_adamset_run with every averaged gradient multiplied by *coef (device memory, read when the
+ * kernel runs: one uniform load per workgroup) right after the division by grad_div and before
+ * maximize and weight decay — clip_grad_norm_'s `g.mul_(clip_coef_clamped)` without rewriting g.
+ * ZS_ERR_INVALID, nothing launched, for a set with the ZeRO-1 carry (what the carry should hold
+ * under clipping is undecided). */
+int zs_adamset_run_clipped(const zs_adamset* as, const zs_adam_hparams* hp, const float* coef,
+                           uintptr_t stream);
+
 /* Single-range form, SURVEY.md §8(b)'s signature: one torch.optim.Adam/AdamW step over n
  * contiguous elements — the update of one flat shard (zero1.py:88 on a flattened group) with no
  * table to build.  p: fp32 master/param, updated in place; p_bf16: optional bf16 copy of the
@@ -329,7 +364,9 @@ int zs_device_alloc_chunked(int64_t bytes, int64_t chunk_bytes, void** out);
  * loads-first kernel of a split master; k = at most k per CU), "adam_loads_first" (1: a full chunk
  * of the vector Adam issues all its loads before its first wait; 0: every chunk through the
  * per-lane predicated body that partial chunks take, one group's loads in flight at a time — the
- * kernel before the loads-first body, kept for A/B runs, tools/adam_ab.py), "sync_host_flags" (1: flag syncs created from now on take words in pinned host
+ * kernel before the loads-first body, kept for A/B runs, tools/adam_ab.py), "sqnorm_nt" (1: the
+ * gradient sum-of-squares pass loads non-temporally; 0: default cache policy; the sum's bits do
+ * not depend on it, tools/clip_ab.py), "sync_host_flags" (1: flag syncs created from now on take words in pinned host
  * memory, whose satisfied waits the host skips; 0: device words, every wait enqueued — the
  * fallback the library takes by itself when pinned memory is refused), "sync_write_kernel" (1: a
  * flag sync's record is a one-wave kernel storing the epoch with a system-scope release; 0:
