@@ -899,14 +899,34 @@ __global__ __launch_bounds__(kThreads) void convert_scalar_kernel(const void* __
 constexpr float kE4M3Max = 448.0f;
 
 __device__ __forceinline__ uint32_t e4m3x4(float a, float b, float c, float d) {
-  // v_cvt_pk_fp8_f32: round to nearest even, OCP E4M3 on gfx950; inputs pre-clamped to ±448
+  // v_cvt_pk_fp8_f32: round to nearest even, OCP E4M3 on gfx950 (no saturation: from 480 on, and
+  // for NaN, the NaN code); finite inputs stay below the tie at 464 (qscaled)
   int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
   w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
   return uint32_t(w);
 }
-__device__ __forceinline__ float qclamp(float x, float inv) {
+// Degenerate rows (DESIGN.md §4 "fp8 rows: the contract").  A row whose amax (the max of |x| over
+// its non-NaN elements; fmaxf drops NaN) lies below 2^-116 is scaled as though amax were 2^-116:
+// 448 / amax would overflow to +inf from amax < 448 / FLT_MAX ~ 1.32e-36 on, and 0 * inf is NaN;
+// with the floor inv <= 1.75 * 2^124 stays finite and scale stays normal.  Rows at or above the
+// floor keep their bits.
+constexpr float kAmaxFloor = 0x1p-116f;
+__device__ __forceinline__ float q_inv(float amax) {
+  return amax > 0.0f ? kE4M3Max / fmaxf(amax, kAmaxFloor) : 1.0f;
+}
+__device__ __forceinline__ float q_scale(float amax) {
+  return amax > 0.0f ? fmaxf(amax, kAmaxFloor) / kE4M3Max : 1.0f;
+}
+// The scaled value handed to the conversion, unclamped.  |x| <= amax and both the division and
+// the product are correctly rounded, so a finite |x * inv| is at most 448 * (1 + 2^-23), and
+// v_cvt_pk_fp8_f32 rounds everything up to the tie at 464 to 448 (RNE, ties to even).  A NaN
+// product (a NaN element, or +-Inf times the inv = 0 of a row that holds an Inf) it stores as
+// the E4M3 NaN code 0xFF whatever the NaN's sign.  The clamp that used to stand here,
+// v_med3_f32(x * inv, 448, -448), answers a NaN operand with the minimum of the three: it stored
+// a NaN as 0xFE, which came back as the finite value -amax.
+__device__ __forceinline__ float qscaled(float x, float inv) {
 #pragma clang fp contract(off)
-  return __builtin_amdgcn_fmed3f(x * inv, kE4M3Max, -kE4M3Max);
+  return x * inv;
 }
 
 // Block-per-row fallback for any row length and alignment (scalar accesses): amax by wave
@@ -928,10 +948,10 @@ __global__ __launch_bounds__(kThreads) void fp8_quantize_rows_kernel(
     __syncthreads();
     amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     __syncthreads();
-    const float inv = amax > 0.0f ? kE4M3Max / amax : 1.0f;
-    if (threadIdx.x == 0) glob(scales)[r] = amax > 0.0f ? amax / kE4M3Max : 1.0f;
+    const float inv = q_inv(amax);
+    if (threadIdx.x == 0) glob(scales)[r] = q_scale(amax);
     for (int64_t i = threadIdx.x; i < row_len; i += kThreads) {
-      const float c = qclamp(to_f32<T>(x[i]), inv);
+      const float c = qscaled(to_f32<T>(x[i]), inv);
       q[i] = (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(c, c, 0, false) & 0xff);
     }
   }
@@ -945,7 +965,7 @@ __global__ __launch_bounds__(kThreads) void fp8_quantize_rows_kernel(
 // row, all of its loads in flight at once; NREG == 0 (longer rows): both passes stream the row in
 // batches of 8 loads in flight per lane, the second from L2 / MALL where it is still cached.  Same
 // arithmetic, same bits as the block-per-row kernel: amax = max|x|, inv = 448/amax,
-// e4m3(RNE(clamp(x*inv))), scale = amax/448.
+// e4m3(RNE(x*inv)), scale = amax/448 (q_inv, q_scale, qscaled above).
 // One row, one wave (lane = threadIdx.x & 63): x -> q (row_len elements), *scale.
 template <typename T, int NREG>
 __device__ __forceinline__ void fp8_quantize_row(const T* __restrict__ src_row,
@@ -987,19 +1007,19 @@ __device__ __forceinline__ void fp8_quantize_row(const T* __restrict__ src_row,
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-  const float inv = amax > 0.0f ? kE4M3Max / amax : 1.0f;
-  if (lane == 0) *glob(scale) = amax > 0.0f ? amax / kE4M3Max : 1.0f;
+  const float inv = q_inv(amax);
+  if (lane == 0) *glob(scale) = q_scale(amax);
   auto emit = [&](int64_t i, const uint4& raw) {
     float v[E];
     unpack(raw, v);
     if constexpr (sizeof(T) == 2) {
       uint2 out;
-      out.x = e4m3x4(qclamp(v[0], inv), qclamp(v[1], inv), qclamp(v[2], inv), qclamp(v[3], inv));
-      out.y = e4m3x4(qclamp(v[4], inv), qclamp(v[5], inv), qclamp(v[6], inv), qclamp(v[7], inv));
+      out.x = e4m3x4(qscaled(v[0], inv), qscaled(v[1], inv), qscaled(v[2], inv), qscaled(v[3], inv));
+      out.y = e4m3x4(qscaled(v[4], inv), qscaled(v[5], inv), qscaled(v[6], inv), qscaled(v[7], inv));
       nt_st8(q + i, out);
     } else {
       *reinterpret_cast<gptr<uint32_t>>(q + i) =
-          e4m3x4(qclamp(v[0], inv), qclamp(v[1], inv), qclamp(v[2], inv), qclamp(v[3], inv));
+          e4m3x4(qscaled(v[0], inv), qscaled(v[1], inv), qscaled(v[2], inv), qscaled(v[3], inv));
     }
   };
   if constexpr (NREG > 0) {

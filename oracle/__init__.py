@@ -11,6 +11,9 @@ Contents
                   file:line it follows.
   adam_oracle.c   plain-C restatement of the same Adam update (fp32 and bf16-grad/bf16-param with
                   fp32 master), used for bit-level checks and as the timed CPU baseline.
+  fp8_oracle.py   numpy statement of OCP E4M3 (from the bit fields, float64) and of the row-scaled
+                  fp8 quantise / dequantise contract of the ZeRO-3 fp8 gather, degenerate rows
+                  included; pinned to torch's float8_e4m3fn by tests/test_fp8_oracle.py.
 
 Pinning: the restatement is checked against golden vectors produced by running the reference's
 own ShardedOptimizer (gloo/CPU) and torch.optim.Adam in the build container
