@@ -1612,9 +1612,13 @@ int zs_scale(void* x, int64_t n, int dtype, double div, uintptr_t stream) {
   if (n == 0) return ZS_OK;
   ZS_REQUIRE(x != nullptr && aligned(reinterpret_cast<uint64_t>(x), 16),
              "zs_scale: x must be non-NULL and 16-byte aligned");
+  // the reciprocal shortcut only where it is exact in fp32: div itself an fp32 power of two whose
+  // reciprocal is one as well (2^-128 and below have inf there, and x * inf is not x / div)
   int e = 0;
-  const int pow2 = std::frexp(div, &e) == 0.5 ? 1 : 0;
   const float fdiv = float(div), inv = float(1.0 / div);
+  const bool exact = double(fdiv) == div && std::frexp(div, &e) == 0.5 && std::isfinite(inv) &&
+                     inv != 0.0f;
+  const int pow2 = exact ? 1 : 0;
   const int64_t span = int64_t(64) * kScaleU * (dtype == ZS_F32 ? 4 : 8);  // elements per wave step
   const int64_t blocks = std::max<int64_t>(1, (n / span + 3) / 4);
   const int grid = int(std::min<int64_t>(blocks, grid_cap()));

@@ -167,8 +167,8 @@ int zs_copy_direct(int64_t n, const uint64_t* src, const uint64_t* dst, const in
 
 /* In-place x[i] /= div over n elements (dtype ZS_F32 / ZS_BF16, x 16-byte aligned): the
  * `param.grad /= dist.get_world_size()` of DDP's sync_gradients (DDP/ddp.py:45-47), applied to a
- * whole all-reduced gradient bucket.  fp32: IEEE division (reciprocal multiply when div is a power
- * of two, which is exact); bf16: computed in fp32, rounded to nearest even. */
+ * whole all-reduced gradient bucket.  fp32: IEEE division (reciprocal multiply when div and 1/div
+ * are both fp32 powers of two, which is exact); bf16: computed in fp32, rounded to nearest even. */
 int zs_scale(void* x, int64_t n, int dtype, double div, uintptr_t stream);
 
 /* n elements fp32 -> bf16 (round to nearest even, NaN stays NaN) or bf16 -> fp32 (exact).  The

@@ -204,6 +204,33 @@ def test_every_instance(gpu, kind, ams, carry):
     _check(gpu, _Case(kind, [(0, 2 * CHUNK[kind] + 4, True)], seed=11, ams=ams, carry=carry))
 
 
+def scalar_table_past_the_grid(cus):
+    """(segments, scalar chunks): a table whose scalar part has more than 2 * cus chunks of 256
+    elements.  Two long segments one element off alignment (scalar throughout) around an aligned
+    7-element one (a 3-element tail entry) and an unaligned one without a gradient."""
+    segs, off, sca_chunks = [], 0, 0
+    for n, has_g, shift in ((256 * cus + 300, True, 1), (7, True, 0), (300, False, 1),
+                            (256 * cus + 513, True, 1)):
+        off = (off + 3) // 4 * 4 + shift  # 16-byte aligned, or one element off
+        segs.append((off, n, has_g))
+        off += n
+        sca_chunks += -(-(n if shift else n % 4) // 256)  # aligned: only the n % 4 tail is scalar
+    return segs, sca_chunks
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("ams", [False, True])
+@pytest.mark.parametrize("carry", [False, True])
+def test_scalar_table_strides_past_the_grid(gpu, kind, ams, carry):
+    """Every scalar instance with one workgroup per CU over a scalar table of more than 2 * cus
+    chunks: every workgroup goes round its stride loop at least twice, and its forward scan
+    crosses all four entries."""
+    cus = torch.cuda.get_device_properties(gpu).multi_processor_count
+    segs, sca_chunks = scalar_table_past_the_grid(cus)
+    assert sca_chunks == 2 * cus + 8 and sca_chunks > 2 * cus
+    _check(gpu, _Case(kind, segs, seed=31, ams=ams, carry=carry), wg_per_cu=1)
+
+
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("hp", [dict(weight_decay=1e-2), dict(maximize=True), dict(grad_div=3.0)],
                          ids=["wd", "maximize", "div3"])

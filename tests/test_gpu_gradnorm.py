@@ -213,6 +213,27 @@ def test_norm_workgroup_strides_over_chunks(gpu, kind):
     _check_sumsq(kind, ss, _sumsq64(kind, g, segs))
 
 
+SCALAR_PARTIALS_CAP = 1024  # partials (= workgroups) of a set's scalar table at the most
+
+
+@gpu_test
+@pytest.mark.parametrize("kind", KINDS)
+def test_norm_scalar_table_strides_over_chunks(gpu, kind):
+    """A scalar table of 1,029 chunks of 256 elements against its 1,024 partials: workgroups 0..4
+    sum two chunks each, and the scan of workgroups 2..4 crosses from the first shifted segment
+    into the second.  The aligned segment in front gives the vector table its one partial."""
+    C = CHUNK[kind]
+    segs = _layout([C, SCALAR_PARTIALS_CAP * 256 + 300, 700], shifted=(1, 2))
+    sca_chunks = sum(-(-n // 256) for _, n, _ in segs[1:])
+    assert sca_chunks == 1029 and sca_chunks > SCALAR_PARTIALS_CAP
+    g = _grad_array(kind, segs, np.random.default_rng(12))
+    d = _Dev(gpu, kind, segs)
+    assert d.aset.sqnorm_partials == 1 + SCALAR_PARTIALS_CAP
+    d.upload(g)
+    _, ss = d.norm()
+    _check_sumsq(kind, ss, _sumsq64(kind, g, segs))
+
+
 @gpu_test
 @pytest.mark.parametrize("kind", ["split", "f32"])
 def test_norm_is_deterministic(gpu, kind):
@@ -349,6 +370,12 @@ def test_clipped_adam_bitwise(gpu, kind, variant):
     """3 steps of norm -> coefficient -> clipped update with gradient scales x1, x40, x0.05, under
     both adam_loads_first settings, every array whole (gaps and slack included) against the oracle
     run with the coefficient the device reported."""
+    C = CHUNK[kind]
+    _clipped_case(gpu, kind, variant,
+                  _layout([2 * C + 4 * 37 + 3, C + 8, 300], no_grad=(1,), shifted=(2,)))
+
+
+def _clipped_case(gpu, kind, variant, segs, wg_per_cu=0):
     import torch
 
     from zero_amd.kernels import adam_hparams
@@ -356,7 +383,6 @@ def test_clipped_adam_bitwise(gpu, kind, variant):
     C = CHUNK[kind]
     v = dict(VARIANTS[variant])
     div, ams = v.pop("div"), v.get("amsgrad", False)
-    segs = _layout([2 * C + 4 * 37 + 3, C + 8, 300], no_grad=(1,), shifted=(2,))
     rng = np.random.default_rng(31)
     N = max(o + n for o, n, _ in segs) + SLACK
     master0 = _master(N, segs, C, rng)
@@ -367,6 +393,7 @@ def test_clipped_adam_bitwise(gpu, kind, variant):
         d = _Dev(gpu, kind, segs, ams=ams, master0=master0)
         coefs = []
         _tune(b"adam_loads_first", lf)
+        _tune(b"adam_wg_per_cu", wg_per_cu)
         try:
             for t, g in enumerate(grads, 1):
                 d.upload(g)
@@ -378,6 +405,7 @@ def test_clipped_adam_bitwise(gpu, kind, variant):
             torch.cuda.synchronize()
         finally:
             _tune(b"adam_loads_first", 1)
+            _tune(b"adam_wg_per_cu", 0)
         results[lf] = (d.arrays(), coefs)
     coefs = results[1][1]
     for a, b in zip(results[0][1], coefs):
@@ -396,6 +424,23 @@ def test_clipped_adam_bitwise(gpu, kind, variant):
             bad = np.flatnonzero(_bits(got[name]) != _bits(ref))
             assert bad.size == 0, (f"{name}, adam_loads_first={lf}: {bad.size} elements differ "
                                    f"from the oracle, first at {bad[:8]}")
+
+
+@gpu_test
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("variant", ["plain", "amsgrad"])
+def test_clipped_scalar_table_strides_past_the_grid(gpu, kind, variant):
+    """The same harness on a table whose scalar part has more than 2 * cus chunks, with one
+    workgroup per CU: every workgroup of the clipped scalar instance goes round its stride loop at
+    least twice and scans across all four entries (two long shifted segments around an aligned
+    7-element one and a shifted one without a gradient)."""
+    import torch
+
+    cus = torch.cuda.get_device_properties(gpu).multi_processor_count
+    lengths, shifted = [256 * cus + 300, 7, 300, 256 * cus + 513], (0, 2, 3)
+    sca_chunks = sum(-(-(n if k in shifted else n % 4) // 256) for k, n in enumerate(lengths))
+    assert sca_chunks == 2 * cus + 8 and sca_chunks > 2 * cus
+    _clipped_case(gpu, kind, variant, _layout(lengths, no_grad=(2,), shifted=shifted), wg_per_cu=1)
 
 
 @gpu_test
