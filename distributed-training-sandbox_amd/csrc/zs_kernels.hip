@@ -623,6 +623,270 @@ __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
 }
 
 // ----------------------------------------------------------------------------------------------
+// fused SGD (momentum, Nesterov)
+// ----------------------------------------------------------------------------------------------
+// The Adam kernels' tables, chunk geometry, addressing and cache policy with torch.optim.SGD's
+// element: field `m` of a segment is the momentum buffer (MOM: the set has one), `v` and `vmax` are
+// unused.  Without MOM no state array is touched.
+struct SgdHP {
+  float neg_lr, momentum, omd, wd, grad_div, inv_div, carry_mul;
+  int div_pow2, nesterov, maximize, first;
+};
+
+// One element of torch.optim.SGD's single-tensor update (sgd.py _single_tensor_sgd), in the
+// rounding order of torch's CPU kernels: add(x, alpha=a) = fma(a, x, self), so
+// grad.add(param, alpha=wd) = fma(wd, p, g), buf.mul_(momentum).add_(grad, alpha=1-dampening) =
+// fma(1-dampening, g, buf*momentum), grad.add(buf, alpha=momentum) = fma(momentum, buf, g) and
+// param.add_(grad, alpha=-lr) = fma(-lr, g, p).  Only explicit fmaf() fuse; the averaging, the
+// carry and CLIP as adam_elem.  `first`: the buffer does not exist yet and becomes the gradient.
+template <bool CARRY, bool CLIP, bool MOM>
+__device__ __forceinline__ void sgd_elem(float gsum, float& p, float& buf, float& carry,
+                                         const SgdHP& hp, float coef) {
+#pragma clang fp contract(off)
+  float s = gsum;
+  if constexpr (CARRY) s = s + hp.carry_mul * carry;
+  float g = hp.div_pow2 ? s * hp.inv_div : s / hp.grad_div;
+  if constexpr (CARRY) carry = g;
+  if constexpr (CLIP) g = g * coef;
+  if (hp.maximize) g = -g;
+  if (hp.wd != 0.0f) g = fmaf(hp.wd, p, g);
+  if constexpr (MOM) {
+    buf = hp.first ? g : fmaf(hp.omd, g, buf * hp.momentum);
+    g = hp.nesterov ? fmaf(hp.momentum, buf, g) : buf;
+  }
+  p = fmaf(hp.neg_lr, g, p);
+}
+
+// Scalar kernel: any alignment, any length (as adam_scalar_kernel).
+template <typename GT, bool CARRY, bool SPLIT, bool CLIP, bool MOM>
+__global__ __launch_bounds__(kThreads) void sgd_scalar_kernel(
+    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
+    int64_t total_chunks, SgdHP hp, const float* __restrict__ coef_ptr) {
+  static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
+  const float coef = clip_coef<CLIP>(coef_ptr);
+  int64_t seg = 0;
+  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
+    while (chunk_prefix[seg + 1] <= c) ++seg;
+    const AdamSeg s = segs[seg];
+    const int64_t i = (c - chunk_prefix[seg]) * kThreads + threadIdx.x;
+    if (i >= s.n) continue;
+    float gs = s.g ? load_g1<GT>(s.g, i) : 0.0f;
+    const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
+    float p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
+                    : glob(s.master)[i];
+    float b = 0.0f;
+    if constexpr (MOM) b = glob(s.m)[i];
+    float cr = CARRY ? glob(s.carry)[i] : 0.0f;
+    sgd_elem<CARRY, CLIP, MOM>(gs, p, b, cr, hp, coef);
+    if constexpr (SPLIT) {
+      const unsigned short h = f32_to_bf16(p);
+      glob(s.p_out)[i] = h;
+      lo[i] = (unsigned short)master_residual(p, h);
+    } else {
+      if (s.master_out) glob(s.master_out)[i] = p;
+      if (s.p_out) glob(s.p_out)[i] = f32_to_bf16(p);
+    }
+    if constexpr (MOM) glob(s.m)[i] = b;
+    if constexpr (CARRY) glob(s.carry)[i] = cr;
+  }
+}
+
+__device__ __forceinline__ void unpack4(const uint4& q, float (&f)[4]) {
+  f[0] = __uint_as_float(q.x), f[1] = __uint_as_float(q.y);
+  f[2] = __uint_as_float(q.z), f[3] = __uint_as_float(q.w);
+}
+__device__ __forceinline__ uint4 pack4(const float (&f)[4]) {
+  return make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]),
+                    __float_as_uint(f[3]));
+}
+
+// One full chunk, as adam_full_chunk: every load of the chunk (g, hi/lo or master, buffer, carry;
+// at most 16 for the split master's G = 4) before anything depends on one, then the arithmetic
+// and the stores group by group.
+template <typename GT, bool CARRY, bool SPLIT, bool HASG, bool CLIP, bool MOM>
+__device__ __forceinline__ void sgd_full_chunk(const AdamSeg& s, int64_t e0, const SgdHP& hp,
+                                               float coef) {
+  constexpr int G = adam_groups(SPLIT);
+  constexpr bool G32 = sizeof(GT) == 4;
+  uint32_t o4 = threadIdx.x * 16u;
+  uint32_t o2 = threadIdx.x * 8u;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(o4), "+v"(o2));  // opaque per chunk, see adam_full_chunk
+#endif
+  typedef ChunkStream<float, G> S4;
+  typedef ChunkStream<unsigned short, G> S2;
+  const S4 gf(HASG && G32 ? (float*)s.g + e0 : nullptr), pm(SPLIT ? nullptr : (float*)s.master + e0);
+  const S4 po(SPLIT ? nullptr : s.master_out + e0), sm(MOM ? s.m + e0 : nullptr);
+  const S4 sc(CARRY ? s.carry + e0 : nullptr);
+  const S2 gh(HASG && !G32 ? (unsigned short*)s.g + e0 : nullptr);
+  const S2 hi(SPLIT ? (unsigned short*)s.master + e0 : nullptr);
+  const S2 lo(SPLIT ? (unsigned short*)s.master_out + e0 : nullptr), pb(s.p_out + e0);
+  uint4 gq[G], pq[G], mq[G], cq[G];
+  uint2 gd[G], hd[G], ld[G];
+#pragma unroll
+  for (int u = 0; u < G; ++u) {
+    if constexpr (HASG) {
+      if constexpr (G32) gq[u] = nt_ld16(gf.at(u, o4));
+      else gd[u] = nt_ld8(gh.at(u, o2));
+    }
+    if constexpr (SPLIT) {
+      hd[u] = nt_ld8(hi.at(u, o2));
+      ld[u] = nt_ld8(lo.at(u, o2));
+    } else {
+      pq[u] = nt_ld16(pm.at(u, o4));
+    }
+    if constexpr (MOM) mq[u] = nt_ld16(sm.at(u, o4));
+    if constexpr (CARRY) cq[u] = nt_ld16(sc.at(u, o4));
+  }
+#pragma unroll
+  for (int u = 0; u < G; ++u) {
+    float gp[4] = {0.f, 0.f, 0.f, 0.f}, pp[4];
+    if constexpr (HASG && G32) {
+      unpack4(gq[u], gp);
+    } else if constexpr (HASG) {
+      gp[0] = __uint_as_float(gd[u].x << 16), gp[1] = __uint_as_float(gd[u].x & 0xffff0000u);
+      gp[2] = __uint_as_float(gd[u].y << 16), gp[3] = __uint_as_float(gd[u].y & 0xffff0000u);
+    }
+    if constexpr (SPLIT) {
+      pp[0] = join_master(hd[u].x & 0xFFFFu, ld[u].x), pp[1] = join_master(hd[u].x >> 16, ld[u].x >> 16);
+      pp[2] = join_master(hd[u].y & 0xFFFFu, ld[u].y), pp[3] = join_master(hd[u].y >> 16, ld[u].y >> 16);
+    } else {
+      unpack4(pq[u], pp);
+    }
+    float mp[4] = {0.f, 0.f, 0.f, 0.f}, cp[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (MOM) unpack4(mq[u], mp);
+    if constexpr (CARRY) unpack4(cq[u], cp);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sgd_elem<CARRY, CLIP, MOM>(gp[j], pp[j], mp[j], cp[j], hp, coef);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(o4), "+v"(o2));  // as above, for the block the stores are in
+#endif
+    if constexpr (SPLIT) {
+      uint32_t h[4], l[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        h[j] = f32_to_bf16(pp[j]);
+        l[j] = master_residual(pp[j], h[j]);
+      }
+      nt_st8(pb.at(u, o2), make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16)));
+      nt_st8(lo.at(u, o2), make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16)));
+    } else {
+      if (s.master_out) nt_st16(po.at(u, o4), pack4(pp));
+      if (s.p_out) {
+        uint2 r;
+        r.x = uint32_t(f32_to_bf16(pp[0])) | (uint32_t(f32_to_bf16(pp[1])) << 16);
+        r.y = uint32_t(f32_to_bf16(pp[2])) | (uint32_t(f32_to_bf16(pp[3])) << 16);
+        nt_st8(pb.at(u, o2), r);
+      }
+    }
+    if constexpr (MOM) nt_st16(sm.at(u, o4), pack4(mp));
+    if constexpr (CARRY) nt_st16(sc.at(u, o4), pack4(cp));
+  }
+}
+
+// The per-lane predicated body, as adam_pred_groups.
+template <typename GT, bool CARRY, bool SPLIT, int G, bool CLIP, bool MOM>
+__device__ __forceinline__ void sgd_pred_groups(const AdamSeg& s, int64_t e0, const SgdHP& hp,
+                                                float coef) {
+  float4 g4[G], p4[G], m4[G], c4[G];
+#pragma unroll
+  for (int u = 0; u < G; ++u) {
+    const int64_t i = e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
+    if (i < s.n) {
+      g4[u] = s.g ? load_g4<GT>(s.g, i) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (SPLIT) {
+        const uint2 h = nt_ld8(reinterpret_cast<const unsigned short*>(s.master) + i);
+        const uint2 l = nt_ld8(reinterpret_cast<const unsigned short*>(s.master_out) + i);
+        p4[u] = make_float4(join_master(h.x & 0xFFFFu, l.x), join_master(h.x >> 16, l.x >> 16),
+                            join_master(h.y & 0xFFFFu, l.y), join_master(h.y >> 16, l.y >> 16));
+      } else {
+        p4[u] = ld4(s.master, i);
+      }
+      if constexpr (MOM) m4[u] = ld4(s.m, i);
+      if constexpr (CARRY) c4[u] = ld4(s.carry, i);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < G; ++u) {
+    const int64_t i = e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
+    if (i < s.n) {
+      float* gp = reinterpret_cast<float*>(&g4[u]);
+      float* pp = reinterpret_cast<float*>(&p4[u]);
+      float* mp = reinterpret_cast<float*>(&m4[u]);
+      float* cp = reinterpret_cast<float*>(&c4[u]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float mv = MOM ? mp[j] : 0.0f;
+        float cv = CARRY ? cp[j] : 0.0f;
+        sgd_elem<CARRY, CLIP, MOM>(gp[j], pp[j], mv, cv, hp, coef);
+        if constexpr (MOM) mp[j] = mv;
+        if constexpr (CARRY) cp[j] = cv;
+      }
+      if constexpr (SPLIT) {
+        uint32_t h[4], l[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          h[j] = f32_to_bf16(pp[j]);
+          l[j] = master_residual(pp[j], h[j]);
+        }
+        nt_st8(s.p_out + i, make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16)));
+        nt_st8(reinterpret_cast<unsigned short*>(s.master_out) + i,
+               make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16)));
+      } else {
+        if (s.master_out) st4(s.master_out, i, p4[u]);
+        if (s.p_out) {
+          uint2 r;
+          r.x = uint32_t(f32_to_bf16(pp[0])) | (uint32_t(f32_to_bf16(pp[1])) << 16);
+          r.y = uint32_t(f32_to_bf16(pp[2])) | (uint32_t(f32_to_bf16(pp[3])) << 16);
+          nt_st8(s.p_out + i, r);
+        }
+      }
+      if constexpr (MOM) st4(s.m, i, m4[u]);
+      if constexpr (CARRY) st4(s.carry, i, c4[u]);
+    }
+  }
+}
+
+// Vector kernel, as adam_segments_kernel: LOADS_FIRST sends full chunks through sgd_full_chunk and
+// the partial one through the predicated body a group at a time; !LOADS_FIRST every chunk through
+// the predicated body.
+template <typename GT, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP, bool MOM>
+__global__ __launch_bounds__(kThreads) void sgd_segments_kernel(
+    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
+    int64_t total_chunks, SgdHP hp, const float* __restrict__ coef_ptr) {
+  static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
+  const float coef = clip_coef<CLIP>(coef_ptr);
+  int64_t seg = 0;
+  if constexpr (LOADS_FIRST) {
+    int64_t hi = nseg;
+    while (hi - seg > 1) {
+      const int64_t mid = (seg + hi) >> 1;
+      if (chunk_prefix[mid] <= int64_t(blockIdx.x)) seg = mid;
+      else hi = mid;
+    }
+  }
+  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
+    while (chunk_prefix[seg + 1] <= c) ++seg;
+    const AdamSeg s = segs[seg];
+    constexpr int G = adam_groups(SPLIT);
+    const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT);
+    if constexpr (LOADS_FIRST) {
+      if (e0 + adam_chunk(SPLIT) <= s.n) {  // uniform per workgroup
+        if (s.g) sgd_full_chunk<GT, CARRY, SPLIT, true, CLIP, MOM>(s, e0, hp, coef);
+        else sgd_full_chunk<GT, CARRY, SPLIT, false, CLIP, MOM>(s, e0, hp, coef);
+      } else {
+#pragma unroll 1
+        for (int u = 0; u < G && e0 + int64_t(u) * kThreads * 4 < s.n; ++u)
+          sgd_pred_groups<GT, CARRY, SPLIT, 1, CLIP, MOM>(s, e0 + int64_t(u) * kThreads * 4, hp,
+                                                          coef);
+      }
+    } else {
+      sgd_pred_groups<GT, CARRY, SPLIT, G, CLIP, MOM>(s, e0, hp, coef);
+    }
+  }
+}
+
+// ----------------------------------------------------------------------------------------------
 // gradient sum of squares over an Adam set (global-norm clipping, clip_grad_norm_'s norm)
 // ----------------------------------------------------------------------------------------------
 // One read-only pass over the gradients a set is bound to, driven by the set's own tables: the
@@ -1338,6 +1602,8 @@ struct zs_adamset {
   // zs_adamset_grad_sqnorm: partials (= workgroups) of the vector and of the scalar table
   int64_t sq_vec = 0, sq_sca = 0;
   int g_dtype = ZS_F32, p_dtype = ZS_BF16, has_carry = 0, has_vmax = 0;
+  // zs_sgdset_create: an SGD set (field m is the momentum buffer, has_mom: it has one)
+  int sgd = 0, has_mom = 0;
   // zs_adamset_set_grads: which input segment each table entry came from (the scalar entries with
   // their byte offset into that input's gradient), the gradient each input is bound to now, its
   // elements, whether it has a vector part (then its gradient must keep the vector alignment), and
@@ -1493,6 +1759,59 @@ static int launch_adam_tables(const AdamSeg* vec, const int64_t* vpre, int64_t n
   }
 #undef ZS_DISPATCH
 #undef ZS_DISPATCH_AC
+#undef ZS_LAUNCH
+  return ZS_OK;
+}
+
+// The SGD instance by grad dtype, split master, carry (never with CLIP) and momentum buffer; the
+// grid policy is the Adam's (adam_grid_cap, "adam_loads_first").
+template <bool CLIP>
+static int launch_sgd_tables(const zs_adamset* as, bool mom, const SgdHP& hp, const float* coef,
+                             hipStream_t st) {
+  const bool split = as->p_dtype == ZS_BF16_SPLIT, carry = as->has_carry != 0;
+  const int g_dtype = as->g_dtype;
+#define ZS_LAUNCH(KERNEL, GT, C, S, M, TAB, PRE, NS, NCH)                                     \
+  hipLaunchKernelGGL((KERNEL<GT, C, S LF, CLIP, M>), dim3(int(std::min<int64_t>(NCH, cap))),  \
+                     dim3(kThreads), 0, st, TAB, PRE, NS, NCH, hp, coef)
+#define ZS_DISPATCH_CM(KERNEL, GT, S, TAB, PRE, NS, NCH)                                      \
+  do {                                                                                        \
+    if constexpr (CLIP) {                                                                     \
+      if (mom) ZS_LAUNCH(KERNEL, GT, false, S, true, TAB, PRE, NS, NCH);                      \
+      else ZS_LAUNCH(KERNEL, GT, false, S, false, TAB, PRE, NS, NCH);                         \
+    } else {                                                                                  \
+      if (carry && mom) ZS_LAUNCH(KERNEL, GT, true, S, true, TAB, PRE, NS, NCH);              \
+      else if (carry) ZS_LAUNCH(KERNEL, GT, true, S, false, TAB, PRE, NS, NCH);               \
+      else if (mom) ZS_LAUNCH(KERNEL, GT, false, S, true, TAB, PRE, NS, NCH);                 \
+      else ZS_LAUNCH(KERNEL, GT, false, S, false, TAB, PRE, NS, NCH);                         \
+    }                                                                                         \
+  } while (0)
+#define ZS_DISPATCH(KERNEL, TAB, PRE, NS, NCH)                                                \
+  do {                                                                                        \
+    if (g_dtype == ZS_F32) ZS_DISPATCH_CM(KERNEL, float, false, TAB, PRE, NS, NCH);          \
+    else if (split) ZS_DISPATCH_CM(KERNEL, unsigned short, true, TAB, PRE, NS, NCH);         \
+    else ZS_DISPATCH_CM(KERNEL, unsigned short, false, TAB, PRE, NS, NCH);                   \
+  } while (0)
+  if (as->vec_chunks) {
+    const bool lf = adam_loads_first() != 0;
+    const int64_t cap =
+        adam_grid_cap(lf && split ? kAdamLoadsFirstWgPerCu : kAdamWgPerCu);
+#define LF , true
+    if (lf) ZS_DISPATCH(sgd_segments_kernel, as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks);
+#undef LF
+#define LF , false
+    else ZS_DISPATCH(sgd_segments_kernel, as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks);
+#undef LF
+    ZS_HIP(hipGetLastError());
+  }
+  if (as->sca_chunks) {
+    const int64_t cap = adam_grid_cap(kAdamWgPerCu);
+#define LF
+    ZS_DISPATCH(sgd_scalar_kernel, as->d_sca, as->d_sca_prefix, as->nsca, as->sca_chunks);
+#undef LF
+    ZS_HIP(hipGetLastError());
+  }
+#undef ZS_DISPATCH
+#undef ZS_DISPATCH_CM
 #undef ZS_LAUNCH
   return ZS_OK;
 }
@@ -1879,19 +2198,21 @@ int zs_adam_hparams_init(double lr, double beta1, double beta2, double eps, doub
   return ZS_OK;
 }
 
-int zs_adamset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype,
-                      zs_adamset** out) {
-  ZS_REQUIRE(out != nullptr, "zs_adamset_create: out is NULL");
+// zs_adamset_create (sgd = false) and zs_sgdset_create (sgd = true: field m is the momentum buffer,
+// on all segments or on none; v and vmax must be 0); `fn` names the entry point in messages.
+static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n, int g_dtype,
+                      int p_dtype, zs_adamset** out) {
+  ZS_REQUIRE(out != nullptr, "%s: out is NULL", fn);
   *out = nullptr;
-  ZS_REQUIRE(n >= 0 && (n == 0 || in), "zs_adamset_create: bad table");
-  ZS_REQUIRE(g_dtype == ZS_F32 || g_dtype == ZS_BF16, "zs_adamset_create: bad g_dtype %d", g_dtype);
+  ZS_REQUIRE(n >= 0 && (n == 0 || in), "%s: bad table", fn);
+  ZS_REQUIRE(g_dtype == ZS_F32 || g_dtype == ZS_BF16, "%s: bad g_dtype %d", fn, g_dtype);
   ZS_REQUIRE(p_dtype == ZS_BF16 || p_dtype == ZS_BF16_SPLIT,
-             "zs_adamset_create: p_dtype must be ZS_BF16 or ZS_BF16_SPLIT (got %d)", p_dtype);
+             "%s: p_dtype must be ZS_BF16 or ZS_BF16_SPLIT (got %d)", fn, p_dtype);
   const bool split = p_dtype == ZS_BF16_SPLIT;
-  ZS_REQUIRE(!split || g_dtype == ZS_BF16, "zs_adamset_create: ZS_BF16_SPLIT needs bf16 grads");
+  ZS_REQUIRE(!split || g_dtype == ZS_BF16, "%s: ZS_BF16_SPLIT needs bf16 grads", fn);
   const int64_t msz = split ? 2 : 4;  // bytes per element of master / master_out
   const int64_t gsz = g_dtype == ZS_F32 ? 4 : 2;
-  ZS_REQUIRE(n < (int64_t(1) << 31), "zs_adamset_create: %lld segments (max 2^31 - 1)",
+  ZS_REQUIRE(n < (int64_t(1) << 31), "%s: %lld segments (max 2^31 - 1)", fn,
              (long long)n);
   std::vector<AdamSeg> vec, sca;
   std::vector<int64_t> vpre(1, 0), spre(1, 0);
@@ -1900,26 +2221,35 @@ int zs_adamset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype
   std::vector<uint64_t> in_g(size_t(n), 0);
   std::vector<int64_t> in_n(size_t(n), 0);
   std::vector<unsigned char> in_vec(size_t(n), 0);
-  int carry_state = -1, vmax_state = -1;
+  int carry_state = -1, vmax_state = -1, mom_state = -1;
   int64_t elems = 0, bytes = 0, bytes_no_g = 0;
   for (int64_t i = 0; i < n; ++i) {
     const zs_adam_seg& s = in[i];
-    ZS_REQUIRE(s.n >= 0, "zs_adamset_create: seg %lld n < 0", (long long)i);
+    ZS_REQUIRE(s.n >= 0, "%s: seg %lld n < 0", fn, (long long)i);
     in_g[size_t(i)] = s.g;
     in_n[size_t(i)] = s.n;
     if (s.n == 0) continue;
-    ZS_REQUIRE(s.master && s.m && s.v, "zs_adamset_create: seg %lld missing master/m/v",
-               (long long)i);
+    if (sgd) {
+      ZS_REQUIRE(s.master, "%s: seg %lld missing master", fn, (long long)i);
+      ZS_REQUIRE(!s.v && !s.vmax, "%s: seg %lld: v and vmax must be 0 in an SGD set", fn,
+                 (long long)i);
+      const int b = s.m ? 1 : 0;
+      ZS_REQUIRE(mom_state < 0 || mom_state == b,
+                 "%s: m (the momentum buffer) must be set on all segments or none", fn);
+      mom_state = b;
+    } else {
+      ZS_REQUIRE(s.master && s.m && s.v, "%s: seg %lld missing master/m/v", fn, (long long)i);
+    }
     ZS_REQUIRE(!split || (s.master_out && s.p_out),
-               "zs_adamset_create: seg %lld: a split master needs master_out (residual) and p_out",
+               "%s: seg %lld: a split master needs master_out (residual) and p_out", fn,
                (long long)i);
     const int c = s.carry ? 1 : 0;
     ZS_REQUIRE(carry_state < 0 || carry_state == c,
-               "zs_adamset_create: carry must be set on all segments or none");
+               "%s: carry must be set on all segments or none", fn);
     carry_state = c;
     const int x = s.vmax ? 1 : 0;
     ZS_REQUIRE(vmax_state < 0 || vmax_state == x,
-               "zs_adamset_create: vmax must be set on all segments or none");
+               "%s: vmax must be set on all segments or none", fn);
     vmax_state = x;
     AdamSeg d;
     d.g = reinterpret_cast<const void*>(s.g);
@@ -1962,7 +2292,7 @@ int zs_adamset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype
       spre.push_back(spre.back() + (t.n + kThreads - 1) / kThreads);
     }
     elems += s.n;
-    int64_t b = msz /*master*/ + 8 /*m*/ + 8 /*v*/;
+    int64_t b = msz /*master*/ + (sgd ? (s.m ? 8 : 0) /*buffer*/ : 8 /*m*/ + 8 /*v*/);
     if (s.master_out) b += split ? 4 /*residual read + write*/ : 4;
     if (s.p_out) b += 2;
     if (s.vmax) b += 8;
@@ -1971,7 +2301,7 @@ int zs_adamset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype
     bytes += (b + (s.g ? gsz : 0)) * s.n;
   }
   zs_adamset* as = new (std::nothrow) zs_adamset();
-  if (!as) return zs::fail(ZS_ERR_NOMEM, "zs_adamset_create: out of memory");
+  if (!as) return zs::fail(ZS_ERR_NOMEM, "%s: out of memory", fn);
   as->nvec = int64_t(vec.size());
   as->vec_chunks = vpre.back();
   as->nsca = int64_t(sca.size());
@@ -1984,6 +2314,8 @@ int zs_adamset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype
   as->p_dtype = p_dtype;
   as->has_carry = carry_state > 0 ? 1 : 0;
   as->has_vmax = vmax_state > 0 ? 1 : 0;
+  as->sgd = sgd ? 1 : 0;
+  as->has_mom = mom_state > 0 ? 1 : 0;
   as->in_g = std::move(in_g);
   as->in_n = std::move(in_n);
   as->in_vec = std::move(in_vec);
@@ -2008,8 +2340,78 @@ int zs_adamset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype
   return ZS_OK;
 }
 
+int zs_adamset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype,
+                      zs_adamset** out) {
+  return set_create("zs_adamset_create", false, in, n, g_dtype, p_dtype, out);
+}
+
+int zs_sgdset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype,
+                     zs_adamset** out) {
+  return set_create("zs_sgdset_create", true, in, n, g_dtype, p_dtype, out);
+}
+
+int zs_sgd_hparams_init(double lr, double momentum, double dampening, double weight_decay,
+                        int nesterov, int maximize, int first, double grad_div, double carry_mul,
+                        zs_sgd_hparams* hp) {
+  ZS_REQUIRE(hp != nullptr, "zs_sgd_hparams_init: hp is NULL");
+  ZS_REQUIRE(grad_div > 0.0, "zs_sgd_hparams_init: grad_div must be > 0");
+  // sgd.py SGD.__init__'s rules
+  ZS_REQUIRE(lr >= 0.0, "zs_sgd_hparams_init: invalid learning rate %g", lr);
+  ZS_REQUIRE(momentum >= 0.0, "zs_sgd_hparams_init: invalid momentum %g", momentum);
+  ZS_REQUIRE(weight_decay >= 0.0, "zs_sgd_hparams_init: invalid weight_decay %g", weight_decay);
+  ZS_REQUIRE(!nesterov || (momentum > 0.0 && dampening == 0.0),
+             "zs_sgd_hparams_init: Nesterov momentum requires a momentum and zero dampening");
+  hp->neg_lr = float(-lr);
+  hp->momentum = float(momentum);
+  hp->one_minus_dampening = float(1.0 - dampening);
+  hp->weight_decay = float(weight_decay);
+  hp->grad_div = float(grad_div);
+  hp->carry_mul = float(carry_mul);
+  hp->nesterov = nesterov ? 1 : 0;
+  hp->maximize = maximize ? 1 : 0;
+  hp->first = first ? 1 : 0;
+  return ZS_OK;
+}
+
+int zs_sgdset_run(const zs_adamset* as, const zs_sgd_hparams* h, const float* coef,
+                  uintptr_t stream) {
+  ZS_REQUIRE(as && h, "zs_sgdset_run: NULL argument");
+  ZS_REQUIRE(as->sgd, "zs_sgdset_run: the set was made by zs_adamset_create (use zs_adamset_run)");
+  // a struct filled by hand gets zs_sgd_hparams_init's rules too (-0.0f is lr = 0)
+  ZS_REQUIRE(h->neg_lr <= 0.0f, "zs_sgdset_run: negative learning rate");
+  ZS_REQUIRE(h->momentum >= 0.0f, "zs_sgdset_run: invalid momentum %g", double(h->momentum));
+  ZS_REQUIRE(h->weight_decay >= 0.0f, "zs_sgdset_run: invalid weight_decay %g",
+             double(h->weight_decay));
+  ZS_REQUIRE(h->grad_div > 0.0f, "zs_sgdset_run: grad_div must be > 0");
+  ZS_REQUIRE(!h->nesterov || (h->momentum > 0.0f && h->one_minus_dampening == 1.0f),
+             "zs_sgdset_run: Nesterov momentum requires a momentum and zero dampening");
+  ZS_REQUIRE(h->momentum == 0.0f || as->has_mom || (as->nvec + as->nsca) == 0,
+             "zs_sgdset_run: momentum %g on a set without momentum buffers", double(h->momentum));
+  ZS_REQUIRE(!coef || !as->has_carry,
+             "zs_sgdset_run: a set with the ZeRO-1 carry cannot be clipped");
+  SgdHP hp;
+  hp.neg_lr = h->neg_lr;
+  hp.momentum = h->momentum;
+  hp.omd = h->one_minus_dampening;
+  hp.wd = h->weight_decay;
+  hp.grad_div = h->grad_div;
+  hp.carry_mul = h->carry_mul;
+  int exp2 = 0;
+  hp.div_pow2 = std::frexp(double(h->grad_div), &exp2) == 0.5 ? 1 : 0;
+  hp.inv_div = float(1.0 / double(h->grad_div));
+  hp.nesterov = h->nesterov ? 1 : 0;
+  hp.maximize = h->maximize ? 1 : 0;
+  hp.first = h->first ? 1 : 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // torch with momentum == 0 never makes a buffer: a set that has one leaves it alone then
+  const bool mom = as->has_mom != 0 && h->momentum != 0.0f;
+  if (coef) return launch_sgd_tables<true>(as, mom, hp, coef, st);
+  return launch_sgd_tables<false>(as, mom, hp, nullptr, st);
+}
+
 int zs_adamset_run(const zs_adamset* as, const zs_adam_hparams* h, uintptr_t stream) {
   ZS_REQUIRE(as && h, "zs_adamset_run: NULL argument");
+  ZS_REQUIRE(!as->sgd, "zs_adamset_run: the set was made by zs_sgdset_create (use zs_sgdset_run)");
   const bool ams = h->amsgrad != 0;
   ZS_REQUIRE(!ams || as->has_vmax || (as->nvec + as->nsca) == 0,
              "zs_adamset_run: amsgrad needs vmax segments");
@@ -2022,6 +2424,8 @@ int zs_adamset_run(const zs_adamset* as, const zs_adam_hparams* h, uintptr_t str
 int zs_adamset_run_clipped(const zs_adamset* as, const zs_adam_hparams* h, const float* coef,
                            uintptr_t stream) {
   ZS_REQUIRE(as && h && coef, "zs_adamset_run_clipped: NULL argument");
+  ZS_REQUIRE(!as->sgd,
+             "zs_adamset_run_clipped: the set was made by zs_sgdset_create (use zs_sgdset_run)");
   ZS_REQUIRE(!as->has_carry,
              "zs_adamset_run_clipped: a set with the ZeRO-1 carry cannot be clipped");
   const bool ams = h->amsgrad != 0;

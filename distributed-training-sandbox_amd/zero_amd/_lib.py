@@ -38,6 +38,7 @@ EXPORTED = (
     "zs_adamset_stats", "zs_adam_step", "zs_adam_step_ex",
     "zs_adamset_sqnorm_partials", "zs_adamset_grad_sqnorm", "zs_sqnorm_reduce", "zs_clip_coef",
     "zs_adamset_run_clipped",
+    "zs_sgd_hparams_init", "zs_sgdset_create", "zs_sgdset_run",
     "zs_comm_unique_id", "zs_comm_init", "zs_comm_destroy", "zs_reduce_scatter", "zs_all_gather",
     "zs_all_reduce", "zs_reduce", "zs_broadcast", "zs_reduce_group", "zs_broadcast_group", "zs_all_gather_group", "zs_reduce_scatter_group",
     "zs_all_gather_group_ordered", "zs_reduce_scatter_group_ordered", "zs_stream_wait_event",
@@ -70,6 +71,14 @@ class AdamHParams(ctypes.Structure):
                 ("weight_decay", ctypes.c_float), ("decay_mul", ctypes.c_float),
                 ("grad_div", ctypes.c_float), ("carry_mul", ctypes.c_float),
                 ("amsgrad", ctypes.c_int32), ("maximize", ctypes.c_int32)]
+
+
+class SgdHParams(ctypes.Structure):
+    _fields_ = [("neg_lr", ctypes.c_float), ("momentum", ctypes.c_float),
+                ("one_minus_dampening", ctypes.c_float), ("weight_decay", ctypes.c_float),
+                ("grad_div", ctypes.c_float), ("carry_mul", ctypes.c_float),
+                ("nesterov", ctypes.c_int32), ("maximize", ctypes.c_int32),
+                ("first", ctypes.c_int32)]
 
 
 _P = ctypes.c_void_p
@@ -127,6 +136,12 @@ _SIGS = {
     "zs_sqnorm_reduce": ([_P, _I64, _P, _U], ctypes.c_int),
     "zs_clip_coef": ([_P, ctypes.c_double, ctypes.c_double, _P, _U], ctypes.c_int),
     "zs_adamset_run_clipped": ([_P, ctypes.POINTER(AdamHParams), _P, _U], ctypes.c_int),
+    "zs_sgd_hparams_init": ([ctypes.c_double] * 4 + [ctypes.c_int] * 3 +
+                            [ctypes.c_double, ctypes.c_double, ctypes.POINTER(SgdHParams)],
+                            ctypes.c_int),
+    "zs_sgdset_create": ([ctypes.POINTER(AdamSeg), _I64, ctypes.c_int, ctypes.c_int,
+                          ctypes.POINTER(_P)], ctypes.c_int),
+    "zs_sgdset_run": ([_P, ctypes.POINTER(SgdHParams), _P, _U], ctypes.c_int),
     "zs_adam_step": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_float] * 5 +
                      [ctypes.c_int, _I64, ctypes.c_float, _P, ctypes.c_float, _U], ctypes.c_int),
     "zs_adam_step_ex": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_double] * 5 +

@@ -5,7 +5,8 @@ The public surface is the reference's: ``ShardedOptimizer(opt
 ``params``, ``local_param_indices``, ``local_params``, ``step_time``, ``communication_time``,
 ``broadcast_count``; the inner optimizer's ``param_groups`` are filtered to the owned parameters
 (zero1.py:71-74) and ``optimizer.state[p]`` holds ``step`` / ``exp_avg`` / ``exp_avg_sq`` for
-every owned parameter (read by memory.py:15-24).  Everything below ``step()`` is the native
+every owned parameter (read by memory.py:15-24); with a ``torch.optim.SGD`` it holds
+``momentum_buffer`` once the parameter has stepped, as torch's does.  Everything below ``step()`` is the native
 engine (engine.py → libzero_amd.so); the inner torch optimizer's own ``step`` is never called.
 """
 from __future__ import annotations
@@ -33,6 +34,31 @@ def adam_group_hparams(group: dict, optimizer: Optimizer) -> dict:
     return dict(lr=lr, beta1=float(beta1), beta2=float(beta2), eps=float(group["eps"]),
                 weight_decay=float(group["weight_decay"]), amsgrad=bool(group.get("amsgrad", False)),
                 maximize=bool(group.get("maximize", False)), decoupled=decoupled)
+
+
+def sgd_group_hparams(group: dict) -> dict:
+    """Hyper-parameters of one torch.optim.SGD param group (sgd.py SGD.__init__); ``foreach`` and
+    ``fused`` only pick torch's implementation and are ignored, ``differentiable`` is refused."""
+    if group.get("differentiable", False):
+        raise ValueError("zero_amd: torch.optim.SGD(differentiable=True) is not supported (the "
+                         "update runs in a HIP kernel outside autograd)")
+    lr = group["lr"]
+    lr = float(lr.item()) if torch.is_tensor(lr) else float(lr)
+    return dict(lr=lr, momentum=float(group.get("momentum", 0.0)),
+                dampening=float(group.get("dampening", 0.0)),
+                weight_decay=float(group.get("weight_decay", 0.0)),
+                nesterov=bool(group.get("nesterov", False)),
+                maximize=bool(group.get("maximize", False)), amsgrad=False)
+
+
+def optimizer_kind(optimizer: Optimizer) -> str:
+    """"adam" (torch.optim.Adam / AdamW) or "sgd" (torch.optim.SGD); TypeError for anything else."""
+    if isinstance(optimizer, torch.optim.Adam):
+        return "adam"
+    if isinstance(optimizer, torch.optim.SGD):
+        return "sgd"
+    raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD "
+                    f"(got {type(optimizer).__name__})")
 
 
 class ShardedOptimizerBase:
@@ -65,9 +91,18 @@ class ShardedOptimizerBase:
         elif layout != "reference" and (layout != "flat" or self._carry):
             self._clip_unsupported = f"layout={layout!r} (it runs on the bucket arena)"
         self._check_clip()
-        if not isinstance(optimizer, torch.optim.Adam):
-            raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW "
-                            f"(got {type(optimizer).__name__})")
+        self._kind = optimizer_kind(optimizer)
+        if self._kind == "sgd":
+            for group in optimizer.param_groups:
+                sgd_group_hparams(group)
+            # the SGD update runs on the flat arena (and its rounds) only
+            if arena == "buckets":
+                raise ValueError("zero_amd: torch.optim.SGD is not supported with arena='buckets' "
+                                 "(the bucket arena); use the flat arena")
+            if layout != "reference" and (layout != "flat" or self._carry):
+                raise ValueError(f"zero_amd: torch.optim.SGD is not supported with layout={layout!r} "
+                                 "(it runs on the bucket arena, arena='buckets')")
+            arena = "flat"  # arena='auto' would time the bucket arena as a candidate
         self.optimizer = optimizer
         self.original_param_groups = optimizer.param_groups
         self.params = [p for group in self.original_param_groups for p in group["params"]]
@@ -201,7 +236,9 @@ class ShardedOptimizerBase:
             self.engine = FlatEngine(self.params, self._group_of, self.world_size, self.rank,
                                      carry=carry, comm=comm, bucket_bytes=self._bucket_bytes,
                                      master=self._master, grad_comm=self._grad_comm,
-                                     layout=self._layout)
+                                     layout=self._layout, kind=self._kind,
+                                     momentum=self._kind == "sgd" and any(
+                                         g.get("momentum", 0) != 0 for g in self._groups))
         else:
             self.engine = ShardEngine(self.params, self._group_of, self.world_size, self.rank,
                                       layout=self._layout, carry=carry, comm=comm,
@@ -214,6 +251,9 @@ class ShardedOptimizerBase:
     def _expose_state(self):
         """optimizer.state[p] = {'step', 'exp_avg', 'exp_avg_sq'} as views of the flat shard."""
         eng = self.engine
+        if self._kind == "sgd":
+            self._update_step_state()
+            return
         for i in eng.owned_param_indices():
             p = self.params[i]
             views = eng.state_views(i)
@@ -226,10 +266,24 @@ class ShardedOptimizerBase:
                 st["max_exp_avg_sq"] = eng.vmax[so:so + p.numel()].view(p.shape)
 
     def _hparams_of(self, gi: int) -> dict:
+        if self._kind == "sgd":
+            return sgd_group_hparams(self._groups[gi])
         return adam_group_hparams(self._groups[gi], self.optimizer)
 
     def _update_step_state(self):
         eng = self.engine
+        if self._kind == "sgd":
+            # torch's SGD state: {} until the parameter's first step, then the buffer alone (its
+            # presence is torch's "not the first step"); nothing at all without momentum
+            for i in eng.owned_param_indices():
+                if eng.steps[i] == 0:
+                    continue
+                st = self.optimizer.state[self.params[i]]
+                if "momentum_buffer" not in st:
+                    buf = (eng.state_views(i) or {}).get("momentum_buffer")
+                    if buf is not None and self._groups[eng.group_of[i]].get("momentum", 0) != 0:
+                        st["momentum_buffer"] = buf
+            return
         for i in eng.owned_param_indices():
             s = int(eng.steps[i])
             if s == 0:
@@ -354,7 +408,11 @@ class ShardedOptimizerBase:
                 if id(p) not in index:
                     continue
                 entry = {k: v.detach().clone() for k, v in self._ckpt_views(i).items()}
-                entry["step"] = torch.tensor(float(self.engine.steps[i]), dtype=torch.float32)
+                if self._kind == "sgd":  # torch's SGD entry: the buffer once it exists, no step
+                    if self.engine.steps[i] == 0 or "momentum_buffer" not in self.optimizer.state[p]:
+                        entry.pop("momentum_buffer", None)
+                else:
+                    entry["step"] = torch.tensor(float(self.engine.steps[i]), dtype=torch.float32)
                 state[index[id(p)]] = entry
         sd["state"] = state
         sd["zero_amd"] = self._ckpt_header()
@@ -395,7 +453,10 @@ class ShardedOptimizerBase:
                         view.copy_(p.detach().reshape(view.shape))
                     else:  # no state: torch's fresh Adam (moments 0), no carry
                         view.zero_()
-                eng.steps[i] = ckpt.step_of(entry)
+                if self._kind == "sgd":  # no buffer saved: the parameter's next step is its first
+                    eng.steps[i] = int(entry.get("momentum_buffer") is not None)
+                else:
+                    eng.steps[i] = ckpt.step_of(entry)
         self.optimizer.state.clear()
         self._expose_state()
         self._update_step_state()

@@ -37,7 +37,7 @@ import torch
 
 from . import _lib
 from .comm import StreamEvent, comm_stream, zs_dtype
-from .kernels import AdamSet, CopySet, adam_hparams
+from .kernels import AdamSet, CopySet, SgdSet, adam_hparams, sgd_hparams
 from .plan import Plan
 
 ALIGN_ELEMS = 64  # every stream piece starts 256 B (f32) / 128 B (bf16) aligned
@@ -294,7 +294,13 @@ def probed_zeros(n: int, dtype, device, tries: int = 8, accept_gbs: float = PROB
 class ShardEngine:
     def __init__(self, params, group_of, ws: int, rank: int, *, layout="reference", carry=False,
                  comm=None, bucket_bytes: int = 256 << 20, align: int = ALIGN_ELEMS,
-                 buckets: str = "ragged", placement_tries: int = 8, master: str = "split"):
+                 buckets: str = "ragged", placement_tries: int = 8, master: str = "split",
+                 kind: str = "adam", momentum: bool = True):
+        if kind not in ("adam", "sgd"):
+            raise ValueError(f"ShardEngine: kind must be 'adam' or 'sgd' (got {kind!r})")
+        # the update: torch.optim.Adam's, or torch.optim.SGD's (`momentum`: some group has a
+        # momentum, so the shard holds a momentum buffer; none of them: no optimizer state at all)
+        self.kind = kind
         if not params:
             raise ValueError("ShardEngine: no parameters")
         dev = params[0].device
@@ -337,11 +343,14 @@ class ShardEngine:
         # exp_avg, exp_avg_sq (+ ZeRO-1 carry, + fp32 master or its int16 residual): one
         # allocation, placed by probe
         L = self.L
-        nf = 2 + int(bool(carry)) + int(self.mixed and not self.split)
+        nmom = 2 if kind == "adam" else int(bool(momentum))  # exp_avg + exp_avg_sq / the buffer
+        nf = nmom + int(bool(carry)) + int(self.mixed and not self.split)
         nlo = (L + 1) // 2 if self.split else 0  # int16 residuals, in fp32 words
         self.state, self.placement = probed_zeros(nf * L + nlo, torch.float32, dev, placement_tries)
         views = iter([self.state[k * L:(k + 1) * L] for k in range(nf)])
-        self.m, self.v = next(views), next(views)
+        # SGD: m is the momentum buffer (None without momentum), there is no v
+        self.m = next(views) if nmom else None
+        self.v = next(views) if nmom == 2 else None
         self.vmax = None
         self.carry = next(views) if carry else None
         self.master = next(views) if self.mixed and not self.split else None
@@ -396,7 +405,11 @@ class ShardEngine:
         po = int(self.pieces.param_off[j])
         p = self.params[i]
         shape = p.shape if (po == 0 and n == p.numel()) else (n,)
-        views = {"exp_avg": self.m[so:so + n].view(shape), "exp_avg_sq": self.v[so:so + n].view(shape)}
+        if self.kind == "sgd":  # torch's SGD state: the buffer alone (absent without momentum)
+            views = {} if self.m is None else {"momentum_buffer": self.m[so:so + n].view(shape)}
+        else:
+            views = {"exp_avg": self.m[so:so + n].view(shape),
+                     "exp_avg_sq": self.v[so:so + n].view(shape)}
         if self.master is not None:
             views["master_param"] = self.master[so:so + n].view(shape)
         if self.lo is not None:  # the fp32 master = the bf16 param's bits << 16 + this residual
@@ -439,8 +452,10 @@ class ShardEngine:
         rows[:, 1] = mst
         rows[:, 2] = mst_out
         rows[:, 3] = p_out
-        rows[:, 4] = np.uint64(self.m.data_ptr()) + so * np.uint64(4)
-        rows[:, 5] = np.uint64(self.v.data_ptr()) + so * np.uint64(4)
+        if self.m is not None:
+            rows[:, 4] = np.uint64(self.m.data_ptr()) + so * np.uint64(4)
+        if self.v is not None:
+            rows[:, 5] = np.uint64(self.v.data_ptr()) + so * np.uint64(4)
         if self.vmax is not None:
             rows[:, 6] = np.uint64(self.vmax.data_ptr()) + so * np.uint64(4)
         if self.carry is not None:
@@ -458,9 +473,37 @@ class ShardEngine:
         mst = np.uint64(self.master.data_ptr()) + so64 * np.uint64(4)
         return self._adam_rows(idx, g, mst, mst, p_out, so, n)
 
+    def new_set(self, rows):
+        """The update's kernel set over ``rows``: AdamSet, or SgdSet for an SGD engine."""
+        gz = getattr(self, "czdtype", self.zdtype)  # dtype of the reduced grad the update reads
+        return (SgdSet if self.kind == "sgd" else AdamSet)(rows, gz, self.p_dtype)
+
+    def hp_key(self, steps):
+        """What of a parameter's step count the hyper-parameter struct depends on: the count
+        itself (Adam's bias correction), or only whether this is its first step (SGD's buffer)."""
+        steps = np.asarray(steps, np.int64)
+        return (steps == 1).astype(np.int64) if self.kind == "sgd" else steps
+
+    def make_hp(self, hpd: dict, key: int, cmul: int):
+        """The kernel's hyper-parameter struct of one (group, hp_key, carry multiplier) part."""
+        carry_mul = float(cmul) if self.carry is not None else 0.0
+        if self.kind == "sgd":
+            if hpd["momentum"] != 0 and self.m is None:
+                raise ValueError("zero_amd: a param group's momentum became non-zero after the "
+                                 "optimizer was built without momentum buffers")
+            return sgd_hparams(hpd["lr"], hpd["momentum"], hpd["dampening"], hpd["weight_decay"],
+                               nesterov=hpd["nesterov"], maximize=hpd["maximize"], first=bool(key),
+                               grad_div=float(self.ws), carry_mul=carry_mul)
+        if hpd["amsgrad"] and self.vmax is None:
+            raise RuntimeError("amsgrad state buffer missing")
+        return adam_hparams(hpd["lr"], hpd["beta1"], hpd["beta2"], hpd["eps"], hpd["weight_decay"],
+                            key, decoupled=hpd["decoupled"], amsgrad=hpd["amsgrad"],
+                            maximize=hpd["maximize"], grad_div=float(self.ws), carry_mul=carry_mul)
+
     def _run_adam(self, tag, rows, param_idx, hparams_of, stream, carry_mul=None, gptr=None,
                   defer=None):
-        """Partition rows by (group, step, carry multiplier) — torch's bias correction is per param,
+        """Partition rows by (group, step, carry multiplier) — torch's bias correction is per param
+        (SGD: by "first step?", the momentum buffer's birth is per param),
         and the ZeRO-1 carry weight depends on which grads survived since the last step — and
         launch one fused-Adam set per part.  ``gptr`` (per row): gradient addresses bound into the
         sets before they run (AdamSet.set_grads; the rows then carry g = 0).  ``defer`` (a list;
@@ -470,25 +513,17 @@ class ShardEngine:
             return
         if carry_mul is None:
             carry_mul = np.full(len(param_idx), self.ws - 1 if self.carry is not None else 0, np.int64)
-        keys = np.stack([np.asarray(self.group_of)[param_idx], self.steps[param_idx],
+        keys = np.stack([np.asarray(self.group_of)[param_idx], self.hp_key(self.steps[param_idx]),
                          np.asarray(carry_mul, np.int64)], axis=1)
         for key in np.unique(keys, axis=0):
             sel = np.nonzero((keys == key).all(axis=1))[0]
             sub = np.ascontiguousarray(rows[sel])
             gidx, step, cmul = int(key[0]), int(key[1]), int(key[2])
-            gz = getattr(self, "czdtype", self.zdtype)  # dtype of the reduced grad Adam reads
             aset = self._cached(("adam", tag, gidx, len(sel), int(sel[0])), sub.tobytes(),
-                                lambda: AdamSet(sub, gz, self.p_dtype))
+                                lambda: self.new_set(sub))
             if gptr is not None and defer is None:
                 aset.set_grads(np.asarray(gptr, np.uint64)[sel], stream)
-            hpd = hparams_of(gidx)
-            if hpd["amsgrad"] and self.vmax is None:
-                raise RuntimeError("amsgrad state buffer missing")
-            hp = adam_hparams(hpd["lr"], hpd["beta1"], hpd["beta2"], hpd["eps"],
-                              hpd["weight_decay"], step, decoupled=hpd["decoupled"],
-                              amsgrad=hpd["amsgrad"], maximize=hpd["maximize"],
-                              grad_div=float(self.ws),
-                              carry_mul=float(cmul) if self.carry is not None else 0.0)
+            hp = self.make_hp(hparams_of(gidx), step, cmul)
             if defer is not None:
                 defer.append((aset, hp, None if gptr is None else np.asarray(gptr, np.uint64)[sel]))
                 continue

@@ -81,7 +81,8 @@ class FlatEngine(ShardEngine):
 
     def __init__(self, params, group_of, ws: int, rank: int, *, carry=False, comm=None,
                  bucket_bytes: int = 256 << 20, master: str = "split", placement_tries: int = 8,
-                 grad_comm: str | None = None, layout: str = "reference"):
+                 grad_comm: str | None = None, layout: str = "reference", kind: str = "adam",
+                 momentum: bool = True):
         if layout not in ("reference", "flat"):
             raise ValueError(f"the flat arena takes layout 'reference' or 'flat' (got {layout!r})")
         if layout == "flat" and carry:
@@ -91,7 +92,7 @@ class FlatEngine(ShardEngine):
         # machinery; its bucket plan (one bucket) is unused
         super().__init__(params, group_of, ws, rank, layout=layout, carry=carry, comm=comm,
                          bucket_bytes=1 << 62, buckets="ragged", placement_tries=placement_tries,
-                         master=master)
+                         master=master, kind=kind, momentum=momentum)
         self.arena_kind = "flat"
         self.layout = layout
         plan, es, dev, dt = self.plan, self.es, self.device, self.dtype
@@ -295,14 +296,11 @@ class FlatEngine(ShardEngine):
         common case: built once, the rows never change because every pointer is the arena's)."""
         sets = getattr(rd, "sets", None)
         if sets is None:
-            from .kernels import AdamSet
-
             groups = np.asarray(self.group_of)[rd.idx]
             sets = []
             for gi in np.unique(groups):
                 sel = np.nonzero(groups == gi)[0]
-                sets.append((int(gi), rd.idx[sel], AdamSet(np.ascontiguousarray(rd.rows[sel]),
-                                                           self.czdtype, self.p_dtype)))
+                sets.append((int(gi), rd.idx[sel], self.new_set(np.ascontiguousarray(rd.rows[sel]))))
             rd.sets = sets
         return sets
 
@@ -746,22 +744,16 @@ class FlatEngine(ShardEngine):
         own = self.owned
         hps = {}
         if has[own].all():
-            from .kernels import adam_hparams
-
             gof = np.asarray(self.group_of)
             for gi in np.unique(gof[own]):
                 sel = own & (gof == gi)
-                st, cm = np.unique(self.steps[sel]), np.unique(cmul[sel])
+                st, cm = np.unique(self.hp_key(self.steps[sel])), np.unique(cmul[sel])
                 if len(st) != 1 or len(cm) != 1:
                     continue
                 h = hparams_of(int(gi))
                 if h["amsgrad"] and self.vmax is None:
                     continue
-                hps[int(gi)] = adam_hparams(
-                    h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"], int(st[0]),
-                    decoupled=h["decoupled"], amsgrad=h["amsgrad"], maximize=h["maximize"],
-                    grad_div=float(self.ws),
-                    carry_mul=float(cm[0]) if self.carry is not None else 0.0)
+                hps[int(gi)] = self.make_hp(h, int(st[0]), int(cm[0]))
         if self.overlap and not self.inplace:
             self._step_overlap(grads, has, view, cmul, hps, hparams_of, stream)
             return

@@ -4,6 +4,7 @@
 ``copy_direct`` — the same copy with the segments in the kernel arguments (no table to keep).
 ``AdamSet``  — one launch of the fused Adam/AdamW update over a list of segments; its
 ``grad_sqnorm`` / ``run_clipped`` with ``sqnorm_reduce`` and ``clip_coef`` are global-norm clipping.
+``SgdSet``   — the same tables with torch.optim.SGD's update (momentum, Nesterov); ``sgd_hparams``.
 ``adam_step`` — the same update over one contiguous range (zs_adam_step_ex; no table to keep).
 
 Both upload their segment table once; ``run(stream)`` only enqueues a kernel on ``stream``.
@@ -17,7 +18,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import AdamHParams, AdamSeg
+from ._lib import AdamHParams, AdamSeg, SgdHParams
 
 _PU64 = ctypes.POINTER(ctypes.c_uint64)
 _PI64 = ctypes.POINTER(ctypes.c_int64)
@@ -133,12 +134,14 @@ class AdamSet:
 
     FIELDS = ("g", "master", "master_out", "p_out", "m", "v", "vmax", "carry", "n")
 
+    _CREATE = "zs_adamset_create"
+
     def __init__(self, segs: np.ndarray, g_dtype: int, p_dtype: int = _lib.ZS_BF16):
         segs = np.ascontiguousarray(np.asarray(segs, dtype=np.uint64).reshape(-1, 9))
         arr = (AdamSeg * max(len(segs), 1))()
         ctypes.memmove(arr, segs.ctypes.data, segs.nbytes)
         h = ctypes.c_void_p()
-        _lib.call("zs_adamset_create", arr, len(segs), int(g_dtype), int(p_dtype), ctypes.byref(h))
+        _lib.call(self._CREATE, arr, len(segs), int(g_dtype), int(p_dtype), ctypes.byref(h))
         self._h = h
         self.nseg = len(segs)
         self._g = np.ascontiguousarray(segs[:, 0])  # the gradients bound now, per input row
@@ -202,6 +205,32 @@ class AdamSet:
             except Exception:  # interpreter teardown
                 pass
             self._h = None
+
+
+def sgd_hparams(lr, momentum=0.0, dampening=0.0, weight_decay=0.0, *, nesterov=False,
+                maximize=False, first=False, grad_div=1.0, carry_mul=0.0) -> SgdHParams:
+    hp = SgdHParams()
+    _lib.call("zs_sgd_hparams_init", float(lr), float(momentum), float(dampening),
+              float(weight_decay), int(bool(nesterov)), int(bool(maximize)), int(bool(first)),
+              float(grad_div), float(carry_mul), ctypes.byref(hp))
+    return hp
+
+
+class SgdSet(AdamSet):
+    """Fused SGD over segments in zs_adam_seg order (zs_sgdset_create): column ``m`` is the
+    momentum buffer, on every row or none; ``v`` and ``vmax`` are 0.  ``set_grads``, ``grad_sqnorm``,
+    ``sqnorm_partials``, ``bytes`` and ``grad_bytes`` as ``AdamSet``."""
+
+    _CREATE = "zs_sgdset_create"
+
+    def run(self, hp: SgdHParams, stream, coef=None) -> None:
+        """One step; ``coef``: None, or the fp32 device scalar (a tensor or its address) every
+        averaged gradient is multiplied by (zs_sgdset_run)."""
+        ptr = None if coef is None else coef if isinstance(coef, int) else coef.data_ptr()
+        _lib.call("zs_sgdset_run", self._h, ctypes.byref(hp), ptr, stream_handle(stream))
+
+    def run_clipped(self, hp, coef, stream) -> None:
+        self.run(hp, stream, coef=coef)
 
 
 def sqnorm_reduce(partials, n: int, sumsq, stream) -> None:

@@ -52,10 +52,10 @@ from . import _lib
 from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
-from ._sharded import adam_group_hparams
+from ._sharded import adam_group_hparams, optimizer_kind, sgd_group_hparams
 from .comm import STREAM_SYNC, RcclComm, Sync, comm_stream, sync_kind, zs_dtype
 from .engine import ALIGN_ELEMS, probed_zeros
-from .kernels import AdamSet, adam_hparams, stream_handle
+from .kernels import AdamSet, SgdSet, adam_hparams, sgd_hparams, stream_handle
 from .training_utils.utils import get
 
 try:  # the hooks' per-module install / release in C++ (csrc/zs_host_ext.cpp, built with the library)
@@ -1679,8 +1679,11 @@ class ShardedOptimizer:
                  gather_dtype=None, bucket_mb: float = RS_BUCKET_MB, grad_comm: str | None = None,
                  gather_wave: int = GATHER_WAVE, side_stream: bool = True,
                  stream_sync: str = STREAM_SYNC):
-        if not isinstance(optimizer, torch.optim.Adam):
-            raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW")
+        # "adam" or "sgd" (TypeError for anything else); reference mode never updates either
+        self._kind = optimizer_kind(optimizer)
+        if self._kind == "sgd":
+            for group in optimizer.param_groups:
+                sgd_group_hparams(group)
         self.optimizer = optimizer
         self.original_param_groups = optimizer.param_groups
         self.params = [p for group in self.original_param_groups for p in group["params"]]
@@ -1759,10 +1762,13 @@ class ShardedOptimizer:
         # exp_avg, exp_avg_sq (+ for bf16 params the split master's int16 residual: the fp32
         # master is the bf16 chunk + residual, include/zero_amd.h ZS_BF16_SPLIT; starts at 0)
         nlo = (L + 1) // 2 if split else 0
-        state, self.placement = probed_zeros(2 * L + nlo, torch.float32, ar.device)
+        # SGD: one momentum buffer if any group has a momentum, no state array otherwise
+        nm = 2 if self._kind == "adam" else int(any(g.get("momentum", 0) != 0 for g in self._groups))
+        state, self.placement = probed_zeros(nm * L + nlo, torch.float32, ar.device)
         self._state = state
-        self._m, self._v = state[:L], state[L:2 * L]
-        self._lo = state[2 * L:].view(torch.int16)[:L] if split else None
+        self._m = state[:L] if nm else None
+        self._v = state[L:2 * L] if nm == 2 else None
+        self._lo = state[nm * L:].view(torch.int16)[:L] if split else None
         self._vmax = None
         self._split = split
         gdt = torch.bfloat16 if self._grad_comm else ar.dtype
@@ -1778,7 +1784,10 @@ class ShardedOptimizer:
         """name -> live view of param i's chunk of the flat update state."""
         ar = self._arena
         s, n, shp = int(ar.slot[i]), int(ar.ln[i]), ar.shard_shapes[i]
-        views = {"exp_avg": self._m[s:s + n].view(shp), "exp_avg_sq": self._v[s:s + n].view(shp)}
+        if self._kind == "sgd":
+            views = {} if self._m is None else {"momentum_buffer": self._m[s:s + n].view(shp)}
+        else:
+            views = {"exp_avg": self._m[s:s + n].view(shp), "exp_avg_sq": self._v[s:s + n].view(shp)}
         if self._lo is not None:  # fp32 master = the bf16 chunk's bits << 16 + this residual
             views["master_residual"] = self._lo[s:s + n].view(shp)
         if self._vmax is not None:
@@ -1788,6 +1797,9 @@ class ShardedOptimizer:
     def _expose_state(self):
         """optimizer.state[p]: views of the flat state (chunk-shaped) and torch's ``step``."""
         self._step_shared_sig = None  # per-param step tensors again: the next step re-shares
+        if self._kind == "sgd":
+            self._expose_sgd(range(len(self.params)))
+            return
         step_t = {}
         for i, p in enumerate(self.params):
             st = self.optimizer.state[p]
@@ -1798,6 +1810,34 @@ class ShardedOptimizer:
                 if t is None:
                     t = step_t[s] = torch.tensor(float(s))
                 st["step"] = t
+
+    def _expose_sgd(self, idx):
+        """torch's SGD state: {} until a parameter's first step, then its momentum buffer alone
+        (nothing without momentum)."""
+        for i in idx:
+            i = int(i)
+            if self._steps[i] == 0 or self._m is None:
+                continue
+            st = self.optimizer.state[self.params[i]]
+            if "momentum_buffer" not in st and self._groups[self._group_of[i]].get("momentum", 0) != 0:
+                st["momentum_buffer"] = self._state_views(i)["momentum_buffer"]
+
+    def _hp_key(self, steps):
+        """Adam: the step count (bias correction); SGD: whether this is the first step."""
+        steps = np.asarray(steps, np.int64)
+        return (steps == 1).astype(np.int64) if self._kind == "sgd" else steps
+
+    def _make_hp(self, h: dict, key: int):
+        if self._kind == "sgd":
+            if h["momentum"] != 0 and self._m is None:
+                raise ValueError("zero_amd: a param group's momentum became non-zero after the "
+                                 "optimizer was built without momentum buffers")
+            return sgd_hparams(h["lr"], h["momentum"], h["dampening"], h["weight_decay"],
+                               nesterov=h["nesterov"], maximize=h["maximize"], first=bool(key),
+                               grad_div=float(self.world_size))
+        return adam_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"], int(key),
+                            decoupled=h["decoupled"], amsgrad=h["amsgrad"], maximize=h["maximize"],
+                            grad_div=float(self.world_size))
 
     def _ensure_vmax(self):
         ar = self._arena
@@ -1866,8 +1906,10 @@ class ShardedOptimizer:
             rows[:, 2] = np.uint64(self._lo.data_ptr()) + so * np.uint64(2)
         else:
             rows[:, 1], rows[:, 2] = pp, pp
-        rows[:, 4] = np.uint64(self._m.data_ptr()) + so * np.uint64(4)
-        rows[:, 5] = np.uint64(self._v.data_ptr()) + so * np.uint64(4)
+        if self._m is not None:
+            rows[:, 4] = np.uint64(self._m.data_ptr()) + so * np.uint64(4)
+        if self._v is not None:
+            rows[:, 5] = np.uint64(self._v.data_ptr()) + so * np.uint64(4)
         if self._vmax is not None:
             rows[:, 6] = np.uint64(self._vmax.data_ptr()) + so * np.uint64(4)
         rows[:, 8] = ar.ln[idx].astype(np.uint64)
@@ -1887,10 +1929,14 @@ class ShardedOptimizer:
                 done.wait(cur.cuda_stream)
         idx = np.nonzero(red.had_grad & (ar.ln > 0))[0]
         self._steps[idx] += 1
-        hps = {gi: adam_group_hparams(self._groups[gi], self.optimizer) for gi in set(self._group_of)}
+        if self._kind == "sgd":
+            hps = {gi: sgd_group_hparams(self._groups[gi]) for gi in set(self._group_of)}
+        else:
+            hps = {gi: adam_group_hparams(self._groups[gi], self.optimizer)
+                   for gi in set(self._group_of)}
         if any(h["amsgrad"] for h in hps.values()) and self._vmax is None:
             self._ensure_vmax()
-        steps = self._steps[idx]
+        steps = self._hp_key(self._steps[idx])
         uniform = len(idx) > 0 and bool((steps == steps[0]).all())
         # (ws == 1: Adam reads the local grads themselves, whose addresses change — no fast path)
         sig = (idx.tobytes(), self._vmax is None) if self.world_size > 1 else None
@@ -1898,9 +1944,7 @@ class ShardedOptimizer:
         if fast is not None:  # the same parameters as last step, one step count: cached sets
             for gi, aset in fast:
                 h = hps[gi]
-                hp = adam_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"],
-                                  int(steps[0]), decoupled=h["decoupled"], amsgrad=h["amsgrad"],
-                                  maximize=h["maximize"], grad_div=float(self.world_size))
+                hp = self._make_hp(h, int(steps[0]))
                 if self.timing_events is not None:
                     e0 = torch.cuda.Event(enable_timing=True)
                     e0.record(cur)
@@ -1910,7 +1954,7 @@ class ShardedOptimizer:
                     aset.run(hp, cur)
         elif len(idx):
             rows = self._adam_rows(idx)
-            keys = np.stack([np.asarray(self._group_of)[idx], self._steps[idx]], axis=1)
+            keys = np.stack([np.asarray(self._group_of)[idx], steps], axis=1)
             used = []
             for key in np.unique(keys, axis=0):
                 sel = np.nonzero((keys == key).all(axis=1))[0]
@@ -1922,13 +1966,12 @@ class ShardedOptimizer:
                         self._retired.append(hit[1])
                     gz = ZS_BF16 if (self._split or (self._grad_comm and self.world_size > 1)) \
                         else ZS_F32
-                    hit = (sub.tobytes(), AdamSet(sub, ZS_BF16, ZS_BF16_SPLIT) if self._split
-                           else AdamSet(sub, gz))
+                    mk = SgdSet if self._kind == "sgd" else AdamSet
+                    hit = (sub.tobytes(), mk(sub, ZS_BF16, ZS_BF16_SPLIT) if self._split
+                           else mk(sub, gz))
                     self._adam_cache[ck] = hit
                 h = hps[int(key[0])]
-                hp = adam_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"],
-                                  int(key[1]), decoupled=h["decoupled"], amsgrad=h["amsgrad"],
-                                  maximize=h["maximize"], grad_div=float(self.world_size))
+                hp = self._make_hp(h, int(key[1]))
                 if self.timing_events is not None:
                     e0 = torch.cuda.Event(enable_timing=True)
                     e0.record(cur)
@@ -1940,7 +1983,9 @@ class ShardedOptimizer:
             # one set per param group and one step count: next step takes the cached sets
             self._fast_sig = sig if uniform else None
             self._fast_sets = used if uniform else None
-        if uniform:  # torch's state['step'] (a CPU tensor): one shared tensor, updated in place
+        if self._kind == "sgd":  # torch's SGD keeps no step: the buffer appears after the first
+            self._expose_sgd(idx)
+        elif uniform:  # torch's state['step'] (a CPU tensor): one shared tensor, updated in place
             t = self._step_shared
             if t is None:
                 t = self._step_shared = torch.tensor(float(steps[0]))
@@ -2039,7 +2084,11 @@ class ShardedOptimizer:
             index = {id(p): k for k, p in enumerate(ckpt.inner_params(self.optimizer))}
             for i, p in enumerate(self.params):
                 entry = {k: v.detach().clone() for k, v in self._state_views(i).items()}
-                entry["step"] = torch.tensor(float(self._steps[i]), dtype=torch.float32)
+                if self._kind == "sgd":  # torch's SGD entry: the buffer once it exists, no step
+                    if "momentum_buffer" not in self.optimizer.state[p]:
+                        entry.pop("momentum_buffer", None)
+                else:
+                    entry["step"] = torch.tensor(float(self._steps[i]), dtype=torch.float32)
                 state[index[id(p)]] = entry
         sd["state"] = state
         sd["zero_amd"] = self._ckpt_header()
@@ -2076,5 +2125,8 @@ class ShardedOptimizer:
                         view.copy_(src.reshape(view.shape))
                     else:  # moments 0 (fresh Adam); residual 0 (master = the bf16 chunk)
                         view.zero_()
-                self._steps[i] = ckpt.step_of(entry)
+                if self._kind == "sgd":  # no buffer saved: the next step is the first again
+                    self._steps[i] = int(entry.get("momentum_buffer") is not None)
+                else:
+                    self._steps[i] = ckpt.step_of(entry)
         self._expose_state()

@@ -313,6 +313,54 @@ int zs_clip_coef(const float* sumsq, double grad_div, double max_norm, float* ou
 int zs_adamset_run_clipped(const zs_adamset* as, const zs_adam_hparams* hp, const float* coef,
                            uintptr_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Fused SGD (momentum, Nesterov), additive in ABI v13.  Replaces torch.optim.SGD.step on the    */
+/* owned shard where the reference's ShardedOptimizer wraps an SGD (zero1.py:88, zero2.py:120,  */
+/* zero3.py:161; the optimizer of DDP/ddp.py:86,125; math of torch/optim/sgd.py                 */
+/* _single_tensor_sgd) plus the grad averaging, through the Adam's tables and kernels' shape.   */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  /* doubles on the host, rounded to f32 once */
+  float neg_lr;              /* -lr */
+  float momentum;
+  float one_minus_dampening; /* 1 - dampening */
+  float weight_decay;        /* L2 coefficient; 0 = off */
+  float grad_div;            /* divide the reduced sum by this (world size) */
+  float carry_mul;           /* ZeRO-1: sum += carry_mul * carry (ws-1) */
+  int32_t nesterov;
+  int32_t maximize;
+  int32_t first;             /* the segments' first step: the momentum buffer becomes the gradient
+                                (sgd.py: `buf = torch.clone(grad)`), its old contents are not read
+                                into the result */
+} zs_sgd_hparams;
+
+/* Fill hp from torch.optim.SGD's group scalars.  ZS_ERR_INVALID for what SGD.__init__ refuses
+ * (lr, momentum or weight_decay < 0; nesterov with momentum <= 0 or dampening != 0) and for
+ * grad_div <= 0. */
+int zs_sgd_hparams_init(double lr, double momentum, double dampening, double weight_decay,
+                        int nesterov, int maximize, int first, double grad_div, double carry_mul,
+                        zs_sgd_hparams* hp);
+/* A zs_adamset whose update is SGD's: segs, g_dtype, p_dtype, alignment and the vector / scalar
+ * split exactly as zs_adamset_create, with m the fp32 momentum_buffer (updated in place), set on
+ * all segments or on none (a set for momentum == 0, which touches no state array), and v == vmax
+ * == 0 (ZS_ERR_INVALID otherwise).  zs_adamset_set_grads, zs_adamset_sqnorm_partials,
+ * zs_adamset_grad_sqnorm, zs_adamset_destroy and zs_adamset_stats (gradient + parameter read and
+ * write + buffer read and write if present) work on it unchanged; zs_adamset_run and
+ * zs_adamset_run_clipped return ZS_ERR_INVALID on it, as zs_sgdset_run does on an Adam set. */
+int zs_sgdset_create(const zs_adam_seg* segs, int64_t n, int g_dtype, int p_dtype,
+                     zs_adamset** out);
+/* One SGD step over the set, per element (fp32, only the written fma fused):
+ *   g = (sum [+ carry_mul * carry]) / grad_div;  [carry = g];  [g *= *coef];  [g = -g]
+ *   [g = fma(wd, p, g)];  buf = first ? g : fma(1 - dampening, g, buf * momentum)
+ *   g = nesterov ? fma(momentum, buf, g) : buf;  p = fma(-lr, g, p)
+ * the buffer lines only with momentum != 0 (a set with buffers run with momentum == 0 leaves them
+ * untouched, as torch never creates them then).  coef: NULL = unclipped, else the device scalar of
+ * zs_clip_coef as in zs_adamset_run_clipped.  ZS_ERR_INVALID, nothing launched: an Adam set;
+ * momentum != 0 on a set without buffers; coef on a set with the ZeRO-1 carry; nesterov with
+ * momentum <= 0 or dampening != 0; negative lr, momentum or weight_decay. */
+int zs_sgdset_run(const zs_adamset* as, const zs_sgd_hparams* hp, const float* coef,
+                  uintptr_t stream);
+
 /* Single-range form, SURVEY.md §8(b)'s signature: one torch.optim.Adam/AdamW step over n
  * contiguous elements — the update of one flat shard (zero1.py:88 on a flattened group) with no
  * table to build.  p: fp32 master/param, updated in place; p_bf16: optional bf16 copy of the
