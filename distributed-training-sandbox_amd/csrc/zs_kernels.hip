@@ -1079,6 +1079,55 @@ __global__ __launch_bounds__(kThreads) void scale_kernel(T* __restrict__ x, int6
 }
 
 // ----------------------------------------------------------------------------------------------
+// accumulate: dst += src (ZeRO-3 update mode's gradient accumulation: a later micro-batch's
+// reduce-scattered chunks, in a staging buffer, added to the grad chunk arena)
+// ----------------------------------------------------------------------------------------------
+// The shape of scale_kernel with a second read stream: a wave step covers kAccU contiguous 1 KiB
+// blocks of each buffer (lane l of block u at 16-B chunk 64u + l), all 2 kAccU loads issued before
+// the first store; grid-stride over wave steps; the tail (n % elements per step) by block 0.
+// 3 x element size bytes per element (dst read, src read, dst written); no atomics, LDS or scratch.
+// fp32: one IEEE add; bf16: both operands widened exactly, one fp32 add, one RNE to bf16 (NaN stays
+// NaN) — torch's add_ on a tensor of that dtype, i.e. what AccumulateGrad does to p.grad.
+// Cache policy by size (NT) over the bytes touched, as zs_scale; `zs_tune("accumulate_nt")`
+// forces either.
+constexpr int kAccU = 4;
+
+template <typename T, bool NT>
+__global__ __launch_bounds__(kThreads) void accumulate_kernel(T* dst, const T* src, int64_t n) {
+#pragma clang fp contract(off)
+  constexpr int V = 16 / sizeof(T);
+  constexpr int64_t kSpan = int64_t(64) * V * kAccU;  // elements per wave step
+  const int64_t steps = n / kSpan;
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = int64_t(gridDim.x) * (kThreads / 64);
+  for (int64_t w = int64_t(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6); w < steps;
+       w += nwaves) {
+    const int64_t off = w * kSpan + int64_t(lane) * V;
+    T* d = dst + off;
+    const T* s = src + off;
+    uint4 a[kAccU], b[kAccU];
+#pragma unroll
+    for (int u = 0; u < kAccU; ++u) a[u] = ld16<NT>(d + u * 64 * V);
+#pragma unroll
+    for (int u = 0; u < kAccU; ++u) b[u] = ld16<NT>(s + u * 64 * V);
+#pragma unroll
+    for (int u = 0; u < kAccU; ++u) {
+      T* x = reinterpret_cast<T*>(&a[u]);
+      const T* y = reinterpret_cast<const T*>(&b[u]);
+#pragma unroll
+      for (int j = 0; j < V; ++j) x[j] = from_f32<T>(to_f32<T>(x[j]) + to_f32<T>(y[j]));
+      st16<NT>(d + u * 64 * V, a[u]);
+    }
+  }
+  if (blockIdx.x == 0) {
+    const gptr<T> gd = glob(dst);
+    const gptr<const T> gs = glob(src);
+    for (int64_t i = steps * kSpan + threadIdx.x; i < n; i += kThreads)
+      gd[i] = from_f32<T>(to_f32<T>(gd[i]) + to_f32<T>(gs[i]));
+  }
+}
+
+// ----------------------------------------------------------------------------------------------
 // fp32 <-> bf16 conversion (the bf16 gradient exchange of fp32-parameter models)
 // ----------------------------------------------------------------------------------------------
 // Wave-dense accesses: a wave step covers kConvSpan elements in kConvU blocks of 256; in block u
@@ -1546,6 +1595,10 @@ int& copy_nt_mode() {
   static int mode = -1;
   return mode;
 }
+int& accumulate_nt_mode() {
+  static int mode = -1;
+  return mode;
+}
 
 int dq_grid(int64_t rows) {
   int64_t cap = grid_cap();
@@ -1952,6 +2005,33 @@ int zs_scale(void* x, int64_t n, int dtype, double div, uintptr_t stream) {
     if (nt) ZS_SCALE(unsigned short, true); else ZS_SCALE(unsigned short, false);
   }
 #undef ZS_SCALE
+  ZS_HIP(hipGetLastError());
+  return ZS_OK;
+}
+
+int zs_accumulate(void* dst, const void* src, int64_t n, int dtype, uintptr_t stream) {
+  ZS_REQUIRE(n >= 0, "zs_accumulate: n < 0");
+  ZS_REQUIRE(dtype == ZS_F32 || dtype == ZS_BF16, "zs_accumulate: bad dtype %d", dtype);
+  if (n == 0) return ZS_OK;
+  ZS_REQUIRE(dst != nullptr && src != nullptr, "zs_accumulate: NULL buffer");
+  ZS_REQUIRE(aligned(reinterpret_cast<uint64_t>(dst), 16) &&
+                 aligned(reinterpret_cast<uint64_t>(src), 16),
+             "zs_accumulate: dst and src must be 16-byte aligned");
+  const int64_t es = dtype == ZS_F32 ? 4 : 2;
+  const int64_t span = int64_t(64) * kAccU * (16 / es);  // elements per wave step
+  const int64_t blocks = std::max<int64_t>(1, (n / span + 3) / 4);
+  const int grid = int(std::min<int64_t>(blocks, grid_cap()));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int force = accumulate_nt_mode();
+  const bool nt = force < 0 ? 3 * n * es > kMallBytes : force == 1;  // by the bytes touched
+#define ZS_ACC(T, NT) hipLaunchKernelGGL((accumulate_kernel<T, NT>), dim3(grid), dim3(kThreads), 0, st, \
+                                         static_cast<T*>(dst), static_cast<const T*>(src), n)
+  if (dtype == ZS_F32) {
+    if (nt) ZS_ACC(float, true); else ZS_ACC(float, false);
+  } else {
+    if (nt) ZS_ACC(unsigned short, true); else ZS_ACC(unsigned short, false);
+  }
+#undef ZS_ACC
   ZS_HIP(hipGetLastError());
   return ZS_OK;
 }
@@ -2751,6 +2831,9 @@ int zs_tune(const char* key, int64_t value, int64_t* previous) {
     ok = value >= -1 && value <= 1;
   } else if (std::strcmp(key, "copy_nt") == 0) {
     slot = &copy_nt_mode();
+    ok = value >= -1 && value <= 1;
+  } else if (std::strcmp(key, "accumulate_nt") == 0) {
+    slot = &accumulate_nt_mode();
     ok = value >= -1 && value <= 1;
   } else if (std::strcmp(key, "adam_wg_per_cu") == 0) {
     slot = &adam_wg_per_cu();

@@ -286,3 +286,26 @@ def convert(src, dst, stream=None) -> None:
     st = torch.cuda.current_stream(src.device) if stream is None else stream
     _lib.call("zs_convert", src.data_ptr(), zs_dtype(src.dtype), dst.data_ptr(), zs_dtype(dst.dtype),
               src.numel(), stream_handle(st))
+
+
+def accumulate(dst, src, stream=None) -> None:
+    """dst[i] += src[i] (zs_accumulate): contiguous, 16-byte aligned fp32 or bf16 tensors of one
+    dtype and element count, enqueued on ``stream``.  fp32: one IEEE add; bf16: an fp32 add rounded
+    to nearest even — torch's ``add_``.  With ``CHECK_EXTENTS`` on, both ranges are checked against
+    the tensors' storage before anything is launched."""
+    import torch
+
+    from .comm import zs_dtype
+
+    if src.dtype != dst.dtype or src.numel() != dst.numel():
+        raise ValueError("zero_amd: accumulate needs dst and src of one dtype and element count")
+    if not (src.is_contiguous() and dst.is_contiguous()):
+        raise ValueError("zero_amd: accumulate needs contiguous tensors")
+    n = dst.numel()
+    if CHECK_EXTENTS:
+        nb = [n * dst.element_size()]
+        check_extents([dst.data_ptr()], nb, [dst], "accumulate destination")
+        check_extents([src.data_ptr()], nb, [src], "accumulate source")
+    st = torch.cuda.current_stream(dst.device) if stream is None else stream
+    _lib.call("zs_accumulate", dst.data_ptr(), src.data_ptr(), n, zs_dtype(dst.dtype),
+              stream_handle(st))

@@ -62,3 +62,18 @@ def train_step(model, optimizer, input_ids):
     optimizer.step()
     optimizer.zero_grad()
     return loss
+
+
+def train_step_accumulated(model, optimizer, micro_batches):
+    """``train_step`` over several micro-batches: each loss divided by their count, one backward
+    per micro-batch, one step (``zero3.ShardedOptimizer(..., update=True, grad_accumulation=True)``,
+    or any optimizer whose gradients accumulate).  Returns the mean loss."""
+    micro_batches = list(micro_batches)
+    total = None
+    for input_ids in micro_batches:
+        loss = model(input_ids=input_ids, labels=input_ids).loss / len(micro_batches)
+        loss.backward()
+        total = loss.detach() if total is None else total + loss.detach()
+    optimizer.step()
+    optimizer.zero_grad()
+    return total

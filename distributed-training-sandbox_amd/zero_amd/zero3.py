@@ -27,6 +27,11 @@ real rows), and ``param.data`` is a view of its slot between gathers.  Two modes
     chunk arena (grad /ws folded in) — data-parallel Adam, sliced.  Every rank updates its chunk
     of every parameter, so the inner optimizer's groups are not filtered in this mode and
     ``optimizer.state[p]`` holds chunk-shaped views of the flat fp32 state.
+    ``grad_accumulation=True`` (opt-in) takes several backward passes per ``step()``: every pass
+    after the first is reduce-scattered into a staging buffer and added to the grad chunk arena
+    by a fused HIP kernel (zs_accumulate) — one rounding per pass in the chunks' dtype, as
+    torch's AccumulateGrad; ``zero_grad()`` discards the accumulation, the caller scales each
+    micro-batch's loss by their count.
 
 ``materialize`` is a zero-copy RCCL all-gather from the chunk slot (already padded to S) straight
 into the full tensor (rows of torch.chunk are contiguous: full = [chunk_0 | … | chunk_{ws-1}]),
@@ -285,6 +290,9 @@ class _GatherRuntime:
         self._rel_syncs = {}        # consumer stream handle -> [flag sync, its latest epoch]
         self._rel_bytes = self._rel_n = 0  # released since the last marker
         self._counted = {}          # pending key -> its bytes counted in _out_bytes
+        # called once at the next materialize, then cleared (gradient accumulation: the shard-
+        # shaped grads a finished backward left on the parameters come off before the next one)
+        self.before_materialize = None
         self._nbytes_of = {}        # id(managers list) -> (that list, its gathered bytes)
         self.n_throttle_waits = 0
 
@@ -742,6 +750,10 @@ class _GatherRuntime:
             self._ensure_wave(i // self.wave, cur_h)
 
     def materialize(self, key, managers):
+        cb = self.before_materialize
+        if cb is not None:
+            self.before_materialize = None
+            cb()
         cur_h = self._cur_h()
         if self.recording:
             self.sequence.append(key)
@@ -1337,10 +1349,22 @@ class _GradReducer:
     event on the stream that produced the grads — and its full gradients are released (their
     memory returns to torch's allocator once the side stream has passed the collective).  The end
     of backward (an autograd callback) launches whatever is left in the same fixed order, so every
-    rank issues the same collective sequence, and makes the compute stream wait for the last one."""
+    rank issues the same collective sequence, and makes the compute stream wait for the last one.
+
+    ``grad_accumulation`` (off: a second backward before step() is an error): every backward is a
+    *pass*.  The first pass after construction, step() or zero_grad() is the above unchanged.  A
+    later pass reduce-scatters bucket k into a staging buffer (the collective overwrites its
+    receive buffer) and adds it to the bucket's contiguous range of the grad chunk arena with one
+    zs_accumulate on the collective's stream; the last bucket's done sync is recorded after its
+    add.  Between passes the per-backward counting is reset and ``had_grad`` keeps the union."""
 
     def __init__(self, opt, bucket_bytes: int):
         self.opt = opt
+        self.grad_accumulation = bool(getattr(opt, "_grad_accumulation", False))
+        self.passes = 0                  # backward passes folded in since the last reset
+        self.n_accumulate_launches = 0   # zs_accumulate launches, ever
+        self._accumulating = False       # the running pass adds to the arena
+        self._staging = None             # an accumulating pass's receive buffer
         arena = opt._arena
         n = len(opt.params)
         es = opt.params[0].element_size()
@@ -1384,6 +1408,14 @@ class _GradReducer:
         self._rfast = {}             # bucket -> its _hostext.ReduceFast, or None
         self._group_idx = [np.asarray(g, np.int64) for g in groups]
         self._counter = None     # the C++ gradient counter (register_hooks)
+        # bucket k's parameters are consecutive, so its slots are one contiguous range of the
+        # arena: (first element, elements), alignment pads included
+        total = int(arena.total)
+        self._range = []
+        for g in groups:
+            lo, hi = min(g), max(g)
+            end = int(arena.slot[hi + 1]) if hi + 1 < n else total
+            self._range.append((int(arena.slot[lo]), end - int(arena.slot[lo])))
         self.reset()
 
     def _ready_sync(self, k: int, cur_h: int) -> Sync:
@@ -1403,8 +1435,72 @@ class _GradReducer:
         self.next = 0
         self.callback_queued = False
         self.launched_in_backward = 0
+        self.passes = 0
+        self._accumulating = False
         if getattr(self, "_counter", None) is not None:
             self._counter.reset()
+        if self.grad_accumulation:
+            self.opt.runtime.before_materialize = None
+
+    # -- gradient accumulation ------------------------------------------------------------------
+    def _begin_pass(self):
+        """The first gradient of a backward: after a finished pass, the buckets run again, adding."""
+        if self.grad_accumulation and self.passes and self.next == self.K:
+            self.next = 0
+            self.launched_in_backward = 0
+            self._accumulating = self.opt.world_size > 1
+            if self._accumulating:
+                # allocated (and zero-filled, on the current stream) here, before any bucket's
+                # ready sync is recorded: the collective's stream waits on that record, so the
+                # fill is behind it for every launch path
+                self.staging()
+
+    def _end_pass(self):
+        """A backward has ended with every bucket launched: the per-backward counting starts
+        over; ``had_grad``, ``next == K`` (step() launches nothing) and the pass count stay."""
+        self.passes += 1
+        self.pending = list(self._size_l)
+        self.marked = [False] * len(self.marked)
+        self.callback_queued = False
+        self._accumulating = False
+        if self._counter is not None:
+            self._counter.reset()
+
+    def incomplete(self) -> bool:
+        """A backward began and never reached its end (it raised): some buckets may have been
+        reduced or added and others not."""
+        return self.grad_accumulation and self.callback_queued
+
+    def staging(self):
+        """The accumulating passes' receive buffer: the largest bucket's range of the arena
+        (at most bucket_mb / ws of full gradient plus pads), allocated at the first accumulating
+        pass and kept, so the tables bound to its addresses stay valid."""
+        st = self._staging
+        if st is None:
+            opt = self.opt
+            n = max(ln for _, ln in self._range)
+            st = self._staging = torch.zeros(n, dtype=opt._G.dtype, device=opt._G.device)
+            if opt.runtime.stream is not None:
+                st.record_stream(opt.runtime.stream)
+        return st
+
+    def _accumulate(self, k: int, stream_h: int):
+        """Bucket k's range of the arena += the staging buffer, on the collective's stream."""
+        G, st = self.opt._G, self._staging
+        s, n = self._range[k]
+        _lib.call("zs_accumulate", G.data_ptr() + s * G.element_size(), st.data_ptr(), n,
+                  zs_dtype(G.dtype), stream_h)
+        self.n_accumulate_launches += 1
+
+    def _drop_shard_grads(self):
+        """Take the shard-shaped grads install_shard_grads handed out off the parameters (only
+        where ``p.grad`` is still that view): the next backward's AccumulateGrad must not meet a
+        chunk-shaped ``.grad`` on a gathered, full-shape parameter."""
+        params, views = self.opt.params, self._shard_grad
+        for i in np.flatnonzero(self.had_grad).tolist():
+            v = views[i]
+            if v is not None and params[i].grad is v:
+                params[i].grad = None
 
     def register_hooks(self):
         """The parameters' post-accumulate-grad counting.  With the host extension: C++ hooks
@@ -1428,6 +1524,7 @@ class _GradReducer:
         inside the backward."""
         if not self.callback_queued:
             self.callback_queued = True
+            self._begin_pass()
             torch.autograd.Variable._execution_engine.queue_callback(self._end_backward)
 
     def _launch_upto(self, upto: int):
@@ -1450,6 +1547,7 @@ class _GradReducer:
         self.pending[self._bucket_of_l[i]] -= 1
         if not self.callback_queued:
             self.callback_queued = True
+            self._begin_pass()
             torch.autograd.Variable._execution_engine.queue_callback(self._end_backward)
         while self.next < self.K and self.pending[self.next] == 0:
             self._launch(self.next)
@@ -1459,6 +1557,8 @@ class _GradReducer:
     def _end_backward(self):
         self.flush()
         self.install_shard_grads()
+        if self.grad_accumulation:
+            self._end_pass()
 
     def flush(self):
         """Launch every bucket not launched yet, in the fixed order."""
@@ -1486,16 +1586,21 @@ class _GradReducer:
                     s, n = int(opt._arena.slot[i]), int(opt._arena.ln[i])
                     v = views[i] = opt._G[s:s + n].view(shapes[i])
                 p.grad = v
+        if self.grad_accumulation:  # off again at the first gather after this backward
+            opt.runtime.before_materialize = WeakCall(self, "_drop_shard_grads")
 
-    def _rs_table(self, k: int):
-        """Bucket k's reduce-scatter destinations (grad chunk-arena slots) and counts, cached."""
-        t = self._rs_tables.get(k)
+    def _rs_table(self, k: int, acc: bool = False):
+        """Bucket k's reduce-scatter destinations (grad chunk-arena slots; ``acc``: the same
+        layout at the head of the staging buffer) and counts, cached."""
+        t = self._rs_tables.get((k, acc))
         if t is None:
-            from .comm import zs_dtype
-
             opt, idx = self.opt, np.asarray(self.groups[k], np.int64)
             G = opt._G
-            recv = np.uint64(G.data_ptr()) + (opt._arena.slot[idx] * G.element_size()).astype(np.uint64)
+            if acc:
+                off = opt._arena.slot[idx] - self._range[k][0]
+                recv = np.uint64(self.staging().data_ptr()) + (off * G.element_size()).astype(np.uint64)
+            else:
+                recv = np.uint64(G.data_ptr()) + (opt._arena.slot[idx] * G.element_size()).astype(np.uint64)
             count = np.ascontiguousarray(opt._arena.S[idx], np.int64)
             send = np.zeros(len(idx), np.uint64)  # refilled per launch with the grads' addresses
             bind = getattr(opt.comm, "reduce_scatter_group_bound", None)
@@ -1503,14 +1608,15 @@ class _GradReducer:
             bind = getattr(opt.comm, "reduce_scatter_group_synced_bound", None)
             ordered = bind(send, recv, count, zs_dtype(G.dtype)) if bind is not None else None
             t = (recv, count, zs_dtype(G.dtype), send, raw, ordered)
-            self._rs_tables[k] = t
+            self._rs_tables[(k, acc)] = t
         return t
 
-    def _reduce_fast(self, k: int):
+    def _reduce_fast(self, k: int, acc: bool = False):
         """Bucket k's ReduceFast (csrc/zs_host_ext.cpp): its gradients' send table, the synced
         group, the stream records and the gradient resets in one call — or None (no extension, a
-        communicator without the raw synced group, a bf16 exchange, uneven chunks)."""
-        rf = self._rfast.get(k, False)
+        communicator without the raw synced group, a bf16 exchange, uneven chunks).  ``acc``: a
+        second instance bound to the staging addresses."""
+        rf = self._rfast.get((k, acc), False)
         if rf is not False:
             return rf
         rf = None
@@ -1521,19 +1627,23 @@ class _GradReducer:
                 and hasattr(_hostext, "ReduceFast") and opt._G.dtype == ar.dtype
                 and hasattr(opt.comm, "reduce_scatter_group")
                 and all(self._N_l[i] == opt.world_size * self._S_l[i] for i in self.groups[k])):
-            recv, count, dt, sp, raw, ordered = self._rs_table(k)
+            recv, count, dt, sp, raw, ordered = self._rs_table(k, acc)
             fn, comm_h, collective = raw_of()
             rf = _hostext.ReduceFast(int(fn), int(comm_h), bool(collective),
                                      [opt.params[i] for i in self.groups[k]],
                                      [int(x) for x in recv], [int(x) for x in count], int(dt),
                                      ar.dtype, int(opt.world_size))
-        self._rfast[k] = rf
+        self._rfast[(k, acc)] = rf
         return rf
 
     def _launch(self, k: int):
         opt = self.opt
         ar, ws = opt._arena, opt.world_size
-        rf = self._reduce_fast(k) if ws > 1 and self.timing is None else None
+        # an accumulating pass: the collective receives in the staging buffer, its done sync is
+        # recorded here, after the add
+        acc = self._accumulating
+        last = k == self.K - 1
+        rf = self._reduce_fast(k, acc) if ws > 1 and self.timing is None else None
         if rf is not None:
             rt = opt.runtime
             cur_h = rt._cur_h()
@@ -1541,9 +1651,13 @@ class _GradReducer:
                 rc = rf.launch(cur_h, 0, 0, 0, cur_h, 0, False)
             else:
                 rc = rf.launch(cur_h, self._ready_sync(k, cur_h).h, self._cs_id, rt._dev_idx,
-                               self._cs_h, self._done_h[k] if k == self.K - 1 else 0, True)
+                               self._cs_h, self._done_h[k] if last and not acc else 0, True)
             if rc == 0:
                 self.had_grad[self._group_idx[k]] = True
+                if acc:
+                    self._accumulate(k, cur_h if rt.stream is None else self._cs_h)
+                    if last and rt.stream is not None:
+                        self.ev_done[k].record(self._cs_h)
                 return
             if rc > 0:
                 _lib.check(rc, "zs_reduce_scatter_group_synced")
@@ -1594,8 +1708,8 @@ class _GradReducer:
                         send[:N].copy_(flat)
             sends.append((i, send))
         single = opt.runtime.stream is None
-        tab = self._rs_tables.get(k) or (self._rs_table(k) if hasattr(opt.comm, "reduce_scatter_group")
-                                         else None)
+        tab = self._rs_tables.get((k, acc)) or (self._rs_table(k, acc)
+                                                if hasattr(opt.comm, "reduce_scatter_group") else None)
         if tab is not None and tab[5] is not None and self.timing is None:
             recv, count, dt, sp, raw, ordered = tab
             for j, (_, t) in enumerate(sends):
@@ -1604,6 +1718,8 @@ class _GradReducer:
             if single:
                 # single-stream mode: the bucket's RCCL group on the stream that produced the grads
                 ordered(cur_h, 0, cur_h, 0)
+                if acc:
+                    self._accumulate(k, cur_h)
                 for i, _ in sends:
                     params[i].grad = None
                 return
@@ -1612,7 +1728,11 @@ class _GradReducer:
             # last bucket's done is waited on (step(), the shard grads): the side stream runs the
             # buckets in order, so the others need no record
             ordered(cur_h, self._ready_sync(k, cur_h).h, self._cs_h,
-                    self._done_h[k] if k == self.K - 1 else 0)
+                    self._done_h[k] if last and not acc else 0)
+            if acc:
+                self._accumulate(k, self._cs_h)
+                if last:
+                    self.ev_done[k].record(self._cs_h)
             cs = opt.runtime.stream
             for i, send in sends:
                 send.record_stream(cs)
@@ -1637,10 +1757,13 @@ class _GradReducer:
             else:
                 opt.comm.reduce_scatter_group(sp, recv, count, dt, cs)
         else:
+            dst, base = (self.staging(), self._range[k][0]) if acc else (opt._G, 0)
             with _group_ctx(opt.comm):
                 for i, send in sends:  # (a zero-copy send is the grad itself: flatten the view)
-                    s = int(ar.slot[i])
-                    opt.comm.reduce_scatter(send.view(-1), opt._G[s:s + int(ar.S[i])], cs)
+                    s = int(ar.slot[i]) - base
+                    opt.comm.reduce_scatter(send.view(-1), dst[s:s + int(ar.S[i])], cs)
+        if acc:
+            self._accumulate(k, cs_h)
         # the group has been enqueued: a buffer freed from here on is only reused after it
         for i, send in sends:
             send.record_stream(cs)
@@ -1678,7 +1801,14 @@ class ShardedOptimizer:
     def __init__(self, optimizer: Optimizer, *, update: bool = False, comm=None, sync: bool = True,
                  gather_dtype=None, bucket_mb: float = RS_BUCKET_MB, grad_comm: str | None = None,
                  gather_wave: int = GATHER_WAVE, side_stream: bool = True,
-                 stream_sync: str = STREAM_SYNC):
+                 stream_sync: str = STREAM_SYNC, grad_accumulation: bool = False):
+        # grad_accumulation (update mode): several backward passes per step(), each reduce-
+        # scattered and added to the chunks already held (_GradReducer); off: the second backward
+        # before step() is an error, as before
+        if grad_accumulation and not update:
+            raise ValueError("grad_accumulation=True applies to update mode (reference mode never "
+                             "updates: zero3.py:150-153 drops every gradient)")
+        self._grad_accumulation = bool(grad_accumulation)
         # "adam" or "sgd" (TypeError for anything else); reference mode never updates either
         self._kind = optimizer_kind(optimizer)
         if self._kind == "sgd":
@@ -1845,8 +1975,24 @@ class ShardedOptimizer:
         self._expose_state()  # (cached Adam rows gain the vmax pointer: rebuilt on their next use)
 
     def grad_arena(self):
-        """The flat gradient chunk arena (update mode, ws > 1): slot i holds param i's summed chunk."""
+        """The flat gradient chunk arena (update mode, ws > 1): slot i holds param i's summed chunk
+        (with ``grad_accumulation``: summed over the ranks and the passes so far).  Only the S_i
+        elements of each slot are defined: with ``grad_accumulation`` the alignment pads between
+        slots (under 64 elements each) may hold stale sums of other buckets — the one staging
+        buffer serves buckets of different layouts — so a pass over the whole buffer must go by
+        the arena's slots, as the collectives and the update do."""
         return self._G
+
+    def grad_staging(self):
+        """The receive buffer of accumulating passes (``grad_accumulation``; None until the second
+        backward of some step): the largest bucket's range of the grad chunk arena.  Its contents
+        between passes are undefined."""
+        return self._reducer._staging if self._reducer is not None else None
+
+    @property
+    def accumulated_passes(self) -> int:
+        """Backward passes folded into the gradient chunks since the last step() / zero_grad()."""
+        return self._reducer.passes if self._reducer is not None else 0
 
     # ------------------------------------------------------------------------------------------
     def _reduce_reference(self):
@@ -1917,6 +2063,11 @@ class ShardedOptimizer:
 
     def _step_update(self):
         red, ar = self._reducer, self._arena
+        if red.incomplete():
+            raise RuntimeError(
+                "zero_amd ZeRO-3: a backward did not finish (it raised), so the accumulated "
+                "gradient chunks may hold some buckets of it and not others; call zero_grad() to "
+                "discard this step's accumulation")
         cur = torch.cuda.current_stream(ar.device)
         red.flush()  # grads assigned outside backward (or backward without hooks firing)
         done = None
@@ -2057,6 +2208,17 @@ class ShardedOptimizer:
         self._comm_spans = keep
 
     def zero_grad(self, set_to_none: bool = True):
+        """The inner optimizer's zero_grad.  With ``grad_accumulation`` it also discards what has
+        been accumulated since the last step(): the next backward is a first pass again (and a
+        backward that raised is forgotten).  ``state_dict()`` never carries a half-accumulated
+        gradient: checkpoint after step()."""
+        if self._grad_accumulation:
+            red = self._reducer
+            if red.passes or red.callback_queued or red.next:
+                # (the chunk views come off here: set_to_none=False would only zero them in place
+                # and leave chunk-shaped grads for the next backward to meet)
+                red._drop_shard_grads()
+                red.reset()
         self.optimizer.zero_grad(set_to_none=set_to_none)
 
     def mark_params_changed(self):

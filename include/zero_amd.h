@@ -171,6 +171,16 @@ int zs_copy_direct(int64_t n, const uint64_t* src, const uint64_t* dst, const in
  * are both fp32 powers of two, which is exact); bf16: computed in fp32, rounded to nearest even. */
 int zs_scale(void* x, int64_t n, int dtype, double div, uintptr_t stream);
 
+/* dst[i] = dst[i] + src[i] over n elements (dtype ZS_F32 / ZS_BF16; dst and src 16-byte aligned):
+ * gradient accumulation on a shard — a later micro-batch's reduce-scattered chunks, received in a
+ * staging buffer (ncclReduceScatter overwrites its receive buffer), added to the chunks already
+ * held (ZeRO-3 update mode, grad_accumulation=True).  fp32: one IEEE add; bf16: both operands
+ * widened exactly, one fp32 add, rounded to nearest even (NaN stays NaN) — torch's add_ on a tensor
+ * of that dtype, which is what AccumulateGrad does to p.grad.  Denormals are kept.  n == 0: ZS_OK,
+ * nothing launched; n < 0, a NULL or misaligned pointer with n > 0, another dtype: ZS_ERR_INVALID,
+ * nothing launched.  Additive to ABI v13. */
+int zs_accumulate(void* dst, const void* src, int64_t n, int dtype, uintptr_t stream);
+
 /* n elements fp32 -> bf16 (round to nearest even, NaN stays NaN) or bf16 -> fp32 (exact).  The
  * bf16 gradient exchange of fp32-parameter models: the reference reduces fp32
  * grads (zero2.py:107); converting them first halves the bytes every collective moves.  16-B
@@ -408,6 +418,7 @@ int zs_device_alloc_chunked(int64_t bytes, int64_t chunk_bytes, void** out);
  * workgroups per CU walking several rows each), "scale_nt" (zs_scale's cache policy: -1 by size,
  * non-temporal above 256 MiB; 0 default policy; 1 non-temporal), "convert_nt" (zs_convert's, the
  * same by source + destination bytes), "copy_nt" (zs_copyset_run's, by 2 x the set's bytes),
+ * "accumulate_nt" (zs_accumulate's, by the 3 x n x element size bytes it touches),
  * "adam_wg_per_cu" (0 = the default grid of the fused Adam: 128 workgroups per CU, 1024 for the
  * loads-first kernel of a split master; k = at most k per CU), "adam_loads_first" (1: a full chunk
  * of the vector Adam issues all its loads before its first wait; 0: every chunk through the

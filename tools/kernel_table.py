@@ -17,8 +17,14 @@ events on the launch stream, achieved GB/s and the fraction of the 8 TB/s HBM pe
                          and a 4 GiB buffer (HBM): 2 x element size per element
   copy_segments_kernel   pack of the C4 set's grads into one rank-major arena (every tensor a
                          segment, bf16): 2 x 2 B/element
+  accumulate_kernel      dst += src (ZeRO-3 gradient accumulation), bf16 and fp32, both cache
+                         policies, on placed buffers: a 64 MiB range (about one default bucket's
+                         chunks at ws = 8 in bf16) and a 1 GiB range (above the MALL); 3 x element
+                         size per element.  Alternated, several rounds in one process, with
+                         zs_scale on the destination and the segment copy source -> destination on
+                         the same buffers: those neighbours are the yardstick.
 
-Usage: python tools/kernel_table.py [--iters 20] [--out profiles/r03_kernels_table.json]
+Usage: python tools/kernel_table.py [--iters 20] [--only accumulate] [--out profiles/r03_kernels_table.json]
 """
 from __future__ import annotations
 
@@ -37,6 +43,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--only", default=None, choices=["accumulate"],
+                    help="run one section of the table alone")
+    ap.add_argument("--rounds", type=int, default=3, help="alternations of the accumulate section")
     args = ap.parse_args()
 
     import numpy as np
@@ -68,6 +77,50 @@ def main():
                "rocprof_kernel": rocprof, "dispatches_per_call": per_call}
         rows.append(row)
         print(json.dumps(row), flush=True)
+
+    def write_out():
+        if args.out:
+            Path(args.out).write_text(json.dumps({"iters": args.iters, "peak_gbs": HBM_PEAK_GBS,
+                                                  "rows": rows}, indent=1))
+
+    def accumulate_section():
+        from zero_amd.kernels import accumulate
+
+        for mib in (64, 1024):
+            for dt, code, es in ((torch.bfloat16, _lib.ZS_BF16, 2), (torch.float32, _lib.ZS_F32, 4)):
+                m = (mib << 20) // es
+                d, _ = probed_zeros(m, dt, dev)
+                s_, _ = probed_zeros(m, dt, dev)
+                d.normal_(std=1e-3)
+                s_.normal_(std=1e-3)
+                nb = m * es
+                cp = CopySet([s_.data_ptr()], [d.data_ptr()], [nb])
+                tn = "bf16" if es == 2 else "f32"
+                tname = "unsigned short" if es == 2 else "float"
+                for r in range(args.rounds):
+                    for nt in (0, 1):
+                        _lib.call("zs_tune", b"accumulate_nt", nt, None)
+                        try:
+                            timed(f"accumulate_kernel<{tn}, nt={nt}> ({mib} MiB range, round {r})",
+                                  lambda: accumulate(d, s_, st), 3 * nb,
+                                  f"{mib} MiB of {dt} chunks += staging", f"accumulate_kernel<{tname},")
+                        finally:
+                            _lib.call("zs_tune", b"accumulate_nt", -1, None)
+                    timed(f"scale_kernel<{tn}> (/3, the same destination, {mib} MiB, round {r})",
+                          lambda: _lib.call("zs_scale", d.data_ptr(), m, code, 3.0, stream_handle(st)),
+                          2 * nb, "neighbour on the same buffer, cache policy by size",
+                          f"scale_kernel<{tname},")
+                    timed(f"copy_segments_kernel (source -> destination, {mib} MiB {tn}, round {r})",
+                          lambda: cp.run(st), 2 * nb, "neighbour on the same buffers, cache policy by size",
+                          "copy_segments_kernel<")
+                    d.normal_(std=1e-3)  # (the scale shrinks it towards the denormals)
+                del d, s_, cp
+                torch.cuda.empty_cache()
+
+    if args.only == "accumulate":
+        accumulate_section()
+        write_out()
+        return
 
     # convert: C3-size gradient (6 x Linear(12800, 12800) + biases)
     n = int(sum(int(np.prod(s)) for s in mlp_shapes(12800)))
@@ -177,9 +230,8 @@ def main():
         cp = CopySet([buf.data_ptr()], [buf.data_ptr()], [nb])
         timed(f"copy_segments_kernel (in place, {nm})", lambda cp=cp: cp.run(st), 2 * nb,
               f"{nb:,} B, the buffer the fp8 rows use", "copy_segments_kernel<")
-    if args.out:
-        Path(args.out).write_text(json.dumps({"iters": args.iters, "peak_gbs": HBM_PEAK_GBS,
-                                              "rows": rows}, indent=1))
+    accumulate_section()
+    write_out()
 
 
 if __name__ == "__main__":
