@@ -212,9 +212,12 @@ struct AdamSeg {
   int64_t n;
 };
 
+// lerp_w / lerp_hi: ATen's lerp (Lerp.h) with weight w = 1-beta1 is self + w*(end-self) for
+// |w| < 0.5 and end - (end-self)*(1-w) otherwise; make_hp holds the fma's coefficient (w, or w-1 in
+// one fp32 subtraction) and which operand it adds to, so the choice is uniform.
 struct HP {
-  float omb1, beta2, omb2, neg_step, bc2_sqrt, eps, wd, decay_mul, grad_div, inv_div, carry_mul;
-  int div_pow2, maximize;
+  float lerp_w, beta2, omb2, neg_step, bc2_sqrt, eps, wd, decay_mul, grad_div, inv_div, carry_mul;
+  int div_pow2, maximize, lerp_hi;
 };
 
 __device__ __forceinline__ float bf16_to_f32(unsigned short h) {
@@ -241,11 +244,14 @@ __device__ __forceinline__ uint32_t master_residual(float p, uint32_t hi) {
   return d == 0x8000u ? 0x7FFFu : (d & 0xFFFFu);
 }
 
-// One element of torch.optim.Adam's single-tensor update (adam.py:394-547), in the rounding order
-// of torch's CPU kernels: lerp = fma(w, end-self, self) (ATen Lerp.h weight<0.5 branch),
-// exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2) = fma((1-b2)*g, g, v*b2), denom = sqrt(v)/bc2_sqrt + eps,
+// One element of torch.optim.Adam's single-tensor update (adam.py:394-547), one fp32 operation
+// per operation of torch's CPU kernels: lerp = fma(w, end-self, self) or fma(w-1, end-self, end)
+// (ATen Lerp.h, by |w| < 0.5), exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2) = fma((1-b2)*g, g, v*b2),
+// max_exp_avg_sq = maximum (NaN in either operand stays), denom = sqrt(v)/bc2_sqrt + eps,
 // param.addcdiv_(m, denom, -step_size) = p + (-step_size*m)/denom.  Only explicit fmaf() fuse;
-// sqrt and '/' are IEEE correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt).
+// sqrt and '/' are IEEE correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt).  m, v and
+// vmax equal live torch bit for bit; p stays within 0.5 ulp + 6 * 2^-24 * |update| of the exact
+// step, like torch's own p, whose vectorized CPU sqrt is not correctly rounded.
 //
 // CLIP (zs_adamset_run_clipped): the averaged gradient times the global-norm clip coefficient
 // (clip_grad_norm_'s `g.mul_(clip_coef_clamped)`), one IEEE multiply before maximize / weight decay;
@@ -263,11 +269,11 @@ __device__ __forceinline__ void adam_elem(float gsum, float& p, float& m, float&
   if (hp.maximize) g = -g;
   if (hp.wd != 0.0f) g = fmaf(hp.wd, p, g);  // grad.add(param, alpha=wd)
   p = p * hp.decay_mul;                       // AdamW: param.mul_(1 - lr*wd); 1.0 otherwise
-  m = fmaf(hp.omb1, g - m, m);
+  m = fmaf(hp.lerp_w, g - m, hp.lerp_hi ? g : m);
   v = fmaf(hp.omb2 * g, g, v * hp.beta2);
   float vv = v;
   if constexpr (AMS) {
-    vmax = fmaxf(vmax, v);
+    vmax = (v > vmax || v != v) ? v : vmax;  // torch.maximum: fmaxf would drop a NaN
     vv = vmax;
   }
   const float denom = sqrtf(vv) / hp.bc2_sqrt + hp.eps;
@@ -1744,7 +1750,9 @@ static int upload(const std::vector<T>& h, T** d) {
 
 static HP make_hp(const zs_adam_hparams* h) {
   HP hp;
-  hp.omb1 = h->one_minus_beta1;
+  const float w = h->one_minus_beta1;
+  hp.lerp_hi = std::fabs(w) < 0.5f ? 0 : 1;  // a NaN weight takes the high form, as in ATen
+  hp.lerp_w = hp.lerp_hi ? w - 1.0f : w;
   hp.beta2 = h->beta2;
   hp.omb2 = h->one_minus_beta2;
   hp.neg_step = h->neg_step_size;

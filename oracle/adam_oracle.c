@@ -3,11 +3,16 @@
  *
  * Restates the non-capturable single-tensor algorithm of torch/optim/adam.py:394-547 (the
  * reference delegates its Adam math there: zero1.py:88, zero2.py:120, zero3.py:161; pinned
- * torch==2.4.1 at pyproject.toml:13) in the rounding order of torch's CPU kernels:
- *   m = fmaf(1-b1, g-m, m)                 exp_avg.lerp_(grad, 1-b1)     (ATen Lerp.h, w < 0.5)
+ * torch==2.4.1 at pyproject.toml:13), one fp32 operation per operation of torch's CPU kernels:
+ *   w = 1-b1                               exp_avg.lerp_(grad, 1-b1)     (ATen Lerp.h)
+ *   m = |w| < 0.5 ? fmaf(w, g-m, m) : fmaf(w-1, g-m, g)
  *   v = fmaf((1-b2)*g, g, v*b2)            exp_avg_sq.mul_(b2).addcmul_(grad, grad, 1-b2)
+ *   vmax = max(vmax, v), NaN if either is  torch.maximum (amsgrad)
  *   denom = sqrtf(v)/bc2_sqrt + eps        (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
  *   p = p + (neg_step*m)/denom             param.addcdiv_(exp_avg, denom, value=-step_size)
+ * m, v and vmax equal live torch bit for bit; p is within 0.5 ulp + 6 * 2^-24 * |update| of the
+ * exact step, as torch's own p is, but not equal to it: torch's vectorized CPU sqrt is not the
+ * correctly rounded one (tests/test_adam_oracle.py).
  * plus the ZeRO grad averaging (zero1.py:84 / zero2.py:111: grad /= ws) and the ZeRO-1 carry
  * A_t = (S + (ws-1)·A_{t-1})/ws.
  *
@@ -54,11 +59,12 @@ static inline float adam_elem(float gsum, float* p, float* m, float* v, float* v
   if (hp->maximize) g = -g;
   if (hp->weight_decay != 0.0f) g = fmaf(hp->weight_decay, *p, g);
   float pp = *p * hp->decay_mul;
-  float mm = fmaf(hp->one_minus_beta1, g - *m, *m);
+  const float w = hp->one_minus_beta1;
+  float mm = fabsf(w) < 0.5f ? fmaf(w, g - *m, *m) : fmaf(w - 1.0f, g - *m, g);
   float vv = fmaf(hp->one_minus_beta2 * g, g, *v * hp->beta2);
   float use = vv;
   if (hp->amsgrad) {
-    *vmax = fmaxf(*vmax, vv);
+    *vmax = (vv > *vmax || vv != vv) ? vv : *vmax; /* NaN in either operand stays */
     use = *vmax;
   }
   const float denom = sqrtf(use) / hp->bc2_sqrt + hp->eps;

@@ -6,7 +6,8 @@ dependency of the reference, ``torch.optim.Adam`` (pinned torch==2.4.1, pyprojec
 non-capturable single-tensor algorithm is unchanged in the torch 2.10 used to capture fixtures,
 torch/optim/adam.py:394-547); it is restated here from that published algorithm.
 
-Pinned by tests/test_oracle.py against tests/golden/*.npz (outputs of the reference itself).
+Pinned by tests/test_oracle.py against tests/golden/*.npz (outputs of the reference itself), and
+``adam_update`` by tests/test_adam_oracle.py against live torch (state bit for bit).
 Never imported by the product (zero_amd).
 """
 from __future__ import annotations
@@ -45,40 +46,85 @@ def chunk_rows(d0: int, ws: int, rank: int) -> tuple[int, int]:
 # Adam (torch.optim.Adam / AdamW, non-capturable single-tensor path)
 # ----------------------------------------------------------------------------------------------
 def fma32(a, b, c):
-    """fp32 fused multiply-add emulated in fp64 (the product of two fp32 is exact in fp64)."""
-    return (np.asarray(a, F64) * np.asarray(b, F64) + np.asarray(c, F64)).astype(F32)
+    """fl32(a * b + c) with one rounding, elementwise over fp32 arrays (or scalars).
+
+    The product of two fp32 is exact in float64; TwoSum with the addend gives the float64-rounded
+    sum and its exact residual; a non-zero residual under an even last mantissa bit moves the sum
+    one float64 towards the residual (round to odd), which makes the final rounding to fp32 the
+    single rounding of the exact result (53 >= 24 + 2 bits)."""
+    a, b, c = np.broadcast_arrays(np.asarray(a, F32), np.asarray(b, F32), np.asarray(c, F32))
+    with np.errstate(all="ignore"):
+        p = a.astype(F64) * b.astype(F64)  # exact
+        c = c.astype(F64)
+        s = p + c
+        bb = s - p
+        err = (p - (s - bb)) + (c - bb)  # exact residual of the sum (TwoSum)
+        fix = np.isfinite(s) & np.isfinite(err) & (err != 0) & ((s.view(np.int64) & 1) == 0)
+        if fix.any():
+            s = s.copy()
+            s[fix] = np.nextafter(s[fix], np.where(err[fix] > 0, np.inf, -np.inf))
+        return s.astype(F32)
+
+
+def lerp32(start, end, w):
+    """ATen's lerp (Lerp.h) in fp32: start + w*(end-start) for |w| < 0.5, end - (end-start)*(1-w)
+    otherwise, each one fma; ``w - 1`` is one fp32 subtraction."""
+    w = F32(w)
+    d = (np.asarray(end, F32) - np.asarray(start, F32)).astype(F32)
+    if abs(w) < F32(0.5):
+        return fma32(w, d, start)
+    return fma32(F32(w - F32(1)), d, end)
 
 
 def adam_update(p, g, m, v, step, *, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                amsgrad=False, maximize=False, decoupled=False, vmax=None):
-    """One update of adam.py:394-547; returns new (p, m, v, vmax).  All arrays fp32.
+                amsgrad=False, maximize=False, decoupled=False, vmax=None, grad_div=1.0,
+                carry=None, carry_mul=0.0, clip_coef=None):
+    """One update of adam.py:394-547; returns new (p, m, v, vmax), and the new carry as a fifth
+    when ``carry`` is given.  All arrays fp32.
 
-    Rounding order follows torch's CPU kernels: lerp_ → fma(1-β1, g-m, m) (ATen Lerp.h,
-    weight < 0.5 branch); mul_(β2).addcmul_(g, g, 1-β2) → fma((1-β2)·g, g, v·β2);
-    denom = sqrt(v)/sqrt(bc2) + eps; addcdiv_(m, denom, -step_size) → p + (-step_size·m)/denom.
+    Every operation is the one fp32 operation of torch's CPU kernels, so exp_avg, exp_avg_sq and
+    max_exp_avg_sq equal torch's bit for bit (tests/test_adam_oracle.py): lerp_ → ``lerp32``;
+    mul_(β2).addcmul_(g, g, 1-β2) → fma((1-β2)·g, g, v·β2); maximum propagates NaN.  The parameter,
+    denom = sqrt(v)/sqrt(bc2) + eps; addcdiv_(m, denom, -step_size) → p + (-step_size·m)/denom,
+    uses the correctly rounded sqrt, which torch's vectorized CPU sqrt is not: p is pinned to torch
+    within a bound only.
+
+    ``g`` is the gradient sum: it is divided by ``grad_div`` (with ``carry``: after adding
+    ``carry_mul * carry``, and the quotient is the new carry), then multiplied by ``clip_coef``
+    when given — the ZeRO averaging, the ZeRO-1 carry and the clip of csrc/zs_kernels.hip adam_elem.
     """
     beta1, beta2 = betas
-    p = np.asarray(p, F32).copy()
-    g = np.asarray(g, F32)
-    if maximize:  # adam.py:402
-        g = -g
-    if weight_decay != 0:
-        if decoupled:  # adam.py:421-423
-            p = (p * F32(1 - lr * weight_decay)).astype(F32)
-        else:  # adam.py:433 grad.add(param, alpha=wd)
-            g = fma32(F32(weight_decay), p, g)
-    m = fma32(F32(1 - beta1), (g - m).astype(F32), m)  # adam.py:463 exp_avg.lerp_(grad, 1-β1)
-    v = fma32((F32(1 - beta2) * g).astype(F32), g, (np.asarray(v, F32) * F32(beta2)).astype(F32))
-    bc1 = 1 - beta1 ** step  # adam.py:532-537 (python floats)
-    bc2 = 1 - beta2 ** step
-    step_size = lr / bc1
-    bc2_sqrt = bc2 ** 0.5
-    vv = v
-    if amsgrad:  # adam.py:539-543
-        vmax = np.maximum(vmax, v).astype(F32)
-        vv = vmax
-    denom = (np.sqrt(vv) / F32(bc2_sqrt)).astype(F32) + F32(eps)
-    p = (p + (F32(-step_size) * m).astype(F32) / denom.astype(F32)).astype(F32)
+    with np.errstate(all="ignore"):
+        p = np.asarray(p, F32).copy()
+        g = np.asarray(g, F32)
+        if carry is not None:
+            g = (g + (F32(carry_mul) * np.asarray(carry, F32)).astype(F32)).astype(F32)
+        g = (g / F32(grad_div)).astype(F32)
+        if carry is not None:
+            carry = g.copy()
+        if clip_coef is not None:
+            g = (g * F32(clip_coef)).astype(F32)
+        if maximize:  # adam.py:402
+            g = -g
+        if weight_decay != 0:
+            if decoupled:  # adam.py:421-423
+                p = (p * F32(1 - lr * weight_decay)).astype(F32)
+            else:  # adam.py:433 grad.add(param, alpha=wd)
+                g = fma32(F32(weight_decay), p, g)
+        m = lerp32(m, g, F32(1 - beta1))  # adam.py:463 exp_avg.lerp_(grad, 1-β1)
+        v = fma32((F32(1 - beta2) * g).astype(F32), g, (np.asarray(v, F32) * F32(beta2)).astype(F32))
+        bc1 = 1 - beta1 ** step  # adam.py:532-537 (python floats)
+        bc2 = 1 - beta2 ** step
+        step_size = lr / bc1
+        bc2_sqrt = bc2 ** 0.5
+        vv = v
+        if amsgrad:  # adam.py:539-543; torch.maximum and np.maximum both propagate NaN
+            vmax = np.maximum(np.asarray(vmax, F32), v).astype(F32)
+            vv = vmax
+        denom = ((np.sqrt(vv) / F32(bc2_sqrt)).astype(F32) + F32(eps)).astype(F32)
+        p = (p + ((F32(-step_size) * m).astype(F32) / denom).astype(F32)).astype(F32)
+    if carry is not None:
+        return p, m.astype(F32), v.astype(F32), vmax, carry
     return p, m.astype(F32), v.astype(F32), vmax
 
 

@@ -10,10 +10,8 @@ torch/optim/sgd.py _single_tensor_sgd), bit for bit in fp32.
                     g   = fma(momentum, buf, g) if nesterov else buf
     p = fma(-lr, g, p)
 
-``fma32`` is an exact fp32 fused multiply-add: the product of two fp32 is exact in float64; TwoSum
-with the addend gives the float64-rounded sum and its exact residual; a non-zero residual under an
-even last mantissa bit moves the sum one float64 towards the residual (round to odd), which makes
-the final rounding to fp32 the single rounding of the exact result (53 >= 24 + 2 bits).
+``fma32`` is the exact fp32 fused multiply-add of oracle/zero_oracle.py (one copy, shared with the
+Adam restatement).
 """
 from __future__ import annotations
 
@@ -21,23 +19,9 @@ import math
 
 import numpy as np
 
+from oracle.zero_oracle import fma32  # noqa: F401  (re-exported: so.fma32)
+
 F32, F64 = np.float32, np.float64
-
-
-def fma32(a, b, c):
-    """fl32(a * b + c) with one rounding, elementwise over fp32 arrays (or scalars)."""
-    a, b, c = np.broadcast_arrays(np.asarray(a, F32), np.asarray(b, F32), np.asarray(c, F32))
-    with np.errstate(all="ignore"):
-        p = a.astype(F64) * b.astype(F64)  # exact
-        c = c.astype(F64)
-        s = p + c
-        bb = s - p
-        err = (p - (s - bb)) + (c - bb)  # exact residual of the sum (TwoSum)
-        fix = np.isfinite(s) & np.isfinite(err) & (err != 0) & ((s.view(np.int64) & 1) == 0)
-        if fix.any():
-            s = s.copy()
-            s[fix] = np.nextafter(s[fix], np.where(err[fix] > 0, np.inf, -np.inf))
-        return s.astype(F32)
 
 
 def fma32_plain(a, b, c):
