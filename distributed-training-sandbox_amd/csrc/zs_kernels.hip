@@ -418,10 +418,20 @@ __device__ __forceinline__ void adam_full_chunk(const AdamSeg& s, int64_t e0, co
   const S2 lo(SPLIT ? (unsigned short*)s.master_out + e0 : nullptr), pb(s.p_out + e0);
   uint4 gq[G], pq[G], mq[G], vq[G], xq[G], cq[G];
   uint2 gd[G], hd[G], ld[G];
+  // fp32 gradients over the split master (G = 4): the gradient's groups 2 and 3 through the first
+  // base and a second lane offset 8 KiB on — one vector register instead of a second pair of
+  // scalar ones, which this instance (five fp32 streams of two bases each under amsgrad) has not
+  uint32_t o4g = o4 + 8192u;
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (HASG && G32 && SPLIT) asm volatile("" : "+v"(o4g));
+#endif
 #pragma unroll
   for (int u = 0; u < G; ++u) {
     if constexpr (HASG) {
-      if constexpr (G32) gq[u] = nt_ld16(gf.at(u, o4));
+      if constexpr (G32 && SPLIT)
+        gq[u] = nt_ld16(u < S4::kPer ? gf.at(u, o4)
+                                     : lane_ptr(gf.base[0], o4g, (u % S4::kPer) * S4::kBytes - 4096));
+      else if constexpr (G32) gq[u] = nt_ld16(gf.at(u, o4));
       else gd[u] = nt_ld8(gh.at(u, o2));
     }
     if constexpr (SPLIT) {
@@ -1134,6 +1144,69 @@ __global__ __launch_bounds__(kThreads) void accumulate_kernel(T* dst, const T* s
 }
 
 // ----------------------------------------------------------------------------------------------
+// widening accumulate: fp32 dst = bf16 a + bf16 src (FIRST), or fp32 dst += bf16 src
+// (accumulation_dtype=torch.float32: later micro-batches' bf16 chunks summed in an fp32 arena)
+// ----------------------------------------------------------------------------------------------
+// Mixed widths, so the wave-dense pattern of convert_kernel below and not accumulate_kernel's
+// lane-contiguous 16 B on every stream: a wave step covers kWidenSpan elements in kWidenU blocks of
+// 256; in block u lane l handles elements [256u + 4l, +4) — one 16-B fp32 access and one 8-B bf16
+// access per stream, every wave instruction one contiguous 1 KiB (fp32) or 512 B (bf16) span.  All
+// of a step's loads (2 kWidenU) are issued before its first store; grid-stride over wave steps; the
+// n % kWidenSpan tail by block 0.  FIRST: 2 + 2 B read, 4 B written per element; otherwise 4 + 2 B
+// read, 4 B written.  No atomics, LDS or scratch.  Widening is exact (bits << 16), then one IEEE
+// fp32 add per element: a NaN stays a NaN, Inf + -Inf is NaN, denormals are kept.
+// Cache policy by size (NT) over the bytes touched, under `zs_tune("accumulate_nt")` as zs_accumulate.
+constexpr int kWidenU = 4;
+constexpr int64_t kWidenSpan = 256 * kWidenU;
+
+__device__ __forceinline__ void widen4(const uint2& h, float (&f)[4]) {
+  f[0] = __uint_as_float(h.x << 16), f[1] = __uint_as_float(h.x & 0xffff0000u);
+  f[2] = __uint_as_float(h.y << 16), f[3] = __uint_as_float(h.y & 0xffff0000u);
+}
+
+template <bool FIRST, bool NT>
+__global__ __launch_bounds__(kThreads) void accumulate_widen_kernel(float* dst,
+                                                                    const unsigned short* a,
+                                                                    const unsigned short* src,
+                                                                    int64_t n) {
+#pragma clang fp contract(off)
+  const int64_t steps = n / kWidenSpan;
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = int64_t(gridDim.x) * (kThreads / 64);
+  for (int64_t w = int64_t(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6); w < steps;
+       w += nwaves) {
+    const int64_t base = w * kWidenSpan + 4 * lane;
+    float* d = dst + base;
+    const unsigned short* s = src + base;
+    uint4 x4[kWidenU];
+    uint2 x2[kWidenU], y2[kWidenU];
+#pragma unroll
+    for (int u = 0; u < kWidenU; ++u) {
+      if constexpr (FIRST) x2[u] = ld8<NT>(a + base + 256 * u);
+      else x4[u] = ld16<NT>(d + 256 * u);
+    }
+#pragma unroll
+    for (int u = 0; u < kWidenU; ++u) y2[u] = ld8<NT>(s + 256 * u);
+#pragma unroll
+    for (int u = 0; u < kWidenU; ++u) {
+      float x[4], y[4];
+      if constexpr (FIRST) widen4(x2[u], x);
+      else unpack4(x4[u], x);
+      widen4(y2[u], y);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x[j] = x[j] + y[j];
+      st16<NT>(d + 256 * u, pack4(x));
+    }
+  }
+  if (blockIdx.x == 0) {
+    const gptr<float> gd = glob(dst);
+    const gptr<const unsigned short> ga = glob(a), gs = glob(src);
+    for (int64_t i = steps * kWidenSpan + threadIdx.x; i < n; i += kThreads)
+      gd[i] = (FIRST ? bf16_to_f32(ga[i]) : gd[i]) + bf16_to_f32(gs[i]);
+  }
+}
+
+// ----------------------------------------------------------------------------------------------
 // fp32 <-> bf16 conversion (the bf16 gradient exchange of fp32-parameter models)
 // ----------------------------------------------------------------------------------------------
 // Wave-dense accesses: a wave step covers kConvSpan elements in kConvU blocks of 256; in block u
@@ -1793,9 +1866,16 @@ static int launch_adam_tables(const AdamSeg* vec, const int64_t* vpre, int64_t n
       else ZS_LAUNCH(KERNEL, GT, false, false, S, TAB, PRE, NS, NCH);                         \
     }                                                                                         \
   } while (0)
+  // fp32 gradients over the split master (no carry: set_create refuses one)
+#define ZS_DISPATCH_A(KERNEL, GT, S, TAB, PRE, NS, NCH)                                       \
+  do {                                                                                        \
+    if (ams) ZS_LAUNCH(KERNEL, GT, true, false, S, TAB, PRE, NS, NCH);                        \
+    else ZS_LAUNCH(KERNEL, GT, false, false, S, TAB, PRE, NS, NCH);                           \
+  } while (0)
 #define ZS_DISPATCH(KERNEL, TAB, PRE, NS, NCH)                                                \
   do {                                                                                        \
-    if (g_dtype == ZS_F32) ZS_DISPATCH_AC(KERNEL, float, false, TAB, PRE, NS, NCH);          \
+    if (g_dtype == ZS_F32 && split) ZS_DISPATCH_A(KERNEL, float, true, TAB, PRE, NS, NCH);   \
+    else if (g_dtype == ZS_F32) ZS_DISPATCH_AC(KERNEL, float, false, TAB, PRE, NS, NCH);     \
     else if (split) ZS_DISPATCH_AC(KERNEL, unsigned short, true, TAB, PRE, NS, NCH);         \
     else ZS_DISPATCH_AC(KERNEL, unsigned short, false, TAB, PRE, NS, NCH);                   \
   } while (0)
@@ -1819,6 +1899,7 @@ static int launch_adam_tables(const AdamSeg* vec, const int64_t* vpre, int64_t n
     ZS_HIP(hipGetLastError());
   }
 #undef ZS_DISPATCH
+#undef ZS_DISPATCH_A
 #undef ZS_DISPATCH_AC
 #undef ZS_LAUNCH
   return ZS_OK;
@@ -1846,9 +1927,16 @@ static int launch_sgd_tables(const zs_adamset* as, bool mom, const SgdHP& hp, co
       else ZS_LAUNCH(KERNEL, GT, false, S, false, TAB, PRE, NS, NCH);                         \
     }                                                                                         \
   } while (0)
+  // fp32 gradients over the split master (no carry: set_create refuses one)
+#define ZS_DISPATCH_M(KERNEL, GT, S, TAB, PRE, NS, NCH)                                       \
+  do {                                                                                        \
+    if (mom) ZS_LAUNCH(KERNEL, GT, false, S, true, TAB, PRE, NS, NCH);                        \
+    else ZS_LAUNCH(KERNEL, GT, false, S, false, TAB, PRE, NS, NCH);                           \
+  } while (0)
 #define ZS_DISPATCH(KERNEL, TAB, PRE, NS, NCH)                                                \
   do {                                                                                        \
-    if (g_dtype == ZS_F32) ZS_DISPATCH_CM(KERNEL, float, false, TAB, PRE, NS, NCH);          \
+    if (g_dtype == ZS_F32 && split) ZS_DISPATCH_M(KERNEL, float, true, TAB, PRE, NS, NCH);   \
+    else if (g_dtype == ZS_F32) ZS_DISPATCH_CM(KERNEL, float, false, TAB, PRE, NS, NCH);     \
     else if (split) ZS_DISPATCH_CM(KERNEL, unsigned short, true, TAB, PRE, NS, NCH);         \
     else ZS_DISPATCH_CM(KERNEL, unsigned short, false, TAB, PRE, NS, NCH);                   \
   } while (0)
@@ -1872,6 +1960,7 @@ static int launch_sgd_tables(const zs_adamset* as, bool mom, const SgdHP& hp, co
     ZS_HIP(hipGetLastError());
   }
 #undef ZS_DISPATCH
+#undef ZS_DISPATCH_M
 #undef ZS_DISPATCH_CM
 #undef ZS_LAUNCH
   return ZS_OK;
@@ -2040,6 +2129,36 @@ int zs_accumulate(void* dst, const void* src, int64_t n, int dtype, uintptr_t st
     if (nt) ZS_ACC(unsigned short, true); else ZS_ACC(unsigned short, false);
   }
 #undef ZS_ACC
+  ZS_HIP(hipGetLastError());
+  return ZS_OK;
+}
+
+int zs_accumulate_widen(float* dst, const void* a_bf16, const void* src_bf16, int64_t n,
+                        uintptr_t stream) {
+  ZS_REQUIRE(n >= 0, "zs_accumulate_widen: n < 0");
+  if (n == 0) return ZS_OK;
+  ZS_REQUIRE(dst != nullptr && src_bf16 != nullptr, "zs_accumulate_widen: NULL buffer");
+  ZS_REQUIRE(aligned(reinterpret_cast<uint64_t>(dst), 16),
+             "zs_accumulate_widen: dst must be 16-byte aligned");
+  ZS_REQUIRE(aligned(reinterpret_cast<uint64_t>(a_bf16), 8) &&
+                 aligned(reinterpret_cast<uint64_t>(src_bf16), 8),
+             "zs_accumulate_widen: a and src must be 8-byte aligned");
+  const bool first = a_bf16 != nullptr;
+  const int64_t blocks = std::max<int64_t>(1, (n / kWidenSpan + 3) / 4);
+  const int grid = int(std::min<int64_t>(blocks, grid_cap()));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int force = accumulate_nt_mode();
+  const bool nt = force < 0 ? n * (first ? 8 : 10) > kMallBytes : force == 1;  // bytes touched
+  const unsigned short* a = static_cast<const unsigned short*>(a_bf16);
+  const unsigned short* s = static_cast<const unsigned short*>(src_bf16);
+#define ZS_ACCW(F, NT) hipLaunchKernelGGL((accumulate_widen_kernel<F, NT>), dim3(grid), dim3(kThreads), 0, st, \
+                                          dst, a, s, n)
+  if (first) {
+    if (nt) ZS_ACCW(true, true); else ZS_ACCW(true, false);
+  } else {
+    if (nt) ZS_ACCW(false, true); else ZS_ACCW(false, false);
+  }
+#undef ZS_ACCW
   ZS_HIP(hipGetLastError());
   return ZS_OK;
 }
@@ -2297,7 +2416,6 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   ZS_REQUIRE(p_dtype == ZS_BF16 || p_dtype == ZS_BF16_SPLIT,
              "%s: p_dtype must be ZS_BF16 or ZS_BF16_SPLIT (got %d)", fn, p_dtype);
   const bool split = p_dtype == ZS_BF16_SPLIT;
-  ZS_REQUIRE(!split || g_dtype == ZS_BF16, "%s: ZS_BF16_SPLIT needs bf16 grads", fn);
   const int64_t msz = split ? 2 : 4;  // bytes per element of master / master_out
   const int64_t gsz = g_dtype == ZS_F32 ? 4 : 2;
   ZS_REQUIRE(n < (int64_t(1) << 31), "%s: %lld segments (max 2^31 - 1)", fn,
@@ -2330,6 +2448,11 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
     }
     ZS_REQUIRE(!split || (s.master_out && s.p_out),
                "%s: seg %lld: a split master needs master_out (residual) and p_out", fn,
+               (long long)i);
+    // fp32 gradients over a split master: ZeRO-3's fp32 accumulation arena; ZeRO-1 (the carry)
+    // never has such a set, so no CARRY instance of it exists
+    ZS_REQUIRE(!(split && g_dtype == ZS_F32 && s.carry),
+               "%s: seg %lld: a ZS_BF16_SPLIT set with fp32 grads takes no carry", fn,
                (long long)i);
     const int c = s.carry ? 1 : 0;
     ZS_REQUIRE(carry_state < 0 || carry_state == c,
@@ -2542,11 +2665,13 @@ int zs_adamset_grad_sqnorm(const zs_adamset* as, double* partials, uintptr_t str
   hipLaunchKernelGGL((grad_sqnorm_kernel<GT, S, NT>), dim3(int(as->sq_vec)), dim3(kThreads), 0, \
                      st, as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks, partials)
     if (sqnorm_nt()) {
-      if (f32) ZS_SQ(float, false, true);
+      if (f32 && split) ZS_SQ(float, true, true);
+      else if (f32) ZS_SQ(float, false, true);
       else if (split) ZS_SQ(unsigned short, true, true);
       else ZS_SQ(unsigned short, false, true);
     } else {
-      if (f32) ZS_SQ(float, false, false);
+      if (f32 && split) ZS_SQ(float, true, false);
+      else if (f32) ZS_SQ(float, false, false);
       else if (split) ZS_SQ(unsigned short, true, false);
       else ZS_SQ(unsigned short, false, false);
     }

@@ -130,13 +130,23 @@ def adam_hparams(lr, beta1, beta2, eps, weight_decay, step, *, decoupled=False, 
 
 class AdamSet:
     """Fused Adam over segments; ``segs`` is an (n, 9) int64/uint64 array in zs_adam_seg order:
-    g, master, master_out, p_out, m, v, vmax, carry, n."""
+    g, master, master_out, p_out, m, v, vmax, carry, n.
+
+    A ``ZS_BF16_SPLIT`` set reads bf16 gradients unless ``wide_grads=True`` says that the ``g``
+    column points at fp32 buffers (ZeRO-3's fp32 accumulation arena).  The library accepts either
+    width and cannot tell which one a raw pointer holds; the wrong one reads twice the buffer, so
+    the wide one is refused here, before the library, unless it is asked for by name."""
 
     FIELDS = ("g", "master", "master_out", "p_out", "m", "v", "vmax", "carry", "n")
 
     _CREATE = "zs_adamset_create"
 
-    def __init__(self, segs: np.ndarray, g_dtype: int, p_dtype: int = _lib.ZS_BF16):
+    def __init__(self, segs: np.ndarray, g_dtype: int, p_dtype: int = _lib.ZS_BF16, *,
+                 wide_grads: bool = False):
+        if int(p_dtype) == _lib.ZS_BF16_SPLIT and int(g_dtype) == _lib.ZS_F32 and not wide_grads:
+            raise _lib.ZeroAmdError(self._CREATE, _lib.ZS_ERR_INVALID,
+                                    "ZS_BF16_SPLIT needs bf16 grads (fp32 gradient buffers: "
+                                    "wide_grads=True)")
         segs = np.ascontiguousarray(np.asarray(segs, dtype=np.uint64).reshape(-1, 9))
         arr = (AdamSeg * max(len(segs), 1))()
         ctypes.memmove(arr, segs.ctypes.data, segs.nbytes)
@@ -309,3 +319,32 @@ def accumulate(dst, src, stream=None) -> None:
     st = torch.cuda.current_stream(dst.device) if stream is None else stream
     _lib.call("zs_accumulate", dst.data_ptr(), src.data_ptr(), n, zs_dtype(dst.dtype),
               stream_handle(st))
+
+
+def accumulate_widen(dst, src, a=None, stream=None) -> None:
+    """fp32 ``dst`` from bf16 contributions (zs_accumulate_widen): ``dst[i] = a[i] + src[i]`` when
+    ``a`` (bf16) is given, ``dst[i] += src[i]`` otherwise; both bf16 operands are widened exactly
+    and each element gets one IEEE fp32 add.  Contiguous tensors of one element count, ``dst``
+    16-byte and ``a`` / ``src`` 8-byte aligned, enqueued on ``stream``.  With ``CHECK_EXTENTS`` on,
+    every range is checked against its tensor's storage before anything is launched."""
+    import torch
+
+    if dst.dtype != torch.float32 or src.dtype != torch.bfloat16 or \
+            (a is not None and a.dtype != torch.bfloat16):
+        raise ValueError("zero_amd: accumulate_widen needs an fp32 dst and bf16 src (and a)")
+    n = dst.numel()
+    if src.numel() != n or (a is not None and a.numel() != n):
+        raise ValueError("zero_amd: accumulate_widen needs dst, src (and a) of one element count")
+    if not (src.is_contiguous() and dst.is_contiguous() and (a is None or a.is_contiguous())):
+        raise ValueError("zero_amd: accumulate_widen needs contiguous tensors")
+    if n and (dst.data_ptr() % 16 or src.data_ptr() % 8 or (a is not None and a.data_ptr() % 8)):
+        raise ValueError("zero_amd: accumulate_widen needs dst 16-byte and src (and a) 8-byte "
+                         "aligned")
+    if CHECK_EXTENTS:
+        check_extents([dst.data_ptr()], [4 * n], [dst], "accumulate_widen destination")
+        check_extents([src.data_ptr()], [2 * n], [src], "accumulate_widen source")
+        if a is not None:
+            check_extents([a.data_ptr()], [2 * n], [a], "accumulate_widen first operand")
+    st = torch.cuda.current_stream(dst.device) if stream is None else stream
+    _lib.call("zs_accumulate_widen", dst.data_ptr(), None if a is None else a.data_ptr(),
+              src.data_ptr(), n, stream_handle(st))

@@ -88,9 +88,10 @@ class MemoryReport:
 def memory_report(model, optimizer, device) -> MemoryReport:
     params = list(model.parameters())
     p_l, p_p = _walk(params)
-    # (ZeRO-3 gradient accumulation: the accumulating passes' staging buffer is gradient memory too)
-    staging = getattr(optimizer, "grad_staging", None)
-    g_l, g_p = _walk([p.grad for p in params] + [staging() if callable(staging) else None])
+    # (ZeRO-3 gradient accumulation: the accumulating passes' staging buffer is gradient memory
+    # too, and so is the fp32 accumulation arena of accumulation_dtype=torch.float32)
+    extra = [getattr(optimizer, name, None) for name in ("grad_staging", "accumulation_arena")]
+    g_l, g_p = _walk([p.grad for p in params] + [f() if callable(f) else None for f in extra])
     o_l, o_p = _walk(_state_tensors(optimizer))
     on_gpu = torch.cuda.is_available() and torch.device(device).type == "cuda"
     from ..engine import placed_bytes, placed_peak_bytes

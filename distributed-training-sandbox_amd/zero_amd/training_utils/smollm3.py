@@ -64,10 +64,22 @@ def train_step(model, optimizer, input_ids):
     return loss
 
 
+def accumulating_optimizer(model, lr: float = 1e-5, *, accumulation_dtype=None, **kw):
+    """train_fsdp.py:85's AdamW behind ZeRO-3 update mode with gradient accumulation, for
+    ``train_step_accumulated``.  ``accumulation_dtype=torch.float32``: the micro-batches' bf16
+    gradient chunks are summed in an fp32 arena (one rounding to 2^-24 per pass instead of 2^-9).
+    Further keywords go to ``zero3.ShardedOptimizer``."""
+    from ..zero3 import ShardedOptimizer
+
+    return ShardedOptimizer(torch.optim.AdamW(model.parameters(), lr=lr), update=True,
+                            grad_accumulation=True, accumulation_dtype=accumulation_dtype, **kw)
+
+
 def train_step_accumulated(model, optimizer, micro_batches):
     """``train_step`` over several micro-batches: each loss divided by their count, one backward
-    per micro-batch, one step (``zero3.ShardedOptimizer(..., update=True, grad_accumulation=True)``,
-    or any optimizer whose gradients accumulate).  Returns the mean loss."""
+    per micro-batch, one step (``accumulating_optimizer`` above, i.e.
+    ``zero3.ShardedOptimizer(..., update=True, grad_accumulation=True[, accumulation_dtype=
+    torch.float32])``, or any optimizer whose gradients accumulate).  Returns the mean loss."""
     micro_batches = list(micro_batches)
     total = None
     for input_ids in micro_batches:

@@ -31,7 +31,14 @@ real rows), and ``param.data`` is a view of its slot between gathers.  Two modes
     after the first is reduce-scattered into a staging buffer and added to the grad chunk arena
     by a fused HIP kernel (zs_accumulate) — one rounding per pass in the chunks' dtype, as
     torch's AccumulateGrad; ``zero_grad()`` discards the accumulation, the caller scales each
-    micro-batch's loss by their count.
+    micro-batch's loss by their count.  ``accumulation_dtype=torch.float32`` (with it) keeps the
+    running sum of bf16 chunks in an fp32 arena from the second pass on (zs_accumulate_widen:
+    exact widening, one fp32 add per pass) and ``step()`` reads that arena through the
+    fp32-gradient instances of the fused update; a step of one pass is untouched, ``p.grad`` of a
+    bf16 parameter stays None after an accumulating pass (torch refuses an fp32 ``.grad`` there)
+    and ``grad_arena()`` / ``accumulation_arena_dtype`` name the arena that holds the sums.  The
+    option is accepted and changes nothing where the chunks already are fp32 and at world size 1
+    (no arena: autograd accumulates into ``p.grad`` itself).
 
 ``materialize`` is a zero-copy RCCL all-gather from the chunk slot (already padded to S) straight
 into the full tensor (rows of torch.chunk are contiguous: full = [chunk_0 | … | chunk_{ws-1}]),
@@ -1356,13 +1363,19 @@ class _GradReducer:
     later pass reduce-scatters bucket k into a staging buffer (the collective overwrites its
     receive buffer) and adds it to the bucket's contiguous range of the grad chunk arena with one
     zs_accumulate on the collective's stream; the last bucket's done sync is recorded after its
-    add.  Between passes the per-backward counting is reset and ``had_grad`` keeps the union."""
+    add.  Between passes the per-backward counting is reset and ``had_grad`` keeps the union.
+    ``accumulation_dtype=torch.float32`` over bf16 chunks (``widen``): the add is
+    zs_accumulate_widen into the fp32 arena ``opt._A`` — the second pass of a step sums the bf16
+    arena's range and the staging buffer into it, later passes add the staging buffer to it."""
 
     def __init__(self, opt, bucket_bytes: int):
         self.opt = opt
         self.grad_accumulation = bool(getattr(opt, "_grad_accumulation", False))
         self.passes = 0                  # backward passes folded in since the last reset
         self.n_accumulate_launches = 0   # zs_accumulate launches, ever
+        self.n_widen_launches = 0        # zs_accumulate_widen launches, ever
+        # accumulation_dtype=float32 over bf16 chunks: accumulating passes add into opt._A
+        self.widen = bool(getattr(opt, "_acc_widen", False))
         self._accumulating = False       # the running pass adds to the arena
         self._staging = None             # an accumulating pass's receive buffer
         arena = opt._arena
@@ -1454,6 +1467,8 @@ class _GradReducer:
                 # ready sync is recorded: the collective's stream waits on that record, so the
                 # fill is behind it for every launch path
                 self.staging()
+                if self.widen:
+                    self.opt._acc_arena()
 
     def _end_pass(self):
         """A backward has ended with every bucket launched: the per-backward counting starts
@@ -1485,9 +1500,17 @@ class _GradReducer:
         return st
 
     def _accumulate(self, k: int, stream_h: int):
-        """Bucket k's range of the arena += the staging buffer, on the collective's stream."""
+        """Bucket k's range of the arena += the staging buffer, on the collective's stream.
+        ``widen``: the fp32 arena's range = the bf16 arena's + staging in the step's second pass,
+        += staging in later ones."""
         G, st = self.opt._G, self._staging
         s, n = self._range[k]
+        if self.widen:
+            A = self.opt._A
+            a = G.data_ptr() + s * G.element_size() if self.passes == 1 else None
+            _lib.call("zs_accumulate_widen", A.data_ptr() + s * 4, a, st.data_ptr(), n, stream_h)
+            self.n_widen_launches += 1
+            return
         _lib.call("zs_accumulate", G.data_ptr() + s * G.element_size(), st.data_ptr(), n,
                   zs_dtype(G.dtype), stream_h)
         self.n_accumulate_launches += 1
@@ -1575,6 +1598,8 @@ class _GradReducer:
         if self.K and opt.runtime.stream is not None:
             self.ev_done[self.K - 1].wait(opt.runtime._cur_h())
         if opt._G.dtype != opt.params[0].dtype:  # a bf16 exchange's chunks stay internal
+            return
+        if self.widen and self.passes:  # the sums are fp32 now: torch refuses such a .grad
             return
         shapes, views = opt._arena.shard_shapes, self._shard_grad
         params = opt.params
@@ -1801,7 +1826,8 @@ class ShardedOptimizer:
     def __init__(self, optimizer: Optimizer, *, update: bool = False, comm=None, sync: bool = True,
                  gather_dtype=None, bucket_mb: float = RS_BUCKET_MB, grad_comm: str | None = None,
                  gather_wave: int = GATHER_WAVE, side_stream: bool = True,
-                 stream_sync: str = STREAM_SYNC, grad_accumulation: bool = False):
+                 stream_sync: str = STREAM_SYNC, grad_accumulation: bool = False,
+                 accumulation_dtype=None):
         # grad_accumulation (update mode): several backward passes per step(), each reduce-
         # scattered and added to the chunks already held (_GradReducer); off: the second backward
         # before step() is an error, as before
@@ -1809,6 +1835,20 @@ class ShardedOptimizer:
             raise ValueError("grad_accumulation=True applies to update mode (reference mode never "
                              "updates: zero3.py:150-153 drops every gradient)")
         self._grad_accumulation = bool(grad_accumulation)
+        # accumulation_dtype=torch.float32: the second and later passes of a step sum the bf16
+        # chunks in an fp32 arena (zs_accumulate_widen) and step() reads that arena; None: the
+        # running sum is rounded to the chunks' dtype every pass, as torch's AccumulateGrad.
+        # Accepted and without effect where the chunks already are fp32 (fp32 parameters without
+        # grad_comm) and at world size 1 (no arena: autograd accumulates into p.grad itself).
+        if accumulation_dtype not in (None, torch.float32):
+            raise ValueError("accumulation_dtype must be None or torch.float32 (got %r)"
+                             % (accumulation_dtype,))
+        if accumulation_dtype is not None and not grad_accumulation:
+            raise ValueError("accumulation_dtype applies to grad_accumulation=True (one backward "
+                             "per step accumulates nothing)")
+        self._accumulation_dtype = accumulation_dtype
+        self._acc_widen = False  # (set with the update state: bf16 chunks at ws > 1)
+        self._A = None
         # "adam" or "sgd" (TypeError for anything else); reference mode never updates either
         self._kind = optimizer_kind(optimizer)
         if self._kind == "sgd":
@@ -1903,9 +1943,12 @@ class ShardedOptimizer:
         self._split = split
         gdt = torch.bfloat16 if self._grad_comm else ar.dtype
         self._G = torch.zeros(L, dtype=gdt, device=ar.device) if self.world_size > 1 else None
+        self._acc_widen = (self._accumulation_dtype is torch.float32 and self._G is not None
+                           and gdt == torch.bfloat16)
         self._steps = np.zeros(len(self.params), np.int64)
         self._adam_cache = {}
-        self._fast_sig = self._fast_sets = None
+        # the sets of the last uniform step, per arena they read (False: _G, True: _A)
+        self._fast_sig, self._fast_sets = {}, {}
         self._step_shared = self._step_shared_sig = None
         self._retired = []
         self._expose_state()
@@ -1980,8 +2023,37 @@ class ShardedOptimizer:
         elements of each slot are defined: with ``grad_accumulation`` the alignment pads between
         slots (under 64 elements each) may hold stale sums of other buckets — the one staging
         buffer serves buckets of different layouts — so a pass over the whole buffer must go by
-        the arena's slots, as the collectives and the update do."""
+        the arena's slots, as the collectives and the update do.
+
+        ``accumulation_dtype=torch.float32`` over bf16 chunks: after two or more passes of a step
+        the sums are in the fp32 accumulation arena (the same geometry), which is what this
+        returns then; after one pass, and after step() or zero_grad(), the bf16 arena."""
+        if self._acc_widen and self._A is not None and self._reducer.passes >= 2:
+            return self._A
         return self._G
+
+    @property
+    def accumulation_arena_dtype(self):
+        """The dtype of ``grad_arena()`` now (None without an arena: world size 1, reference
+        mode)."""
+        a = self.grad_arena()
+        return None if a is None else a.dtype
+
+    def accumulation_arena(self):
+        """The fp32 accumulation arena (``accumulation_dtype=torch.float32`` over bf16 chunks; None
+        until the second backward of some step).  Its contents are the step's sums only while
+        ``grad_arena()`` returns it."""
+        return self._A
+
+    def _acc_arena(self):
+        """The fp32 accumulation arena: _G's geometry, allocated at the first accumulating pass
+        (zero-filled on the current stream, before any bucket's ready record) and kept."""
+        A = self._A
+        if A is None:
+            A = self._A = torch.zeros(self._G.numel(), dtype=torch.float32, device=self._G.device)
+            if self.runtime.stream is not None:
+                A.record_stream(self.runtime.stream)
+        return A
 
     def grad_staging(self):
         """The receive buffer of accumulating passes (``grad_accumulation``; None until the second
@@ -2035,15 +2107,16 @@ class ShardedOptimizer:
             param.grad = None
         return done
 
-    def _adam_rows(self, idx):
+    def _adam_rows(self, idx, acc: bool = False):
         """zs_adam_seg rows (g, master, master_out, p_out, m, v, vmax, carry, n) of the chunks of
-        the params in ``idx``."""
+        the params in ``idx``; ``acc``: the gradients are the fp32 accumulation arena's."""
         ar, red = self._arena, self._reducer
         es = ar.P.element_size()
         so = ar.slot[idx].astype(np.uint64)
         rows = np.zeros((len(idx), 9), np.uint64)
         if self.world_size > 1:
-            rows[:, 0] = np.uint64(self._G.data_ptr()) + so * np.uint64(self._G.element_size())
+            G = self._A if acc else self._G
+            rows[:, 0] = np.uint64(G.data_ptr()) + so * np.uint64(G.element_size())
         else:
             rows[:, 0] = [red.local_grads[i].data_ptr() for i in idx]
         pp = np.uint64(ar.P.data_ptr()) + so * np.uint64(es)
@@ -2080,6 +2153,8 @@ class ShardedOptimizer:
                 done.wait(cur.cuda_stream)
         idx = np.nonzero(red.had_grad & (ar.ln > 0))[0]
         self._steps[idx] += 1
+        # two or more passes under accumulation_dtype=float32: the sums are in _A (fp32)
+        acc = self._acc_widen and red.passes >= 2
         if self._kind == "sgd":
             hps = {gi: sgd_group_hparams(self._groups[gi]) for gi in set(self._group_of)}
         else:
@@ -2091,7 +2166,8 @@ class ShardedOptimizer:
         uniform = len(idx) > 0 and bool((steps == steps[0]).all())
         # (ws == 1: Adam reads the local grads themselves, whose addresses change — no fast path)
         sig = (idx.tobytes(), self._vmax is None) if self.world_size > 1 else None
-        fast = self._fast_sets if uniform and sig is not None and self._fast_sig == sig else None
+        fast = self._fast_sets.get(acc) if uniform and sig is not None \
+            and self._fast_sig.get(acc) == sig else None
         if fast is not None:  # the same parameters as last step, one step count: cached sets
             for gi, aset in fast:
                 h = hps[gi]
@@ -2104,21 +2180,21 @@ class ShardedOptimizer:
                 else:
                     aset.run(hp, cur)
         elif len(idx):
-            rows = self._adam_rows(idx)
+            rows = self._adam_rows(idx, acc)
             keys = np.stack([np.asarray(self._group_of)[idx], steps], axis=1)
             used = []
             for key in np.unique(keys, axis=0):
                 sel = np.nonzero((keys == key).all(axis=1))[0]
                 sub = np.ascontiguousarray(rows[sel])
-                ck = (int(key[0]), len(sel), int(sel[0]))
+                ck = (int(key[0]), len(sel), int(sel[0]), acc)
                 hit = self._adam_cache.get(ck)
                 if hit is None or hit[0] != sub.tobytes():
                     if hit is not None:  # keep until the device is idle (hipFree would sync it)
                         self._retired.append(hit[1])
-                    gz = ZS_BF16 if (self._split or (self._grad_comm and self.world_size > 1)) \
-                        else ZS_F32
+                    gz = ZS_F32 if acc else ZS_BF16 if (
+                        self._split or (self._grad_comm and self.world_size > 1)) else ZS_F32
                     mk = SgdSet if self._kind == "sgd" else AdamSet
-                    hit = (sub.tobytes(), mk(sub, ZS_BF16, ZS_BF16_SPLIT) if self._split
+                    hit = (sub.tobytes(), mk(sub, gz, ZS_BF16_SPLIT, wide_grads=acc) if self._split
                            else mk(sub, gz))
                     self._adam_cache[ck] = hit
                 h = hps[int(key[0])]
@@ -2132,8 +2208,8 @@ class ShardedOptimizer:
                     hit[1].run(hp, cur)
                 used.append((int(key[0]), hit[1]))
             # one set per param group and one step count: next step takes the cached sets
-            self._fast_sig = sig if uniform else None
-            self._fast_sets = used if uniform else None
+            self._fast_sig[acc] = sig if uniform else None
+            self._fast_sets[acc] = used if uniform else None
         if self._kind == "sgd":  # torch's SGD keeps no step: the buffer appears after the first
             self._expose_sgd(idx)
         elif uniform:  # torch's state['step'] (a CPU tensor): one shared tensor, updated in place

@@ -181,6 +181,18 @@ int zs_scale(void* x, int64_t n, int dtype, double div, uintptr_t stream);
  * nothing launched.  Additive to ABI v13. */
 int zs_accumulate(void* dst, const void* src, int64_t n, int dtype, uintptr_t stream);
 
+/* The same accumulation with an fp32 sum of bf16 contributions (ZeRO-3 update mode,
+ * accumulation_dtype=torch.float32), over n elements:
+ *   a_bf16 != NULL:  dst[i] = widen(a[i]) + widen(src[i])   (the first accumulating pass: the
+ *                    first pass's bf16 chunks plus the staging buffer; 2 + 2 B read, 4 B written)
+ *   a_bf16 == NULL:  dst[i] = dst[i] + widen(src[i])        (later passes; 4 + 2 B read, 4 written)
+ * Widening is exact; one IEEE fp32 add per element (NaN stays NaN, Inf + -Inf is NaN, denormals
+ * are kept).  dst 16-byte aligned, a and src 8-byte aligned.  n == 0: ZS_OK, nothing launched;
+ * n < 0, a NULL dst or src or a misaligned pointer with n > 0: ZS_ERR_INVALID, nothing launched.
+ * Cache policy under zs_tune("accumulate_nt").  Additive to ABI v13. */
+int zs_accumulate_widen(float* dst, const void* a_bf16, const void* src_bf16, int64_t n,
+                        uintptr_t stream);
+
 /* n elements fp32 -> bf16 (round to nearest even, NaN stays NaN) or bf16 -> fp32 (exact).  The
  * bf16 gradient exchange of fp32-parameter models: the reference reduces fp32
  * grads (zero2.py:107); converting them first halves the bytes every collective moves.  16-B
@@ -235,7 +247,9 @@ typedef struct {
   uint64_t carry;      /* fp32 ZeRO-1 carried average A_{t-1}, rewritten with A_t; or 0 */
   int64_t n;           /* elements */
 } zs_adam_seg;
-/* p_dtype ZS_BF16_SPLIT (bf16 params; g must be bf16): the fp32 master is not stored as such.
+/* p_dtype ZS_BF16_SPLIT (bf16 params; g bf16, or fp32 — ZeRO-3's fp32 accumulation arena — on a
+ * set without carry: 28 B/element, and a carry on such a set is ZS_ERR_INVALID; zs_sgdset_create
+ * the same): the fp32 master is not stored as such.
  * Its bits u are the bf16 param hi = RNE(u) and the int16 residual lo = u - (hi << 16):
  *   master     = bf16 param read (hi), 8-byte aligned for the vector path
  *   master_out = int16 residual lo, read and rewritten in place
@@ -418,7 +432,8 @@ int zs_device_alloc_chunked(int64_t bytes, int64_t chunk_bytes, void** out);
  * workgroups per CU walking several rows each), "scale_nt" (zs_scale's cache policy: -1 by size,
  * non-temporal above 256 MiB; 0 default policy; 1 non-temporal), "convert_nt" (zs_convert's, the
  * same by source + destination bytes), "copy_nt" (zs_copyset_run's, by 2 x the set's bytes),
- * "accumulate_nt" (zs_accumulate's, by the 3 x n x element size bytes it touches),
+ * "accumulate_nt" (zs_accumulate's, by the 3 x n x element size bytes it touches, and
+ * zs_accumulate_widen's, by its 8 or 10 B per element),
  * "adam_wg_per_cu" (0 = the default grid of the fused Adam: 128 workgroups per CU, 1024 for the
  * loads-first kernel of a split master; k = at most k per CU), "adam_loads_first" (1: a full chunk
  * of the vector Adam issues all its loads before its first wait; 0: every chunk through the

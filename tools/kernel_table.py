@@ -23,8 +23,14 @@ events on the launch stream, achieved GB/s and the fraction of the 8 TB/s HBM pe
                          size per element.  Alternated, several rounds in one process, with
                          zs_scale on the destination and the segment copy source -> destination on
                          the same buffers: those neighbours are the yardstick.
+  accumulate_widen_kernel  fp32 dst = bf16 a + bf16 src (8 B/element) and fp32 dst += bf16 src
+                         (10 B/element): ZeRO-3's accumulation_dtype=torch.float32, both cache
+                         policies, on placed buffers with 64 MiB and 1 GiB of bf16 source.
+                         Alternated with zs_accumulate (bf16, dst and src of the source's size,
+                         6 B/element) and zs_convert (bf16 -> fp32, 6 B/element) on the same
+                         buffers: the neighbours it is judged against.
 
-Usage: python tools/kernel_table.py [--iters 20] [--only accumulate] [--out profiles/r03_kernels_table.json]
+Usage: python tools/kernel_table.py [--iters 20] [--only accumulate|accumulate_widen] [--out profiles/r03_kernels_table.json]
 """
 from __future__ import annotations
 
@@ -43,9 +49,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", default=None, choices=["accumulate"],
+    ap.add_argument("--only", default=None, choices=["accumulate", "accumulate_widen"],
                     help="run one section of the table alone")
-    ap.add_argument("--rounds", type=int, default=3, help="alternations of the accumulate section")
+    ap.add_argument("--rounds", type=int, default=3, help="alternations of the accumulate sections")
     args = ap.parse_args()
 
     import numpy as np
@@ -117,8 +123,46 @@ def main():
                 del d, s_, cp
                 torch.cuda.empty_cache()
 
+    def accumulate_widen_section():
+        from zero_amd.kernels import accumulate, accumulate_widen
+
+        for mib in (64, 1024):
+            n = (mib << 20) // 2  # elements: `mib` MiB of bf16 source
+            d, _ = probed_zeros(n, torch.float32, dev)
+            a, _ = probed_zeros(n, torch.bfloat16, dev)
+            s_, _ = probed_zeros(n, torch.bfloat16, dev)
+            a.normal_(std=1e-3)
+            s_.normal_(std=1e-3)
+            for r in range(args.rounds):
+                for nt in (0, 1):
+                    _lib.call("zs_tune", b"accumulate_nt", nt, None)
+                    try:
+                        timed(f"accumulate_widen_kernel<first, nt={nt}> ({mib} MiB source, round {r})",
+                              lambda: accumulate_widen(d, s_, a=a, stream=st), 8 * n,
+                              f"fp32 arena = {mib} MiB of bf16 chunks + staging",
+                              "accumulate_widen_kernel<true,")
+                        timed(f"accumulate_widen_kernel<later, nt={nt}> ({mib} MiB source, round {r})",
+                              lambda: accumulate_widen(d, s_, stream=st), 10 * n,
+                              f"fp32 arena += {mib} MiB of bf16 staging",
+                              "accumulate_widen_kernel<false,")
+                        timed(f"accumulate_kernel<bf16, nt={nt}> (the same a and src, round {r})",
+                              lambda: accumulate(a, s_, st), 6 * n, "neighbour on the same buffers",
+                              "accumulate_kernel<unsigned short,")
+                    finally:
+                        _lib.call("zs_tune", b"accumulate_nt", -1, None)
+                    a.normal_(std=1e-3)
+                timed(f"convert_kernel<false> (src -> the fp32 arena, {mib} MiB source, round {r})",
+                      lambda: convert(s_, d, st), 6 * n,
+                      "neighbour on the same buffers, cache policy by size", "convert_kernel<false,")
+            del d, a, s_
+            torch.cuda.empty_cache()
+
     if args.only == "accumulate":
         accumulate_section()
+        write_out()
+        return
+    if args.only == "accumulate_widen":
+        accumulate_widen_section()
         write_out()
         return
 
@@ -231,6 +275,7 @@ def main():
         timed(f"copy_segments_kernel (in place, {nm})", lambda cp=cp: cp.run(st), 2 * nb,
               f"{nb:,} B, the buffer the fp8 rows use", "copy_segments_kernel<")
     accumulate_section()
+    accumulate_widen_section()
     write_out()
 
 
