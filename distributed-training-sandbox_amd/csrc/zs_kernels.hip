@@ -20,6 +20,7 @@
 #include <map>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "zs_common.h"
@@ -32,7 +33,7 @@ constexpr int kCopyUnrollDefault = 4;
 constexpr int64_t copy_chunk_bytes(int u) { return int64_t(kThreads) * 16 * u; }
 // float4 groups per thread: 2 (2048-element chunks); 4 (4096) for the split master, whose 26 B/elem
 // stream has one fp32 array fewer per group (+1 % measured with the predicated body, which has one
-// group's loads in flight at a time: profiles/r01_adam_split_master.log).  adam_full_chunk has all
+// group's loads in flight at a time: profiles/r01_adam_split_master.log).  update_full_chunk has all
 // G groups' loads in flight at once: 5 G loads, 14 G raw registers per lane for the split master.
 constexpr int adam_groups(bool split) { return split ? 4 : 2; }
 constexpr int64_t adam_chunk(bool split) { return int64_t(kThreads) * 4 * adam_groups(split); }
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(kThreads) void copy_direct_kernel(const DirectSet s
 }
 
 // ----------------------------------------------------------------------------------------------
-// fused Adam
+// fused optimizer update: one chunk-streaming skeleton, two element rules (Adam, SGD)
 // ----------------------------------------------------------------------------------------------
 struct AdamSeg {
   const void* g;
@@ -210,14 +211,6 @@ struct AdamSeg {
   float* vmax;
   float* carry;
   int64_t n;
-};
-
-// lerp_w / lerp_hi: ATen's lerp (Lerp.h) with weight w = 1-beta1 is self + w*(end-self) for
-// |w| < 0.5 and end - (end-self)*(1-w) otherwise; make_hp holds the fma's coefficient (w, or w-1 in
-// one fp32 subtraction) and which operand it adds to, so the choice is uniform.
-struct HP {
-  float lerp_w, beta2, omb2, neg_step, bc2_sqrt, eps, wd, decay_mul, grad_div, inv_div, carry_mul;
-  int div_pow2, maximize, lerp_hi;
 };
 
 __device__ __forceinline__ float bf16_to_f32(unsigned short h) {
@@ -244,21 +237,52 @@ __device__ __forceinline__ uint32_t master_residual(float p, uint32_t hi) {
   return d == 0x8000u ? 0x7FFFu : (d & 0xFFFFu);
 }
 
-// One element of torch.optim.Adam's single-tensor update (adam.py:394-547), one fp32 operation
-// per operation of torch's CPU kernels: lerp = fma(w, end-self, self) or fma(w-1, end-self, end)
-// (ATen Lerp.h, by |w| < 0.5), exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2) = fma((1-b2)*g, g, v*b2),
-// max_exp_avg_sq = maximum (NaN in either operand stays), denom = sqrt(v)/bc2_sqrt + eps,
-// param.addcdiv_(m, denom, -step_size) = p + (-step_size*m)/denom.  Only explicit fmaf() fuse;
-// sqrt and '/' are IEEE correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt).  m, v and
-// vmax equal live torch bit for bit; p stays within 0.5 ulp + 6 * 2^-24 * |update| of the exact
-// step, like torch's own p, whose vectorized CPU sqrt is not correctly rounded.
+// The four elements of one lane access and back: fp32 in 16 bytes, bf16 in 8, and the split
+// master's hi and lo words (8 bytes each).  Callers name a packed value before they form the
+// address it goes to where the code did so before: the order of the two shows in the schedule.
+__device__ __forceinline__ void unpack4(const uint4& q, float* f) {
+  f[0] = __uint_as_float(q.x), f[1] = __uint_as_float(q.y);
+  f[2] = __uint_as_float(q.z), f[3] = __uint_as_float(q.w);
+}
+__device__ __forceinline__ uint4 pack4(const float* f) {
+  return make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]),
+                    __float_as_uint(f[3]));
+}
+__device__ __forceinline__ void unpack_bf16x4(const uint2& d, float* f) {
+  f[0] = __uint_as_float(d.x << 16), f[1] = __uint_as_float(d.x & 0xffff0000u);
+  f[2] = __uint_as_float(d.y << 16), f[3] = __uint_as_float(d.y & 0xffff0000u);
+}
+__device__ __forceinline__ uint2 pack_bf16x4(const float* f) {
+  uint2 r;
+  r.x = uint32_t(f32_to_bf16(f[0])) | (uint32_t(f32_to_bf16(f[1])) << 16);
+  r.y = uint32_t(f32_to_bf16(f[2])) | (uint32_t(f32_to_bf16(f[3])) << 16);
+  return r;
+}
+__device__ __forceinline__ void join_master4(const uint2& h, const uint2& l, float* p) {
+  p[0] = join_master(h.x & 0xFFFFu, l.x), p[1] = join_master(h.x >> 16, l.x >> 16);
+  p[2] = join_master(h.y & 0xFFFFu, l.y), p[3] = join_master(h.y >> 16, l.y >> 16);
+}
+// four masters as their bf16 params h and residuals l, 16 bits each, and four such in 8 bytes
+__device__ __forceinline__ void split_master4(const float* p, uint32_t* h, uint32_t* l) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    h[j] = f32_to_bf16(p[j]);
+    l[j] = master_residual(p[j], h[j]);
+  }
+}
+__device__ __forceinline__ uint2 pack_u16x4(const uint32_t* h) {
+  return make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+}
+
+// The gradient both rules start from (HPT: HP or SgdHP, which name these fields alike): the ZeRO-1
+// carry, the averaging, CLIP and maximize, one fp32 operation each.  The coupled weight decay that
+// follows, fma(wd, p, g), stands in each rule: read here, p is loaded a block earlier than it was.
 //
-// CLIP (zs_adamset_run_clipped): the averaged gradient times the global-norm clip coefficient
-// (clip_grad_norm_'s `g.mul_(clip_coef_clamped)`), one IEEE multiply before maximize / weight decay;
-// `coef` is uniform (a scalar register) and unused otherwise.
-template <bool AMS, bool CARRY, bool CLIP>
-__device__ __forceinline__ void adam_elem(float gsum, float& p, float& m, float& v, float& vmax,
-                                          float& carry, const HP& hp, float coef) {
+// CLIP (zs_adamset_run_clipped, zs_sgdset_run with a coefficient): the averaged gradient times the
+// global-norm clip coefficient (clip_grad_norm_'s `g.mul_(clip_coef_clamped)`), one IEEE multiply
+// before maximize / weight decay; `coef` is uniform (a scalar register) and unused otherwise.
+template <bool CARRY, bool CLIP, typename HPT>
+__device__ __forceinline__ float prep_grad(float gsum, float& carry, const HPT& hp, float coef) {
 #pragma clang fp contract(off)
   float s = gsum;
   if constexpr (CARRY) s = s + hp.carry_mul * carry;  // ZeRO-1: Σ G + (ws-1)·A_{t-1}
@@ -267,18 +291,86 @@ __device__ __forceinline__ void adam_elem(float gsum, float& p, float& m, float&
   if constexpr (CARRY) carry = g;
   if constexpr (CLIP) g = g * coef;
   if (hp.maximize) g = -g;
-  if (hp.wd != 0.0f) g = fmaf(hp.wd, p, g);  // grad.add(param, alpha=wd)
-  p = p * hp.decay_mul;                       // AdamW: param.mul_(1 - lr*wd); 1.0 otherwise
-  m = fmaf(hp.lerp_w, g - m, hp.lerp_hi ? g : m);
-  v = fmaf(hp.omb2 * g, g, v * hp.beta2);
-  float vv = v;
-  if constexpr (AMS) {
-    vmax = (v > vmax || v != v) ? v : vmax;  // torch.maximum: fmaxf would drop a NaN
-    vv = vmax;
-  }
-  const float denom = sqrtf(vv) / hp.bc2_sqrt + hp.eps;
-  p = p + (hp.neg_step * m) / denom;
+  return g;
 }
+
+// An element rule gives the skeleton below its hyperparameter struct (Hyper), which of a
+// segment's state arrays an instance reads and writes (kM: m, kV: v, kX: vmax) and the update of
+// one element, elem<CARRY, CLIP>(gsum, p, m, v, vmax, carry, hp, coef); state it does not touch is
+// passed as a dummy.  kGradOffset2: see update_full_chunk.
+
+// lerp_w / lerp_hi: ATen's lerp (Lerp.h) with weight w = 1-beta1 is self + w*(end-self) for
+// |w| < 0.5 and end - (end-self)*(1-w) otherwise; make_hp holds the fma's coefficient (w, or w-1 in
+// one fp32 subtraction) and which operand it adds to, so the choice is uniform.
+struct HP {
+  float lerp_w, beta2, omb2, neg_step, bc2_sqrt, eps, wd, decay_mul, grad_div, inv_div, carry_mul;
+  int div_pow2, maximize, lerp_hi;
+};
+
+template <bool AMS>
+struct AdamRule {
+  using Hyper = HP;
+  static constexpr bool kM = true, kV = true, kX = AMS, kGradOffset2 = true;
+
+  // One element of torch.optim.Adam's single-tensor update (adam.py:394-547), one fp32 operation
+  // per operation of torch's CPU kernels: lerp = fma(w, end-self, self) or fma(w-1, end-self, end)
+  // (ATen Lerp.h, by |w| < 0.5), exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2) = fma((1-b2)*g, g, v*b2),
+  // max_exp_avg_sq = maximum (NaN in either operand stays), denom = sqrt(v)/bc2_sqrt + eps,
+  // param.addcdiv_(m, denom, -step_size) = p + (-step_size*m)/denom.  Only explicit fmaf() fuse;
+  // sqrt and '/' are IEEE correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt).  m, v and
+  // vmax equal live torch bit for bit; p stays within 0.5 ulp + 6 * 2^-24 * |update| of the exact
+  // step, like torch's own p, whose vectorized CPU sqrt is not correctly rounded.
+  template <bool CARRY, bool CLIP>
+  static __device__ __forceinline__ void elem(float gsum, float& p, float& m, float& v,
+                                              float& vmax, float& carry, const HP& hp,
+                                              float coef) {
+#pragma clang fp contract(off)
+    float g = prep_grad<CARRY, CLIP>(gsum, carry, hp, coef);
+    if (hp.wd != 0.0f) g = fmaf(hp.wd, p, g);  // grad.add(param, alpha=wd)
+    p = p * hp.decay_mul;  // AdamW: param.mul_(1 - lr*wd); 1.0 otherwise
+    m = fmaf(hp.lerp_w, g - m, hp.lerp_hi ? g : m);
+    v = fmaf(hp.omb2 * g, g, v * hp.beta2);
+    float vv = v;
+    if constexpr (AMS) {
+      vmax = (v > vmax || v != v) ? v : vmax;  // torch.maximum: fmaxf would drop a NaN
+      vv = vmax;
+    }
+    const float denom = sqrtf(vv) / hp.bc2_sqrt + hp.eps;
+    p = p + (hp.neg_step * m) / denom;
+  }
+};
+
+// torch.optim.SGD over the same tables: field `m` of a segment is the momentum buffer (MOM: the
+// set has one), `v` and `vmax` are unused.  Without MOM no state array is touched.
+struct SgdHP {
+  float neg_lr, momentum, omd, wd, grad_div, inv_div, carry_mul;
+  int div_pow2, nesterov, maximize, first;
+};
+
+template <bool MOM>
+struct SgdRule {
+  using Hyper = SgdHP;
+  static constexpr bool kM = MOM, kV = false, kX = false, kGradOffset2 = false;
+
+  // One element of torch.optim.SGD's single-tensor update (sgd.py _single_tensor_sgd), in the
+  // rounding order of torch's CPU kernels: add(x, alpha=a) = fma(a, x, self), so
+  // grad.add(param, alpha=wd) = fma(wd, p, g), buf.mul_(momentum).add_(grad, alpha=1-dampening) =
+  // fma(1-dampening, g, buf*momentum), grad.add(buf, alpha=momentum) = fma(momentum, buf, g) and
+  // param.add_(grad, alpha=-lr) = fma(-lr, g, p).  Only explicit fmaf() fuse.  `first`: the buffer
+  // does not exist yet and becomes the gradient.
+  template <bool CARRY, bool CLIP>
+  static __device__ __forceinline__ void elem(float gsum, float& p, float& buf, float&, float&,
+                                              float& carry, const SgdHP& hp, float coef) {
+#pragma clang fp contract(off)
+    float g = prep_grad<CARRY, CLIP>(gsum, carry, hp, coef);
+    if (hp.wd != 0.0f) g = fmaf(hp.wd, p, g);  // grad.add(param, alpha=wd)
+    if constexpr (MOM) {
+      buf = hp.first ? g : fmaf(hp.omd, g, buf * hp.momentum);
+      g = hp.nesterov ? fmaf(hp.momentum, buf, g) : buf;
+    }
+    p = fmaf(hp.neg_lr, g, p);
+  }
+};
 
 template <typename GT>
 __device__ __forceinline__ float load_g1(const void* g, int64_t i) {
@@ -301,42 +393,6 @@ __device__ __forceinline__ float clip_coef(const float* __restrict__ coef_ptr) {
   }
 }
 
-// Scalar kernel: any alignment, any length (segment tails and unaligned segments; tiny).
-template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool CLIP>
-__global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
-    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
-    int64_t total_chunks, HP hp, const float* __restrict__ coef_ptr) {
-  static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
-  const float coef = clip_coef<CLIP>(coef_ptr);
-  int64_t seg = 0;
-  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
-    while (chunk_prefix[seg + 1] <= c) ++seg;
-    const AdamSeg s = segs[seg];
-    const int64_t i = (c - chunk_prefix[seg]) * kThreads + threadIdx.x;
-    if (i >= s.n) continue;
-    float gs = s.g ? load_g1<GT>(s.g, i) : 0.0f;
-    const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
-    float p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
-                    : glob(s.master)[i];
-    float m = glob(s.m)[i], v = glob(s.v)[i];
-    float vm = AMS ? glob(s.vmax)[i] : 0.0f;
-    float cr = CARRY ? glob(s.carry)[i] : 0.0f;
-    adam_elem<AMS, CARRY, CLIP>(gs, p, m, v, vm, cr, hp, coef);
-    if constexpr (SPLIT) {
-      const unsigned short h = f32_to_bf16(p);
-      glob(s.p_out)[i] = h;
-      lo[i] = (unsigned short)master_residual(p, h);
-    } else {
-      if (s.master_out) glob(s.master_out)[i] = p;
-      if (s.p_out) glob(s.p_out)[i] = f32_to_bf16(p);
-    }
-    glob(s.m)[i] = m;
-    glob(s.v)[i] = v;
-    if constexpr (AMS) glob(s.vmax)[i] = vm;
-    if constexpr (CARRY) glob(s.carry)[i] = cr;
-  }
-}
-
 __device__ __forceinline__ float4 ld4(const float* p, int64_t i) {
   const uint4 r = nt_ld16(p + i);
   return make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z),
@@ -353,8 +409,9 @@ __device__ __forceinline__ float4 load_g4(const void* g, int64_t i) {
     return ld4(static_cast<const float*>(g), i);
   } else {
     const uint2 r = nt_ld8(static_cast<const unsigned short*>(g) + i);
-    return make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u),
-                       __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u));
+    float4 f;
+    unpack_bf16x4(r, reinterpret_cast<float*>(&f));
+    return f;
   }
 }
 
@@ -391,14 +448,19 @@ struct ChunkStream {
     return lane_ptr(base[u / kPer], lane_off, (u % kPer) * kBytes - 4096);
   }
 };
+// in the place of a stream that a rule does not have (SGD: v, vmax): no bases, no registers
+struct NoStream {
+  __device__ __forceinline__ explicit NoStream(const void*) {}
+};
 
 // One full chunk [e0, e0 + adam_chunk) of a segment, no per-lane predicate; HASG (the segment has a
 // gradient) is resolved by the caller, once per chunk.  First loop: every load of the chunk (g,
-// hi/lo or master, m, v, vmax, carry; 20 for the split master's G = 4) goes into raw registers
-// before anything depends on one.  Second loop: unpack, adam_elem and the stores, group by group.
-template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool HASG, bool CLIP>
-__device__ __forceinline__ void adam_full_chunk(const AdamSeg& s, int64_t e0, const HP& hp,
-                                                float coef) {
+// hi/lo or master, m, v, vmax, carry; 20 for the split-master Adam's G = 4) goes into raw registers
+// before anything depends on one.  Second loop: unpack, the rule's elem and the stores, group by
+// group.
+template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool HASG, bool CLIP>
+__device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
+                                                  const typename Rule::Hyper& hp, float coef) {
   constexpr int G = adam_groups(SPLIT);
   constexpr bool G32 = sizeof(GT) == 4;
   uint32_t o4 = threadIdx.x * 16u;                   // lane byte offset in an fp32 stream
@@ -410,25 +472,29 @@ __device__ __forceinline__ void adam_full_chunk(const AdamSeg& s, int64_t e0, co
 #endif
   typedef ChunkStream<float, G> S4;
   typedef ChunkStream<unsigned short, G> S2;
+  typedef std::conditional_t<Rule::kV, S4, NoStream> SV;  // v and its running maximum vmax
   const S4 gf(HASG && G32 ? (float*)s.g + e0 : nullptr), pm(SPLIT ? nullptr : (float*)s.master + e0);
-  const S4 po(SPLIT ? nullptr : s.master_out + e0), sm(s.m + e0), sv(s.v + e0);
-  const S4 sx(AMS ? s.vmax + e0 : nullptr), sc(CARRY ? s.carry + e0 : nullptr);
+  const S4 po(SPLIT ? nullptr : s.master_out + e0), sm(Rule::kM ? s.m + e0 : nullptr);
+  const SV sv(s.v + e0), sx(Rule::kX ? s.vmax + e0 : nullptr);
+  const S4 sc(CARRY ? s.carry + e0 : nullptr);
   const S2 gh(HASG && !G32 ? (unsigned short*)s.g + e0 : nullptr);
   const S2 hi(SPLIT ? (unsigned short*)s.master + e0 : nullptr);
   const S2 lo(SPLIT ? (unsigned short*)s.master_out + e0 : nullptr), pb(s.p_out + e0);
   uint4 gq[G], pq[G], mq[G], vq[G], xq[G], cq[G];
   uint2 gd[G], hd[G], ld[G];
-  // fp32 gradients over the split master (G = 4): the gradient's groups 2 and 3 through the first
-  // base and a second lane offset 8 KiB on — one vector register instead of a second pair of
-  // scalar ones, which this instance (five fp32 streams of two bases each under amsgrad) has not
+  // kGradOffset2 (Adam), fp32 gradients over the split master (G = 4): the gradient's groups 2 and
+  // 3 through the first base and a second lane offset 8 KiB on — one vector register instead of a
+  // second pair of scalar ones, which this instance (five fp32 streams of two bases each under
+  // amsgrad) has not
+  constexpr bool GOFF2 = Rule::kGradOffset2 && HASG && G32 && SPLIT;
   uint32_t o4g = o4 + 8192u;
 #if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (HASG && G32 && SPLIT) asm volatile("" : "+v"(o4g));
+  if constexpr (GOFF2) asm volatile("" : "+v"(o4g));
 #endif
 #pragma unroll
   for (int u = 0; u < G; ++u) {
     if constexpr (HASG) {
-      if constexpr (G32 && SPLIT)
+      if constexpr (GOFF2)
         gq[u] = nt_ld16(u < S4::kPer ? gf.at(u, o4)
                                      : lane_ptr(gf.base[0], o4g, (u % S4::kPer) * S4::kBytes - 4096));
       else if constexpr (G32) gq[u] = nt_ld16(gf.at(u, o4));
@@ -440,92 +506,59 @@ __device__ __forceinline__ void adam_full_chunk(const AdamSeg& s, int64_t e0, co
     } else {
       pq[u] = nt_ld16(pm.at(u, o4));
     }
-    mq[u] = nt_ld16(sm.at(u, o4));
-    vq[u] = nt_ld16(sv.at(u, o4));
-    if constexpr (AMS) xq[u] = nt_ld16(sx.at(u, o4));
+    if constexpr (Rule::kM) mq[u] = nt_ld16(sm.at(u, o4));
+    if constexpr (Rule::kV) vq[u] = nt_ld16(sv.at(u, o4));
+    if constexpr (Rule::kX) xq[u] = nt_ld16(sx.at(u, o4));
     if constexpr (CARRY) cq[u] = nt_ld16(sc.at(u, o4));
   }
 #pragma unroll
   for (int u = 0; u < G; ++u) {
     float gp[4] = {0.f, 0.f, 0.f, 0.f}, pp[4];
-    if constexpr (HASG && G32) {
-      gp[0] = __uint_as_float(gq[u].x), gp[1] = __uint_as_float(gq[u].y);
-      gp[2] = __uint_as_float(gq[u].z), gp[3] = __uint_as_float(gq[u].w);
-    } else if constexpr (HASG) {
-      gp[0] = __uint_as_float(gd[u].x << 16), gp[1] = __uint_as_float(gd[u].x & 0xffff0000u);
-      gp[2] = __uint_as_float(gd[u].y << 16), gp[3] = __uint_as_float(gd[u].y & 0xffff0000u);
-    }
-    if constexpr (SPLIT) {
-      pp[0] = join_master(hd[u].x & 0xFFFFu, ld[u].x), pp[1] = join_master(hd[u].x >> 16, ld[u].x >> 16);
-      pp[2] = join_master(hd[u].y & 0xFFFFu, ld[u].y), pp[3] = join_master(hd[u].y >> 16, ld[u].y >> 16);
-    } else {
-      pp[0] = __uint_as_float(pq[u].x), pp[1] = __uint_as_float(pq[u].y);
-      pp[2] = __uint_as_float(pq[u].z), pp[3] = __uint_as_float(pq[u].w);
-    }
-    float mp[4] = {__uint_as_float(mq[u].x), __uint_as_float(mq[u].y), __uint_as_float(mq[u].z),
-                   __uint_as_float(mq[u].w)};
-    float vp[4] = {__uint_as_float(vq[u].x), __uint_as_float(vq[u].y), __uint_as_float(vq[u].z),
-                   __uint_as_float(vq[u].w)};
+    if constexpr (HASG && G32) unpack4(gq[u], gp);
+    else if constexpr (HASG) unpack_bf16x4(gd[u], gp);
+    if constexpr (SPLIT) join_master4(hd[u], ld[u], pp);
+    else unpack4(pq[u], pp);
+    float mp[4] = {0.f, 0.f, 0.f, 0.f}, vp[4] = {0.f, 0.f, 0.f, 0.f};
     float xp[4] = {0.f, 0.f, 0.f, 0.f}, cp[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (AMS) {
-      xp[0] = __uint_as_float(xq[u].x), xp[1] = __uint_as_float(xq[u].y);
-      xp[2] = __uint_as_float(xq[u].z), xp[3] = __uint_as_float(xq[u].w);
-    }
-    if constexpr (CARRY) {
-      cp[0] = __uint_as_float(cq[u].x), cp[1] = __uint_as_float(cq[u].y);
-      cp[2] = __uint_as_float(cq[u].z), cp[3] = __uint_as_float(cq[u].w);
-    }
+    if constexpr (Rule::kM) unpack4(mq[u], mp);
+    if constexpr (Rule::kV) unpack4(vq[u], vp);
+    if constexpr (Rule::kX) unpack4(xq[u], xp);
+    if constexpr (CARRY) unpack4(cq[u], cp);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      adam_elem<AMS, CARRY, CLIP>(gp[j], pp[j], mp[j], vp[j], xp[j], cp[j], hp, coef);
+      Rule::template elem<CARRY, CLIP>(gp[j], pp[j], mp[j], vp[j], xp[j], cp[j], hp, coef);
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(o4), "+v"(o2));  // as above, for the block the stores are in
 #endif
     if constexpr (SPLIT) {
       uint32_t h[4], l[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        h[j] = f32_to_bf16(pp[j]);
+      for (int j = 0; j < 4; ++j) {  // split_master4, in place: through the call 16 instances
+        h[j] = f32_to_bf16(pp[j]);   // of this body schedule differently
         l[j] = master_residual(pp[j], h[j]);
       }
-      nt_st8(pb.at(u, o2),
-             make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16)));
-      nt_st8(lo.at(u, o2), make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16)));
+      nt_st8(pb.at(u, o2), pack_u16x4(h));
+      nt_st8(lo.at(u, o2), pack_u16x4(l));
     } else {
-      if (s.master_out)
-        nt_st16(po.at(u, o4),
-                make_uint4(__float_as_uint(pp[0]), __float_as_uint(pp[1]), __float_as_uint(pp[2]),
-                           __float_as_uint(pp[3])));
+      if (s.master_out) nt_st16(po.at(u, o4), pack4(pp));
       if (s.p_out) {
-        uint2 r;
-        r.x = uint32_t(f32_to_bf16(pp[0])) | (uint32_t(f32_to_bf16(pp[1])) << 16);
-        r.y = uint32_t(f32_to_bf16(pp[2])) | (uint32_t(f32_to_bf16(pp[3])) << 16);
+        const uint2 r = pack_bf16x4(pp);
         nt_st8(pb.at(u, o2), r);
       }
     }
-    nt_st16(sm.at(u, o4),
-            make_uint4(__float_as_uint(mp[0]), __float_as_uint(mp[1]), __float_as_uint(mp[2]),
-                       __float_as_uint(mp[3])));
-    nt_st16(sv.at(u, o4),
-            make_uint4(__float_as_uint(vp[0]), __float_as_uint(vp[1]), __float_as_uint(vp[2]),
-                       __float_as_uint(vp[3])));
-    if constexpr (AMS)
-      nt_st16(sx.at(u, o4),
-              make_uint4(__float_as_uint(xp[0]), __float_as_uint(xp[1]), __float_as_uint(xp[2]),
-                         __float_as_uint(xp[3])));
-    if constexpr (CARRY)
-      nt_st16(sc.at(u, o4),
-              make_uint4(__float_as_uint(cp[0]), __float_as_uint(cp[1]), __float_as_uint(cp[2]),
-                         __float_as_uint(cp[3])));
+    if constexpr (Rule::kM) nt_st16(sm.at(u, o4), pack4(mp));
+    if constexpr (Rule::kV) nt_st16(sv.at(u, o4), pack4(vp));
+    if constexpr (Rule::kX) nt_st16(sx.at(u, o4), pack4(xp));
+    if constexpr (CARRY) nt_st16(sc.at(u, o4), pack4(cp));
   }
 }
 
 // The per-lane predicated body: G float4 groups from element e0 of a segment, each group under its
 // own `i < s.n`.  The branches keep each group's loads and their waits in a block of their own, so
 // a wave has one group's loads in flight at a time.
-template <typename GT, bool AMS, bool CARRY, bool SPLIT, int G, bool CLIP>
-__device__ __forceinline__ void adam_pred_groups(const AdamSeg& s, int64_t e0, const HP& hp,
-                                                 float coef) {
+template <typename Rule, typename GT, bool CARRY, bool SPLIT, int G, bool CLIP>
+__device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
+                                                   const typename Rule::Hyper& hp, float coef) {
   float4 g4[G], p4[G], m4[G], v4[G];
   float4 x4[G], c4[G];
 #pragma unroll
@@ -536,14 +569,13 @@ __device__ __forceinline__ void adam_pred_groups(const AdamSeg& s, int64_t e0, c
       if constexpr (SPLIT) {
         const uint2 h = nt_ld8(reinterpret_cast<const unsigned short*>(s.master) + i);
         const uint2 l = nt_ld8(reinterpret_cast<const unsigned short*>(s.master_out) + i);
-        p4[u] = make_float4(join_master(h.x & 0xFFFFu, l.x), join_master(h.x >> 16, l.x >> 16),
-                            join_master(h.y & 0xFFFFu, l.y), join_master(h.y >> 16, l.y >> 16));
+        join_master4(h, l, reinterpret_cast<float*>(&p4[u]));
       } else {
         p4[u] = ld4(s.master, i);
       }
-      m4[u] = ld4(s.m, i);
-      v4[u] = ld4(s.v, i);
-      if constexpr (AMS) x4[u] = ld4(s.vmax, i);
+      if constexpr (Rule::kM) m4[u] = ld4(s.m, i);
+      if constexpr (Rule::kV) v4[u] = ld4(s.v, i);
+      if constexpr (Rule::kX) x4[u] = ld4(s.vmax, i);
       if constexpr (CARRY) c4[u] = ld4(s.carry, i);
     }
   }
@@ -559,57 +591,58 @@ __device__ __forceinline__ void adam_pred_groups(const AdamSeg& s, int64_t e0, c
       float* cp = reinterpret_cast<float*>(&c4[u]);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float xv = AMS ? xp[j] : 0.0f;
+        float mv = Rule::kM ? mp[j] : 0.0f;
+        float vv = Rule::kV ? vp[j] : 0.0f;
+        float xv = Rule::kX ? xp[j] : 0.0f;
         float cv = CARRY ? cp[j] : 0.0f;
-        adam_elem<AMS, CARRY, CLIP>(gp[j], pp[j], mp[j], vp[j], xv, cv, hp, coef);
-        if constexpr (AMS) xp[j] = xv;
+        Rule::template elem<CARRY, CLIP>(gp[j], pp[j], mv, vv, xv, cv, hp, coef);
+        if constexpr (Rule::kM) mp[j] = mv;
+        if constexpr (Rule::kV) vp[j] = vv;
+        if constexpr (Rule::kX) xp[j] = xv;
         if constexpr (CARRY) cp[j] = cv;
       }
       if constexpr (SPLIT) {
         uint32_t h[4], l[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          h[j] = f32_to_bf16(pp[j]);
-          l[j] = master_residual(pp[j], h[j]);
-        }
-        nt_st8(s.p_out + i, make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16)));
-        nt_st8(reinterpret_cast<unsigned short*>(s.master_out) + i,
-               make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16)));
+        split_master4(pp, h, l);
+        nt_st8(s.p_out + i, pack_u16x4(h));
+        nt_st8(reinterpret_cast<unsigned short*>(s.master_out) + i, pack_u16x4(l));
       } else {
         if (s.master_out) st4(s.master_out, i, p4[u]);
         if (s.p_out) {
-          uint2 r;
-          r.x = uint32_t(f32_to_bf16(pp[0])) | (uint32_t(f32_to_bf16(pp[1])) << 16);
-          r.y = uint32_t(f32_to_bf16(pp[2])) | (uint32_t(f32_to_bf16(pp[3])) << 16);
+          const uint2 r = pack_bf16x4(pp);
           nt_st8(s.p_out + i, r);
         }
       }
-      st4(s.m, i, m4[u]);
-      st4(s.v, i, v4[u]);
-      if constexpr (AMS) st4(s.vmax, i, x4[u]);
+      if constexpr (Rule::kM) st4(s.m, i, m4[u]);
+      if constexpr (Rule::kV) st4(s.v, i, v4[u]);
+      if constexpr (Rule::kX) st4(s.vmax, i, x4[u]);
       if constexpr (CARRY) st4(s.carry, i, c4[u]);
     }
   }
 }
 
+// The kernels.  The chunk loop, the routing of a chunk and the scalar body stand in each kernel
+// itself, once per rule: behind a function of their own they compile to other code than they did
+// (the return block moves and with it what the loop hoists, and sinking stops at the call), and
+// `make asm` must show the kernels unchanged.  CLIP instances exist without the carry only.
+//
 // Vector kernel: every segment 16-B aligned (8-B for bf16 arrays) with n % 4 == 0 (the host
 // splits tails off into the scalar table).  adam_groups() float4 groups per thread, lane-contiguous
 // (16 B per lane per access), so each wave instruction touches one contiguous 1 KiB (f32) /
 // 512 B (bf16) run.  LOADS_FIRST (the default): a full chunk, all but the last of a segment, goes
-// through adam_full_chunk and the partial one through the predicated body a group at a time (it
+// through update_full_chunk and the partial one through the predicated body a group at a time (it
 // is one chunk per segment, and a group at a time it stays out of the kernel's register budget).
 // !LOADS_FIRST (`zs_tune("adam_loads_first", 0)`): every chunk through the predicated body, all
-// groups unrolled -- the kernel as it was before adam_full_chunk, kept for A/B runs.
+// groups unrolled -- the kernel as it was before update_full_chunk, kept for A/B runs.
 template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP>
 __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
     const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
     int64_t total_chunks, HP hp, const float* __restrict__ coef_ptr) {
   static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
   const float coef = clip_coef<CLIP>(coef_ptr);
+  using Rule = AdamRule<AMS>;
   int64_t seg = 0;
   if constexpr (LOADS_FIRST) {
-    // The segment of the first chunk by bisection: with a grid near one workgroup per chunk a
-    // forward scan from 0 would cost a workgroup more than its chunks do.
     int64_t hi = nseg;
     while (hi - seg > 1) {
       const int64_t mid = (seg + hi) >> 1;
@@ -624,62 +657,27 @@ __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
     const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT);
     if constexpr (LOADS_FIRST) {
       if (e0 + adam_chunk(SPLIT) <= s.n) {  // uniform per workgroup
-        if (s.g) adam_full_chunk<GT, AMS, CARRY, SPLIT, true, CLIP>(s, e0, hp, coef);
-        else adam_full_chunk<GT, AMS, CARRY, SPLIT, false, CLIP>(s, e0, hp, coef);
+        if (s.g) update_full_chunk<Rule, GT, CARRY, SPLIT, true, CLIP>(s, e0, hp, coef);
+        else update_full_chunk<Rule, GT, CARRY, SPLIT, false, CLIP>(s, e0, hp, coef);
       } else {
 #pragma unroll 1
         for (int u = 0; u < G && e0 + int64_t(u) * kThreads * 4 < s.n; ++u)
-          adam_pred_groups<GT, AMS, CARRY, SPLIT, 1, CLIP>(s, e0 + int64_t(u) * kThreads * 4, hp,
-                                                           coef);
+          update_pred_groups<Rule, GT, CARRY, SPLIT, 1, CLIP>(s, e0 + int64_t(u) * kThreads * 4, hp,
+                                                              coef);
       }
     } else {
-      adam_pred_groups<GT, AMS, CARRY, SPLIT, G, CLIP>(s, e0, hp, coef);
+      update_pred_groups<Rule, GT, CARRY, SPLIT, G, CLIP>(s, e0, hp, coef);
     }
   }
 }
 
-// ----------------------------------------------------------------------------------------------
-// fused SGD (momentum, Nesterov)
-// ----------------------------------------------------------------------------------------------
-// The Adam kernels' tables, chunk geometry, addressing and cache policy with torch.optim.SGD's
-// element: field `m` of a segment is the momentum buffer (MOM: the set has one), `v` and `vmax` are
-// unused.  Without MOM no state array is touched.
-struct SgdHP {
-  float neg_lr, momentum, omd, wd, grad_div, inv_div, carry_mul;
-  int div_pow2, nesterov, maximize, first;
-};
-
-// One element of torch.optim.SGD's single-tensor update (sgd.py _single_tensor_sgd), in the
-// rounding order of torch's CPU kernels: add(x, alpha=a) = fma(a, x, self), so
-// grad.add(param, alpha=wd) = fma(wd, p, g), buf.mul_(momentum).add_(grad, alpha=1-dampening) =
-// fma(1-dampening, g, buf*momentum), grad.add(buf, alpha=momentum) = fma(momentum, buf, g) and
-// param.add_(grad, alpha=-lr) = fma(-lr, g, p).  Only explicit fmaf() fuse; the averaging, the
-// carry and CLIP as adam_elem.  `first`: the buffer does not exist yet and becomes the gradient.
-template <bool CARRY, bool CLIP, bool MOM>
-__device__ __forceinline__ void sgd_elem(float gsum, float& p, float& buf, float& carry,
-                                         const SgdHP& hp, float coef) {
-#pragma clang fp contract(off)
-  float s = gsum;
-  if constexpr (CARRY) s = s + hp.carry_mul * carry;
-  float g = hp.div_pow2 ? s * hp.inv_div : s / hp.grad_div;
-  if constexpr (CARRY) carry = g;
-  if constexpr (CLIP) g = g * coef;
-  if (hp.maximize) g = -g;
-  if (hp.wd != 0.0f) g = fmaf(hp.wd, p, g);
-  if constexpr (MOM) {
-    buf = hp.first ? g : fmaf(hp.omd, g, buf * hp.momentum);
-    g = hp.nesterov ? fmaf(hp.momentum, buf, g) : buf;
-  }
-  p = fmaf(hp.neg_lr, g, p);
-}
-
-// Scalar kernel: any alignment, any length (as adam_scalar_kernel).
-template <typename GT, bool CARRY, bool SPLIT, bool CLIP, bool MOM>
-__global__ __launch_bounds__(kThreads) void sgd_scalar_kernel(
+template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool CLIP>
+__global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
-    int64_t total_chunks, SgdHP hp, const float* __restrict__ coef_ptr) {
+    int64_t total_chunks, HP hp, const float* __restrict__ coef_ptr) {
   static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
   const float coef = clip_coef<CLIP>(coef_ptr);
+  using Rule = AdamRule<AMS>;
   int64_t seg = 0;
   for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
     while (chunk_prefix[seg + 1] <= c) ++seg;
@@ -690,10 +688,12 @@ __global__ __launch_bounds__(kThreads) void sgd_scalar_kernel(
     const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
     float p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
                     : glob(s.master)[i];
-    float b = 0.0f;
-    if constexpr (MOM) b = glob(s.m)[i];
+    float m = 0.0f, v = 0.0f, vm = 0.0f;
+    if constexpr (Rule::kM) m = glob(s.m)[i];
+    if constexpr (Rule::kV) v = glob(s.v)[i];
+    if constexpr (Rule::kX) vm = glob(s.vmax)[i];
     float cr = CARRY ? glob(s.carry)[i] : 0.0f;
-    sgd_elem<CARRY, CLIP, MOM>(gs, p, b, cr, hp, coef);
+    Rule::template elem<CARRY, CLIP>(gs, p, m, v, vm, cr, hp, coef);
     if constexpr (SPLIT) {
       const unsigned short h = f32_to_bf16(p);
       glob(s.p_out)[i] = h;
@@ -702,176 +702,20 @@ __global__ __launch_bounds__(kThreads) void sgd_scalar_kernel(
       if (s.master_out) glob(s.master_out)[i] = p;
       if (s.p_out) glob(s.p_out)[i] = f32_to_bf16(p);
     }
-    if constexpr (MOM) glob(s.m)[i] = b;
+    if constexpr (Rule::kM) glob(s.m)[i] = m;
+    if constexpr (Rule::kV) glob(s.v)[i] = v;
+    if constexpr (Rule::kX) glob(s.vmax)[i] = vm;
     if constexpr (CARRY) glob(s.carry)[i] = cr;
   }
 }
 
-__device__ __forceinline__ void unpack4(const uint4& q, float (&f)[4]) {
-  f[0] = __uint_as_float(q.x), f[1] = __uint_as_float(q.y);
-  f[2] = __uint_as_float(q.z), f[3] = __uint_as_float(q.w);
-}
-__device__ __forceinline__ uint4 pack4(const float (&f)[4]) {
-  return make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]),
-                    __float_as_uint(f[3]));
-}
-
-// One full chunk, as adam_full_chunk: every load of the chunk (g, hi/lo or master, buffer, carry;
-// at most 16 for the split master's G = 4) before anything depends on one, then the arithmetic
-// and the stores group by group.
-template <typename GT, bool CARRY, bool SPLIT, bool HASG, bool CLIP, bool MOM>
-__device__ __forceinline__ void sgd_full_chunk(const AdamSeg& s, int64_t e0, const SgdHP& hp,
-                                               float coef) {
-  constexpr int G = adam_groups(SPLIT);
-  constexpr bool G32 = sizeof(GT) == 4;
-  uint32_t o4 = threadIdx.x * 16u;
-  uint32_t o2 = threadIdx.x * 8u;
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(o4), "+v"(o2));  // opaque per chunk, see adam_full_chunk
-#endif
-  typedef ChunkStream<float, G> S4;
-  typedef ChunkStream<unsigned short, G> S2;
-  const S4 gf(HASG && G32 ? (float*)s.g + e0 : nullptr), pm(SPLIT ? nullptr : (float*)s.master + e0);
-  const S4 po(SPLIT ? nullptr : s.master_out + e0), sm(MOM ? s.m + e0 : nullptr);
-  const S4 sc(CARRY ? s.carry + e0 : nullptr);
-  const S2 gh(HASG && !G32 ? (unsigned short*)s.g + e0 : nullptr);
-  const S2 hi(SPLIT ? (unsigned short*)s.master + e0 : nullptr);
-  const S2 lo(SPLIT ? (unsigned short*)s.master_out + e0 : nullptr), pb(s.p_out + e0);
-  uint4 gq[G], pq[G], mq[G], cq[G];
-  uint2 gd[G], hd[G], ld[G];
-#pragma unroll
-  for (int u = 0; u < G; ++u) {
-    if constexpr (HASG) {
-      if constexpr (G32) gq[u] = nt_ld16(gf.at(u, o4));
-      else gd[u] = nt_ld8(gh.at(u, o2));
-    }
-    if constexpr (SPLIT) {
-      hd[u] = nt_ld8(hi.at(u, o2));
-      ld[u] = nt_ld8(lo.at(u, o2));
-    } else {
-      pq[u] = nt_ld16(pm.at(u, o4));
-    }
-    if constexpr (MOM) mq[u] = nt_ld16(sm.at(u, o4));
-    if constexpr (CARRY) cq[u] = nt_ld16(sc.at(u, o4));
-  }
-#pragma unroll
-  for (int u = 0; u < G; ++u) {
-    float gp[4] = {0.f, 0.f, 0.f, 0.f}, pp[4];
-    if constexpr (HASG && G32) {
-      unpack4(gq[u], gp);
-    } else if constexpr (HASG) {
-      gp[0] = __uint_as_float(gd[u].x << 16), gp[1] = __uint_as_float(gd[u].x & 0xffff0000u);
-      gp[2] = __uint_as_float(gd[u].y << 16), gp[3] = __uint_as_float(gd[u].y & 0xffff0000u);
-    }
-    if constexpr (SPLIT) {
-      pp[0] = join_master(hd[u].x & 0xFFFFu, ld[u].x), pp[1] = join_master(hd[u].x >> 16, ld[u].x >> 16);
-      pp[2] = join_master(hd[u].y & 0xFFFFu, ld[u].y), pp[3] = join_master(hd[u].y >> 16, ld[u].y >> 16);
-    } else {
-      unpack4(pq[u], pp);
-    }
-    float mp[4] = {0.f, 0.f, 0.f, 0.f}, cp[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (MOM) unpack4(mq[u], mp);
-    if constexpr (CARRY) unpack4(cq[u], cp);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sgd_elem<CARRY, CLIP, MOM>(gp[j], pp[j], mp[j], cp[j], hp, coef);
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(o4), "+v"(o2));  // as above, for the block the stores are in
-#endif
-    if constexpr (SPLIT) {
-      uint32_t h[4], l[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        h[j] = f32_to_bf16(pp[j]);
-        l[j] = master_residual(pp[j], h[j]);
-      }
-      nt_st8(pb.at(u, o2), make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16)));
-      nt_st8(lo.at(u, o2), make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16)));
-    } else {
-      if (s.master_out) nt_st16(po.at(u, o4), pack4(pp));
-      if (s.p_out) {
-        uint2 r;
-        r.x = uint32_t(f32_to_bf16(pp[0])) | (uint32_t(f32_to_bf16(pp[1])) << 16);
-        r.y = uint32_t(f32_to_bf16(pp[2])) | (uint32_t(f32_to_bf16(pp[3])) << 16);
-        nt_st8(pb.at(u, o2), r);
-      }
-    }
-    if constexpr (MOM) nt_st16(sm.at(u, o4), pack4(mp));
-    if constexpr (CARRY) nt_st16(sc.at(u, o4), pack4(cp));
-  }
-}
-
-// The per-lane predicated body, as adam_pred_groups.
-template <typename GT, bool CARRY, bool SPLIT, int G, bool CLIP, bool MOM>
-__device__ __forceinline__ void sgd_pred_groups(const AdamSeg& s, int64_t e0, const SgdHP& hp,
-                                                float coef) {
-  float4 g4[G], p4[G], m4[G], c4[G];
-#pragma unroll
-  for (int u = 0; u < G; ++u) {
-    const int64_t i = e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
-    if (i < s.n) {
-      g4[u] = s.g ? load_g4<GT>(s.g, i) : make_float4(0.f, 0.f, 0.f, 0.f);
-      if constexpr (SPLIT) {
-        const uint2 h = nt_ld8(reinterpret_cast<const unsigned short*>(s.master) + i);
-        const uint2 l = nt_ld8(reinterpret_cast<const unsigned short*>(s.master_out) + i);
-        p4[u] = make_float4(join_master(h.x & 0xFFFFu, l.x), join_master(h.x >> 16, l.x >> 16),
-                            join_master(h.y & 0xFFFFu, l.y), join_master(h.y >> 16, l.y >> 16));
-      } else {
-        p4[u] = ld4(s.master, i);
-      }
-      if constexpr (MOM) m4[u] = ld4(s.m, i);
-      if constexpr (CARRY) c4[u] = ld4(s.carry, i);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < G; ++u) {
-    const int64_t i = e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
-    if (i < s.n) {
-      float* gp = reinterpret_cast<float*>(&g4[u]);
-      float* pp = reinterpret_cast<float*>(&p4[u]);
-      float* mp = reinterpret_cast<float*>(&m4[u]);
-      float* cp = reinterpret_cast<float*>(&c4[u]);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float mv = MOM ? mp[j] : 0.0f;
-        float cv = CARRY ? cp[j] : 0.0f;
-        sgd_elem<CARRY, CLIP, MOM>(gp[j], pp[j], mv, cv, hp, coef);
-        if constexpr (MOM) mp[j] = mv;
-        if constexpr (CARRY) cp[j] = cv;
-      }
-      if constexpr (SPLIT) {
-        uint32_t h[4], l[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          h[j] = f32_to_bf16(pp[j]);
-          l[j] = master_residual(pp[j], h[j]);
-        }
-        nt_st8(s.p_out + i, make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16)));
-        nt_st8(reinterpret_cast<unsigned short*>(s.master_out) + i,
-               make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16)));
-      } else {
-        if (s.master_out) st4(s.master_out, i, p4[u]);
-        if (s.p_out) {
-          uint2 r;
-          r.x = uint32_t(f32_to_bf16(pp[0])) | (uint32_t(f32_to_bf16(pp[1])) << 16);
-          r.y = uint32_t(f32_to_bf16(pp[2])) | (uint32_t(f32_to_bf16(pp[3])) << 16);
-          nt_st8(s.p_out + i, r);
-        }
-      }
-      if constexpr (MOM) st4(s.m, i, m4[u]);
-      if constexpr (CARRY) st4(s.carry, i, c4[u]);
-    }
-  }
-}
-
-// Vector kernel, as adam_segments_kernel: LOADS_FIRST sends full chunks through sgd_full_chunk and
-// the partial one through the predicated body a group at a time; !LOADS_FIRST every chunk through
-// the predicated body.
 template <typename GT, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP, bool MOM>
 __global__ __launch_bounds__(kThreads) void sgd_segments_kernel(
     const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
     int64_t total_chunks, SgdHP hp, const float* __restrict__ coef_ptr) {
   static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
   const float coef = clip_coef<CLIP>(coef_ptr);
+  using Rule = SgdRule<MOM>;
   int64_t seg = 0;
   if constexpr (LOADS_FIRST) {
     int64_t hi = nseg;
@@ -888,17 +732,55 @@ __global__ __launch_bounds__(kThreads) void sgd_segments_kernel(
     const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT);
     if constexpr (LOADS_FIRST) {
       if (e0 + adam_chunk(SPLIT) <= s.n) {  // uniform per workgroup
-        if (s.g) sgd_full_chunk<GT, CARRY, SPLIT, true, CLIP, MOM>(s, e0, hp, coef);
-        else sgd_full_chunk<GT, CARRY, SPLIT, false, CLIP, MOM>(s, e0, hp, coef);
+        if (s.g) update_full_chunk<Rule, GT, CARRY, SPLIT, true, CLIP>(s, e0, hp, coef);
+        else update_full_chunk<Rule, GT, CARRY, SPLIT, false, CLIP>(s, e0, hp, coef);
       } else {
 #pragma unroll 1
         for (int u = 0; u < G && e0 + int64_t(u) * kThreads * 4 < s.n; ++u)
-          sgd_pred_groups<GT, CARRY, SPLIT, 1, CLIP, MOM>(s, e0 + int64_t(u) * kThreads * 4, hp,
-                                                          coef);
+          update_pred_groups<Rule, GT, CARRY, SPLIT, 1, CLIP>(s, e0 + int64_t(u) * kThreads * 4, hp,
+                                                              coef);
       }
     } else {
-      sgd_pred_groups<GT, CARRY, SPLIT, G, CLIP, MOM>(s, e0, hp, coef);
+      update_pred_groups<Rule, GT, CARRY, SPLIT, G, CLIP>(s, e0, hp, coef);
     }
+  }
+}
+
+template <typename GT, bool CARRY, bool SPLIT, bool CLIP, bool MOM>
+__global__ __launch_bounds__(kThreads) void sgd_scalar_kernel(
+    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
+    int64_t total_chunks, SgdHP hp, const float* __restrict__ coef_ptr) {
+  static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
+  const float coef = clip_coef<CLIP>(coef_ptr);
+  using Rule = SgdRule<MOM>;
+  int64_t seg = 0;
+  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
+    while (chunk_prefix[seg + 1] <= c) ++seg;
+    const AdamSeg s = segs[seg];
+    const int64_t i = (c - chunk_prefix[seg]) * kThreads + threadIdx.x;
+    if (i >= s.n) continue;
+    float gs = s.g ? load_g1<GT>(s.g, i) : 0.0f;
+    const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
+    float p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
+                    : glob(s.master)[i];
+    float m = 0.0f, v = 0.0f, vm = 0.0f;
+    if constexpr (Rule::kM) m = glob(s.m)[i];
+    if constexpr (Rule::kV) v = glob(s.v)[i];
+    if constexpr (Rule::kX) vm = glob(s.vmax)[i];
+    float cr = CARRY ? glob(s.carry)[i] : 0.0f;
+    Rule::template elem<CARRY, CLIP>(gs, p, m, v, vm, cr, hp, coef);
+    if constexpr (SPLIT) {
+      const unsigned short h = f32_to_bf16(p);
+      glob(s.p_out)[i] = h;
+      lo[i] = (unsigned short)master_residual(p, h);
+    } else {
+      if (s.master_out) glob(s.master_out)[i] = p;
+      if (s.p_out) glob(s.p_out)[i] = f32_to_bf16(p);
+    }
+    if constexpr (Rule::kM) glob(s.m)[i] = m;
+    if constexpr (Rule::kV) glob(s.v)[i] = v;
+    if constexpr (Rule::kX) glob(s.vmax)[i] = vm;
+    if constexpr (CARRY) glob(s.carry)[i] = cr;
   }
 }
 
@@ -977,13 +859,8 @@ __global__ __launch_bounds__(kThreads) void grad_sqnorm_kernel(
 #pragma unroll
     for (int u = 0; u < G; ++u) {
       float x[4];
-      if constexpr (G32) {
-        x[0] = __uint_as_float(r[u].x), x[1] = __uint_as_float(r[u].y);
-        x[2] = __uint_as_float(r[u].z), x[3] = __uint_as_float(r[u].w);
-      } else {
-        x[0] = __uint_as_float(r[u].x << 16), x[1] = __uint_as_float(r[u].x & 0xffff0000u);
-        x[2] = __uint_as_float(r[u].y << 16), x[3] = __uint_as_float(r[u].y & 0xffff0000u);
-      }
+      if constexpr (G32) unpack4(r[u], x);
+      else unpack_bf16x4(make_uint2(r[u].x, r[u].y), x);
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc = fmaf(x[j], x[j], acc);
     }
@@ -1642,7 +1519,7 @@ int& adam_wg_per_cu() {
   static int v = 0;
   return v;
 }
-// Full chunks' issue order (zs_tune "adam_loads_first", diagnostic A/B): 1 = adam_full_chunk (all
+// Full chunks' issue order (zs_tune "adam_loads_first", diagnostic A/B): 1 = update_full_chunk (all
 // of a chunk's loads before its first wait), 0 = every chunk through the predicated body that
 // partial chunks take
 int& adam_loads_first() {
@@ -1821,6 +1698,15 @@ static int upload(const std::vector<T>& h, T** d) {
   return ZS_OK;
 }
 
+// HP's and SgdHP's `grad / grad_div`: a power-of-two divisor is an exact reciprocal multiply
+template <typename HPT>
+static void set_grad_div(HPT* hp, float grad_div) {
+  int exp2 = 0;
+  hp->grad_div = grad_div;
+  hp->div_pow2 = std::frexp(double(grad_div), &exp2) == 0.5 ? 1 : 0;
+  hp->inv_div = float(1.0 / double(grad_div));
+}
+
 static HP make_hp(const zs_adam_hparams* h) {
   HP hp;
   const float w = h->one_minus_beta1;
@@ -1833,136 +1719,82 @@ static HP make_hp(const zs_adam_hparams* h) {
   hp.eps = h->eps;
   hp.wd = h->weight_decay;
   hp.decay_mul = h->decay_mul;
-  hp.grad_div = h->grad_div;
   hp.carry_mul = h->carry_mul;
-  int exp2 = 0;
-  hp.div_pow2 = std::frexp(double(h->grad_div), &exp2) == 0.5 ? 1 : 0;
-  hp.inv_div = float(1.0 / double(h->grad_div));
+  set_grad_div(&hp, h->grad_div);
   hp.maximize = h->maximize;
   return hp;
 }
 
-// Vector table (aligned, n % 4 == 0) then scalar table (tails, unaligned), each a segment array
-// with its chunk prefix; the template instance is picked by grad dtype, split master, amsgrad
-// and carry.
-template <bool CLIP>
-static int launch_adam_tables(const AdamSeg* vec, const int64_t* vpre, int64_t nvec, int64_t vch,
-                              const AdamSeg* sca, const int64_t* spre, int64_t nsca, int64_t sch,
-                              int g_dtype, bool split, bool ams, bool carry, const HP& hp,
-                              const float* coef, hipStream_t st) {
-  // CLIP instances exist without the carry only (zs_adamset_run_clipped refuses a set with one)
-#define ZS_LAUNCH(KERNEL, GT, A, C, S, TAB, PRE, NS, NCH)                                     \
-  hipLaunchKernelGGL((KERNEL<GT, A, C, S LF, CLIP>), dim3(int(std::min<int64_t>(NCH, cap))),  \
-                     dim3(kThreads), 0, st, TAB, PRE, NS, NCH, hp, coef)
-#define ZS_DISPATCH_AC(KERNEL, GT, S, TAB, PRE, NS, NCH)                                      \
-  do {                                                                                        \
-    if constexpr (CLIP) {                                                                     \
-      if (ams) ZS_LAUNCH(KERNEL, GT, true, false, S, TAB, PRE, NS, NCH);                      \
-      else ZS_LAUNCH(KERNEL, GT, false, false, S, TAB, PRE, NS, NCH);                         \
-    } else {                                                                                  \
-      if (ams && carry) ZS_LAUNCH(KERNEL, GT, true, true, S, TAB, PRE, NS, NCH);              \
-      else if (ams) ZS_LAUNCH(KERNEL, GT, true, false, S, TAB, PRE, NS, NCH);                 \
-      else if (carry) ZS_LAUNCH(KERNEL, GT, false, true, S, TAB, PRE, NS, NCH);               \
-      else ZS_LAUNCH(KERNEL, GT, false, false, S, TAB, PRE, NS, NCH);                         \
-    }                                                                                         \
-  } while (0)
-  // fp32 gradients over the split master (no carry: set_create refuses one)
-#define ZS_DISPATCH_A(KERNEL, GT, S, TAB, PRE, NS, NCH)                                       \
-  do {                                                                                        \
-    if (ams) ZS_LAUNCH(KERNEL, GT, true, false, S, TAB, PRE, NS, NCH);                        \
-    else ZS_LAUNCH(KERNEL, GT, false, false, S, TAB, PRE, NS, NCH);                           \
-  } while (0)
-#define ZS_DISPATCH(KERNEL, TAB, PRE, NS, NCH)                                                \
-  do {                                                                                        \
-    if (g_dtype == ZS_F32 && split) ZS_DISPATCH_A(KERNEL, float, true, TAB, PRE, NS, NCH);   \
-    else if (g_dtype == ZS_F32) ZS_DISPATCH_AC(KERNEL, float, false, TAB, PRE, NS, NCH);     \
-    else if (split) ZS_DISPATCH_AC(KERNEL, unsigned short, true, TAB, PRE, NS, NCH);         \
-    else ZS_DISPATCH_AC(KERNEL, unsigned short, false, TAB, PRE, NS, NCH);                   \
-  } while (0)
-  if (vch) {
-    const bool lf = adam_loads_first() != 0;
-    const int64_t cap =
-        adam_grid_cap(lf && split ? kAdamLoadsFirstWgPerCu : kAdamWgPerCu);
-#define LF , true
-    if (lf) ZS_DISPATCH(adam_segments_kernel, vec, vpre, nvec, vch);
-#undef LF
-#define LF , false
-    else ZS_DISPATCH(adam_segments_kernel, vec, vpre, nvec, vch);
-#undef LF
-    ZS_HIP(hipGetLastError());
+// A family's vector (VEC) or scalar kernel by <grad type, rule flag (amsgrad / momentum), carry,
+// split, loads-first, clip>, whatever order the kernel itself lists them in.
+struct AdamKernels {
+  template <bool VEC, typename GT, bool AMS, bool C, bool S, bool LF, bool CLIP>
+  static auto get() {
+    if constexpr (VEC) return adam_segments_kernel<GT, AMS, C, S, LF, CLIP>;
+    else return adam_scalar_kernel<GT, AMS, C, S, CLIP>;
   }
-  if (sch) {
-    const int64_t cap = adam_grid_cap(kAdamWgPerCu);
-#define LF
-    ZS_DISPATCH(adam_scalar_kernel, sca, spre, nsca, sch);
-#undef LF
-    ZS_HIP(hipGetLastError());
+};
+struct SgdKernels {
+  template <bool VEC, typename GT, bool MOM, bool C, bool S, bool LF, bool CLIP>
+  static auto get() {
+    if constexpr (VEC) return sgd_segments_kernel<GT, C, S, LF, CLIP, MOM>;
+    else return sgd_scalar_kernel<GT, C, S, CLIP, MOM>;
   }
-#undef ZS_DISPATCH
-#undef ZS_DISPATCH_A
-#undef ZS_DISPATCH_AC
-#undef ZS_LAUNCH
-  return ZS_OK;
+};
+
+struct UpdateTable {  // a segment array with its chunk prefix
+  const AdamSeg* segs;
+  const int64_t* prefix;
+  int64_t nseg, chunks;
+};
+static UpdateTable vec_table(const zs_adamset* as) {
+  return {as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks};
+}
+static UpdateTable sca_table(const zs_adamset* as) {
+  return {as->d_sca, as->d_sca_prefix, as->nsca, as->sca_chunks};
 }
 
-// The SGD instance by grad dtype, split master, carry (never with CLIP) and momentum buffer; the
-// grid policy is the Adam's (adam_grid_cap, "adam_loads_first").
-template <bool CLIP>
-static int launch_sgd_tables(const zs_adamset* as, bool mom, const SgdHP& hp, const float* coef,
-                             hipStream_t st) {
-  const bool split = as->p_dtype == ZS_BF16_SPLIT, carry = as->has_carry != 0;
-  const int g_dtype = as->g_dtype;
-#define ZS_LAUNCH(KERNEL, GT, C, S, M, TAB, PRE, NS, NCH)                                     \
-  hipLaunchKernelGGL((KERNEL<GT, C, S LF, CLIP, M>), dim3(int(std::min<int64_t>(NCH, cap))),  \
-                     dim3(kThreads), 0, st, TAB, PRE, NS, NCH, hp, coef)
-#define ZS_DISPATCH_CM(KERNEL, GT, S, TAB, PRE, NS, NCH)                                      \
-  do {                                                                                        \
-    if constexpr (CLIP) {                                                                     \
-      if (mom) ZS_LAUNCH(KERNEL, GT, false, S, true, TAB, PRE, NS, NCH);                      \
-      else ZS_LAUNCH(KERNEL, GT, false, S, false, TAB, PRE, NS, NCH);                         \
-    } else {                                                                                  \
-      if (carry && mom) ZS_LAUNCH(KERNEL, GT, true, S, true, TAB, PRE, NS, NCH);              \
-      else if (carry) ZS_LAUNCH(KERNEL, GT, true, S, false, TAB, PRE, NS, NCH);               \
-      else if (mom) ZS_LAUNCH(KERNEL, GT, false, S, true, TAB, PRE, NS, NCH);                 \
-      else ZS_LAUNCH(KERNEL, GT, false, S, false, TAB, PRE, NS, NCH);                         \
-    }                                                                                         \
-  } while (0)
-  // fp32 gradients over the split master (no carry: set_create refuses one)
-#define ZS_DISPATCH_M(KERNEL, GT, S, TAB, PRE, NS, NCH)                                       \
-  do {                                                                                        \
-    if (mom) ZS_LAUNCH(KERNEL, GT, false, S, true, TAB, PRE, NS, NCH);                        \
-    else ZS_LAUNCH(KERNEL, GT, false, S, false, TAB, PRE, NS, NCH);                           \
-  } while (0)
-#define ZS_DISPATCH(KERNEL, TAB, PRE, NS, NCH)                                                \
-  do {                                                                                        \
-    if (g_dtype == ZS_F32 && split) ZS_DISPATCH_M(KERNEL, float, true, TAB, PRE, NS, NCH);   \
-    else if (g_dtype == ZS_F32) ZS_DISPATCH_CM(KERNEL, float, false, TAB, PRE, NS, NCH);     \
-    else if (split) ZS_DISPATCH_CM(KERNEL, unsigned short, true, TAB, PRE, NS, NCH);         \
-    else ZS_DISPATCH_CM(KERNEL, unsigned short, false, TAB, PRE, NS, NCH);                   \
-  } while (0)
-  if (as->vec_chunks) {
+// Vector table (aligned, n % 4 == 0) then scalar table (tails, unaligned); the instance of K's
+// kernels (AdamKernels, SgdKernels) is picked by grad dtype, split master, the rule's flag (amsgrad
+// / momentum buffer) and carry.  No instance has the carry with CLIP (the clipped entry points
+// refuse a set with one) or with fp32 gradients over the split master (set_create refuses one).
+template <typename K, bool CLIP, typename HPT>
+static int launch_update_tables(const UpdateTable& vec, const UpdateTable& sca, int g_dtype,
+                                bool split, bool flag, bool carry, const HPT& hp,
+                                const float* coef, hipStream_t st) {
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  auto table = [&](const UpdateTable& t, auto is_vec, auto lf, int64_t cap) {
+    auto launch = [&](auto gt, auto s, auto f, auto c) {
+      hipLaunchKernelGGL((K::template get<decltype(is_vec)::value, decltype(gt), decltype(f)::value,
+                                          decltype(c)::value, decltype(s)::value,
+                                          decltype(lf)::value, CLIP>()),
+                         dim3(int(std::min<int64_t>(t.chunks, cap))), dim3(kThreads), 0, st, t.segs,
+                         t.prefix, t.nseg, t.chunks, hp, coef);
+    };
+    auto flags = [&](auto gt, auto s) {
+      if constexpr (!CLIP && !(sizeof(gt) == 4 && decltype(s)::value)) {
+        if (carry) return flag ? launch(gt, s, yes, yes) : launch(gt, s, no, yes);
+      }
+      return flag ? launch(gt, s, yes, no) : launch(gt, s, no, no);
+    };
+    if (g_dtype == ZS_F32 && split) flags(float(), yes);
+    else if (g_dtype == ZS_F32) flags(float(), no);
+    else if (split) flags((unsigned short)0, yes);
+    else flags((unsigned short)0, no);
+  };
+  if (vec.chunks) {
     const bool lf = adam_loads_first() != 0;
     const int64_t cap =
         adam_grid_cap(lf && split ? kAdamLoadsFirstWgPerCu : kAdamWgPerCu);
-#define LF , true
-    if (lf) ZS_DISPATCH(sgd_segments_kernel, as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks);
-#undef LF
-#define LF , false
-    else ZS_DISPATCH(sgd_segments_kernel, as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks);
-#undef LF
+    if (lf) table(vec, yes, yes, cap);
+    else table(vec, yes, no, cap);
     ZS_HIP(hipGetLastError());
   }
-  if (as->sca_chunks) {
-    const int64_t cap = adam_grid_cap(kAdamWgPerCu);
-#define LF
-    ZS_DISPATCH(sgd_scalar_kernel, as->d_sca, as->d_sca_prefix, as->nsca, as->sca_chunks);
-#undef LF
+  if (sca.chunks) {
+    table(sca, no, no, adam_grid_cap(kAdamWgPerCu));
     ZS_HIP(hipGetLastError());
   }
-#undef ZS_DISPATCH
-#undef ZS_DISPATCH_M
-#undef ZS_DISPATCH_CM
-#undef ZS_LAUNCH
   return ZS_OK;
 }
 
@@ -2605,19 +2437,20 @@ int zs_sgdset_run(const zs_adamset* as, const zs_sgd_hparams* h, const float* co
   hp.momentum = h->momentum;
   hp.omd = h->one_minus_dampening;
   hp.wd = h->weight_decay;
-  hp.grad_div = h->grad_div;
   hp.carry_mul = h->carry_mul;
-  int exp2 = 0;
-  hp.div_pow2 = std::frexp(double(h->grad_div), &exp2) == 0.5 ? 1 : 0;
-  hp.inv_div = float(1.0 / double(h->grad_div));
+  set_grad_div(&hp, h->grad_div);
   hp.nesterov = h->nesterov ? 1 : 0;
   hp.maximize = h->maximize ? 1 : 0;
   hp.first = h->first ? 1 : 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // torch with momentum == 0 never makes a buffer: a set that has one leaves it alone then
   const bool mom = as->has_mom != 0 && h->momentum != 0.0f;
-  if (coef) return launch_sgd_tables<true>(as, mom, hp, coef, st);
-  return launch_sgd_tables<false>(as, mom, hp, nullptr, st);
+  const bool split = as->p_dtype == ZS_BF16_SPLIT;
+  if (coef)
+    return launch_update_tables<SgdKernels, true>(vec_table(as), sca_table(as), as->g_dtype, split,
+                                                  mom, false, hp, coef, st);
+  return launch_update_tables<SgdKernels, false>(vec_table(as), sca_table(as), as->g_dtype, split,
+                                                 mom, as->has_carry != 0, hp, nullptr, st);
 }
 
 int zs_adamset_run(const zs_adamset* as, const zs_adam_hparams* h, uintptr_t stream) {
@@ -2626,10 +2459,9 @@ int zs_adamset_run(const zs_adamset* as, const zs_adam_hparams* h, uintptr_t str
   const bool ams = h->amsgrad != 0;
   ZS_REQUIRE(!ams || as->has_vmax || (as->nvec + as->nsca) == 0,
              "zs_adamset_run: amsgrad needs vmax segments");
-  return launch_adam_tables<false>(as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks, as->d_sca,
-                                   as->d_sca_prefix, as->nsca, as->sca_chunks, as->g_dtype,
-                                   as->p_dtype == ZS_BF16_SPLIT, ams, as->has_carry != 0,
-                                   make_hp(h), nullptr, reinterpret_cast<hipStream_t>(stream));
+  return launch_update_tables<AdamKernels, false>(
+      vec_table(as), sca_table(as), as->g_dtype, as->p_dtype == ZS_BF16_SPLIT, ams,
+      as->has_carry != 0, make_hp(h), nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
 int zs_adamset_run_clipped(const zs_adamset* as, const zs_adam_hparams* h, const float* coef,
@@ -2642,10 +2474,9 @@ int zs_adamset_run_clipped(const zs_adamset* as, const zs_adam_hparams* h, const
   const bool ams = h->amsgrad != 0;
   ZS_REQUIRE(!ams || as->has_vmax || (as->nvec + as->nsca) == 0,
              "zs_adamset_run_clipped: amsgrad needs vmax segments");
-  return launch_adam_tables<true>(as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks, as->d_sca,
-                                  as->d_sca_prefix, as->nsca, as->sca_chunks, as->g_dtype,
-                                  as->p_dtype == ZS_BF16_SPLIT, ams, false, make_hp(h), coef,
-                                  reinterpret_cast<hipStream_t>(stream));
+  return launch_update_tables<AdamKernels, true>(
+      vec_table(as), sca_table(as), as->g_dtype, as->p_dtype == ZS_BF16_SPLIT, ams, false,
+      make_hp(h), coef, reinterpret_cast<hipStream_t>(stream));
 }
 
 int zs_adamset_sqnorm_partials(const zs_adamset* as, int64_t* n) {
@@ -2768,9 +2599,10 @@ int zs_adam_step_ex(float* p, uint16_t* p_bf16, const void* g, int g_dtype, floa
   hipLaunchKernelGGL(write_tables_kernel, dim3(1), dim3(1), 0, st, d, t);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) {
-    rc = launch_adam_tables<false>(d->seg, d->prefix, 1, vch, d->seg + 1, d->prefix + 2, 1, sch,
-                                   g_dtype, false, false, carry != nullptr, make_hp(&h), nullptr,
-                                   st);
+    rc = launch_update_tables<AdamKernels, false>({d->seg, d->prefix, 1, vch},
+                                                  {d->seg + 1, d->prefix + 2, 1, sch}, g_dtype,
+                                                  false, false, carry != nullptr, make_hp(&h),
+                                                  nullptr, st);
   }
   const hipError_t ef = hipFreeAsync(d, st);  // after the launches, in stream order
   if (e != hipSuccess)

@@ -91,7 +91,7 @@ def adam_update(p, g, m, v, step, *, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weig
 
     ``g`` is the gradient sum: it is divided by ``grad_div`` (with ``carry``: after adding
     ``carry_mul * carry``, and the quotient is the new carry), then multiplied by ``clip_coef``
-    when given — the ZeRO averaging, the ZeRO-1 carry and the clip of csrc/zs_kernels.hip adam_elem.
+    when given — the ZeRO averaging, the ZeRO-1 carry and the clip of csrc/zs_kernels.hip prep_grad.
     """
     beta1, beta2 = betas
     with np.errstate(all="ignore"):

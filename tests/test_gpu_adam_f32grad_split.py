@@ -112,7 +112,8 @@ def _reference(master, grads, kind, cfg, ws, rounded=False):
     return out
 
 
-def _run_gpu(gpu, master, grads, kind, cfg, ws, lf, g_bf16=False):
+def _run_gpu(gpu, master, grads, kind, cfg, ws, lf, g_bf16=False, coef=None):
+    """``coef``: run clipped, with this coefficient read from device memory."""
     from zero_amd._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_F32
     from zero_amd.kernels import AdamSet, SgdSet, adam_hparams, sgd_hparams
 
@@ -147,6 +148,8 @@ def _run_gpu(gpu, master, grads, kind, cfg, ws, lf, g_bf16=False):
         n_all = sum(n for _, n, _ in SEGS)
         assert aset.elems == n_all and aset.bytes == per * n_all - 4 * (n_all - n_g)
     st = torch.cuda.current_stream()
+    coef_t = None if coef is None else torch.full((1,), coef, device=gpu)
+    run = aset.run if coef is None else lambda hp, st: aset.run_clipped(hp, coef_t, st)
     _tune(b"adam_loads_first", lf)
     try:
         for t in range(1, STEPS + 1):
@@ -154,11 +157,11 @@ def _run_gpu(gpu, master, grads, kind, cfg, ws, lf, g_bf16=False):
             G.copy_(torch.from_numpy(so.f32_to_bf16_bits(g).view(np.int16) if g_bf16 else g))
             if kind == "adam":
                 c = dict(cfg)
-                aset.run(adam_hparams(c.pop("lr", 1e-3), c.pop("beta1", 0.9), c.pop("beta2", 0.999),
-                                      c.pop("eps", 1e-8), c.pop("weight_decay", 0.0), t,
-                                      grad_div=float(ws), **c), st)
+                run(adam_hparams(c.pop("lr", 1e-3), c.pop("beta1", 0.9), c.pop("beta2", 0.999),
+                                 c.pop("eps", 1e-8), c.pop("weight_decay", 0.0), t,
+                                 grad_div=float(ws), **c), st)
             else:
-                aset.run(sgd_hparams(first=t == 1, grad_div=float(ws), **cfg), st)
+                run(sgd_hparams(first=t == 1, grad_div=float(ws), **cfg), st)
         torch.cuda.synchronize()
     finally:
         _tune(b"adam_loads_first", 1)
@@ -310,6 +313,28 @@ def test_clipped_run_equals_the_pre_scaled_gradient(gpu):
                                vmax=x)
     assert np.array_equal(outs[0][0].view(np.uint16), h) and np.array_equal(outs[0][1].view(np.uint16), l)
     assert np.array_equal(outs[0][4].view(np.uint32), x.view(np.uint32))
+
+
+CLIPPED_CASES = {
+    "adam": ("adam", dict(weight_decay=1e-2)),
+    "adam_amsgrad": ("adam", dict(amsgrad=True, weight_decay=1e-2)),
+    "sgd": ("sgd", dict(lr=0.05, weight_decay=1e-2)),
+    "sgd_momentum": ("sgd", dict(lr=0.05, momentum=0.9, weight_decay=1e-2)),
+}
+
+
+@pytest.mark.parametrize("case", list(CLIPPED_CASES))
+def test_clipped_instances(gpu, case):
+    """Every clipped instance of these sets, with and without amsgrad / a momentum buffer, with
+    ``adam_loads_first`` at 0 and at 1, over the full and partial chunks, the scalar tails and the
+    segment without a gradient of SPEC: coefficient 0.5 on g (a power of two, as grad_div = 2: both
+    products are exact) equals the oracle on 0.5 * g."""
+    kind, cfg = CLIPPED_CASES[case]
+    master, grads = _inputs(27)
+    want = _reference(master, [g * np.float32(0.5) for g in grads], kind, cfg, 2)
+    for lf in (0, 1):
+        got, _, _ = _run_gpu(gpu, master, grads, kind, cfg, 2, lf, coef=0.5)
+        _compare(got, want, f"clipped {case} adam_loads_first={lf}")
 
 
 def test_refusals(gpu):
