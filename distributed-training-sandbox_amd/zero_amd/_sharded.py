@@ -20,6 +20,7 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
+from ._update import owner_range
 from .engine import ShardEngine
 from .training_utils.utils import get
 
@@ -49,6 +50,11 @@ def sgd_group_hparams(group: dict) -> dict:
                 weight_decay=float(group.get("weight_decay", 0.0)),
                 nesterov=bool(group.get("nesterov", False)),
                 maximize=bool(group.get("maximize", False)), amsgrad=False)
+
+
+def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
+    """One param group's hyper-parameters for the ``kind`` ("adam" / "sgd") update."""
+    return sgd_group_hparams(group) if kind == "sgd" else adam_group_hparams(group, optimizer)
 
 
 def optimizer_kind(optimizer: Optimizer) -> str:
@@ -92,9 +98,9 @@ class ShardedOptimizerBase:
             self._clip_unsupported = f"layout={layout!r} (it runs on the bucket arena)"
         self._check_clip()
         self._kind = optimizer_kind(optimizer)
+        for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
+            group_hparams(self._kind, group, optimizer)
         if self._kind == "sgd":
-            for group in optimizer.param_groups:
-                sgd_group_hparams(group)
             # the SGD update runs on the flat arena (and its rounds) only
             if arena == "buckets":
                 raise ValueError("zero_amd: torch.optim.SGD is not supported with arena='buckets' "
@@ -115,11 +121,7 @@ class ShardedOptimizerBase:
         world_size = get("ws")
         rank = get("rank")
         # zero1.py:55-62 / zero2.py:51-58 (the planner computes the same ranges natively)
-        params_per_rank = len(self.params) // world_size
-        remainder = len(self.params) % world_size
-        start_idx = rank * params_per_rank + min(rank, remainder)
-        end_idx = start_idx + params_per_rank + (1 if rank < remainder else 0)
-        self.local_param_indices = list(range(start_idx, end_idx))
+        self.local_param_indices = list(range(*owner_range(len(self.params), world_size, rank)))
         self.local_params = set(self.params[i] for i in self.local_param_indices)
         self._shard_optimizer_params()
         ckpt.bind_inner_load(self)  # opt.optimizer.load_state_dict fills the flat state
@@ -255,34 +257,18 @@ class ShardedOptimizerBase:
             self._update_step_state()
             return
         for i in eng.owned_param_indices():
-            p = self.params[i]
             views = eng.state_views(i)
-            if views is None:
-                continue
-            st = self.optimizer.state[p]
-            st.update(views)
-            if eng.vmax is not None:
-                so = int(eng.pieces.stream_off[eng.pieces.param == i][0])
-                st["max_exp_avg_sq"] = eng.vmax[so:so + p.numel()].view(p.shape)
+            if views is not None:
+                self.optimizer.state[self.params[i]].update(views)
 
     def _hparams_of(self, gi: int) -> dict:
-        if self._kind == "sgd":
-            return sgd_group_hparams(self._groups[gi])
-        return adam_group_hparams(self._groups[gi], self.optimizer)
+        return group_hparams(self._kind, self._groups[gi], self.optimizer)
 
     def _update_step_state(self):
         eng = self.engine
         if self._kind == "sgd":
-            # torch's SGD state: {} until the parameter's first step, then the buffer alone (its
-            # presence is torch's "not the first step"); nothing at all without momentum
-            for i in eng.owned_param_indices():
-                if eng.steps[i] == 0:
-                    continue
-                st = self.optimizer.state[self.params[i]]
-                if "momentum_buffer" not in st:
-                    buf = (eng.state_views(i) or {}).get("momentum_buffer")
-                    if buf is not None and self._groups[eng.group_of[i]].get("momentum", 0) != 0:
-                        st["momentum_buffer"] = buf
+            eng.expose_sgd(self.optimizer, self.params, self._groups, eng.owned_param_indices(),
+                           eng.state_views)
             return
         for i in eng.owned_param_indices():
             s = int(eng.steps[i])
@@ -380,16 +366,9 @@ class ShardedOptimizerBase:
 
     def _ckpt_views(self, i: int) -> dict:
         """name -> live view of param i's flat state (the owned params of Layout R)."""
-        eng = self.engine
-        views = eng.state_views(i)
+        views = self.engine.state_views(i, ckpt=True)
         if views is None:
             raise NotImplementedError("zero_amd: state_dict() needs the reference (whole-param) layout")
-        if eng.vmax is not None:
-            so = int(eng.pieces.stream_off[eng.pieces.param == i][0])
-            views["max_exp_avg_sq"] = eng.vmax[so:so + self.params[i].numel()].view(self.params[i].shape)
-        if eng.carry is not None:
-            so = int(eng.pieces.stream_off[eng.pieces.param == i][0])
-            views["zero1_carry"] = eng.carry[so:so + self.params[i].numel()].view(self.params[i].shape)
         return views
 
     @on_param_device
@@ -407,13 +386,8 @@ class ShardedOptimizerBase:
                 p = self.params[i]
                 if id(p) not in index:
                     continue
-                entry = {k: v.detach().clone() for k, v in self._ckpt_views(i).items()}
-                if self._kind == "sgd":  # torch's SGD entry: the buffer once it exists, no step
-                    if self.engine.steps[i] == 0 or "momentum_buffer" not in self.optimizer.state[p]:
-                        entry.pop("momentum_buffer", None)
-                else:
-                    entry["step"] = torch.tensor(float(self.engine.steps[i]), dtype=torch.float32)
-                state[index[id(p)]] = entry
+                state[index[id(p)]] = self.engine.save_entry(i, self._ckpt_views(i),
+                                                             self.optimizer.state[p])
         sd["state"] = state
         sd["zero_amd"] = self._ckpt_header()
         return sd
@@ -442,21 +416,7 @@ class ShardedOptimizerBase:
             for i in eng.owned_param_indices():
                 p = self.params[i]
                 entry = saved.get(index.get(id(p), -1), {})
-                views = self._ckpt_views(i)
-                for name, view in views.items():
-                    src = entry.get(name)
-                    if src is not None:
-                        view.copy_(src.reshape(view.shape))
-                    elif name == "master_residual":  # master = the bf16 param exactly
-                        view.zero_()
-                    elif name == "master_param":
-                        view.copy_(p.detach().reshape(view.shape))
-                    else:  # no state: torch's fresh Adam (moments 0), no carry
-                        view.zero_()
-                if self._kind == "sgd":  # no buffer saved: the parameter's next step is its first
-                    eng.steps[i] = int(entry.get("momentum_buffer") is not None)
-                else:
-                    eng.steps[i] = ckpt.step_of(entry)
+                eng.load_entry(i, self._ckpt_views(i), entry, p)
         self.optimizer.state.clear()
         self._expose_state()
         self._update_step_state()
@@ -473,13 +433,8 @@ CALIBRATION_BYTES = 256 << 20  # gradient bytes per calibration exchange (capped
 def _owner_bytes(opt) -> list:
     """Gradient bytes each rank owns under the reference's index ranges (zero1.py:55-62)."""
     ws, n = opt.world_size, len(opt.params)
-    ppr, rem = n // ws, n % ws
-    out = []
-    for r in range(ws):
-        a = r * ppr + min(r, rem)
-        b = a + ppr + (1 if r < rem else 0)
-        out.append(sum(p.numel() * p.element_size() for p in opt.params[a:b]))
-    return out
+    return [sum(p.numel() * p.element_size() for p in opt.params[slice(*owner_range(n, ws, r))])
+            for r in range(ws)]
 
 
 def calibrate_arena(opt, iters: int = 3) -> dict:

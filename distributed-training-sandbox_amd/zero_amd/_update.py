@@ -1,0 +1,247 @@
+"""The fused update over one flat shard: what ZeRO-1/2's engines and ZeRO-3's update mode share.
+
+``UpdateCore`` owns, for a shard of ``L`` elements, the flat fp32 optimizer state (one placed
+allocation: ``[m][v][carry][master]`` + the split master's int16 residuals), the per-parameter step
+counts, the cache of kernel sets with its retire list, and the one timed launch.  It knows nothing
+of how gradients reach the shard: ``ShardEngine`` (engine.py, flat.py) is a core plus an exchange,
+``zero3.ShardedOptimizer`` holds one over its chunk arena.  Callers hand it ``zs_adam_seg`` rows
+(include/zero_amd.h) whose pointer columns they filled; the core fills the state columns, cuts the
+rows into (group, step key, carry multiplier) parts and launches one AdamSet / SgdSet per part.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .checkpoint import step_of
+from .kernels import adam_hparams, sgd_hparams
+
+
+def owner_range(n: int, ws: int, rank: int):
+    """(start, end) of the parameter indices ``rank`` owns out of ``n`` (zero1.py:55-62: equal
+    runs, the first ``n % ws`` ranks one longer)."""
+    per, rem = n // ws, n % ws
+    start = rank * per + min(rank, rem)
+    return start, start + per + (1 if rank < rem else 0)
+
+
+def check_params(params):
+    """(device, dtype) shared by ``params``; they must live on one GPU in one dtype."""
+    dev, dtype = params[0].device, params[0].dtype
+    if dev.type != "cuda":
+        raise RuntimeError(f"zero_amd: parameters must live on a GPU (got {dev}); "
+                           "there is no CPU path")
+    for p in params:
+        if p.device != dev or p.dtype != dtype:
+            raise TypeError("zero_amd: all parameters must share one device and dtype")
+    return dev, dtype
+
+
+def state_layout(kind: str, L: int, *, split: bool, fp32_master: bool, carry: bool,
+                 momentum: bool = True):
+    """(total fp32 words, {name: (word offset, dtype)}) of the flat state of an ``L``-element
+    shard: ``m``, ``v`` (Adam; SGD: ``m`` alone, the momentum buffer, and only with ``momentum``),
+    ``carry`` (ZeRO-1), ``master`` (fp32 master of bf16 params), each ``L`` fp32, then ``lo``:
+    ``L`` int16 residuals of the split master in ``(L + 1) // 2`` words."""
+    names = ["m", "v"][:2 if kind == "adam" else int(bool(momentum))]
+    names += ["carry"] * bool(carry) + ["master"] * bool(fp32_master)
+    lay = {name: (k * L, torch.float32) for k, name in enumerate(names)}
+    total = len(names) * L
+    if split:
+        lay["lo"] = (total, torch.int16)
+        total += (L + 1) // 2
+    return total, lay
+
+
+class UpdateCore:
+    def __init__(self, kind: str, L: int, device, ws: int, group_of, n_params: int, *,
+                 split: bool = False, fp32_master: bool = False, carry: bool = False,
+                 momentum: bool = True, placement_tries: int = 8):
+        from .engine import probed_zeros  # (engine.py builds on this module)
+
+        if kind not in ("adam", "sgd"):
+            raise ValueError(f"UpdateCore: kind must be 'adam' or 'sgd' (got {kind!r})")
+        # the update: torch.optim.Adam's, or torch.optim.SGD's (`momentum`: some group has a
+        # momentum, so the shard holds a momentum buffer; none of them: no optimizer state at all)
+        self.kind, self.L, self.device, self.ws = kind, int(L), device, ws
+        self.group_of = list(group_of)
+        total, lay = state_layout(kind, self.L, split=split, fp32_master=fp32_master, carry=carry,
+                                  momentum=momentum)
+        self.state, self.placement = probed_zeros(total, torch.float32, device, placement_tries)
+        for name in ("m", "v", "carry", "master", "lo"):  # residual 0: master = the bf16 param
+            off, dt = lay.get(name, (0, None))
+            setattr(self, name, None if dt is None else self.state[off:].view(dt)[:self.L])
+        self.vmax = None
+        self.steps = np.zeros(n_params, np.int64)  # torch's per-param state['step']
+        self._cache = {}
+        self.retired = []
+        self.timing_events = None  # optional list of (start, end, bytes) per update launch
+        self.last_adam_bytes = 0
+
+    # state ------------------------------------------------------------------------------------
+    def views(self, so: int, n: int, shape, *, ckpt: bool = False) -> dict:
+        """name -> live view of the state of the parameter at [so, so + n) of the shard, under
+        torch's names (what ``optimizer.state[p]`` holds); ``ckpt``: also what only a checkpoint
+        carries (ZeRO-1's carry)."""
+        cut = lambda t: t[so:so + n].view(shape)  # noqa: E731
+        if self.kind == "sgd":  # torch's SGD state: the buffer alone (absent without momentum)
+            views = {} if self.m is None else {"momentum_buffer": cut(self.m)}
+        else:
+            views = {"exp_avg": cut(self.m), "exp_avg_sq": cut(self.v)}
+        if self.master is not None:
+            views["master_param"] = cut(self.master)
+        if self.lo is not None:  # the fp32 master = the bf16 param's bits << 16 + this residual
+            views["master_residual"] = cut(self.lo)
+        if self.vmax is not None:
+            views["max_exp_avg_sq"] = cut(self.vmax)
+        if ckpt and self.carry is not None:
+            views["zero1_carry"] = cut(self.carry)
+        return views
+
+    def ensure_vmax(self):
+        if self.vmax is None:
+            self.vmax = torch.zeros(self.L, dtype=torch.float32, device=self.device)
+        return self.vmax
+
+    def state_cols(self, rows, so) -> None:
+        """Columns 4-7 (m, v, vmax, carry) of zs_adam_seg ``rows`` at shard offsets ``so``."""
+        so = np.asarray(so).astype(np.uint64) * np.uint64(4)
+        for col, t in ((4, self.m), (5, self.v), (6, self.vmax), (7, self.carry)):
+            if t is not None:
+                rows[:, col] = np.uint64(t.data_ptr()) + so
+
+    def expose_sgd(self, optimizer, params, groups, idx, views_of) -> None:
+        """torch's SGD state for the parameters ``idx``: {} until a parameter's first step, then
+        its momentum buffer alone (its presence is torch's "not the first step"); nothing at all
+        without momentum.  ``views_of(i)``: parameter i's views (None: not whole in this shard)."""
+        for i in idx:
+            i = int(i)
+            if self.steps[i] == 0 or self.m is None:
+                continue
+            st = optimizer.state[params[i]]
+            if "momentum_buffer" not in st and groups[self.group_of[i]].get("momentum", 0) != 0:
+                buf = (views_of(i) or {}).get("momentum_buffer")
+                if buf is not None:
+                    st["momentum_buffer"] = buf
+
+    def save_entry(self, i: int, views: dict, torch_state: dict) -> dict:
+        """Parameter i's checkpoint entry: copies of ``views``, in torch's format."""
+        entry = {k: v.detach().clone() for k, v in views.items()}
+        if self.kind == "sgd":  # torch's SGD entry: the buffer once it exists, no step
+            if self.steps[i] == 0 or "momentum_buffer" not in torch_state:
+                entry.pop("momentum_buffer", None)
+        else:
+            entry["step"] = torch.tensor(float(self.steps[i]), dtype=torch.float32)
+        return entry
+
+    def load_entry(self, i: int, views: dict, entry: dict, param) -> None:
+        """``entry`` into parameter i's ``views`` and step count.  What it lacks starts fresh:
+        moments and carry 0 (torch's new Adam), the master = ``param`` as it is (residual 0)."""
+        for name, view in views.items():
+            src = entry.get(name)
+            if src is not None:
+                view.copy_(src.reshape(view.shape))
+            elif name == "master_param":
+                view.copy_(param.detach().reshape(view.shape))
+            else:
+                view.zero_()
+        if self.kind == "sgd":  # no buffer saved: the parameter's next step is its first
+            self.steps[i] = int(entry.get("momentum_buffer") is not None)
+        else:
+            self.steps[i] = step_of(entry)
+
+    # hyper-parameters ---------------------------------------------------------------------------
+    def hp_key(self, steps):
+        """What of a parameter's step count the hyper-parameter struct depends on: the count
+        itself (Adam's bias correction), or only whether this is its first step (SGD's buffer)."""
+        steps = np.asarray(steps, np.int64)
+        return (steps == 1).astype(np.int64) if self.kind == "sgd" else steps
+
+    def make_hp(self, hpd: dict, key: int, cmul: int = 0):
+        """The kernel's hyper-parameter struct of one (group, hp_key, carry multiplier) part."""
+        carry_mul = float(cmul) if self.carry is not None else 0.0
+        if self.kind == "sgd":
+            if hpd["momentum"] != 0 and self.m is None:
+                raise ValueError("zero_amd: a param group's momentum became non-zero after the "
+                                 "optimizer was built without momentum buffers")
+            return sgd_hparams(hpd["lr"], hpd["momentum"], hpd["dampening"], hpd["weight_decay"],
+                               nesterov=hpd["nesterov"], maximize=hpd["maximize"], first=bool(key),
+                               grad_div=float(self.ws), carry_mul=carry_mul)
+        if hpd["amsgrad"] and self.vmax is None:
+            raise RuntimeError("amsgrad state buffer missing")
+        return adam_hparams(hpd["lr"], hpd["beta1"], hpd["beta2"], hpd["eps"], hpd["weight_decay"],
+                            int(key), decoupled=hpd["decoupled"], amsgrad=hpd["amsgrad"],
+                            maximize=hpd["maximize"], grad_div=float(self.ws), carry_mul=carry_mul)
+
+    # kernel sets --------------------------------------------------------------------------------
+    def cached(self, key, sig: bytes, build):
+        hit = self._cache.get(key)
+        if hit is not None and hit[0] == sig:
+            return hit[1]
+        obj = build()
+        if hit is not None:
+            # tensors moved: the old table may still be read by queued kernels, and hipFree
+            # synchronises the device — keep it until the next point the device is idle
+            self.retired.append(hit[1])
+        self._cache[key] = (sig, obj)
+        return obj
+
+    def n_retired(self) -> int:
+        return len(self.retired)
+
+    def release_retired(self):
+        """Free replaced segment tables; call only after the device has been synchronised."""
+        self.retired.clear()
+
+    def launch(self, aset, hp, stream, coef=None) -> None:
+        """Run ``aset`` (``coef``: with the clip coefficient, a device scalar's address); with
+        ``timing_events`` on, between two HIP events."""
+        ev = self.timing_events
+        if ev is not None:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+        if coef is None:
+            aset.run(hp, stream)
+        else:
+            aset.run_clipped(hp, coef, stream)
+        if ev is not None:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record(stream)
+            ev.append((e0, e1, aset.bytes))
+        self.last_adam_bytes += aset.bytes
+
+    def run_parts(self, tag, rows, param_idx, hparams_of, stream, *, carry_mul=None, gptr=None,
+                  defer=None, new_set=None):
+        """Partition rows by (group, step key, carry multiplier) — torch's bias correction is per
+        param (SGD: by "first step?", the momentum buffer's birth is per param), and the ZeRO-1
+        carry weight depends on which grads survived since the last step — and launch one fused
+        set per part, built by ``new_set(rows)`` (default: ``self.new_set``) and cached under
+        ``(group, rows, first row, tag)`` while its rows stay the same.  ``gptr`` (per row): gradient addresses bound into
+        the sets before they run (AdamSet.set_grads; the rows then carry g = 0).  ``defer`` (a
+        list; gradient clipping): nothing is launched, every part is appended as ``(aset, hp, gptr
+        of its rows or None)`` for the caller to run once the clip coefficient exists.
+        Returns the parts as ``(group, aset)``."""
+        parts = []
+        if len(rows) == 0:
+            return parts
+        new_set = self.new_set if new_set is None else new_set
+        if carry_mul is None:
+            carry_mul = np.full(len(param_idx), self.ws - 1 if self.carry is not None else 0, np.int64)
+        keys = np.stack([np.asarray(self.group_of)[param_idx], self.hp_key(self.steps[param_idx]),
+                         np.asarray(carry_mul, np.int64)], axis=1)
+        for key in np.unique(keys, axis=0):
+            sel = np.nonzero((keys == key).all(axis=1))[0]
+            sub = np.ascontiguousarray(rows[sel])
+            gidx, step, cmul = int(key[0]), int(key[1]), int(key[2])
+            aset = self.cached((gidx, len(sel), int(sel[0]), tag), sub.tobytes(),
+                               lambda: new_set(sub))
+            parts.append((gidx, aset))
+            g = None if gptr is None else np.asarray(gptr, np.uint64)[sel]
+            hp = self.make_hp(hparams_of(gidx), step, cmul)
+            if defer is not None:
+                defer.append((aset, hp, g))
+                continue
+            if g is not None:
+                aset.set_grads(g, stream)
+            self.launch(aset, hp, stream)
+        return parts

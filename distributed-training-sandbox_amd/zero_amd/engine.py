@@ -1,9 +1,9 @@
 """The bucketed ZeRO step: pack → reduce-scatter → fused Adam → all-gather → unpack.
 
-One ``ShardEngine`` per ``ShardedOptimizer``.  It owns, for this rank's optimizer shard (the
-*stream* the planner assigns it), flat fp32 buffers for exp_avg / exp_avg_sq (+ max_exp_avg_sq,
-the fp32 master of bf16 params, and the ZeRO-1 gradient carry), and one persistent *arena* of
-bucket buffers in the parameter dtype.  A bucket buffer is one window of every rank's stream,
+One ``ShardEngine`` per ``ShardedOptimizer``.  It is an ``UpdateCore`` (_update.py: the flat fp32
+state of this rank's optimizer shard — the *stream* the planner assigns it — with its views, the
+hyper-parameter structs, the cached kernel sets and their launches) plus the exchange: one
+persistent *arena* of bucket buffers in the parameter dtype.  A bucket buffer is one window of every rank's stream,
 rank-major.  In an *even* bucket (stream positions every rank has) the windows are equal, so a
 single in-place RCCL reduce-scatter hands every rank the summed gradient of its own window and a
 single in-place all-gather hands every rank all updated windows.  Layout R's streams differ in
@@ -37,7 +37,8 @@ import torch
 
 from . import _lib
 from .comm import StreamEvent, comm_stream, zs_dtype
-from .kernels import AdamSet, CopySet, SgdSet, adam_hparams, sgd_hparams
+from ._update import UpdateCore, check_params
+from .kernels import AdamSet, CopySet, SgdSet
 from .plan import Plan
 
 ALIGN_ELEMS = 64  # every stream piece starts 256 B (f32) / 128 B (bf16) aligned
@@ -291,33 +292,24 @@ def probed_zeros(n: int, dtype, device, tries: int = 8, accept_gbs: float = PROB
     return out, info
 
 
-class ShardEngine:
+class ShardEngine(UpdateCore):
+    """An update core (its flat state, set cache and launches: _update.py) plus the exchange that
+    brings this rank's stream its reduced gradients and sends the updated parameters back."""
+
     def __init__(self, params, group_of, ws: int, rank: int, *, layout="reference", carry=False,
                  comm=None, bucket_bytes: int = 256 << 20, align: int = ALIGN_ELEMS,
                  buckets: str = "ragged", placement_tries: int = 8, master: str = "split",
                  kind: str = "adam", momentum: bool = True):
         if kind not in ("adam", "sgd"):
             raise ValueError(f"ShardEngine: kind must be 'adam' or 'sgd' (got {kind!r})")
-        # the update: torch.optim.Adam's, or torch.optim.SGD's (`momentum`: some group has a
-        # momentum, so the shard holds a momentum buffer; none of them: no optimizer state at all)
-        self.kind = kind
         if not params:
             raise ValueError("ShardEngine: no parameters")
-        dev = params[0].device
-        if dev.type != "cuda":
-            raise RuntimeError(f"zero_amd: parameters must live on a GPU (got {dev}); "
-                               "there is no CPU path")
-        dtype = params[0].dtype
-        for p in params:
-            if p.device != dev or p.dtype != dtype:
-                raise TypeError("zero_amd: all parameters must share one device and dtype")
-            if not p.is_contiguous():
-                raise ValueError("zero_amd: parameters must be contiguous")
+        dev, dtype = check_params(params)
+        if not all(p.is_contiguous() for p in params):
+            raise ValueError("zero_amd: parameters must be contiguous")
         self.zdtype = zs_dtype(dtype)
         self.params = list(params)
-        self.group_of = list(group_of)
-        self.ws, self.rank = ws, rank
-        self.device, self.dtype = dev, dtype
+        self.rank, self.dtype = rank, dtype
         self.es = params[0].element_size()
         self.mixed = dtype == torch.bfloat16  # bf16 params → an fp32 master in the shard
         if master not in ("split", "fp32"):
@@ -337,25 +329,11 @@ class ShardEngine:
         self.plan = Plan(numels, ws, rank, layout, dim0=dim0, align_elems=align, window_elems=window,
                          buckets=buckets)
         self.W, self.K = self.plan.window, self.plan.num_buckets
-        self.L = self.plan.stream_len(rank)
         self.pieces = self.plan.pieces(rank)
-
-        # exp_avg, exp_avg_sq (+ ZeRO-1 carry, + fp32 master or its int16 residual): one
-        # allocation, placed by probe
-        L = self.L
-        nmom = 2 if kind == "adam" else int(bool(momentum))  # exp_avg + exp_avg_sq / the buffer
-        nf = nmom + int(bool(carry)) + int(self.mixed and not self.split)
-        nlo = (L + 1) // 2 if self.split else 0  # int16 residuals, in fp32 words
-        self.state, self.placement = probed_zeros(nf * L + nlo, torch.float32, dev, placement_tries)
-        views = iter([self.state[k * L:(k + 1) * L] for k in range(nf)])
-        # SGD: m is the momentum buffer (None without momentum), there is no v
-        self.m = next(views) if nmom else None
-        self.v = next(views) if nmom == 2 else None
-        self.vmax = None
-        self.carry = next(views) if carry else None
-        self.master = next(views) if self.mixed and not self.split else None
-        # residual 0 everywhere: the master starts as the bf16 param exactly
-        self.lo = self.state[nf * L:].view(torch.int16)[:L] if self.split else None
+        # exp_avg, exp_avg_sq (+ ZeRO-1 carry, + fp32 master or its int16 residual) of the stream
+        UpdateCore.__init__(self, kind, self.plan.stream_len(rank), dev, ws, group_of, len(params),
+                            split=self.split, fp32_master=self.mixed and not self.split,
+                            carry=carry, momentum=momentum, placement_tries=placement_tries)
         if self.master is not None:
             for i, po, so, n in zip(*self._piece_cols()):
                 self.master[so:so + n].copy_(params[i].detach().reshape(-1)[po:po + n])
@@ -369,14 +347,9 @@ class ShardEngine:
             self.ev_pack, self.ev_rs, self.ev_adam, self.ev_ag = mk(), mk(), mk(), mk()
         self.ev_c0 = torch.cuda.Event(enable_timing=True)
         self.ev_c1 = torch.cuda.Event(enable_timing=True)
-        self.steps = np.zeros(len(params), np.int64)  # torch's per-param state['step']
-        self._cache = {}
-        self.retired = []
-        self.timing_events = None  # optional list of (start, end) events around each Adam launch
         self.comm_events = None    # optional list of (kind, even, start, end, bus_bytes) per collective
         self.copy_events = None    # optional list of (kind, start, end, bytes) per pack / unpack
         self.capture_reduced = None  # optional tensor (stream-long): the reduced grads, for checks
-        self.last_adam_bytes = 0
         # global gradient-norm clipping (flat arena only; flat.py _clip_*): the limit of this step
         # (None = off), bytes the last step's norm pass read, and the device results
         self.max_grad_norm = None
@@ -395,46 +368,20 @@ class ShardEngine:
                                                                      self.pieces.length) if n > 0))
         return own
 
-    def state_views(self, i: int):
-        """exp_avg / exp_avg_sq views of param i's shard (Layout R: the whole param)."""
+    def state_views(self, i: int, *, ckpt: bool = False):
+        """The views of param i's shard state (Layout R: the whole param; None when the param is
+        split over pieces): ``UpdateCore.views``."""
         sel = np.nonzero(self.pieces.param == i)[0]
         if len(sel) != 1:
             return None
         j = int(sel[0])
         so, n = int(self.pieces.stream_off[j]), int(self.pieces.length[j])
-        po = int(self.pieces.param_off[j])
         p = self.params[i]
-        shape = p.shape if (po == 0 and n == p.numel()) else (n,)
-        if self.kind == "sgd":  # torch's SGD state: the buffer alone (absent without momentum)
-            views = {} if self.m is None else {"momentum_buffer": self.m[so:so + n].view(shape)}
-        else:
-            views = {"exp_avg": self.m[so:so + n].view(shape),
-                     "exp_avg_sq": self.v[so:so + n].view(shape)}
-        if self.master is not None:
-            views["master_param"] = self.master[so:so + n].view(shape)
-        if self.lo is not None:  # the fp32 master = the bf16 param's bits << 16 + this residual
-            views["master_residual"] = self.lo[so:so + n].view(shape)
-        return views
-
-    def ensure_vmax(self):
-        if self.vmax is None:
-            self.vmax = torch.zeros(self.L, dtype=torch.float32, device=self.device)
-        return self.vmax
-
-    def _cached(self, key, sig: bytes, build):
-        hit = self._cache.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        obj = build()
-        if hit is not None:
-            # tensors moved: the old table may still be read by queued kernels, and hipFree
-            # synchronises the device — keep it until the next point the device is idle
-            self.retired.append(hit[1])
-        self._cache[key] = (sig, obj)
-        return obj
+        whole = int(self.pieces.param_off[j]) == 0 and n == p.numel()
+        return self.views(so, n, p.shape if whole else (n,), ckpt=ckpt)
 
     def n_retired(self) -> int:
-        gb = getattr(self, "gb", None)
+        gb = getattr(self, "gb", None)  # (overlap mode: the grad buckets' own tables)
         return len(self.retired) + (len(gb.retired) if gb is not None else 0)
 
     def release_retired(self):
@@ -447,19 +394,11 @@ class ShardEngine:
     def _adam_rows(self, idx, g_ptr, mst, mst_out, p_out, so, n):
         """Vectorised zs_adam_seg rows (numpy uint64 (n, 9))."""
         rows = np.zeros((len(idx), 9), np.uint64)
-        so = so.astype(np.uint64)
         rows[:, 0] = g_ptr
         rows[:, 1] = mst
         rows[:, 2] = mst_out
         rows[:, 3] = p_out
-        if self.m is not None:
-            rows[:, 4] = np.uint64(self.m.data_ptr()) + so * np.uint64(4)
-        if self.v is not None:
-            rows[:, 5] = np.uint64(self.v.data_ptr()) + so * np.uint64(4)
-        if self.vmax is not None:
-            rows[:, 6] = np.uint64(self.vmax.data_ptr()) + so * np.uint64(4)
-        if self.carry is not None:
-            rows[:, 7] = np.uint64(self.carry.data_ptr()) + so * np.uint64(4)
+        self.state_cols(rows, so)
         rows[:, 8] = n.astype(np.uint64)
         return rows
 
@@ -477,65 +416,6 @@ class ShardEngine:
         """The update's kernel set over ``rows``: AdamSet, or SgdSet for an SGD engine."""
         gz = getattr(self, "czdtype", self.zdtype)  # dtype of the reduced grad the update reads
         return (SgdSet if self.kind == "sgd" else AdamSet)(rows, gz, self.p_dtype)
-
-    def hp_key(self, steps):
-        """What of a parameter's step count the hyper-parameter struct depends on: the count
-        itself (Adam's bias correction), or only whether this is its first step (SGD's buffer)."""
-        steps = np.asarray(steps, np.int64)
-        return (steps == 1).astype(np.int64) if self.kind == "sgd" else steps
-
-    def make_hp(self, hpd: dict, key: int, cmul: int):
-        """The kernel's hyper-parameter struct of one (group, hp_key, carry multiplier) part."""
-        carry_mul = float(cmul) if self.carry is not None else 0.0
-        if self.kind == "sgd":
-            if hpd["momentum"] != 0 and self.m is None:
-                raise ValueError("zero_amd: a param group's momentum became non-zero after the "
-                                 "optimizer was built without momentum buffers")
-            return sgd_hparams(hpd["lr"], hpd["momentum"], hpd["dampening"], hpd["weight_decay"],
-                               nesterov=hpd["nesterov"], maximize=hpd["maximize"], first=bool(key),
-                               grad_div=float(self.ws), carry_mul=carry_mul)
-        if hpd["amsgrad"] and self.vmax is None:
-            raise RuntimeError("amsgrad state buffer missing")
-        return adam_hparams(hpd["lr"], hpd["beta1"], hpd["beta2"], hpd["eps"], hpd["weight_decay"],
-                            key, decoupled=hpd["decoupled"], amsgrad=hpd["amsgrad"],
-                            maximize=hpd["maximize"], grad_div=float(self.ws), carry_mul=carry_mul)
-
-    def _run_adam(self, tag, rows, param_idx, hparams_of, stream, carry_mul=None, gptr=None,
-                  defer=None):
-        """Partition rows by (group, step, carry multiplier) — torch's bias correction is per param
-        (SGD: by "first step?", the momentum buffer's birth is per param),
-        and the ZeRO-1 carry weight depends on which grads survived since the last step — and
-        launch one fused-Adam set per part.  ``gptr`` (per row): gradient addresses bound into the
-        sets before they run (AdamSet.set_grads; the rows then carry g = 0).  ``defer`` (a list;
-        gradient clipping): nothing is launched, every part is appended as ``(aset, hp, gptr of
-        its rows or None)`` for the caller to run once the clip coefficient exists."""
-        if len(rows) == 0:
-            return
-        if carry_mul is None:
-            carry_mul = np.full(len(param_idx), self.ws - 1 if self.carry is not None else 0, np.int64)
-        keys = np.stack([np.asarray(self.group_of)[param_idx], self.hp_key(self.steps[param_idx]),
-                         np.asarray(carry_mul, np.int64)], axis=1)
-        for key in np.unique(keys, axis=0):
-            sel = np.nonzero((keys == key).all(axis=1))[0]
-            sub = np.ascontiguousarray(rows[sel])
-            gidx, step, cmul = int(key[0]), int(key[1]), int(key[2])
-            aset = self._cached(("adam", tag, gidx, len(sel), int(sel[0])), sub.tobytes(),
-                                lambda: self.new_set(sub))
-            if gptr is not None and defer is None:
-                aset.set_grads(np.asarray(gptr, np.uint64)[sel], stream)
-            hp = self.make_hp(hparams_of(gidx), step, cmul)
-            if defer is not None:
-                defer.append((aset, hp, None if gptr is None else np.asarray(gptr, np.uint64)[sel]))
-                continue
-            if self.timing_events is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                aset.run(hp, stream)
-                e1.record(stream)
-                self.timing_events.append((e0, e1, aset.bytes))
-            else:
-                aset.run(hp, stream)
-            self.last_adam_bytes += aset.bytes
 
     # ------------------------------------------------------------------------------------------
     def step(self, grads, hparams_of, stream=None):
@@ -582,7 +462,7 @@ class ShardEngine:
             p = pptr + po.astype(np.uint64) * np.uint64(4)
             rows = self._adam_rows(idx, g, p, p, 0, so, n)
         with _lib.phase_range("optimizer_step"):  # zero1.py:88
-            self._run_adam("local", rows, idx, hparams_of, stream)
+            self.run_parts("local", rows, idx, hparams_of, stream)
 
     def _run_copy(self, kind, cs, stream):
         """Launch a pack / unpack CopySet; with timing on, bracket it with HIP events (algorithmic
@@ -651,7 +531,7 @@ class ShardEngine:
                     nb.append(s.length * self.es)
                 src, dst, nb = np.concatenate(src), np.concatenate(dst), np.concatenate(nb)
                 sig = src.tobytes() + dst.tobytes()
-                pack = self._cached(("pack", gi), sig, lambda: CopySet(
+                pack = self.cached(("pack", gi), sig, lambda: CopySet(
                     src, dst, nb, bounds=(list(grads), [self.arena]) if CHECK_EXTENTS else None))
                 self._run_copy("pack", pack, stream)
                 for k in grp:
@@ -677,12 +557,12 @@ class ShardEngine:
                 else:
                     p = pptr[idx] + po * np.uint64(4)
                     rows = self._adam_rows(idx, slot, p, slot, 0, so, ln)
-                self._run_adam(("bucket", k), rows[live], idx[live], hparams_of, stream)
+                self.run_parts(("bucket", k), rows[live], idx[live], hparams_of, stream)
                 if not live.all():  # params without a grad keep their value: copy it into the slot
                     dead = np.nonzero(~live)[0]
                     src = pptr[idx[dead]] + po[dead] * es
                     nb = ln[dead] * self.es
-                    self._cached(("pass", k), src.tobytes() + slot[dead].tobytes(),
+                    self.cached(("pass", k), src.tobytes() + slot[dead].tobytes(),
                                  lambda: CopySet(src, slot[dead], nb)).run(stream)
                 self.ev_adam[k].record(stream)
         with _lib.phase_range("broadcast_parameters"):  # zero1.py:91-102: all-gather + unpack
@@ -701,7 +581,7 @@ class ShardEngine:
                     dst.append(pptr[s.param] + s.param_off.astype(np.uint64) * es)
                     nb.append(s.length * self.es)
                 src, dst, nb = np.concatenate(src), np.concatenate(dst), np.concatenate(nb)
-                unpack = self._cached(("unpack", gi), src.tobytes() + dst.tobytes(),
+                unpack = self.cached(("unpack", gi), src.tobytes() + dst.tobytes(),
                                       lambda: CopySet(src, dst, nb, bounds=(
                                           [self.arena], self.params) if CHECK_EXTENTS else None))
                 self._run_copy("unpack", unpack, stream)
@@ -761,12 +641,12 @@ class ShardEngine:
                         rows = self._mixed_rows(idx, slot, p, out, so, ln)
                     else:
                         rows = self._adam_rows(idx, slot, p, out, 0, so, ln)
-                    self._run_adam(("overlap", k), rows, idx, hparams_of, stream)
+                    self.run_parts(("overlap", k), rows, idx, hparams_of, stream)
                 dead = [i for i in gb.groups[k] if not has[i]]
                 if dead and self.ws > 1:  # params without a grad keep their value: copy into the slot
                     src = [_ptr(self.params[i]) for i in dead]
                     dst = [int(base) + int(gb.slot[i]) * self.es for i in dead]
-                    self._cached(("opass", k), np.array(src + dst, np.uint64).tobytes(),
+                    self.cached(("opass", k), np.array(src + dst, np.uint64).tobytes(),
                                  lambda: CopySet(src, dst, [self.params[i].numel() * self.es
                                                             for i in dead])).run(stream)
                 self.ev_oadam[k].record(stream)
@@ -789,7 +669,7 @@ class ShardEngine:
                 g = gb.groups[k]
                 src = [int(base) + int(gb.slot[i]) * self.es for i in g]
                 dst = [_ptr(self.params[i]) for i in g]
-                self._cached(("ounpack", k), np.array(dst, np.uint64).tobytes(),
+                self.cached(("ounpack", k), np.array(dst, np.uint64).tobytes(),
                              lambda: CopySet(src, dst, [self.params[i].numel() * self.es
                                                         for i in g])).run(stream)
         gb.reset()

@@ -321,15 +321,7 @@ class FlatEngine(ShardEngine):
         for gi, idx, aset in sets:
             if gptr is not None:
                 aset.set_grads(gptr[idx], stream)
-            if self.timing_events is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                aset.run(hps[gi], stream)
-                e1.record(stream)
-                self.timing_events.append((e0, e1, aset.bytes))
-            else:
-                aset.run(hps[gi], stream)
-            self.last_adam_bytes += aset.bytes
+            self.launch(aset, hps[gi], stream)
         return True
 
     def _adam_round(self, rd: _Round, has, cmul, hps, hparams_of, stream, gptr=None, defer=None):
@@ -339,7 +331,7 @@ class FlatEngine(ShardEngine):
             return
         live = has[rd.idx]
         rows, idx = (rd.rows, rd.idx) if live.all() else (rd.rows[live], rd.idx[live])
-        self._run_adam(("flat", rd.j), rows, idx, hparams_of, stream, carry_mul=cmul[idx],
+        self.run_parts(("flat", rd.j), rows, idx, hparams_of, stream, carry_mul=cmul[idx],
                        gptr=None if gptr is None else gptr[idx], defer=defer)
 
     # ------------------------------------------------------------------------------------------
@@ -406,15 +398,7 @@ class FlatEngine(ShardEngine):
         """Stage 4 for ``deferred[first:last]``: the update with the coefficient."""
         coef = self.clip_out.data_ptr() + 4
         for aset, hp, _ in deferred[first:last]:
-            if self.timing_events is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                aset.run_clipped(hp, coef, stream)
-                e1.record(stream)
-                self.timing_events.append((e0, e1, aset.bytes))
-            else:
-                aset.run_clipped(hp, coef, stream)
-            self.last_adam_bytes += aset.bytes
+            self.launch(aset, hp, stream, coef)
 
     # ------------------------------------------------------------------------------------------
     def _reduce_round(self, rd: _Round, cs):
@@ -684,7 +668,7 @@ class FlatEngine(ShardEngine):
                 if len(rd.idx) and not (hps and self._adam_round_fast(rd, hps, stream)):
                     live = has[rd.idx]
                     rows, idx = (rd.rows, rd.idx) if live.all() else (rd.rows[live], rd.idx[live])
-                    self._run_adam(("flat", rd.j), rows, idx, hparams_of, stream,
+                    self.run_parts(("flat", rd.j), rows, idx, hparams_of, stream,
                                    carry_mul=cmul[idx])
                 self.ev_adam[rd.j].record(stream)
         if self.ws > 1:

@@ -26,7 +26,11 @@ real rows), and ``param.data`` is a view of its slot between gathers.  Two modes
     bucket in flight plus 1/ws of the model.  ``step()`` is one fused HIP Adam launch over the
     chunk arena (grad /ws folded in) — data-parallel Adam, sliced.  Every rank updates its chunk
     of every parameter, so the inner optimizer's groups are not filtered in this mode and
-    ``optimizer.state[p]`` holds chunk-shaped views of the flat fp32 state.
+    ``optimizer.state[p]`` holds chunk-shaped views of the flat fp32 state.  That state, the
+    hyper-parameter structs, the cached kernel sets and their launches are an ``UpdateCore``'s
+    (_update.py, the one ZeRO-1/2's engines are built on); this module builds the rows over the
+    chunk arena and keeps the step-level fast path (the same parameters and one step count as
+    last step: last step's sets, no rows built).
     ``grad_accumulation=True`` (opt-in) takes several backward passes per ``step()``: every pass
     after the first is reduce-scattered into a staging buffer and added to the grad chunk arena
     by a fused HIP kernel (zs_accumulate) — one rounding per pass in the chunks' dtype, as
@@ -64,10 +68,11 @@ from . import _lib
 from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
-from ._sharded import adam_group_hparams, optimizer_kind, sgd_group_hparams
+from ._sharded import group_hparams, optimizer_kind
+from ._update import UpdateCore, check_params, owner_range
 from .comm import STREAM_SYNC, RcclComm, Sync, comm_stream, sync_kind, zs_dtype
-from .engine import ALIGN_ELEMS, probed_zeros
-from .kernels import AdamSet, SgdSet, adam_hparams, sgd_hparams, stream_handle
+from .engine import ALIGN_ELEMS
+from .kernels import AdamSet, SgdSet, stream_handle
 from .training_utils.utils import get
 
 try:  # the hooks' per-module install / release in C++ (csrc/zs_host_ext.cpp, built with the library)
@@ -1819,6 +1824,10 @@ GATHER_WAVE = 1
 # waits keep a HIP runtime thread polling — profiles/r05_event_poll_probe.jsonl)
 
 
+_CORE_NAMES = {"_state": "state", "_m": "m", "_v": "v", "_lo": "lo", "_vmax": "vmax",
+               "_steps": "steps", "_retired": "retired", "_adam_cache": "_cache"}
+
+
 class ShardedOptimizer:
     """zero3.py:81-168 with ``update`` selecting reference (no-op) or real ZeRO-3 updates."""
 
@@ -1851,9 +1860,8 @@ class ShardedOptimizer:
         self._A = None
         # "adam" or "sgd" (TypeError for anything else); reference mode never updates either
         self._kind = optimizer_kind(optimizer)
-        if self._kind == "sgd":
-            for group in optimizer.param_groups:
-                sgd_group_hparams(group)
+        for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
+            group_hparams(self._kind, group, optimizer)
         self.optimizer = optimizer
         self.original_param_groups = optimizer.param_groups
         self.params = [p for group in self.original_param_groups for p in group["params"]]
@@ -1862,11 +1870,7 @@ class ShardedOptimizer:
         self._groups = list(self.original_param_groups)
         world_size = get("ws")
         rank = get("rank")
-        params_per_rank = len(self.params) // world_size
-        remainder = len(self.params) % world_size
-        start_idx = rank * params_per_rank + min(rank, remainder)
-        end_idx = start_idx + params_per_rank + (1 if rank < remainder else 0)
-        self.local_param_indices = list(range(start_idx, end_idx))
+        self.local_param_indices = list(range(*owner_range(len(self.params), world_size, rank)))
         self.local_params = set(self.params[i] for i in self.local_param_indices)
         self.world_size, self.rank = world_size, rank
         self.update = bool(update)
@@ -1880,13 +1884,7 @@ class ShardedOptimizer:
                              "reference's fp32 all-reduce)")
         self._grad_comm = grad_comm if self.params[0].dtype == torch.float32 else None
 
-        dev = self.params[0].device
-        if dev.type != "cuda":
-            raise RuntimeError("zero_amd: parameters must live on a GPU; there is no CPU path")
-        dtype = self.params[0].dtype
-        for p in self.params:
-            if p.device != dev or p.dtype != dtype:
-                raise TypeError("zero_amd: all parameters must share one device and dtype")
+        dev, _ = check_params(self.params)
         if comm is None:
             comm = RcclComm()
         self.comm = comm
@@ -1914,7 +1912,8 @@ class ShardedOptimizer:
         self.communication_time = 0.0
         self.step_time = 0.0
         self.last_reduced_grads = None
-        self.timing_events = None  # optional list of (start, end, bytes) around each Adam launch
+        self._core = None          # the fused update's state and launches (update mode)
+        self._timing_events = None
         self._comm_spans = []      # (start event, end event) pairs not yet added to comm time
         self._reducer = None
         self._G = None
@@ -1927,45 +1926,47 @@ class ShardedOptimizer:
     # ------------------------------------------------------------------------------------------
     def _build_update_state(self):
         ar = self._arena
-        L = ar.total
-        split = ar.dtype == torch.bfloat16
-        # exp_avg, exp_avg_sq (+ for bf16 params the split master's int16 residual: the fp32
+        # the update core over the chunk arena: exp_avg, exp_avg_sq (SGD: one momentum buffer if
+        # any group has a momentum) + for bf16 params the split master's int16 residual (the fp32
         # master is the bf16 chunk + residual, include/zero_amd.h ZS_BF16_SPLIT; starts at 0)
-        nlo = (L + 1) // 2 if split else 0
-        # SGD: one momentum buffer if any group has a momentum, no state array otherwise
-        nm = 2 if self._kind == "adam" else int(any(g.get("momentum", 0) != 0 for g in self._groups))
-        state, self.placement = probed_zeros(nm * L + nlo, torch.float32, ar.device)
-        self._state = state
-        self._m = state[:L] if nm else None
-        self._v = state[L:2 * L] if nm == 2 else None
-        self._lo = state[nm * L:].view(torch.int16)[:L] if split else None
-        self._vmax = None
-        self._split = split
+        self._split = ar.dtype == torch.bfloat16
+        self._core = UpdateCore(self._kind, ar.total, ar.device, self.world_size, self._group_of,
+                                len(self.params), split=self._split,
+                                momentum=any(g.get("momentum", 0) != 0 for g in self._groups))
+        self._core.timing_events = self._timing_events
+        self.placement = self._core.placement
         gdt = torch.bfloat16 if self._grad_comm else ar.dtype
-        self._G = torch.zeros(L, dtype=gdt, device=ar.device) if self.world_size > 1 else None
+        self._G = torch.zeros(ar.total, dtype=gdt, device=ar.device) if self.world_size > 1 else None
         self._acc_widen = (self._accumulation_dtype is torch.float32 and self._G is not None
                            and gdt == torch.bfloat16)
-        self._steps = np.zeros(len(self.params), np.int64)
-        self._adam_cache = {}
         # the sets of the last uniform step, per arena they read (False: _G, True: _A)
         self._fast_sig, self._fast_sets = {}, {}
         self._step_shared = self._step_shared_sig = None
-        self._retired = []
         self._expose_state()
+
+    @property
+    def timing_events(self):
+        """Optional list of (start, end, bytes) around each update launch (the core's)."""
+        return self._timing_events if self._core is None else self._core.timing_events
+
+    @timing_events.setter
+    def timing_events(self, events):
+        if self._core is None:
+            self._timing_events = events
+        else:
+            self._core.timing_events = events
+
+    def __getattr__(self, name):
+        """The update state under the names it had on this wrapper: the core's attributes."""
+        alias = _CORE_NAMES.get(name)
+        if alias is None or self.__dict__.get("_core") is None:
+            raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+        return getattr(self._core, alias)
 
     def _state_views(self, i: int) -> dict:
         """name -> live view of param i's chunk of the flat update state."""
         ar = self._arena
-        s, n, shp = int(ar.slot[i]), int(ar.ln[i]), ar.shard_shapes[i]
-        if self._kind == "sgd":
-            views = {} if self._m is None else {"momentum_buffer": self._m[s:s + n].view(shp)}
-        else:
-            views = {"exp_avg": self._m[s:s + n].view(shp), "exp_avg_sq": self._v[s:s + n].view(shp)}
-        if self._lo is not None:  # fp32 master = the bf16 chunk's bits << 16 + this residual
-            views["master_residual"] = self._lo[s:s + n].view(shp)
-        if self._vmax is not None:
-            views["max_exp_avg_sq"] = self._vmax[s:s + n].view(shp)
-        return views
+        return self._core.views(int(ar.slot[i]), int(ar.ln[i]), ar.shard_shapes[i])
 
     def _expose_state(self):
         """optimizer.state[p]: views of the flat state (chunk-shaped) and torch's ``step``."""
@@ -1977,7 +1978,7 @@ class ShardedOptimizer:
         for i, p in enumerate(self.params):
             st = self.optimizer.state[p]
             st.update(self._state_views(i))
-            s = int(self._steps[i])
+            s = int(self._core.steps[i])
             if s:
                 t = step_t.get(s)
                 if t is None:
@@ -1985,36 +1986,10 @@ class ShardedOptimizer:
                 st["step"] = t
 
     def _expose_sgd(self, idx):
-        """torch's SGD state: {} until a parameter's first step, then its momentum buffer alone
-        (nothing without momentum)."""
-        for i in idx:
-            i = int(i)
-            if self._steps[i] == 0 or self._m is None:
-                continue
-            st = self.optimizer.state[self.params[i]]
-            if "momentum_buffer" not in st and self._groups[self._group_of[i]].get("momentum", 0) != 0:
-                st["momentum_buffer"] = self._state_views(i)["momentum_buffer"]
-
-    def _hp_key(self, steps):
-        """Adam: the step count (bias correction); SGD: whether this is the first step."""
-        steps = np.asarray(steps, np.int64)
-        return (steps == 1).astype(np.int64) if self._kind == "sgd" else steps
-
-    def _make_hp(self, h: dict, key: int):
-        if self._kind == "sgd":
-            if h["momentum"] != 0 and self._m is None:
-                raise ValueError("zero_amd: a param group's momentum became non-zero after the "
-                                 "optimizer was built without momentum buffers")
-            return sgd_hparams(h["lr"], h["momentum"], h["dampening"], h["weight_decay"],
-                               nesterov=h["nesterov"], maximize=h["maximize"], first=bool(key),
-                               grad_div=float(self.world_size))
-        return adam_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"], int(key),
-                            decoupled=h["decoupled"], amsgrad=h["amsgrad"], maximize=h["maximize"],
-                            grad_div=float(self.world_size))
+        self._core.expose_sgd(self.optimizer, self.params, self._groups, idx, self._state_views)
 
     def _ensure_vmax(self):
-        ar = self._arena
-        self._vmax = torch.zeros(ar.total, dtype=torch.float32, device=ar.device)
+        self._core.ensure_vmax()
         self._expose_state()  # (cached Adam rows gain the vmax pointer: rebuilt on their next use)
 
     def grad_arena(self):
@@ -2122,17 +2097,19 @@ class ShardedOptimizer:
         pp = np.uint64(ar.P.data_ptr()) + so * np.uint64(es)
         if self._split:  # master = bf16 chunk (in and out) + int16 residual
             rows[:, 1], rows[:, 3] = pp, pp
-            rows[:, 2] = np.uint64(self._lo.data_ptr()) + so * np.uint64(2)
+            rows[:, 2] = np.uint64(self._core.lo.data_ptr()) + so * np.uint64(2)
         else:
             rows[:, 1], rows[:, 2] = pp, pp
-        if self._m is not None:
-            rows[:, 4] = np.uint64(self._m.data_ptr()) + so * np.uint64(4)
-        if self._v is not None:
-            rows[:, 5] = np.uint64(self._v.data_ptr()) + so * np.uint64(4)
-        if self._vmax is not None:
-            rows[:, 6] = np.uint64(self._vmax.data_ptr()) + so * np.uint64(4)
+        self._core.state_cols(rows, so)
         rows[:, 8] = ar.ln[idx].astype(np.uint64)
         return rows
+
+    def _new_set(self, rows, acc: bool):
+        """The update's kernel set over ``rows``; ``acc``: fp32 gradients (the accumulation arena)."""
+        gz = ZS_F32 if acc else ZS_BF16 if (
+            self._split or (self._grad_comm and self.world_size > 1)) else ZS_F32
+        mk = SgdSet if self._kind == "sgd" else AdamSet
+        return mk(rows, gz, ZS_BF16_SPLIT, wide_grads=acc) if self._split else mk(rows, gz)
 
     def _step_update(self):
         red, ar = self._reducer, self._arena
@@ -2151,62 +2128,28 @@ class ShardedOptimizer:
             else:
                 done = red.ev_done[red.K - 1]
                 done.wait(cur.cuda_stream)
+        core = self._core
         idx = np.nonzero(red.had_grad & (ar.ln > 0))[0]
-        self._steps[idx] += 1
+        core.steps[idx] += 1
+        core.last_adam_bytes = 0
         # two or more passes under accumulation_dtype=float32: the sums are in _A (fp32)
         acc = self._acc_widen and red.passes >= 2
-        if self._kind == "sgd":
-            hps = {gi: sgd_group_hparams(self._groups[gi]) for gi in set(self._group_of)}
-        else:
-            hps = {gi: adam_group_hparams(self._groups[gi], self.optimizer)
-                   for gi in set(self._group_of)}
-        if any(h["amsgrad"] for h in hps.values()) and self._vmax is None:
+        hps = {gi: group_hparams(self._kind, self._groups[gi], self.optimizer)
+               for gi in set(self._group_of)}
+        if any(h["amsgrad"] for h in hps.values()) and core.vmax is None:
             self._ensure_vmax()
-        steps = self._hp_key(self._steps[idx])
+        steps = core.hp_key(core.steps[idx])
         uniform = len(idx) > 0 and bool((steps == steps[0]).all())
         # (ws == 1: Adam reads the local grads themselves, whose addresses change — no fast path)
-        sig = (idx.tobytes(), self._vmax is None) if self.world_size > 1 else None
+        sig = (idx.tobytes(), core.vmax is None) if self.world_size > 1 else None
         fast = self._fast_sets.get(acc) if uniform and sig is not None \
             and self._fast_sig.get(acc) == sig else None
         if fast is not None:  # the same parameters as last step, one step count: cached sets
             for gi, aset in fast:
-                h = hps[gi]
-                hp = self._make_hp(h, int(steps[0]))
-                if self.timing_events is not None:
-                    e0 = torch.cuda.Event(enable_timing=True)
-                    e0.record(cur)
-                    aset.run(hp, cur)
-                    self.timing_events.append((e0, _timed_after(cur), aset.bytes))
-                else:
-                    aset.run(hp, cur)
+                core.launch(aset, core.make_hp(hps[gi], int(steps[0])), cur)
         elif len(idx):
-            rows = self._adam_rows(idx, acc)
-            keys = np.stack([np.asarray(self._group_of)[idx], steps], axis=1)
-            used = []
-            for key in np.unique(keys, axis=0):
-                sel = np.nonzero((keys == key).all(axis=1))[0]
-                sub = np.ascontiguousarray(rows[sel])
-                ck = (int(key[0]), len(sel), int(sel[0]), acc)
-                hit = self._adam_cache.get(ck)
-                if hit is None or hit[0] != sub.tobytes():
-                    if hit is not None:  # keep until the device is idle (hipFree would sync it)
-                        self._retired.append(hit[1])
-                    gz = ZS_F32 if acc else ZS_BF16 if (
-                        self._split or (self._grad_comm and self.world_size > 1)) else ZS_F32
-                    mk = SgdSet if self._kind == "sgd" else AdamSet
-                    hit = (sub.tobytes(), mk(sub, gz, ZS_BF16_SPLIT, wide_grads=acc) if self._split
-                           else mk(sub, gz))
-                    self._adam_cache[ck] = hit
-                h = hps[int(key[0])]
-                hp = self._make_hp(h, int(key[1]))
-                if self.timing_events is not None:
-                    e0 = torch.cuda.Event(enable_timing=True)
-                    e0.record(cur)
-                    hit[1].run(hp, cur)
-                    self.timing_events.append((e0, _timed_after(cur), hit[1].bytes))
-                else:
-                    hit[1].run(hp, cur)
-                used.append((int(key[0]), hit[1]))
+            used = core.run_parts(acc, self._adam_rows(idx, acc), idx, hps.__getitem__, cur,
+                                  new_set=lambda rows: self._new_set(rows, acc))
             # one set per param group and one step count: next step takes the cached sets
             self._fast_sig[acc] = sig if uniform else None
             self._fast_sets[acc] = used if uniform else None
@@ -2226,7 +2169,7 @@ class ShardedOptimizer:
             self._step_shared_sig = None
             step_t = {}
             for i in idx:
-                s_ = int(self._steps[i])
+                s_ = int(core.steps[i])
                 t = step_t.get(s_)
                 if t is None:
                     t = step_t[s_] = torch.tensor(float(s_))
@@ -2254,11 +2197,10 @@ class ShardedOptimizer:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record(self.runtime.stream)  # after the last gradient collective
             self._comm_spans.append((e0, e1))
-        retired = len(self._retired) if self.update else 0
-        if self._sync or retired > 64:
+        if self._sync or (self.update and self._core.n_retired() > 64):
             torch.cuda.synchronize()
             if self.update:
-                self._retired.clear()
+                self._core.release_retired()
             self._collect_comm_time()
         else:  # asynchronous steps: count the spans whose end the device has passed
             self._collect_comm_time(completed_only=True)
@@ -2321,13 +2263,8 @@ class ShardedOptimizer:
         if self.update:
             index = {id(p): k for k, p in enumerate(ckpt.inner_params(self.optimizer))}
             for i, p in enumerate(self.params):
-                entry = {k: v.detach().clone() for k, v in self._state_views(i).items()}
-                if self._kind == "sgd":  # torch's SGD entry: the buffer once it exists, no step
-                    if "momentum_buffer" not in self.optimizer.state[p]:
-                        entry.pop("momentum_buffer", None)
-                else:
-                    entry["step"] = torch.tensor(float(self._steps[i]), dtype=torch.float32)
-                state[index[id(p)]] = entry
+                state[index[id(p)]] = self._core.save_entry(i, self._state_views(i),
+                                                            self.optimizer.state[p])
         sd["state"] = state
         sd["zero_amd"] = self._ckpt_header()
         return sd
@@ -2352,19 +2289,10 @@ class ShardedOptimizer:
         saved = state_dict.get("state", {})
         params = ckpt.inner_params(self.optimizer)
         index = {id(p): k for k, p in enumerate(params)}
-        if any("max_exp_avg_sq" in e for e in saved.values()) and self._vmax is None:
+        if any("max_exp_avg_sq" in e for e in saved.values()) and self._core.vmax is None:
             self._ensure_vmax()
         with torch.no_grad():
             for i, p in enumerate(self.params):
                 entry = saved.get(index.get(id(p), -1), {})
-                for name, view in self._state_views(i).items():
-                    src = entry.get(name)
-                    if src is not None:
-                        view.copy_(src.reshape(view.shape))
-                    else:  # moments 0 (fresh Adam); residual 0 (master = the bf16 chunk)
-                        view.zero_()
-                if self._kind == "sgd":  # no buffer saved: the next step is the first again
-                    self._steps[i] = int(entry.get("momentum_buffer") is not None)
-                else:
-                    self._steps[i] = ckpt.step_of(entry)
+                self._core.load_entry(i, self._state_views(i), entry, p)
         self._expose_state()
