@@ -457,12 +457,18 @@ struct NoStream {
 // gradient) is resolved by the caller, once per chunk.  First loop: every load of the chunk (g,
 // hi/lo or master, m, v, vmax, carry; 20 for the split-master Adam's G = 4) goes into raw registers
 // before anything depends on one.  Second loop: unpack, the rule's elem and the stores, group by
-// group.
-template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool HASG, bool CLIP>
+// group.  ST: the element type of m and v in memory, float or unsigned short (bf16 moments: 8 bytes
+// per lane per access through the 16-bit streams, widened before the rule and rounded to nearest
+// even after it; the rule itself and the parameter it leaves see fp32 moments only).
+template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool HASG, bool CLIP,
+          typename ST = float>
 __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
                                                   const typename Rule::Hyper& hp, float coef) {
   constexpr int G = adam_groups(SPLIT);
   constexpr bool G32 = sizeof(GT) == 4;
+  constexpr bool S16 = sizeof(ST) == 2;
+  static_assert(!S16 || (Rule::kM && Rule::kV && !Rule::kX && !CARRY),
+                "bf16 state: Adam's m and v, no amsgrad, no carry");
   uint32_t o4 = threadIdx.x * 16u;                   // lane byte offset in an fp32 stream
   uint32_t o2 = threadIdx.x * 8u;                    // ... in a bf16 stream
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -472,16 +478,20 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
 #endif
   typedef ChunkStream<float, G> S4;
   typedef ChunkStream<unsigned short, G> S2;
-  typedef std::conditional_t<Rule::kV, S4, NoStream> SV;  // v and its running maximum vmax
+  typedef std::conditional_t<Rule::kV && !S16, S4, NoStream> SV;  // v and its running maximum vmax
+  typedef std::conditional_t<S16, NoStream, S4> SM;                // m as fp32
+  typedef std::conditional_t<S16, S2, NoStream> SH;                // m and v as bf16
   const S4 gf(HASG && G32 ? (float*)s.g + e0 : nullptr), pm(SPLIT ? nullptr : (float*)s.master + e0);
-  const S4 po(SPLIT ? nullptr : s.master_out + e0), sm(Rule::kM ? s.m + e0 : nullptr);
+  const S4 po(SPLIT ? nullptr : s.master_out + e0);
+  const SM sm(Rule::kM ? s.m + e0 : nullptr);
   const SV sv(s.v + e0), sx(Rule::kX ? s.vmax + e0 : nullptr);
   const S4 sc(CARRY ? s.carry + e0 : nullptr);
   const S2 gh(HASG && !G32 ? (unsigned short*)s.g + e0 : nullptr);
   const S2 hi(SPLIT ? (unsigned short*)s.master + e0 : nullptr);
   const S2 lo(SPLIT ? (unsigned short*)s.master_out + e0 : nullptr), pb(s.p_out + e0);
+  const SH mh((unsigned short*)s.m + e0), vh((unsigned short*)s.v + e0);
   uint4 gq[G], pq[G], mq[G], vq[G], xq[G], cq[G];
-  uint2 gd[G], hd[G], ld[G];
+  uint2 gd[G], hd[G], ld[G], md[G], vd[G];
   // kGradOffset2 (Adam), fp32 gradients over the split master (G = 4): the gradient's groups 2 and
   // 3 through the first base and a second lane offset 8 KiB on — one vector register instead of a
   // second pair of scalar ones, which this instance (five fp32 streams of two bases each under
@@ -506,8 +516,13 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
     } else {
       pq[u] = nt_ld16(pm.at(u, o4));
     }
-    if constexpr (Rule::kM) mq[u] = nt_ld16(sm.at(u, o4));
-    if constexpr (Rule::kV) vq[u] = nt_ld16(sv.at(u, o4));
+    if constexpr (S16) {
+      md[u] = nt_ld8(mh.at(u, o2));
+      vd[u] = nt_ld8(vh.at(u, o2));
+    } else {
+      if constexpr (Rule::kM) mq[u] = nt_ld16(sm.at(u, o4));
+      if constexpr (Rule::kV) vq[u] = nt_ld16(sv.at(u, o4));
+    }
     if constexpr (Rule::kX) xq[u] = nt_ld16(sx.at(u, o4));
     if constexpr (CARRY) cq[u] = nt_ld16(sc.at(u, o4));
   }
@@ -520,8 +535,13 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
     else unpack4(pq[u], pp);
     float mp[4] = {0.f, 0.f, 0.f, 0.f}, vp[4] = {0.f, 0.f, 0.f, 0.f};
     float xp[4] = {0.f, 0.f, 0.f, 0.f}, cp[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (Rule::kM) unpack4(mq[u], mp);
-    if constexpr (Rule::kV) unpack4(vq[u], vp);
+    if constexpr (S16) {
+      unpack_bf16x4(md[u], mp);
+      unpack_bf16x4(vd[u], vp);
+    } else {
+      if constexpr (Rule::kM) unpack4(mq[u], mp);
+      if constexpr (Rule::kV) unpack4(vq[u], vp);
+    }
     if constexpr (Rule::kX) unpack4(xq[u], xp);
     if constexpr (CARRY) unpack4(cq[u], cp);
 #pragma unroll
@@ -546,8 +566,14 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
         nt_st8(pb.at(u, o2), r);
       }
     }
-    if constexpr (Rule::kM) nt_st16(sm.at(u, o4), pack4(mp));
-    if constexpr (Rule::kV) nt_st16(sv.at(u, o4), pack4(vp));
+    if constexpr (S16) {
+      const uint2 mr = pack_bf16x4(mp), vr = pack_bf16x4(vp);
+      nt_st8(mh.at(u, o2), mr);
+      nt_st8(vh.at(u, o2), vr);
+    } else {
+      if constexpr (Rule::kM) nt_st16(sm.at(u, o4), pack4(mp));
+      if constexpr (Rule::kV) nt_st16(sv.at(u, o4), pack4(vp));
+    }
     if constexpr (Rule::kX) nt_st16(sx.at(u, o4), pack4(xp));
     if constexpr (CARRY) nt_st16(sc.at(u, o4), pack4(cp));
   }
@@ -555,10 +581,14 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
 
 // The per-lane predicated body: G float4 groups from element e0 of a segment, each group under its
 // own `i < s.n`.  The branches keep each group's loads and their waits in a block of their own, so
-// a wave has one group's loads in flight at a time.
-template <typename Rule, typename GT, bool CARRY, bool SPLIT, int G, bool CLIP>
+// a wave has one group's loads in flight at a time.  ST as in update_full_chunk.
+template <typename Rule, typename GT, bool CARRY, bool SPLIT, int G, bool CLIP,
+          typename ST = float>
 __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
                                                    const typename Rule::Hyper& hp, float coef) {
+  constexpr bool S16 = sizeof(ST) == 2;
+  static_assert(!S16 || (Rule::kM && Rule::kV && !Rule::kX && !CARRY),
+                "bf16 state: Adam's m and v, no amsgrad, no carry");
   float4 g4[G], p4[G], m4[G], v4[G];
   float4 x4[G], c4[G];
 #pragma unroll
@@ -573,8 +603,15 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
       } else {
         p4[u] = ld4(s.master, i);
       }
-      if constexpr (Rule::kM) m4[u] = ld4(s.m, i);
-      if constexpr (Rule::kV) v4[u] = ld4(s.v, i);
+      if constexpr (S16) {
+        const uint2 mr = nt_ld8(reinterpret_cast<const unsigned short*>(s.m) + i);
+        const uint2 vr = nt_ld8(reinterpret_cast<const unsigned short*>(s.v) + i);
+        unpack_bf16x4(mr, reinterpret_cast<float*>(&m4[u]));
+        unpack_bf16x4(vr, reinterpret_cast<float*>(&v4[u]));
+      } else {
+        if constexpr (Rule::kM) m4[u] = ld4(s.m, i);
+        if constexpr (Rule::kV) v4[u] = ld4(s.v, i);
+      }
       if constexpr (Rule::kX) x4[u] = ld4(s.vmax, i);
       if constexpr (CARRY) c4[u] = ld4(s.carry, i);
     }
@@ -613,8 +650,14 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
           nt_st8(s.p_out + i, r);
         }
       }
-      if constexpr (Rule::kM) st4(s.m, i, m4[u]);
-      if constexpr (Rule::kV) st4(s.v, i, v4[u]);
+      if constexpr (S16) {
+        const uint2 mr = pack_bf16x4(mp), vr = pack_bf16x4(vp);
+        nt_st8(reinterpret_cast<unsigned short*>(s.m) + i, mr);
+        nt_st8(reinterpret_cast<unsigned short*>(s.v) + i, vr);
+      } else {
+        if constexpr (Rule::kM) st4(s.m, i, m4[u]);
+        if constexpr (Rule::kV) st4(s.v, i, v4[u]);
+      }
       if constexpr (Rule::kX) st4(s.vmax, i, x4[u]);
       if constexpr (CARRY) st4(s.carry, i, c4[u]);
     }
@@ -634,7 +677,10 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
 // is one chunk per segment, and a group at a time it stays out of the kernel's register budget).
 // !LOADS_FIRST (`zs_tune("adam_loads_first", 0)`): every chunk through the predicated body, all
 // groups unrolled -- the kernel as it was before update_full_chunk, kept for A/B runs.
-template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP>
+// ST = unsigned short (zs_adamset_create_ex with ZS_BF16 state): m and v are bf16 arrays, 8-B
+// aligned like the other 16-bit ones; the chunk geometry is the fp32-state instance's.
+template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP,
+          typename ST = float>
 __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
     const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
     int64_t total_chunks, HP hp, const float* __restrict__ coef_ptr) {
@@ -657,27 +703,29 @@ __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
     const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT);
     if constexpr (LOADS_FIRST) {
       if (e0 + adam_chunk(SPLIT) <= s.n) {  // uniform per workgroup
-        if (s.g) update_full_chunk<Rule, GT, CARRY, SPLIT, true, CLIP>(s, e0, hp, coef);
-        else update_full_chunk<Rule, GT, CARRY, SPLIT, false, CLIP>(s, e0, hp, coef);
+        if (s.g) update_full_chunk<Rule, GT, CARRY, SPLIT, true, CLIP, ST>(s, e0, hp, coef);
+        else update_full_chunk<Rule, GT, CARRY, SPLIT, false, CLIP, ST>(s, e0, hp, coef);
       } else {
 #pragma unroll 1
         for (int u = 0; u < G && e0 + int64_t(u) * kThreads * 4 < s.n; ++u)
-          update_pred_groups<Rule, GT, CARRY, SPLIT, 1, CLIP>(s, e0 + int64_t(u) * kThreads * 4, hp,
-                                                              coef);
+          update_pred_groups<Rule, GT, CARRY, SPLIT, 1, CLIP, ST>(
+              s, e0 + int64_t(u) * kThreads * 4, hp, coef);
       }
     } else {
-      update_pred_groups<Rule, GT, CARRY, SPLIT, G, CLIP>(s, e0, hp, coef);
+      update_pred_groups<Rule, GT, CARRY, SPLIT, G, CLIP, ST>(s, e0, hp, coef);
     }
   }
 }
 
-template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool CLIP>
+template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool CLIP, typename ST = float>
 __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
     int64_t total_chunks, HP hp, const float* __restrict__ coef_ptr) {
   static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
   const float coef = clip_coef<CLIP>(coef_ptr);
   using Rule = AdamRule<AMS>;
+  constexpr bool S16 = sizeof(ST) == 2;
+  static_assert(!S16 || (!AMS && !CARRY), "bf16 state: no amsgrad, no carry");
   int64_t seg = 0;
   for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
     while (chunk_prefix[seg + 1] <= c) ++seg;
@@ -689,8 +737,13 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     float p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
                     : glob(s.master)[i];
     float m = 0.0f, v = 0.0f, vm = 0.0f;
-    if constexpr (Rule::kM) m = glob(s.m)[i];
-    if constexpr (Rule::kV) v = glob(s.v)[i];
+    if constexpr (S16) {
+      m = bf16_to_f32(glob(reinterpret_cast<unsigned short*>(s.m))[i]);
+      v = bf16_to_f32(glob(reinterpret_cast<unsigned short*>(s.v))[i]);
+    } else {
+      if constexpr (Rule::kM) m = glob(s.m)[i];
+      if constexpr (Rule::kV) v = glob(s.v)[i];
+    }
     if constexpr (Rule::kX) vm = glob(s.vmax)[i];
     float cr = CARRY ? glob(s.carry)[i] : 0.0f;
     Rule::template elem<CARRY, CLIP>(gs, p, m, v, vm, cr, hp, coef);
@@ -702,8 +755,13 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
       if (s.master_out) glob(s.master_out)[i] = p;
       if (s.p_out) glob(s.p_out)[i] = f32_to_bf16(p);
     }
-    if constexpr (Rule::kM) glob(s.m)[i] = m;
-    if constexpr (Rule::kV) glob(s.v)[i] = v;
+    if constexpr (S16) {
+      glob(reinterpret_cast<unsigned short*>(s.m))[i] = f32_to_bf16(m);
+      glob(reinterpret_cast<unsigned short*>(s.v))[i] = f32_to_bf16(v);
+    } else {
+      if constexpr (Rule::kM) glob(s.m)[i] = m;
+      if constexpr (Rule::kV) glob(s.v)[i] = v;
+    }
     if constexpr (Rule::kX) glob(s.vmax)[i] = vm;
     if constexpr (CARRY) glob(s.carry)[i] = cr;
   }
@@ -1613,6 +1671,8 @@ struct zs_adamset {
   int g_dtype = ZS_F32, p_dtype = ZS_BF16, has_carry = 0, has_vmax = 0;
   // zs_sgdset_create: an SGD set (field m is the momentum buffer, has_mom: it has one)
   int sgd = 0, has_mom = 0;
+  // zs_adamset_create_ex: the element type of m and v, ZS_F32 or ZS_BF16
+  int state_dtype = ZS_F32;
   // zs_adamset_set_grads: which input segment each table entry came from (the scalar entries with
   // their byte offset into that input's gradient), the gradient each input is bound to now, its
   // elements, whether it has a vector part (then its gradient must keep the vector alignment), and
@@ -1732,6 +1792,15 @@ struct AdamKernels {
   static auto get() {
     if constexpr (VEC) return adam_segments_kernel<GT, AMS, C, S, LF, CLIP>;
     else return adam_scalar_kernel<GT, AMS, C, S, CLIP>;
+  }
+};
+// bf16 moments (zs_adamset_create_ex, ZS_BF16 state): no amsgrad and no carry instance exists; the
+// entry points refuse both, so whatever the two flags say names the one plain instance
+struct AdamBf16StateKernels {
+  template <bool VEC, typename GT, bool AMS, bool C, bool S, bool LF, bool CLIP>
+  static auto get() {
+    if constexpr (VEC) return adam_segments_kernel<GT, false, false, S, LF, CLIP, unsigned short>;
+    else return adam_scalar_kernel<GT, false, false, S, CLIP, unsigned short>;
   }
 };
 struct SgdKernels {
@@ -2239,16 +2308,20 @@ int zs_adam_hparams_init(double lr, double beta1, double beta2, double eps, doub
 
 // zs_adamset_create (sgd = false) and zs_sgdset_create (sgd = true: field m is the momentum buffer,
 // on all segments or on none; v and vmax must be 0); `fn` names the entry point in messages.
+// state_dtype: the element type of m and v (ZS_BF16: zs_adamset_create_ex's bf16 moments).
 static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n, int g_dtype,
-                      int p_dtype, zs_adamset** out) {
+                      int p_dtype, int state_dtype, zs_adamset** out) {
   ZS_REQUIRE(out != nullptr, "%s: out is NULL", fn);
   *out = nullptr;
   ZS_REQUIRE(n >= 0 && (n == 0 || in), "%s: bad table", fn);
   ZS_REQUIRE(g_dtype == ZS_F32 || g_dtype == ZS_BF16, "%s: bad g_dtype %d", fn, g_dtype);
   ZS_REQUIRE(p_dtype == ZS_BF16 || p_dtype == ZS_BF16_SPLIT,
              "%s: p_dtype must be ZS_BF16 or ZS_BF16_SPLIT (got %d)", fn, p_dtype);
+  ZS_REQUIRE(state_dtype == ZS_F32 || (state_dtype == ZS_BF16 && !sgd),
+             "%s: state_dtype must be ZS_F32 or ZS_BF16 (got %d)", fn, state_dtype);
   const bool split = p_dtype == ZS_BF16_SPLIT;
   const int64_t msz = split ? 2 : 4;  // bytes per element of master / master_out
+  const int64_t ssz = state_dtype == ZS_BF16 ? 2 : 4;  // ... of m, v (and vmax)
   const int64_t gsz = g_dtype == ZS_F32 ? 4 : 2;
   ZS_REQUIRE(n < (int64_t(1) << 31), "%s: %lld segments (max 2^31 - 1)", fn,
              (long long)n);
@@ -2286,6 +2359,9 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
     ZS_REQUIRE(!(split && g_dtype == ZS_F32 && s.carry),
                "%s: seg %lld: a ZS_BF16_SPLIT set with fp32 grads takes no carry", fn,
                (long long)i);
+    ZS_REQUIRE(ssz == 4 || (!s.vmax && !s.carry),
+               "%s: seg %lld: a set with ZS_BF16 state takes no vmax (amsgrad) and no carry", fn,
+               (long long)i);
     const int c = s.carry ? 1 : 0;
     ZS_REQUIRE(carry_state < 0 || carry_state == c,
                "%s: carry must be set on all segments or none", fn);
@@ -2304,8 +2380,9 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
     d.vmax = reinterpret_cast<float*>(s.vmax);
     d.carry = reinterpret_cast<float*>(s.carry);
     const bool ok = aligned(s.g, uint64_t(gsz) * 4) && aligned(s.master, uint64_t(msz) * 4) &&
-                    aligned(s.master_out, uint64_t(msz) * 4) && aligned(s.p_out, 8) && aligned(s.m, 16) &&
-                    aligned(s.v, 16) && aligned(s.vmax, 16) && aligned(s.carry, 16);
+                    aligned(s.master_out, uint64_t(msz) * 4) && aligned(s.p_out, 8) &&
+                    aligned(s.m, uint64_t(ssz) * 4) && aligned(s.v, uint64_t(ssz) * 4) &&
+                    aligned(s.vmax, uint64_t(ssz) * 4) && aligned(s.carry, 16);
     const int64_t nv = ok ? (s.n & ~int64_t(3)) : 0;
     if (nv) {
       d.n = nv;
@@ -2324,9 +2401,9 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
       t.master = adv(d.master, msz);
       t.master_out = adv(d.master_out, msz);
       t.p_out = adv(d.p_out, 2);
-      t.m = adv(d.m, 4);
-      t.v = adv(d.v, 4);
-      t.vmax = adv(d.vmax, 4);
+      t.m = adv(d.m, ssz);
+      t.v = adv(d.v, ssz);
+      t.vmax = adv(d.vmax, ssz);
       t.carry = adv(d.carry, 4);
       t.n = s.n - nv;
       sca.push_back(t);
@@ -2335,10 +2412,10 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
       spre.push_back(spre.back() + (t.n + kThreads - 1) / kThreads);
     }
     elems += s.n;
-    int64_t b = msz /*master*/ + (sgd ? (s.m ? 8 : 0) /*buffer*/ : 8 /*m*/ + 8 /*v*/);
+    int64_t b = msz /*master*/ + (sgd ? (s.m ? 8 : 0) /*buffer*/ : 2 * ssz /*m*/ + 2 * ssz /*v*/);
     if (s.master_out) b += split ? 4 /*residual read + write*/ : 4;
     if (s.p_out) b += 2;
-    if (s.vmax) b += 8;
+    if (s.vmax) b += 2 * ssz;
     if (s.carry) b += 8;
     bytes_no_g += b * s.n;
     bytes += (b + (s.g ? gsz : 0)) * s.n;
@@ -2359,6 +2436,7 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   as->has_vmax = vmax_state > 0 ? 1 : 0;
   as->sgd = sgd ? 1 : 0;
   as->has_mom = mom_state > 0 ? 1 : 0;
+  as->state_dtype = state_dtype;
   as->in_g = std::move(in_g);
   as->in_n = std::move(in_n);
   as->in_vec = std::move(in_vec);
@@ -2385,12 +2463,17 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
 
 int zs_adamset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype,
                       zs_adamset** out) {
-  return set_create("zs_adamset_create", false, in, n, g_dtype, p_dtype, out);
+  return set_create("zs_adamset_create", false, in, n, g_dtype, p_dtype, ZS_F32, out);
+}
+
+int zs_adamset_create_ex(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype,
+                         int state_dtype, zs_adamset** out) {
+  return set_create("zs_adamset_create_ex", false, in, n, g_dtype, p_dtype, state_dtype, out);
 }
 
 int zs_sgdset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype,
                      zs_adamset** out) {
-  return set_create("zs_sgdset_create", true, in, n, g_dtype, p_dtype, out);
+  return set_create("zs_sgdset_create", true, in, n, g_dtype, p_dtype, ZS_F32, out);
 }
 
 int zs_sgd_hparams_init(double lr, double momentum, double dampening, double weight_decay,
@@ -2459,6 +2542,12 @@ int zs_adamset_run(const zs_adamset* as, const zs_adam_hparams* h, uintptr_t str
   const bool ams = h->amsgrad != 0;
   ZS_REQUIRE(!ams || as->has_vmax || (as->nvec + as->nsca) == 0,
              "zs_adamset_run: amsgrad needs vmax segments");
+  if (as->state_dtype == ZS_BF16) {
+    ZS_REQUIRE(!ams, "zs_adamset_run: a set with ZS_BF16 state has no amsgrad");
+    return launch_update_tables<AdamBf16StateKernels, false>(
+        vec_table(as), sca_table(as), as->g_dtype, as->p_dtype == ZS_BF16_SPLIT, false, false,
+        make_hp(h), nullptr, reinterpret_cast<hipStream_t>(stream));
+  }
   return launch_update_tables<AdamKernels, false>(
       vec_table(as), sca_table(as), as->g_dtype, as->p_dtype == ZS_BF16_SPLIT, ams,
       as->has_carry != 0, make_hp(h), nullptr, reinterpret_cast<hipStream_t>(stream));
@@ -2474,6 +2563,12 @@ int zs_adamset_run_clipped(const zs_adamset* as, const zs_adam_hparams* h, const
   const bool ams = h->amsgrad != 0;
   ZS_REQUIRE(!ams || as->has_vmax || (as->nvec + as->nsca) == 0,
              "zs_adamset_run_clipped: amsgrad needs vmax segments");
+  if (as->state_dtype == ZS_BF16) {
+    ZS_REQUIRE(!ams, "zs_adamset_run_clipped: a set with ZS_BF16 state has no amsgrad");
+    return launch_update_tables<AdamBf16StateKernels, true>(
+        vec_table(as), sca_table(as), as->g_dtype, as->p_dtype == ZS_BF16_SPLIT, false, false,
+        make_hp(h), coef, reinterpret_cast<hipStream_t>(stream));
+  }
   return launch_update_tables<AdamKernels, true>(
       vec_table(as), sca_table(as), as->g_dtype, as->p_dtype == ZS_BF16_SPLIT, ams, false,
       make_hp(h), coef, reinterpret_cast<hipStream_t>(stream));

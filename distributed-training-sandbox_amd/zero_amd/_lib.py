@@ -35,7 +35,7 @@ EXPORTED = (
     "zs_accumulate", "zs_accumulate_widen",
     "zs_convert", "zs_fp8_quantize_rows", "zs_fp8_dequantize_rows", "zs_fp8_quantize_rowset",
     "zs_fp8_dequantize_gathered",
-    "zs_adam_hparams_init", "zs_adamset_create", "zs_adamset_run", "zs_adamset_set_grads", "zs_adamset_destroy",
+    "zs_adam_hparams_init", "zs_adamset_create", "zs_adamset_create_ex", "zs_adamset_run", "zs_adamset_set_grads", "zs_adamset_destroy",
     "zs_adamset_stats", "zs_adam_step", "zs_adam_step_ex",
     "zs_adamset_sqnorm_partials", "zs_adamset_grad_sqnorm", "zs_sqnorm_reduce", "zs_clip_coef",
     "zs_adamset_run_clipped",
@@ -130,6 +130,8 @@ _SIGS = {
                              ctypes.c_int),
     "zs_adamset_create": ([ctypes.POINTER(AdamSeg), _I64, ctypes.c_int, ctypes.c_int,
                            ctypes.POINTER(_P)], ctypes.c_int),
+    "zs_adamset_create_ex": ([ctypes.POINTER(AdamSeg), _I64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                              ctypes.POINTER(_P)], ctypes.c_int),
     "zs_adamset_run": ([_P, ctypes.POINTER(AdamHParams), _U], ctypes.c_int),
     "zs_adamset_set_grads": ([_P, _I64, _P, _U], ctypes.c_int),
     "zs_adamset_destroy": ([_P], ctypes.c_int),

@@ -20,7 +20,7 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import owner_range
+from ._update import check_bf16_state_group, check_state_dtype, owner_range
 from .engine import ShardEngine
 from .training_utils.utils import get
 
@@ -78,9 +78,14 @@ class ShardedOptimizerBase:
                  bucket_mb: float | None = None, comm=None, sync: bool = True, buckets: str = "ragged",
                  overlap: bool = False, overlap_bucket_mb: float = 64.0, master: str = "split",
                  arena: str = "flat", grad_comm: str | None = None,
-                 max_grad_norm: float | None = None):
+                 max_grad_norm: float | None = None, state_dtype=None):
         if arena not in ("flat", "buckets", "auto"):
             raise ValueError(f"arena must be 'flat', 'buckets' or 'auto' (got {arena!r})")
+        # the moments' dtype: None / torch.float32, or torch.bfloat16 (opt-in: exp_avg and
+        # exp_avg_sq stored in bf16, the arithmetic in fp32 as before).  What it
+        # cannot be combined with is refused below, on every rank and before anything collective
+        self.state_dtype = check_state_dtype(state_dtype)
+        bf16_state = self.state_dtype == torch.bfloat16
         # global gradient-norm clipping inside step() (None = off); a plain attribute, it may be
         # changed between steps.  What it cannot be combined with is refused here, on every rank
         # and before anything collective
@@ -99,7 +104,20 @@ class ShardedOptimizerBase:
         self._check_clip()
         self._kind = optimizer_kind(optimizer)
         for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
-            group_hparams(self._kind, group, optimizer)
+            hpd = group_hparams(self._kind, group, optimizer)
+            if bf16_state and self._kind == "adam":
+                check_bf16_state_group(hpd)
+        if bf16_state:
+            if self._kind == "sgd":
+                raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with "
+                                 "torch.optim.SGD (bf16 moments are Adam's)")
+            if self._carry and get("ws") > 1:
+                raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with "
+                                 "ZeRO-1 at world size > 1 (the gradient carry stays fp32)")
+            if arena == "buckets" or (layout != "reference" and (layout != "flat" or self._carry)):
+                raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with the "
+                                 f"bucket arena (arena={arena!r}, layout={layout!r}); use the "
+                                 "flat arena")
         if self._kind == "sgd":
             # the SGD update runs on the flat arena (and its rounds) only
             if arena == "buckets":
@@ -145,6 +163,9 @@ class ShardedOptimizerBase:
                 if arena == "buckets":  # (rank 0's choice, broadcast: every rank raises alike)
                     self._clip_unsupported = "arena='auto' that resolved to the bucket arena"
                     self._check_clip()
+                    if bf16_state:
+                        raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported "
+                                         "with arena='auto' that resolved to the bucket arena")
         # bytes per bucket (bucket arena) / per round (flat arena, all owners' windows together);
         # default 256 MiB / 1 GiB: a flat round has no pack to pipeline, so fewer, larger rounds
         # cost only the last round's Adam as exposed tail and cut the launches per step
@@ -239,6 +260,7 @@ class ShardedOptimizerBase:
                                      carry=carry, comm=comm, bucket_bytes=self._bucket_bytes,
                                      master=self._master, grad_comm=self._grad_comm,
                                      layout=self._layout, kind=self._kind,
+                                     state_dtype=self.state_dtype,
                                      momentum=self._kind == "sgd" and any(
                                          g.get("momentum", 0) != 0 for g in self._groups))
         else:
@@ -293,6 +315,9 @@ class ShardedOptimizerBase:
         if self.engine is None:
             self._build_engine()
         self._check_clip()
+        if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
+            for gi in range(len(self._groups)):
+                check_bf16_state_group(self._hparams_of(gi))
         self.engine.max_grad_norm = self.max_grad_norm
         had_vmax = self.engine.vmax is not None
         grads = [p.grad for p in self.params]

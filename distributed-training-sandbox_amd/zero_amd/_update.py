@@ -37,12 +37,57 @@ def check_params(params):
     return dev, dtype
 
 
+# bf16 moments keep 8 significant bits: a pure decay x <- beta * x moves every stored value only
+# while 1 - beta >= 2^-8 ("bf16 moments"); below that exp_avg_sq could never shrink
+BF16_STATE_MIN_ONE_MINUS_BETA = 2.0 ** -8
+
+
+def check_state_dtype(state_dtype):
+    """``state_dtype`` of an optimizer as torch.float32 (None: the default) or torch.bfloat16;
+    ValueError for anything else."""
+    if state_dtype is None or state_dtype == torch.float32:
+        return torch.float32
+    if state_dtype == torch.bfloat16:
+        return torch.bfloat16
+    raise ValueError("zero_amd: state_dtype must be None, torch.float32 or torch.bfloat16 "
+                     f"(got {state_dtype!r})")
+
+
+def check_bf16_state_group(hpd: dict) -> None:
+    """What a param group may ask of bf16 moments: no amsgrad, and both betas at or below
+    1 - 2^-8 = 0.99609375, so that every bf16 value moves under the decay; ValueError otherwise."""
+    if hpd.get("amsgrad"):
+        raise ValueError("zero_amd: state_dtype=torch.bfloat16 does not support amsgrad")
+    for name in ("beta1", "beta2"):
+        if 1.0 - float(hpd[name]) < BF16_STATE_MIN_ONE_MINUS_BETA:
+            raise ValueError(
+                f"zero_amd: state_dtype=torch.bfloat16 needs 1 - {name} >= 2^-8 = 0.00390625, that "
+                f"is {name} <= 0.99609375 (got {name} = {hpd[name]!r}): bf16 keeps 8 significant "
+                "bits and a smaller decay is rounded away, so the moment could never shrink")
+
+
 def state_layout(kind: str, L: int, *, split: bool, fp32_master: bool, carry: bool,
-                 momentum: bool = True):
+                 momentum: bool = True, state_dtype=None):
     """(total fp32 words, {name: (word offset, dtype)}) of the flat state of an ``L``-element
     shard: ``m``, ``v`` (Adam; SGD: ``m`` alone, the momentum buffer, and only with ``momentum``),
     ``carry`` (ZeRO-1), ``master`` (fp32 master of bf16 params), each ``L`` fp32, then ``lo``:
-    ``L`` int16 residuals of the split master in ``(L + 1) // 2`` words."""
+    ``L`` int16 residuals of the split master in ``(L + 1) // 2`` words.  ``state_dtype``
+    torch.bfloat16 (Adam without carry): ``m`` and ``v`` are ``L`` bf16 each, every array from
+    ``master`` on starting at a multiple of 4 words (16 bytes)."""
+    if check_state_dtype(state_dtype) == torch.bfloat16:
+        if kind != "adam" or carry:
+            raise ValueError("state_layout: bf16 state is Adam's, without the ZeRO-1 carry")
+        words = (L + 1) // 2  # of one bf16 array
+        pad = lambda w: (w + 3) // 4 * 4  # noqa: E731
+        lay = {"m": (0, torch.bfloat16), "v": (pad(words), torch.bfloat16)}
+        total = pad(words) + words
+        if fp32_master:
+            lay["master"] = (pad(total), torch.float32)
+            total = pad(total) + L
+        if split:
+            lay["lo"] = (pad(total), torch.int16)
+            total = pad(total) + words
+        return total, lay
     names = ["m", "v"][:2 if kind == "adam" else int(bool(momentum))]
     names += ["carry"] * bool(carry) + ["master"] * bool(fp32_master)
     lay = {name: (k * L, torch.float32) for k, name in enumerate(names)}
@@ -56,7 +101,7 @@ def state_layout(kind: str, L: int, *, split: bool, fp32_master: bool, carry: bo
 class UpdateCore:
     def __init__(self, kind: str, L: int, device, ws: int, group_of, n_params: int, *,
                  split: bool = False, fp32_master: bool = False, carry: bool = False,
-                 momentum: bool = True, placement_tries: int = 8):
+                 momentum: bool = True, placement_tries: int = 8, state_dtype=None):
         from .engine import probed_zeros  # (engine.py builds on this module)
 
         if kind not in ("adam", "sgd"):
@@ -65,8 +110,14 @@ class UpdateCore:
         # momentum, so the shard holds a momentum buffer; none of them: no optimizer state at all)
         self.kind, self.L, self.device, self.ws = kind, int(L), device, ws
         self.group_of = list(group_of)
+        # the moments' dtype: torch.float32, or torch.bfloat16 (Adam without amsgrad or carry; one
+        # step widens them, runs the fp32 update and stores them rounded to nearest even)
+        self.state_dtype = check_state_dtype(state_dtype)
+        if self.state_dtype == torch.bfloat16 and (kind != "adam" or carry):
+            raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with " +
+                             ("torch.optim.SGD" if kind != "adam" else "the ZeRO-1 gradient carry"))
         total, lay = state_layout(kind, self.L, split=split, fp32_master=fp32_master, carry=carry,
-                                  momentum=momentum)
+                                  momentum=momentum, state_dtype=self.state_dtype)
         self.state, self.placement = probed_zeros(total, torch.float32, device, placement_tries)
         for name in ("m", "v", "carry", "master", "lo"):  # residual 0: master = the bf16 param
             off, dt = lay.get(name, (0, None))
@@ -99,16 +150,18 @@ class UpdateCore:
         return views
 
     def ensure_vmax(self):
+        if self.state_dtype == torch.bfloat16:
+            raise ValueError("zero_amd: state_dtype=torch.bfloat16 does not support amsgrad")
         if self.vmax is None:
             self.vmax = torch.zeros(self.L, dtype=torch.float32, device=self.device)
         return self.vmax
 
     def state_cols(self, rows, so) -> None:
         """Columns 4-7 (m, v, vmax, carry) of zs_adam_seg ``rows`` at shard offsets ``so``."""
-        so = np.asarray(so).astype(np.uint64) * np.uint64(4)
+        so = np.asarray(so).astype(np.uint64)
         for col, t in ((4, self.m), (5, self.v), (6, self.vmax), (7, self.carry)):
             if t is not None:
-                rows[:, col] = np.uint64(t.data_ptr()) + so
+                rows[:, col] = np.uint64(t.data_ptr()) + so * np.uint64(t.element_size())
 
     def expose_sgd(self, optimizer, params, groups, idx, views_of) -> None:
         """torch's SGD state for the parameters ``idx``: {} until a parameter's first step, then
@@ -167,6 +220,8 @@ class UpdateCore:
             return sgd_hparams(hpd["lr"], hpd["momentum"], hpd["dampening"], hpd["weight_decay"],
                                nesterov=hpd["nesterov"], maximize=hpd["maximize"], first=bool(key),
                                grad_div=float(self.ws), carry_mul=carry_mul)
+        if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
+            check_bf16_state_group(hpd)
         if hpd["amsgrad"] and self.vmax is None:
             raise RuntimeError("amsgrad state buffer missing")
         return adam_hparams(hpd["lr"], hpd["beta1"], hpd["beta2"], hpd["eps"], hpd["weight_decay"],

@@ -299,7 +299,7 @@ class ShardEngine(UpdateCore):
     def __init__(self, params, group_of, ws: int, rank: int, *, layout="reference", carry=False,
                  comm=None, bucket_bytes: int = 256 << 20, align: int = ALIGN_ELEMS,
                  buckets: str = "ragged", placement_tries: int = 8, master: str = "split",
-                 kind: str = "adam", momentum: bool = True):
+                 kind: str = "adam", momentum: bool = True, state_dtype=None):
         if kind not in ("adam", "sgd"):
             raise ValueError(f"ShardEngine: kind must be 'adam' or 'sgd' (got {kind!r})")
         if not params:
@@ -333,7 +333,8 @@ class ShardEngine(UpdateCore):
         # exp_avg, exp_avg_sq (+ ZeRO-1 carry, + fp32 master or its int16 residual) of the stream
         UpdateCore.__init__(self, kind, self.plan.stream_len(rank), dev, ws, group_of, len(params),
                             split=self.split, fp32_master=self.mixed and not self.split,
-                            carry=carry, momentum=momentum, placement_tries=placement_tries)
+                            carry=carry, momentum=momentum, placement_tries=placement_tries,
+                            state_dtype=state_dtype)
         if self.master is not None:
             for i, po, so, n in zip(*self._piece_cols()):
                 self.master[so:so + n].copy_(params[i].detach().reshape(-1)[po:po + n])
@@ -415,7 +416,9 @@ class ShardEngine(UpdateCore):
     def new_set(self, rows):
         """The update's kernel set over ``rows``: AdamSet, or SgdSet for an SGD engine."""
         gz = getattr(self, "czdtype", self.zdtype)  # dtype of the reduced grad the update reads
-        return (SgdSet if self.kind == "sgd" else AdamSet)(rows, gz, self.p_dtype)
+        if self.kind == "sgd":
+            return SgdSet(rows, gz, self.p_dtype)
+        return AdamSet(rows, gz, self.p_dtype, state_dtype=zs_dtype(self.state_dtype))
 
     # ------------------------------------------------------------------------------------------
     def step(self, grads, hparams_of, stream=None):

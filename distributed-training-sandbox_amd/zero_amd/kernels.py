@@ -135,14 +135,19 @@ class AdamSet:
     A ``ZS_BF16_SPLIT`` set reads bf16 gradients unless ``wide_grads=True`` says that the ``g``
     column points at fp32 buffers (ZeRO-3's fp32 accumulation arena).  The library accepts either
     width and cannot tell which one a raw pointer holds; the wrong one reads twice the buffer, so
-    the wide one is refused here, before the library, unless it is asked for by name."""
+    the wide one is refused here, before the library, unless it is asked for by name.
+
+    ``state_dtype``: None / ``ZS_F32`` — the ``m`` and ``v`` columns point at fp32 arrays — or
+    ``ZS_BF16``: at bf16 arrays (zs_adamset_create_ex: bf16 moments; no vmax, no carry, no
+    amsgrad)."""
 
     FIELDS = ("g", "master", "master_out", "p_out", "m", "v", "vmax", "carry", "n")
 
     _CREATE = "zs_adamset_create"
 
     def __init__(self, segs: np.ndarray, g_dtype: int, p_dtype: int = _lib.ZS_BF16, *,
-                 wide_grads: bool = False):
+                 wide_grads: bool = False, state_dtype: int | None = None):
+        state_dtype = _lib.ZS_F32 if state_dtype is None else int(state_dtype)
         if int(p_dtype) == _lib.ZS_BF16_SPLIT and int(g_dtype) == _lib.ZS_F32 and not wide_grads:
             raise _lib.ZeroAmdError(self._CREATE, _lib.ZS_ERR_INVALID,
                                     "ZS_BF16_SPLIT needs bf16 grads (fp32 gradient buffers: "
@@ -151,7 +156,15 @@ class AdamSet:
         arr = (AdamSeg * max(len(segs), 1))()
         ctypes.memmove(arr, segs.ctypes.data, segs.nbytes)
         h = ctypes.c_void_p()
-        _lib.call(self._CREATE, arr, len(segs), int(g_dtype), int(p_dtype), ctypes.byref(h))
+        if state_dtype == _lib.ZS_F32:
+            _lib.call(self._CREATE, arr, len(segs), int(g_dtype), int(p_dtype), ctypes.byref(h))
+        elif self._CREATE != "zs_adamset_create":
+            raise _lib.ZeroAmdError(self._CREATE, _lib.ZS_ERR_INVALID,
+                                    "only the Adam set takes a state_dtype")
+        else:
+            _lib.call("zs_adamset_create_ex", arr, len(segs), int(g_dtype), int(p_dtype),
+                      state_dtype, ctypes.byref(h))
+        self.state_dtype = state_dtype
         self._h = h
         self.nseg = len(segs)
         self._g = np.ascontiguousarray(segs[:, 0])  # the gradients bound now, per input row

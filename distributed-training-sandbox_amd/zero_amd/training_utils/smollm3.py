@@ -64,15 +64,22 @@ def train_step(model, optimizer, input_ids):
     return loss
 
 
-def accumulating_optimizer(model, lr: float = 1e-5, *, accumulation_dtype=None, **kw):
+def accumulating_optimizer(model, lr: float = 1e-5, *, accumulation_dtype=None, state_dtype=None,
+                           betas=None, **kw):
     """train_fsdp.py:85's AdamW behind ZeRO-3 update mode with gradient accumulation, for
     ``train_step_accumulated``.  ``accumulation_dtype=torch.float32``: the micro-batches' bf16
     gradient chunks are summed in an fp32 arena (one rounding to 2^-24 per pass instead of 2^-9).
+    ``state_dtype=torch.bfloat16``: exp_avg and exp_avg_sq are stored in bf16 (half the optimizer
+    state); that needs both betas at or below 0.99609375, so ``betas`` then defaults to the LLM
+    setting (0.9, 0.95) instead of torch's (0.9, 0.999).
     Further keywords go to ``zero3.ShardedOptimizer``."""
     from ..zero3 import ShardedOptimizer
 
-    return ShardedOptimizer(torch.optim.AdamW(model.parameters(), lr=lr), update=True,
-                            grad_accumulation=True, accumulation_dtype=accumulation_dtype, **kw)
+    if betas is None:
+        betas = (0.9, 0.95) if state_dtype == torch.bfloat16 else (0.9, 0.999)
+    return ShardedOptimizer(torch.optim.AdamW(model.parameters(), lr=lr, betas=betas), update=True,
+                            grad_accumulation=True, accumulation_dtype=accumulation_dtype,
+                            state_dtype=state_dtype, **kw)
 
 
 def train_step_accumulated(model, optimizer, micro_batches):

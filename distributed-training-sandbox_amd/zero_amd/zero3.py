@@ -69,7 +69,8 @@ from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
 from ._sharded import group_hparams, optimizer_kind
-from ._update import UpdateCore, check_params, owner_range
+from ._update import (UpdateCore, check_bf16_state_group, check_params, check_state_dtype,
+                      owner_range)
 from .comm import STREAM_SYNC, RcclComm, Sync, comm_stream, sync_kind, zs_dtype
 from .engine import ALIGN_ELEMS
 from .kernels import AdamSet, SgdSet, stream_handle
@@ -1836,7 +1837,13 @@ class ShardedOptimizer:
                  gather_dtype=None, bucket_mb: float = RS_BUCKET_MB, grad_comm: str | None = None,
                  gather_wave: int = GATHER_WAVE, side_stream: bool = True,
                  stream_sync: str = STREAM_SYNC, grad_accumulation: bool = False,
-                 accumulation_dtype=None):
+                 accumulation_dtype=None, state_dtype=None):
+        # state_dtype=torch.bfloat16 (update mode, Adam without amsgrad): exp_avg and exp_avg_sq are
+        # stored in bf16, the arithmetic stays fp32; None / torch.float32: fp32
+        self.state_dtype = check_state_dtype(state_dtype)
+        if self.state_dtype == torch.bfloat16 and not update:
+            raise ValueError("zero_amd: state_dtype=torch.bfloat16 applies to update mode "
+                             "(reference mode never updates and holds no optimizer state)")
         # grad_accumulation (update mode): several backward passes per step(), each reduce-
         # scattered and added to the chunks already held (_GradReducer); off: the second backward
         # before step() is an error, as before
@@ -1861,7 +1868,12 @@ class ShardedOptimizer:
         # "adam" or "sgd" (TypeError for anything else); reference mode never updates either
         self._kind = optimizer_kind(optimizer)
         for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
-            group_hparams(self._kind, group, optimizer)
+            hpd = group_hparams(self._kind, group, optimizer)
+            if self.state_dtype == torch.bfloat16 and self._kind == "adam":
+                check_bf16_state_group(hpd)
+        if self.state_dtype == torch.bfloat16 and self._kind == "sgd":
+            raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with "
+                             "torch.optim.SGD (bf16 moments are Adam's)")
         self.optimizer = optimizer
         self.original_param_groups = optimizer.param_groups
         self.params = [p for group in self.original_param_groups for p in group["params"]]
@@ -1932,6 +1944,7 @@ class ShardedOptimizer:
         self._split = ar.dtype == torch.bfloat16
         self._core = UpdateCore(self._kind, ar.total, ar.device, self.world_size, self._group_of,
                                 len(self.params), split=self._split,
+                                state_dtype=self.state_dtype,
                                 momentum=any(g.get("momentum", 0) != 0 for g in self._groups))
         self._core.timing_events = self._timing_events
         self.placement = self._core.placement
@@ -2108,11 +2121,17 @@ class ShardedOptimizer:
         """The update's kernel set over ``rows``; ``acc``: fp32 gradients (the accumulation arena)."""
         gz = ZS_F32 if acc else ZS_BF16 if (
             self._split or (self._grad_comm and self.world_size > 1)) else ZS_F32
+        kw = {} if self._kind == "sgd" else dict(state_dtype=zs_dtype(self.state_dtype))
         mk = SgdSet if self._kind == "sgd" else AdamSet
-        return mk(rows, gz, ZS_BF16_SPLIT, wide_grads=acc) if self._split else mk(rows, gz)
+        if self._split:
+            return mk(rows, gz, ZS_BF16_SPLIT, wide_grads=acc, **kw)
+        return mk(rows, gz, **kw)
 
     def _step_update(self):
         red, ar = self._reducer, self._arena
+        if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
+            for group in self._groups:
+                check_bf16_state_group(group_hparams(self._kind, group, self.optimizer))
         if red.incomplete():
             raise RuntimeError(
                 "zero_amd ZeRO-3: a backward did not finish (it raised), so the accumulated "

@@ -1,0 +1,137 @@
+"""In-process A/B of the fused Adam with fp32 and with bf16 moments on one C4-size parameter set.
+
+ONE ZeRO-2 optimizer at world size 1 is built, so parameters, residuals and state are placed once
+(placement differs from process to process by ~3 %).  Over its arena three kernel sets are made
+from the engine's own rows: the fp32-state set, a second fp32-state set over the same rows (the
+A/B's own spread: what two equal settings differ by), and a bf16-state set whose ``m`` and ``v`` lie
+over the front halves of the same exp_avg / exp_avg_sq arrays.  They run in alternating blocks on
+the same buffers and the same gradients, every launch timed with HIP events on the compute stream.
+One untimed round comes first.  Per setting: the median of each round, their median, the spread
+between rounds, the algorithmic bytes (zs_adamset_stats) and the rate against the 8 TB/s peak; then
+the verdict: is bf16 state faster than fp32 state in every round by more than the largest
+fp32-against-fp32 difference of any round?
+
+Usage: python tools/state_dtype_ab.py [--rounds 7] [--steps 30] [--kind split|fp32]
+                                      [--config C4] [--out FILE.json]
+``--kind split``: bf16 parameters with the split master, bf16 gradients (26 against 18 B/element);
+``--kind fp32``: fp32 parameters and gradients (28 against 20).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(REPO / "distributed-training-sandbox_amd"))
+
+PEAK_GBS = 8000.0
+SETTINGS = ("f32", "f32_again", "bf16")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--kind", default="split", choices=["split", "fp32"])
+    ap.add_argument("--config", default="C4", choices=["C2", "C3", "C4", "C5"])
+    ap.add_argument("--port", type=int, default=29551)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert args.rounds >= 5 and args.steps >= 20, "at least 5 rounds of at least 20 steps"
+
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    from zero_amd import _lib, zero2
+    from zero_amd.kernels import AdamSet, adam_hparams
+    from zero_amd.shapes import CONFIGS
+
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{args.port}", rank=0, world_size=1)
+    name, shape_fn = CONFIGS[args.config]
+    shapes = shape_fn()
+    pdt = torch.bfloat16 if args.kind == "split" else torch.float32
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+    params = [torch.nn.Parameter(torch.empty(s, dtype=torch.float32, device=dev).normal_(
+        0.0, 0.02, generator=gen).to(pdt)) for s in shapes]
+    gen.manual_seed(1)
+    grads = [(torch.empty(s, dtype=torch.float32, device=dev).normal_(generator=gen) * 1e-3).to(pdt)
+             for s in shapes]
+    opt = zero2.ShardedOptimizer(torch.optim.Adam(params, lr=1e-3, betas=(0.9, 0.95)), sync=False)
+    if opt.engine is None:
+        opt._build_engine()
+    eng = opt.engine
+    assert eng.ws == 1 and eng.K == 1 and eng.split == (args.kind == "split")
+    stream = torch.cuda.current_stream(dev)
+    rd = eng.rounds[0]
+    rows = rd.rows.copy()  # the engine's rows over its placed arena; gradients read in place
+    rows[:, 0] = np.fromiter((grads[int(i)].data_ptr() for i in rd.idx), np.uint64, len(rd.idx))
+    half = rows.copy()  # bf16 m and v: the same shard offsets, 2 bytes an element
+    for col, t in ((4, eng.m), (5, eng.v)):
+        base = np.uint64(t.data_ptr())
+        half[:, col] = base + (rows[:, col] - base) // np.uint64(2)
+    sets = {"f32": AdamSet(rows, eng.zdtype, eng.p_dtype),
+            "f32_again": AdamSet(rows, eng.zdtype, eng.p_dtype),
+            "bf16": AdamSet(half, eng.zdtype, eng.p_dtype, state_dtype=_lib.ZS_BF16)}
+    count = {s: 0 for s in SETTINGS}
+
+    def block(s, n):
+        ev = []
+        for _ in range(n):
+            count[s] += 1
+            h = adam_hparams(1e-3, 0.9, 0.95, 1e-8, 0.0, count[s])
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            sets[s].run(h, stream)
+            e1.record(stream)
+            ev.append((e0, e1))
+        torch.cuda.synchronize()
+        return [a.elapsed_time(b) for a, b in ev]
+
+    rounds = {s: [] for s in SETTINGS}
+    for s in SETTINGS:  # one untimed round: code load, page tables, clocks
+        block(s, args.steps)
+    for r in range(args.rounds):
+        for s in (SETTINGS if r % 2 == 0 else SETTINGS[::-1]):
+            ms = block(s, args.steps)
+            rounds[s].append(float(np.median(ms)))
+            print(json.dumps({"round": r, "setting": s, "median_ms": rounds[s][-1],
+                              "min_ms": min(ms), "max_ms": max(ms)}), flush=True)
+    n_el = int(sum(p.numel() for p in params))
+    summary = {"config": f"{args.config} {name}", "params": n_el, "kind": args.kind,
+               "rounds": args.rounds, "steps_per_round": args.steps,
+               "placement": getattr(eng, "placement", None), "settings": []}
+    for s in SETTINGS:
+        med = float(np.median(rounds[s]))
+        nbytes = sets[s].bytes
+        gbs = nbytes / med / 1e6
+        summary["settings"].append({
+            "setting": s, "round_medians_ms": rounds[s], "median_ms": med,
+            "spread_ms": max(rounds[s]) - min(rounds[s]), "bytes": int(nbytes),
+            "bytes_per_element": nbytes / n_el, "gbs": gbs, "frac_of_8tbs": gbs / PEAK_GBS,
+            "frac_round_min_max": [nbytes / m / 1e6 / PEAK_GBS
+                                   for m in (max(rounds[s]), min(rounds[s]))]})
+    same = [abs(a - b) for a, b in zip(rounds["f32"], rounds["f32_again"])]
+    gain = [min(a, b) - c for a, b, c in zip(rounds["f32"], rounds["f32_again"], rounds["bf16"])]
+    f32_ms = float(np.median(rounds["f32"] + rounds["f32_again"]))
+    b16 = summary["settings"][2]
+    summary["verdict"] = {
+        "f32_vs_f32_abs_diff_ms_per_round": same, "ab_spread_ms": max(same),
+        "bf16_gain_ms_per_round": gain, "min_gain_ms": min(gain),
+        "bf16_faster_in_every_round_by_more_than_the_spread": bool(min(gain) > max(same)),
+        "time_ratio_bf16_over_f32": b16["median_ms"] / f32_ms,
+        "bytes_ratio_bf16_over_f32": b16["bytes"] / summary["settings"][0]["bytes"]}
+    print(json.dumps(summary), flush=True)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(json.dumps(summary, indent=1) + "\n")
+    dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()
