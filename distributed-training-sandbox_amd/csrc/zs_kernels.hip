@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "zs_common.h"
+#include "zs_sr.h"
 
 namespace {
 
@@ -340,6 +341,61 @@ struct AdamRule {
   }
 };
 
+// Stochastic rounding of bf16 moments (zs_adamset_run_sr).  SrBf16 as ST names the stochastic
+// instances: 16-bit m and v like `unsigned short`, stored through zs_sr::round_bf16 with 16 bits of
+// zs_sr::bits(e, k0, k1) each, e = the element's index in the shard's m array (its address less
+// m_base, in elements).  The keys and m_base ride behind Adam's HP, so no other instance sees them.
+struct SrBf16 {
+  unsigned short bits;
+};
+struct SrHP : HP {
+  uint32_t k0, k1;
+  uint64_t m_base;
+};
+struct AdamSrRule : AdamRule<false> {
+  using Hyper = SrHP;
+};
+template <typename ST>
+inline constexpr bool kStochastic = std::is_same_v<ST, SrBf16>;
+
+// index of a segment's element 0 in the shard's m array (uniform: scalar registers)
+__device__ __forceinline__ uint64_t sr_seg_index(const float* m, const SrHP& hp) {
+  return (uint64_t(reinterpret_cast<uintptr_t>(m)) - hp.m_base) >> 1;
+}
+// zs_sr::bits(eu + off, k0, k1) for a uniform eu and a per-lane off: the high word of the sum is
+// eu's or one more, so its multiply and the xor with k0 stay scalar and a lane selects
+__device__ __forceinline__ uint32_t sr_bits_at(uint64_t eu, uint32_t off, const SrHP& hp) {
+  const uint32_t lo0 = uint32_t(eu), hi = uint32_t(eu >> 32);
+  const uint32_t lo = lo0 + off;
+  const uint32_t ka = hp.k0 ^ (hi * 0x9E3779B9u), kb = hp.k0 ^ ((hi + 1u) * 0x9E3779B9u);
+  return zs_sr::lowbias32(lo ^ (lo < lo0 ? kb : ka)) ^ hp.k1;
+}
+// zs_sr::round_bf16(u, r16, zs_sr::nan_bf16(u)) with the code left in the word's high half: one
+// add, and a NaN (quiet, its payload's high bits kept) selected over it; two such words pack in
+// one operation.  sr_narrow: m and v of one element, one draw for both.
+__device__ __forceinline__ uint32_t sr_word(float x, uint32_t r16) {
+  const uint32_t u = __float_as_uint(x);
+  return x != x ? (u | 0x00400000u) : u + r16;
+}
+__device__ __forceinline__ void sr_narrow(float m, float v, uint32_t r, uint32_t& mw, uint32_t& vw) {
+  mw = sr_word(m, r & 0xFFFFu);
+  vw = sr_word(v, r >> 16);
+}
+__device__ __forceinline__ uint32_t sr_pack2(uint32_t w0, uint32_t w1) {
+  return (w0 >> 16) | (w1 & 0xFFFF0000u);
+}
+// Four elements from index eu + off on, packed for one 8-byte store each.  HPT: the instance's
+// Hyper (SrHP wherever this is reached).
+template <typename HPT>
+__device__ __forceinline__ void sr_pack_bf16x4(const float* mp, const float* vp, uint64_t eu,
+                                               uint32_t off, const HPT& hp, uint2& mr, uint2& vr) {
+  uint32_t mw[4], vw[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) sr_narrow(mp[j], vp[j], sr_bits_at(eu, off + j, hp), mw[j], vw[j]);
+  mr = make_uint2(sr_pack2(mw[0], mw[1]), sr_pack2(mw[2], mw[3]));
+  vr = make_uint2(sr_pack2(vw[0], vw[1]), sr_pack2(vw[2], vw[3]));
+}
+
 // torch.optim.SGD over the same tables: field `m` of a segment is the momentum buffer (MOM: the
 // set has one), `v` and `vmax` are unused.  Without MOM no state array is touched.
 struct SgdHP {
@@ -459,7 +515,8 @@ struct NoStream {
 // before anything depends on one.  Second loop: unpack, the rule's elem and the stores, group by
 // group.  ST: the element type of m and v in memory, float or unsigned short (bf16 moments: 8 bytes
 // per lane per access through the 16-bit streams, widened before the rule and rounded to nearest
-// even after it; the rule itself and the parameter it leaves see fp32 moments only).
+// even after it — SrBf16: stochastically, sr_pack_bf16x4; the rule itself and the parameter it
+// leaves see fp32 moments only).
 template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool HASG, bool CLIP,
           typename ST = float>
 __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
@@ -566,7 +623,14 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
         nt_st8(pb.at(u, o2), r);
       }
     }
-    if constexpr (S16) {
+    if constexpr (kStochastic<ST>) {
+      uint2 mr, vr;
+      // (one uniform index per chunk: the group's offset rides in the lane's part, an immediate)
+      sr_pack_bf16x4(mp, vp, sr_seg_index(s.m, hp) + uint64_t(e0),
+                     (uint32_t(u) * kThreads + threadIdx.x) * 4u, hp, mr, vr);
+      nt_st8(mh.at(u, o2), mr);
+      nt_st8(vh.at(u, o2), vr);
+    } else if constexpr (S16) {
       const uint2 mr = pack_bf16x4(mp), vr = pack_bf16x4(vp);
       nt_st8(mh.at(u, o2), mr);
       nt_st8(vh.at(u, o2), vr);
@@ -650,7 +714,13 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
           nt_st8(s.p_out + i, r);
         }
       }
-      if constexpr (S16) {
+      if constexpr (kStochastic<ST>) {
+        uint2 mr, vr;
+        sr_pack_bf16x4(mp, vp, sr_seg_index(s.m, hp) + uint64_t(e0),
+                       (uint32_t(u) * kThreads + threadIdx.x) * 4u, hp, mr, vr);
+        nt_st8(reinterpret_cast<unsigned short*>(s.m) + i, mr);
+        nt_st8(reinterpret_cast<unsigned short*>(s.v) + i, vr);
+      } else if constexpr (S16) {
         const uint2 mr = pack_bf16x4(mp), vr = pack_bf16x4(vp);
         nt_st8(reinterpret_cast<unsigned short*>(s.m) + i, mr);
         nt_st8(reinterpret_cast<unsigned short*>(s.v) + i, vr);
@@ -764,6 +834,80 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     }
     if constexpr (Rule::kX) glob(s.vmax)[i] = vm;
     if constexpr (CARRY) glob(s.carry)[i] = cr;
+  }
+}
+
+// The bf16-state Adam kernels with stochastic rounding (zs_adamset_run_sr): the two kernels above
+// over AdamSrRule / SrBf16, whose Hyper carries the keys and m_base.  Kernels of their own, so the
+// ones above keep their signature.
+template <typename GT, bool SPLIT, bool LOADS_FIRST, bool CLIP>
+__global__ __launch_bounds__(kThreads) void adam_sr_segments_kernel(
+    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
+    int64_t total_chunks, SrHP hp, const float* __restrict__ coef_ptr) {
+  const float coef = clip_coef<CLIP>(coef_ptr);
+  using Rule = AdamSrRule;
+  int64_t seg = 0;
+  if constexpr (LOADS_FIRST) {
+    int64_t hi = nseg;
+    while (hi - seg > 1) {
+      const int64_t mid = (seg + hi) >> 1;
+      if (chunk_prefix[mid] <= int64_t(blockIdx.x)) seg = mid;
+      else hi = mid;
+    }
+  }
+  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
+    while (chunk_prefix[seg + 1] <= c) ++seg;
+    const AdamSeg s = segs[seg];
+    constexpr int G = adam_groups(SPLIT);
+    const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT);
+    if constexpr (LOADS_FIRST) {
+      if (e0 + adam_chunk(SPLIT) <= s.n) {  // uniform per workgroup
+        if (s.g) update_full_chunk<Rule, GT, false, SPLIT, true, CLIP, SrBf16>(s, e0, hp, coef);
+        else update_full_chunk<Rule, GT, false, SPLIT, false, CLIP, SrBf16>(s, e0, hp, coef);
+      } else {
+#pragma unroll 1
+        for (int u = 0; u < G && e0 + int64_t(u) * kThreads * 4 < s.n; ++u)
+          update_pred_groups<Rule, GT, false, SPLIT, 1, CLIP, SrBf16>(
+              s, e0 + int64_t(u) * kThreads * 4, hp, coef);
+      }
+    } else {
+      update_pred_groups<Rule, GT, false, SPLIT, G, CLIP, SrBf16>(s, e0, hp, coef);
+    }
+  }
+}
+
+template <typename GT, bool SPLIT, bool CLIP>
+__global__ __launch_bounds__(kThreads) void adam_sr_scalar_kernel(
+    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
+    int64_t total_chunks, SrHP hp, const float* __restrict__ coef_ptr) {
+  const float coef = clip_coef<CLIP>(coef_ptr);
+  int64_t seg = 0;
+  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
+    while (chunk_prefix[seg + 1] <= c) ++seg;
+    const AdamSeg s = segs[seg];
+    const int64_t i0 = (c - chunk_prefix[seg]) * kThreads;  // uniform
+    const int64_t i = i0 + threadIdx.x;
+    if (i >= s.n) continue;
+    float gs = s.g ? load_g1<GT>(s.g, i) : 0.0f;
+    const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
+    float p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
+                    : glob(s.master)[i];
+    const gptr<unsigned short> mb = glob(reinterpret_cast<unsigned short*>(s.m));
+    const gptr<unsigned short> vb = glob(reinterpret_cast<unsigned short*>(s.v));
+    float m = bf16_to_f32(mb[i]), v = bf16_to_f32(vb[i]), vm = 0.0f, cr = 0.0f;
+    AdamSrRule::template elem<false, CLIP>(gs, p, m, v, vm, cr, hp, coef);
+    if constexpr (SPLIT) {
+      const unsigned short h = f32_to_bf16(p);
+      glob(s.p_out)[i] = h;
+      lo[i] = (unsigned short)master_residual(p, h);
+    } else {
+      if (s.master_out) glob(s.master_out)[i] = p;
+      if (s.p_out) glob(s.p_out)[i] = f32_to_bf16(p);
+    }
+    uint32_t mh, vh;
+    sr_narrow(m, v, sr_bits_at(sr_seg_index(s.m, hp) + uint64_t(i0), threadIdx.x, hp), mh, vh);
+    mb[i] = (unsigned short)(mh >> 16);
+    vb[i] = (unsigned short)(vh >> 16);
   }
 }
 
@@ -1684,6 +1828,10 @@ struct zs_adamset {
   std::vector<int64_t> in_n;
   std::vector<unsigned char> in_vec;
   int64_t bytes_no_g = 0;
+  // zs_adamset_run_sr: the lowest m address of the inputs (~0: none) and whether they all share
+  // its parity (an element index is a whole number of bf16 elements from m_base)
+  uint64_t m_lowest = ~uint64_t(0);
+  int m_one_parity = 1;
 };
 
 namespace {
@@ -1801,6 +1949,14 @@ struct AdamBf16StateKernels {
   static auto get() {
     if constexpr (VEC) return adam_segments_kernel<GT, false, false, S, LF, CLIP, unsigned short>;
     else return adam_scalar_kernel<GT, false, false, S, CLIP, unsigned short>;
+  }
+};
+// ... stored with stochastic rounding (zs_adamset_run_sr): the same 24 instances over SrBf16
+struct AdamSrKernels {
+  template <bool VEC, typename GT, bool AMS, bool C, bool S, bool LF, bool CLIP>
+  static auto get() {
+    if constexpr (VEC) return adam_sr_segments_kernel<GT, S, LF, CLIP>;
+    else return adam_sr_scalar_kernel<GT, S, CLIP>;
   }
 };
 struct SgdKernels {
@@ -2332,7 +2488,8 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   std::vector<uint64_t> in_g(size_t(n), 0);
   std::vector<int64_t> in_n(size_t(n), 0);
   std::vector<unsigned char> in_vec(size_t(n), 0);
-  int carry_state = -1, vmax_state = -1, mom_state = -1;
+  int carry_state = -1, vmax_state = -1, mom_state = -1, m_one_parity = 1;
+  uint64_t m_lowest = ~uint64_t(0);
   int64_t elems = 0, bytes = 0, bytes_no_g = 0;
   for (int64_t i = 0; i < n; ++i) {
     const zs_adam_seg& s = in[i];
@@ -2411,6 +2568,8 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
       sca_goff.push_back(nv * gsz);
       spre.push_back(spre.back() + (t.n + kThreads - 1) / kThreads);
     }
+    if (m_lowest != ~uint64_t(0) && ((s.m ^ m_lowest) & 1)) m_one_parity = 0;
+    m_lowest = std::min<uint64_t>(m_lowest, s.m);
     elems += s.n;
     int64_t b = msz /*master*/ + (sgd ? (s.m ? 8 : 0) /*buffer*/ : 2 * ssz /*m*/ + 2 * ssz /*v*/);
     if (s.master_out) b += split ? 4 /*residual read + write*/ : 4;
@@ -2441,6 +2600,8 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   as->in_n = std::move(in_n);
   as->in_vec = std::move(in_vec);
   as->bytes_no_g = bytes_no_g;
+  as->m_lowest = m_lowest;
+  as->m_one_parity = m_one_parity;
   int rc = ZS_OK;
   if (as->nvec) {
     rc = upload(vec, &as->d_vec);
@@ -2572,6 +2733,34 @@ int zs_adamset_run_clipped(const zs_adamset* as, const zs_adam_hparams* h, const
   return launch_update_tables<AdamKernels, true>(
       vec_table(as), sca_table(as), as->g_dtype, as->p_dtype == ZS_BF16_SPLIT, ams, false,
       make_hp(h), coef, reinterpret_cast<hipStream_t>(stream));
+}
+
+int zs_adamset_run_sr(const zs_adamset* as, const zs_adam_hparams* h, const float* coef,
+                      uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream) {
+  ZS_REQUIRE(as && h, "zs_adamset_run_sr: NULL argument");
+  ZS_REQUIRE(!as->sgd && as->state_dtype == ZS_BF16,
+             "zs_adamset_run_sr: stochastic rounding needs an Adam set with ZS_BF16 state "
+             "(zs_adamset_create_ex)");
+  ZS_REQUIRE(!h->amsgrad, "zs_adamset_run_sr: a set with ZS_BF16 state has no amsgrad");
+  if (as->nvec + as->nsca) {  // every element's index: its m address less m_base, in elements
+    ZS_REQUIRE(as->m_lowest >= m_base,
+               "zs_adamset_run_sr: a segment's m lies below m_base (%#llx < %#llx)",
+               (unsigned long long)as->m_lowest, (unsigned long long)m_base);
+    ZS_REQUIRE(as->m_one_parity && ((as->m_lowest - m_base) & 1) == 0,
+               "zs_adamset_run_sr: a segment's m lies at an odd byte distance from m_base");
+  }
+  SrHP hp;
+  static_cast<HP&>(hp) = make_hp(h);
+  hp.k0 = key0;
+  hp.k1 = key1;
+  hp.m_base = m_base;
+  const bool split = as->p_dtype == ZS_BF16_SPLIT;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (coef)
+    return launch_update_tables<AdamSrKernels, true>(vec_table(as), sca_table(as), as->g_dtype,
+                                                     split, false, false, hp, coef, st);
+  return launch_update_tables<AdamSrKernels, false>(vec_table(as), sca_table(as), as->g_dtype,
+                                                    split, false, false, hp, nullptr, st);
 }
 
 int zs_adamset_sqnorm_partials(const zs_adamset* as, int64_t* n) {

@@ -20,7 +20,8 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import check_bf16_state_group, check_state_dtype, owner_range
+from ._update import (check_bf16_state_group, check_state_dtype, check_state_rounding,
+                      owner_range)
 from .engine import ShardEngine
 from .training_utils.utils import get
 
@@ -78,7 +79,8 @@ class ShardedOptimizerBase:
                  bucket_mb: float | None = None, comm=None, sync: bool = True, buckets: str = "ragged",
                  overlap: bool = False, overlap_bucket_mb: float = 64.0, master: str = "split",
                  arena: str = "flat", grad_comm: str | None = None,
-                 max_grad_norm: float | None = None, state_dtype=None):
+                 max_grad_norm: float | None = None, state_dtype=None,
+                 state_rounding: str | None = None, state_seed: int = 0):
         if arena not in ("flat", "buckets", "auto"):
             raise ValueError(f"arena must be 'flat', 'buckets' or 'auto' (got {arena!r})")
         # the moments' dtype: None / torch.float32, or torch.bfloat16 (opt-in: exp_avg and
@@ -86,6 +88,11 @@ class ShardedOptimizerBase:
         # cannot be combined with is refused below, on every rank and before anything collective
         self.state_dtype = check_state_dtype(state_dtype)
         bf16_state = self.state_dtype == torch.bfloat16
+        # how bf16 moments are rounded when stored: None / "nearest", or "stochastic" (opt-in: the
+        # fused update rounds them from a counter-based generator keyed by state_seed, the step
+        # and the element's index in its shard, which lifts the bound on the betas)
+        self.state_rounding, self.state_seed = check_state_rounding(state_rounding, state_seed,
+                                                                    self.state_dtype)
         # global gradient-norm clipping inside step() (None = off); a plain attribute, it may be
         # changed between steps.  What it cannot be combined with is refused here, on every rank
         # and before anything collective
@@ -106,7 +113,7 @@ class ShardedOptimizerBase:
         for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
             hpd = group_hparams(self._kind, group, optimizer)
             if bf16_state and self._kind == "adam":
-                check_bf16_state_group(hpd)
+                check_bf16_state_group(hpd, self.state_rounding)
         if bf16_state:
             if self._kind == "sgd":
                 raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with "
@@ -261,6 +268,8 @@ class ShardedOptimizerBase:
                                      master=self._master, grad_comm=self._grad_comm,
                                      layout=self._layout, kind=self._kind,
                                      state_dtype=self.state_dtype,
+                                     state_rounding=self.state_rounding,
+                                     state_seed=self.state_seed,
                                      momentum=self._kind == "sgd" and any(
                                          g.get("momentum", 0) != 0 for g in self._groups))
         else:
@@ -317,7 +326,7 @@ class ShardedOptimizerBase:
         self._check_clip()
         if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
             for gi in range(len(self._groups)):
-                check_bf16_state_group(self._hparams_of(gi))
+                check_bf16_state_group(self._hparams_of(gi), self.state_rounding)
         self.engine.max_grad_norm = self.max_grad_norm
         had_vmax = self.engine.vmax is not None
         grads = [p.grad for p in self.params]
@@ -387,7 +396,9 @@ class ShardedOptimizerBase:
 
     # checkpointing (zero_amd/checkpoint.py) -------------------------------------------------------
     def _ckpt_header(self):
-        return ckpt.header(self._variant, self.world_size, self.rank, self.local_param_indices)
+        seed = self.state_seed if self.state_rounding == "stochastic" else None
+        return ckpt.header(self._variant, self.world_size, self.rank, self.local_param_indices,
+                           state_seed=seed)
 
     def _ckpt_views(self, i: int) -> dict:
         """name -> live view of param i's flat state (the owned params of Layout R)."""
@@ -427,6 +438,9 @@ class ShardedOptimizerBase:
             self._build_engine()
         eng = self.engine
         torch.cuda.synchronize(eng.device)
+        seed = ckpt.saved_state_seed(state_dict)
+        if seed is not None and self.state_rounding == "stochastic":
+            self.state_seed = eng.state_seed = seed  # the saved run's bits continue
         ckpt.load_param_groups(self.optimizer, state_dict)
         self.original_param_groups = self.optimizer.param_groups
         self._groups = list(self.optimizer.param_groups)

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from .checkpoint import step_of
-from .kernels import adam_hparams, sgd_hparams
+from .kernels import adam_hparams, sgd_hparams, sr_keys
 
 
 def owner_range(n: int, ws: int, rank: int):
@@ -53,11 +53,32 @@ def check_state_dtype(state_dtype):
                      f"(got {state_dtype!r})")
 
 
-def check_bf16_state_group(hpd: dict) -> None:
-    """What a param group may ask of bf16 moments: no amsgrad, and both betas at or below
-    1 - 2^-8 = 0.99609375, so that every bf16 value moves under the decay; ValueError otherwise."""
+def check_state_rounding(state_rounding, state_seed, state_dtype):
+    """(``state_rounding`` as "nearest" (None: the default) or "stochastic", ``state_seed`` as an
+    int); ValueError for another rounding, a seed outside [0, 2^64) or stochastic rounding of
+    anything but bf16 moments (``state_dtype`` as ``check_state_dtype`` returns it)."""
+    rounding = "nearest" if state_rounding is None else state_rounding
+    if rounding not in ("nearest", "stochastic"):
+        raise ValueError("zero_amd: state_rounding must be None, 'nearest' or 'stochastic' "
+                         f"(got {state_rounding!r})")
+    if isinstance(state_seed, bool) or not isinstance(state_seed, (int, np.integer)) or \
+            not 0 <= int(state_seed) < 1 << 64:
+        raise ValueError(f"zero_amd: state_seed must be an int in [0, 2^64) (got {state_seed!r})")
+    if rounding == "stochastic" and state_dtype != torch.bfloat16:
+        raise ValueError("zero_amd: state_rounding='stochastic' rounds bf16 moments: it needs "
+                         "state_dtype=torch.bfloat16")
+    return rounding, int(state_seed)
+
+
+def check_bf16_state_group(hpd: dict, state_rounding=None) -> None:
+    """What a param group may ask of bf16 moments: no amsgrad, and — rounded to nearest — both
+    betas at or below 1 - 2^-8 = 0.99609375, so that every bf16 value moves under the decay;
+    ValueError otherwise.  ``state_rounding`` "stochastic": any beta (the rounding is unbiased, so
+    the decay acts in expectation)."""
     if hpd.get("amsgrad"):
         raise ValueError("zero_amd: state_dtype=torch.bfloat16 does not support amsgrad")
+    if state_rounding == "stochastic":
+        return
     for name in ("beta1", "beta2"):
         if 1.0 - float(hpd[name]) < BF16_STATE_MIN_ONE_MINUS_BETA:
             raise ValueError(
@@ -101,7 +122,8 @@ def state_layout(kind: str, L: int, *, split: bool, fp32_master: bool, carry: bo
 class UpdateCore:
     def __init__(self, kind: str, L: int, device, ws: int, group_of, n_params: int, *,
                  split: bool = False, fp32_master: bool = False, carry: bool = False,
-                 momentum: bool = True, placement_tries: int = 8, state_dtype=None):
+                 momentum: bool = True, placement_tries: int = 8, state_dtype=None,
+                 state_rounding=None, state_seed: int = 0):
         from .engine import probed_zeros  # (engine.py builds on this module)
 
         if kind not in ("adam", "sgd"):
@@ -111,11 +133,16 @@ class UpdateCore:
         self.kind, self.L, self.device, self.ws = kind, int(L), device, ws
         self.group_of = list(group_of)
         # the moments' dtype: torch.float32, or torch.bfloat16 (Adam without amsgrad or carry; one
-        # step widens them, runs the fp32 update and stores them rounded to nearest even)
+        # step widens them, runs the fp32 update and stores them rounded to nearest even, or
+        # stochastically: state_rounding below)
         self.state_dtype = check_state_dtype(state_dtype)
         if self.state_dtype == torch.bfloat16 and (kind != "adam" or carry):
             raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with " +
                              ("torch.optim.SGD" if kind != "adam" else "the ZeRO-1 gradient carry"))
+        # how the bf16 moments are rounded when stored: "nearest", or "stochastic" from the
+        # counter-based generator keyed by (state_seed, the part's step, the element's shard index)
+        self.state_rounding, self.state_seed = check_state_rounding(state_rounding, state_seed,
+                                                                    self.state_dtype)
         total, lay = state_layout(kind, self.L, split=split, fp32_master=fp32_master, carry=carry,
                                   momentum=momentum, state_dtype=self.state_dtype)
         self.state, self.placement = probed_zeros(total, torch.float32, device, placement_tries)
@@ -221,9 +248,15 @@ class UpdateCore:
                                nesterov=hpd["nesterov"], maximize=hpd["maximize"], first=bool(key),
                                grad_div=float(self.ws), carry_mul=carry_mul)
         if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
-            check_bf16_state_group(hpd)
+            check_bf16_state_group(hpd, self.state_rounding)
         if hpd["amsgrad"] and self.vmax is None:
             raise RuntimeError("amsgrad state buffer missing")
+        hp = self._adam_hp(hpd, key, carry_mul)
+        if self.state_rounding == "stochastic":  # the launch's keys travel with its struct
+            hp.sr_keys = sr_keys(self.state_seed, int(key))
+        return hp
+
+    def _adam_hp(self, hpd: dict, key: int, carry_mul: float):
         return adam_hparams(hpd["lr"], hpd["beta1"], hpd["beta2"], hpd["eps"], hpd["weight_decay"],
                             int(key), decoupled=hpd["decoupled"], amsgrad=hpd["amsgrad"],
                             maximize=hpd["maximize"], grad_div=float(self.ws), carry_mul=carry_mul)
@@ -255,7 +288,9 @@ class UpdateCore:
         if ev is not None:
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record(stream)
-        if coef is None:
+        if self.state_rounding == "stochastic":
+            aset.run_sr(hp, self.m.data_ptr(), hp.sr_keys, stream, coef=coef)
+        elif coef is None:
             aset.run(hp, stream)
         else:
             aset.run_clipped(hp, coef, stream)

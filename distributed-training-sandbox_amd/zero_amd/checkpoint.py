@@ -14,7 +14,8 @@ Per-parameter entries: ``step`` (fp32 CPU scalar, torch's convention), ``exp_avg
 (+ ``max_exp_avg_sq``) and, beyond torch's Adam, what the engine needs to continue bit for bit:
 ``master_residual`` (int16; bf16 params, split master: master = bf16 param bits << 16 + residual),
 ``master_param`` (fp32 master), ``zero1_carry`` (ZeRO-1's A_{t-1}).  A
-``zero_amd`` header names the variant, world size, rank and ownership; loading a dict written at a
+``zero_amd`` header names the variant, world size, rank and ownership (and, with stochastic rounding
+of bf16 moments, the generator's ``state_seed``, which a loading optimizer adopts); loading a dict written at a
 different world size or rank raises instead of silently mis-assigning shards.  A dict without the
 header (a plain torch Adam state dict, e.g. the reference's ``opt.optimizer.state_dict()``) loads
 by index; missing extras start from the parameter as it is (residual 0 / master = param, carry 0).
@@ -27,12 +28,22 @@ from torch.optim import Optimizer
 FORMAT = 1
 
 
-def header(variant: int, ws: int, rank: int, owned, update=None) -> dict:
+def header(variant: int, ws: int, rank: int, owned, update=None, state_seed=None) -> dict:
     h = {"format": FORMAT, "variant": int(variant), "world_size": int(ws), "rank": int(rank),
          "local_param_indices": [int(i) for i in owned]}
     if update is not None:
         h["update"] = bool(update)
+    if state_seed is not None:  # stochastic rounding of bf16 moments: the generator's seed
+        h["state_seed"] = int(state_seed)
     return h
+
+
+def saved_state_seed(sd: dict):
+    """The ``state_seed`` a state dict was written with, or None (it is not compared by
+    ``check_header``: an optimizer with stochastic rounding adopts it, so that a resumed run draws
+    the uninterrupted run's bits)."""
+    seed = (sd.get("zero_amd") or {}).get("state_seed")
+    return None if seed is None else int(seed)
 
 
 def check_header(sd: dict, expect: dict) -> None:

@@ -299,7 +299,8 @@ class ShardEngine(UpdateCore):
     def __init__(self, params, group_of, ws: int, rank: int, *, layout="reference", carry=False,
                  comm=None, bucket_bytes: int = 256 << 20, align: int = ALIGN_ELEMS,
                  buckets: str = "ragged", placement_tries: int = 8, master: str = "split",
-                 kind: str = "adam", momentum: bool = True, state_dtype=None):
+                 kind: str = "adam", momentum: bool = True, state_dtype=None,
+                 state_rounding=None, state_seed: int = 0):
         if kind not in ("adam", "sgd"):
             raise ValueError(f"ShardEngine: kind must be 'adam' or 'sgd' (got {kind!r})")
         if not params:
@@ -334,7 +335,8 @@ class ShardEngine(UpdateCore):
         UpdateCore.__init__(self, kind, self.plan.stream_len(rank), dev, ws, group_of, len(params),
                             split=self.split, fp32_master=self.mixed and not self.split,
                             carry=carry, momentum=momentum, placement_tries=placement_tries,
-                            state_dtype=state_dtype)
+                            state_dtype=state_dtype, state_rounding=state_rounding,
+                            state_seed=state_seed)
         if self.master is not None:
             for i, po, so, n in zip(*self._piece_cols()):
                 self.master[so:so + n].copy_(params[i].detach().reshape(-1)[po:po + n])

@@ -82,7 +82,8 @@ class FlatEngine(ShardEngine):
     def __init__(self, params, group_of, ws: int, rank: int, *, carry=False, comm=None,
                  bucket_bytes: int = 256 << 20, master: str = "split", placement_tries: int = 8,
                  grad_comm: str | None = None, layout: str = "reference", kind: str = "adam",
-                 momentum: bool = True, state_dtype=None):
+                 momentum: bool = True, state_dtype=None, state_rounding=None,
+                 state_seed: int = 0):
         if layout not in ("reference", "flat"):
             raise ValueError(f"the flat arena takes layout 'reference' or 'flat' (got {layout!r})")
         if layout == "flat" and carry:
@@ -92,7 +93,8 @@ class FlatEngine(ShardEngine):
         # machinery; its bucket plan (one bucket) is unused
         super().__init__(params, group_of, ws, rank, layout=layout, carry=carry, comm=comm,
                          bucket_bytes=1 << 62, buckets="ragged", placement_tries=placement_tries,
-                         master=master, kind=kind, momentum=momentum, state_dtype=state_dtype)
+                         master=master, kind=kind, momentum=momentum, state_dtype=state_dtype,
+                         state_rounding=state_rounding, state_seed=state_seed)
         self.arena_kind = "flat"
         self.layout = layout
         plan, es, dev, dt = self.plan, self.es, self.device, self.dtype

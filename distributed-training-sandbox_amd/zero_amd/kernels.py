@@ -3,7 +3,8 @@
 ``CopySet``  — one launch of the descriptor-driven gather/scatter copy (pack / unpack).
 ``copy_direct`` — the same copy with the segments in the kernel arguments (no table to keep).
 ``AdamSet``  — one launch of the fused Adam/AdamW update over a list of segments; its
-``grad_sqnorm`` / ``run_clipped`` with ``sqnorm_reduce`` and ``clip_coef`` are global-norm clipping.
+``grad_sqnorm`` / ``run_clipped`` with ``sqnorm_reduce`` and ``clip_coef`` are global-norm clipping;
+``run_sr`` with ``sr_keys`` stores bf16 moments with stochastic rounding.
 ``SgdSet``   — the same tables with torch.optim.SGD's update (momentum, Nesterov); ``sgd_hparams``.
 ``adam_step`` — the same update over one contiguous range (zs_adam_step_ex; no table to keep).
 
@@ -220,6 +221,15 @@ class AdamSet:
         ptr = coef if isinstance(coef, int) else coef.data_ptr()
         _lib.call("zs_adamset_run_clipped", self._h, ctypes.byref(hp), ptr, stream_handle(stream))
 
+    def run_sr(self, hp: AdamHParams, m_base: int, keys, stream, coef=None) -> None:
+        """``run`` (``coef`` None) or ``run_clipped`` of a set with ``ZS_BF16`` state, the moments
+        stored with stochastic rounding (zs_adamset_run_sr): ``keys`` = ``sr_keys(seed, step)``,
+        ``m_base`` the address of element 0 of the moment array the ``m`` column points into (only
+        subtracted from, never read)."""
+        ptr = None if coef is None else coef if isinstance(coef, int) else coef.data_ptr()
+        _lib.call("zs_adamset_run_sr", self._h, ctypes.byref(hp), ptr, int(m_base), int(keys[0]),
+                  int(keys[1]), stream_handle(stream))
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib is not None:
@@ -228,6 +238,22 @@ class AdamSet:
             except Exception:  # interpreter teardown
                 pass
             self._h = None
+
+
+def sr_keys(seed: int, step: int):
+    """(key0, key1) of one stochastic-rounding launch from the optimizer's seed and the step count
+    of the launched part (zs_sr_keys; a host function)."""
+    k0, k1 = ctypes.c_uint32(), ctypes.c_uint32()
+    _lib.call("zs_sr_keys", int(seed), int(step), ctypes.byref(k0), ctypes.byref(k1))
+    return k0.value, k1.value
+
+
+def sr_bits(e: int, keys) -> int:
+    """The 32 random bits of element ``e`` under ``keys`` (zs_sr_bits; a host function): exp_avg
+    rounds with the low 16, exp_avg_sq with the high 16."""
+    r = ctypes.c_uint32()
+    _lib.call("zs_sr_bits", int(e), int(keys[0]), int(keys[1]), ctypes.byref(r))
+    return r.value
 
 
 def sgd_hparams(lr, momentum=0.0, dampening=0.0, weight_decay=0.0, *, nesterov=False,

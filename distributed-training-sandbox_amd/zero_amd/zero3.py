@@ -70,7 +70,7 @@ from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
 from ._sharded import group_hparams, optimizer_kind
 from ._update import (UpdateCore, check_bf16_state_group, check_params, check_state_dtype,
-                      owner_range)
+                      check_state_rounding, owner_range)
 from .comm import STREAM_SYNC, RcclComm, Sync, comm_stream, sync_kind, zs_dtype
 from .engine import ALIGN_ELEMS
 from .kernels import AdamSet, SgdSet, stream_handle
@@ -1837,10 +1837,15 @@ class ShardedOptimizer:
                  gather_dtype=None, bucket_mb: float = RS_BUCKET_MB, grad_comm: str | None = None,
                  gather_wave: int = GATHER_WAVE, side_stream: bool = True,
                  stream_sync: str = STREAM_SYNC, grad_accumulation: bool = False,
-                 accumulation_dtype=None, state_dtype=None):
+                 accumulation_dtype=None, state_dtype=None, state_rounding: str | None = None,
+                 state_seed: int = 0):
         # state_dtype=torch.bfloat16 (update mode, Adam without amsgrad): exp_avg and exp_avg_sq are
-        # stored in bf16, the arithmetic stays fp32; None / torch.float32: fp32
+        # stored in bf16, the arithmetic stays fp32; None / torch.float32: fp32.
+        # state_rounding="stochastic" (None / "nearest": as before): they are stored with
+        # stochastic rounding keyed by state_seed, which lifts the bound on the betas
         self.state_dtype = check_state_dtype(state_dtype)
+        self.state_rounding, self.state_seed = check_state_rounding(state_rounding, state_seed,
+                                                                    self.state_dtype)
         if self.state_dtype == torch.bfloat16 and not update:
             raise ValueError("zero_amd: state_dtype=torch.bfloat16 applies to update mode "
                              "(reference mode never updates and holds no optimizer state)")
@@ -1870,7 +1875,7 @@ class ShardedOptimizer:
         for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
             hpd = group_hparams(self._kind, group, optimizer)
             if self.state_dtype == torch.bfloat16 and self._kind == "adam":
-                check_bf16_state_group(hpd)
+                check_bf16_state_group(hpd, self.state_rounding)
         if self.state_dtype == torch.bfloat16 and self._kind == "sgd":
             raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with "
                              "torch.optim.SGD (bf16 moments are Adam's)")
@@ -1945,6 +1950,7 @@ class ShardedOptimizer:
         self._core = UpdateCore(self._kind, ar.total, ar.device, self.world_size, self._group_of,
                                 len(self.params), split=self._split,
                                 state_dtype=self.state_dtype,
+                                state_rounding=self.state_rounding, state_seed=self.state_seed,
                                 momentum=any(g.get("momentum", 0) != 0 for g in self._groups))
         self._core.timing_events = self._timing_events
         self.placement = self._core.placement
@@ -2131,7 +2137,8 @@ class ShardedOptimizer:
         red, ar = self._reducer, self._arena
         if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
             for group in self._groups:
-                check_bf16_state_group(group_hparams(self._kind, group, self.optimizer))
+                check_bf16_state_group(group_hparams(self._kind, group, self.optimizer),
+                                       self.state_rounding)
         if red.incomplete():
             raise RuntimeError(
                 "zero_amd ZeRO-3: a backward did not finish (it raised), so the accumulated "
@@ -2268,7 +2275,9 @@ class ShardedOptimizer:
 
     # checkpointing (zero_amd/checkpoint.py) -------------------------------------------------------
     def _ckpt_header(self):
-        return ckpt.header(3, self.world_size, self.rank, self.local_param_indices, update=self.update)
+        seed = self.state_seed if self.state_rounding == "stochastic" else None
+        return ckpt.header(3, self.world_size, self.rank, self.local_param_indices,
+                           update=self.update, state_seed=seed)
 
     @on_param_device
     def state_dict(self):
@@ -2305,6 +2314,9 @@ class ShardedOptimizer:
         self.optimizer.state.clear()
         if not self.update:
             return
+        seed = ckpt.saved_state_seed(state_dict)
+        if seed is not None and self.state_rounding == "stochastic":
+            self.state_seed = self._core.state_seed = seed  # the saved run's bits continue
         saved = state_dict.get("state", {})
         params = ckpt.inner_params(self.optimizer)
         index = {id(p): k for k, p in enumerate(params)}

@@ -349,6 +349,36 @@ int zs_clip_coef(const float* sumsq, double grad_div, double max_norm, float* ou
 int zs_adamset_run_clipped(const zs_adamset* as, const zs_adam_hparams* hp, const float* coef,
                            uintptr_t stream);
 
+/* Stochastic rounding of bf16 moments (additive in ABI v13).  zs_adamset_run_sr is zs_adamset_run
+ * (coef == NULL) or zs_adamset_run_clipped (coef: the device scalar) of a set with ZS_BF16 state,
+ * except that m and v are stored rounded stochastically: for a finite fp32 value with bits u and 16
+ * random bits r the stored code is (u + r) >> 16 — away from zero with probability
+ * low16(u) / 65536, exact when low16(u) == 0, Inf past the largest finite value, never a NaN; a
+ * NaN or Inf is stored as zs_adamset_run stores it.  The rounding is unbiased, so a decay
+ * v <- beta * v moves every stored value in expectation at any beta: the bound on the betas that
+ * zs_adamset_create_ex states does not apply to these runs.  The parameter is computed from the
+ * unrounded fp32 moments as before, and the bytes moved are the same.
+ *
+ * The random bits come from no state and no memory.  With
+ *   lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ * over uint32, element e draws
+ *   r = lowbias32(lo32(e) ^ key0 ^ (hi32(e) * 0x9E3779B9)) ^ key1;
+ * m rounds with r & 0xFFFF and v with r >> 16.  e = (the element's address in m - m_base) / 2: its
+ * index in the caller's moment array, so the bits do not depend on how the array is cut into
+ * segments, on alignment, on zs_tune or on where the array lies.  m_base is never dereferenced.
+ * zs_sr_keys derives the keys of one launch from a 64-bit seed and the step count t of the
+ * segments (torch's state['step'] after the step):
+ *   key0 = lowbias32(lo32(t) ^ lo32(seed));
+ *   key1 = lowbias32((key0 ^ hi32(seed) ^ hi32(t)) + 0x9E3779B9).
+ * ZS_ERR_INVALID, nothing launched: a set without ZS_BF16 state (or an SGD set), hp->amsgrad, a
+ * segment whose m lies below m_base or at an odd byte distance from it.
+ * zs_sr_keys and zs_sr_bits are host functions (no device is touched): the definition above, for
+ * callers and tests that restate the rounding. */
+int zs_adamset_run_sr(const zs_adamset* as, const zs_adam_hparams* hp, const float* coef,
+                      uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream);
+int zs_sr_keys(uint64_t seed, uint64_t step, uint32_t* key0, uint32_t* key1);
+int zs_sr_bits(uint64_t e, uint32_t key0, uint32_t key1, uint32_t* r);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Fused SGD (momentum, Nesterov), additive in ABI v13.  Replaces torch.optim.SGD.step on the    */
 /* owned shard where the reference's ShardedOptimizer wraps an SGD (zero1.py:88, zero2.py:120,  */

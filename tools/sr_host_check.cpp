@@ -1,0 +1,108 @@
+// Stand-alone host check of the stochastic-rounding generator and rounding (csrc/zs_sr.h,
+// csrc/zs_sr.cpp), meant to be built with -fsanitize=address,undefined and run on the CPU:
+//   make -C distributed-training-sandbox_amd sr-host-check
+// It needs no GPU and loads nothing into another process.  Exit status 0: every check passed.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "zero_amd.h"
+#include "zs_sr.h"
+
+namespace {
+
+int g_bad = 0;
+#define CHECK(cond, ...)            \
+  do {                              \
+    if (!(cond)) {                  \
+      ++g_bad;                      \
+      std::fprintf(stderr, __VA_ARGS__); \
+      std::fputc('\n', stderr);     \
+    }                               \
+  } while (0)
+
+// round to nearest even, a NaN kept quiet: the project's oracle (zero_oracle.f32_to_bf16_bits)
+uint16_t rne(uint32_t u) {
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return uint16_t((u >> 16) | 0x40u);
+  return uint16_t((uint64_t(u) + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+uint16_t sr(uint32_t u, uint32_t r16) { return zs_sr::round_bf16(u, r16, zs_sr::nan_bf16(u)); }
+
+// known answers from the numpy restatement (tests/_bf16_state_sr_oracle.py):
+// seed, step, e, key0, key1, bits
+const struct {
+  uint64_t seed, step, e;
+  uint32_t k0, k1, r;
+} kKat[] = {
+    {0ull, 1ull, 0ull, 1753845952u, 2988215890u, 3941189415u},
+    {0ull, 1ull, 4294967295ull, 1753845952u, 2988215890u, 52218292u},
+    {0ull, 1ull, 4294967296ull, 1753845952u, 2988215890u, 4023129460u},
+    {0ull, 1ull, 1099511627783ull, 1753845952u, 2988215890u, 194493990u},
+    {0ull, 4294967297ull, 0ull, 1753845952u, 775946097u, 1992996356u},
+    {0ull, 4294967297ull, 4294967295ull, 1753845952u, 775946097u, 2671753367u},
+    {0ull, 4294967297ull, 4294967296ull, 1753845952u, 775946097u, 1945068631u},
+    {0ull, 4294967297ull, 1099511627783ull, 1753845952u, 775946097u, 2545209093u},
+    {4294979641ull, 1ull, 0ull, 3020340486u, 717996u, 2063926896u},
+    {4294979641ull, 1ull, 4294967295ull, 3020340486u, 717996u, 1028865400u},
+    {4294979641ull, 1ull, 4294967296ull, 3020340486u, 717996u, 1940632039u},
+    {4294979641ull, 1ull, 1099511627783ull, 3020340486u, 717996u, 176032015u},
+    {4294979641ull, 4294967297ull, 0ull, 3020340486u, 130576045u, 2093456497u},
+    {4294979641ull, 4294967297ull, 4294967295ull, 3020340486u, 130576045u, 982624121u},
+    {4294979641ull, 4294967297ull, 4294967296ull, 3020340486u, 130576045u, 1953049574u},
+    {4294979641ull, 4294967297ull, 1099511627783ull, 3020340486u, 130576045u, 230462222u},
+};
+
+}  // namespace
+
+int main() {
+  // the generator through the C entry points
+  for (const auto& k : kKat) {
+    uint32_t k0 = 0, k1 = 0, r = 0;
+    CHECK(zs_sr_keys(k.seed, k.step, &k0, &k1) == ZS_OK, "zs_sr_keys failed");
+    CHECK(k0 == k.k0 && k1 == k.k1, "keys(%llu, %llu) = %u, %u", (unsigned long long)k.seed,
+          (unsigned long long)k.step, k0, k1);
+    CHECK(zs_sr_bits(k.e, k0, k1, &r) == ZS_OK, "zs_sr_bits failed");
+    CHECK(r == k.r, "bits(%llu) = %u, expected %u", (unsigned long long)k.e, r, k.r);
+  }
+  uint32_t x = 0;
+  CHECK(zs_sr_keys(0, 1, nullptr, &x) == ZS_ERR_INVALID, "zs_sr_keys(NULL) was accepted");
+  CHECK(zs_sr_bits(0, 0, 0, nullptr) == ZS_ERR_INVALID, "zs_sr_bits(NULL) was accepted");
+
+  // the rounding: with r = 0x7FFF + lsb it is round-to-nearest-even on every finite value
+  std::vector<uint32_t> vals = {0x00000000u, 0x80000000u, 0x7F800000u, 0xFF800000u, 0x00000001u,
+                                0x007FFFFFu, 0x00800000u, 0x7F7FFFFFu, 0x7F7F0000u, 0x3F808000u,
+                                0x3F818000u, 0x7F7F7FFFu, 0x7F7F8000u, 0xFF7FFFFFu};
+  uint32_t s = 12345u;
+  for (int i = 0; i < 200000; ++i) {
+    s = zs_sr::lowbias32(s + 0x9E3779B9u);
+    if ((s & 0x7F800000u) != 0x7F800000u) vals.push_back(s);
+  }
+  for (uint32_t u : vals)
+    CHECK(sr(u, 0x7FFFu + ((u >> 16) & 1u)) == rne(u), "identity fails at %#x", u);
+  // non-finite values take the round-to-nearest result for any r
+  for (uint32_t u : {0x7F800000u, 0xFF800000u, 0x7FC00000u, 0x7F800001u, 0xFFFFFFFFu, 0x7FFFFFFFu})
+    for (uint32_t r : {0u, 1u, 0x7FFFu, 0x8000u, 0xFFFFu})
+      CHECK(sr(u, r) == rne(u), "non-finite %#x with r = %#x", u, r);
+  // for a fixed high half and every low half L, exactly L of the 65,536 r round away from zero
+  for (uint32_t hi : {0x3F80u, 0x0000u, 0x8001u, 0x7F7Eu, 0xC2F7u}) {
+    for (uint32_t k = 0; k < 65536u + 257u; k += 257u) {  // (a lattice of low halves and both ends)
+      const uint32_t lo = k < 65536u ? k : 65535u;
+      uint32_t away = 0;
+      for (uint32_t r = 0; r < 65536u; ++r) away += sr((hi << 16) | lo, r) != hi;
+      CHECK(away == lo, "hi %#x lo %#x: %u of 65536 round away", hi, lo, away);
+    }
+  }
+  // the largest finite bf16 plus a carry is Inf of its sign, never a NaN
+  CHECK(sr(0x7F7FFFFFu, 1u) == 0x7F80u && sr(0xFF7FFFFFu, 1u) == 0xFF80u, "carry into Inf");
+  CHECK(sr(0x7F7F0001u, 0xFFFFu) == 0x7F80u && sr(0x7F7F0000u, 0xFFFFu) == 0x7F7Fu, "edge");
+
+  if (g_bad) {
+    std::fprintf(stderr, "sr_host_check: %d checks failed\n", g_bad);
+    return 1;
+  }
+  std::puts("sr_host_check: ok");
+  return 0;
+}

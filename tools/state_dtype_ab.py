@@ -11,8 +11,14 @@ between rounds, the algorithmic bytes (zs_adamset_stats) and the rate against th
 the verdict: is bf16 state faster than fp32 state in every round by more than the largest
 fp32-against-fp32 difference of any round?
 
+``--sr`` (stochastic rounding of the bf16 moments): the settings are the fp32-state set, a bf16-state
+set rounded to nearest, a second one over the same rows (the A/B's own spread) and a bf16-state set
+run through zs_adamset_run_sr with torch's default betas; the verdict: is the stochastic step faster
+than the fp32-state step in every round, and what is its ratio to the nearest one beside the spread
+of the two equal nearest sets?
+
 Usage: python tools/state_dtype_ab.py [--rounds 7] [--steps 30] [--kind split|fp32]
-                                      [--config C4] [--out FILE.json]
+                                      [--config C4] [--sr] [--out FILE.json]
 ``--kind split``: bf16 parameters with the split master, bf16 gradients (26 against 18 B/element);
 ``--kind fp32``: fp32 parameters and gradients (28 against 20).
 """
@@ -28,6 +34,7 @@ sys.path.insert(0, str(REPO / "distributed-training-sandbox_amd"))
 
 PEAK_GBS = 8000.0
 SETTINGS = ("f32", "f32_again", "bf16")
+SR_SETTINGS = ("f32", "bf16", "bf16_again", "bf16_sr")
 
 
 def main():
@@ -37,8 +44,10 @@ def main():
     ap.add_argument("--kind", default="split", choices=["split", "fp32"])
     ap.add_argument("--config", default="C4", choices=["C2", "C3", "C4", "C5"])
     ap.add_argument("--port", type=int, default=29551)
+    ap.add_argument("--sr", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    SETTINGS = SR_SETTINGS if args.sr else globals()["SETTINGS"]
     assert args.rounds >= 5 and args.steps >= 20, "at least 5 rounds of at least 20 steps"
 
     import numpy as np
@@ -46,7 +55,7 @@ def main():
     import torch.distributed as dist
 
     from zero_amd import _lib, zero2
-    from zero_amd.kernels import AdamSet, adam_hparams
+    from zero_amd.kernels import AdamSet, adam_hparams, sr_keys
     from zero_amd.shapes import CONFIGS
 
     dev = torch.device("cuda:0")
@@ -75,19 +84,27 @@ def main():
     for col, t in ((4, eng.m), (5, eng.v)):
         base = np.uint64(t.data_ptr())
         half[:, col] = base + (rows[:, col] - base) // np.uint64(2)
-    sets = {"f32": AdamSet(rows, eng.zdtype, eng.p_dtype),
-            "f32_again": AdamSet(rows, eng.zdtype, eng.p_dtype),
-            "bf16": AdamSet(half, eng.zdtype, eng.p_dtype, state_dtype=_lib.ZS_BF16)}
+    mk16 = lambda: AdamSet(half, eng.zdtype, eng.p_dtype, state_dtype=_lib.ZS_BF16)  # noqa: E731
+    sets = {"f32": AdamSet(rows, eng.zdtype, eng.p_dtype)}
+    if args.sr:
+        sets.update(bf16=mk16(), bf16_again=mk16(), bf16_sr=mk16())
+    else:
+        sets.update(f32_again=AdamSet(rows, eng.zdtype, eng.p_dtype), bf16=mk16())
     count = {s: 0 for s in SETTINGS}
+    m_base = eng.m.data_ptr()
 
     def block(s, n):
         ev = []
         for _ in range(n):
             count[s] += 1
-            h = adam_hparams(1e-3, 0.9, 0.95, 1e-8, 0.0, count[s])
+            h = adam_hparams(1e-3, 0.9, 0.999 if s == "bf16_sr" else 0.95, 1e-8, 0.0, count[s])
+            keys = sr_keys(0, count[s]) if s == "bf16_sr" else None
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
-            sets[s].run(h, stream)
+            if keys is None:
+                sets[s].run(h, stream)
+            else:
+                sets[s].run_sr(h, m_base, keys, stream)
             e1.record(stream)
             ev.append((e0, e1))
         torch.cuda.synchronize()
@@ -116,6 +133,27 @@ def main():
             "bytes_per_element": nbytes / n_el, "gbs": gbs, "frac_of_8tbs": gbs / PEAK_GBS,
             "frac_round_min_max": [nbytes / m / 1e6 / PEAK_GBS
                                    for m in (max(rounds[s]), min(rounds[s]))]})
+    if args.sr:
+        by = {x["setting"]: x for x in summary["settings"]}
+        same = [abs(a - b) for a, b in zip(rounds["bf16"], rounds["bf16_again"])]
+        near_ms = float(np.median(rounds["bf16"] + rounds["bf16_again"]))
+        over = [c - max(a, b) for a, b, c in zip(rounds["bf16"], rounds["bf16_again"], rounds["bf16_sr"])]
+        summary["verdict"] = {
+            "nearest_vs_nearest_abs_diff_ms_per_round": same, "ab_spread_ms": max(same),
+            "sr_minus_slower_nearest_ms_per_round": over,
+            "sr_slower_than_nearest_by_more_than_the_spread": bool(max(over) > max(same)),
+            "sr_faster_than_f32_in_every_round": bool(all(
+                c < a for a, c in zip(rounds["f32"], rounds["bf16_sr"]))),
+            "time_ratio_sr_over_nearest": by["bf16_sr"]["median_ms"] / near_ms,
+            "spread_over_nearest": max(same) / near_ms,
+            "time_ratio_sr_over_f32": by["bf16_sr"]["median_ms"] / by["f32"]["median_ms"],
+            "bytes_ratio_sr_over_nearest": by["bf16_sr"]["bytes"] / by["bf16"]["bytes"]}
+        print(json.dumps(summary), flush=True)
+        if args.out:
+            Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.out).write_text(json.dumps(summary, indent=1) + "\n")
+        dist.destroy_process_group()
+        return
     same = [abs(a - b) for a, b in zip(rounds["f32"], rounds["f32_again"])]
     gain = [min(a, b) - c for a, b, c in zip(rounds["f32"], rounds["f32_again"], rounds["bf16"])]
     f32_ms = float(np.median(rounds["f32"] + rounds["f32_again"]))
