@@ -1,13 +1,19 @@
-// CDNA4 (gfx950) kernels of the ZeRO step: segment copy (pack / unpack), the fused Adam, its clip.
+// CDNA4 (gfx950) kernels of the ZeRO step and the C entry points that launch them: segment copy
+// (pack / unpack), the fused optimizer update (one vector and one scalar kernel, instantiated over
+// the element rules: Adam, Adam with bf16 moments rounded to nearest or stochastically, SGD), the
+// gradient sum of squares and clip coefficient, scale, accumulate, convert, the fp8 row quantizer
+// and gather, and the flag kernels.
 //
-// Both kernels are HBM-bound streaming kernels (no MFMA, no LDS): 64-wide waves, 256-thread
-// workgroups, 16-byte-per-lane coalesced accesses, a grid of 128 workgroups per CU (16x the 8
-// resident; 1024 per CU for the split-master Adam) that strides over fixed-size chunks of a
-// segment table.  A workgroup finds the segment of its chunk with a forward scan from the previous
-// one (chunks are visited in increasing order), so the lookup is a couple of scalar loads, not a
-// per-chunk binary search (the Adam bisects once, for its first chunk).  The Adam issues all of a
-// full chunk's loads (20 for the split master) before its first wait and addresses them from
-// scalar bases, which keeps its headline instance at 79 VGPRs (6 waves per SIMD), no scratch.
+// The copy and update kernels are HBM-bound streaming kernels (no MFMA, no LDS): 64-wide waves,
+// 256-thread workgroups, 16-byte-per-lane coalesced accesses, a grid of 128 workgroups per CU (16x
+// the 8 resident; 1024 per CU for the split-master update) that strides over fixed-size chunks of
+// a segment table.  A workgroup finds the segment of its chunk with a forward scan from the
+// previous one (chunks are visited in increasing order), so the lookup is a couple of scalar loads,
+// not a per-chunk binary search (the update bisects once, for its first chunk).  The update issues
+// all of a full chunk's loads (20 for the split-master Adam) before its first wait and addresses
+// them from scalar bases, which keeps its headline instance, adam_segments_kernel<AdamRule<false>,
+// unsigned short, false, true, true, false, float> (bf16 gradients, split master, loads first), at
+// 79 VGPRs and 106 SGPRs: 6 waves per SIMD, no scratch.
 //
 // Tables (segment pointers + chunk prefix sums) are uploaded once per set and reused every step:
 // the step itself only launches kernels (no host sync), so it can be captured into a hipGraph.
@@ -734,10 +740,15 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
   }
 }
 
-// The kernels.  The chunk loop, the routing of a chunk and the scalar body stand in each kernel
-// itself, once per rule: behind a function of their own they compile to other code than they did
-// (the return block moves and with it what the loop hoists, and sinking stops at the call), and
-// `make asm` must show the kernels unchanged.  CLIP instances exist without the carry only.
+// The kernels: one vector and one scalar kernel, instantiated per element rule.  The chunk loop, the
+// routing of a chunk and the scalar body stand in the kernel itself and not in a function: behind a
+// function of their own they compile to other code than they did (the return block moves and with
+// it what the loop hoists, and sinking stops at the call), and `make asm` must show the kernels
+// unchanged.  A kernel template over the rule is the same text instantiated per rule, so one text
+// serves Adam, Adam with stochastically rounded bf16 moments and SGD.  Both keep the name they had
+// when Adam was the only rule (the roofline label, the profiles and the ABI test key on it), so an
+// SGD launch shows under a profiler as adam_segments_kernel<SgdRule<true>, ...> -- like AdamSeg and
+// zs_adamset, which carry SGD sets too.  CLIP instances exist without the carry only.
 //
 // Vector kernel: every segment 16-B aligned (8-B for bf16 arrays) with n % 4 == 0 (the host
 // splits tails off into the scalar table).  adam_groups() float4 groups per thread, lane-contiguous
@@ -748,15 +759,16 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
 // !LOADS_FIRST (`zs_tune("adam_loads_first", 0)`): every chunk through the predicated body, all
 // groups unrolled -- the kernel as it was before update_full_chunk, kept for A/B runs.
 // ST = unsigned short (zs_adamset_create_ex with ZS_BF16 state): m and v are bf16 arrays, 8-B
-// aligned like the other 16-bit ones; the chunk geometry is the fp32-state instance's.
-template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP,
+// aligned like the other 16-bit ones; the chunk geometry is the fp32-state instance's.  ST = SrBf16
+// (zs_adamset_run_sr, over AdamSrRule, whose Hyper carries the keys and m_base): the same arrays,
+// stored with stochastic rounding.
+template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP,
           typename ST = float>
 __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
     const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
-    int64_t total_chunks, HP hp, const float* __restrict__ coef_ptr) {
+    int64_t total_chunks, typename Rule::Hyper hp, const float* __restrict__ coef_ptr) {
   static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
   const float coef = clip_coef<CLIP>(coef_ptr);
-  using Rule = AdamRule<AMS>;
   int64_t seg = 0;
   if constexpr (LOADS_FIRST) {
     int64_t hi = nseg;
@@ -787,29 +799,35 @@ __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
   }
 }
 
-template <typename GT, bool AMS, bool CARRY, bool SPLIT, bool CLIP, typename ST = float>
+// Scalar kernel: one element per lane, 256-element chunks.  m and v as ST stores them: stochastic
+// (one draw for both, the chunk's uniform index i0 plus the lane), bf16 to nearest, or the rule's
+// own fp32 arrays.
+template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool CLIP, typename ST = float>
 __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
-    int64_t total_chunks, HP hp, const float* __restrict__ coef_ptr) {
+    int64_t total_chunks, typename Rule::Hyper hp, const float* __restrict__ coef_ptr) {
   static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
   const float coef = clip_coef<CLIP>(coef_ptr);
-  using Rule = AdamRule<AMS>;
   constexpr bool S16 = sizeof(ST) == 2;
-  static_assert(!S16 || (!AMS && !CARRY), "bf16 state: no amsgrad, no carry");
+  static_assert(!S16 || (Rule::kM && Rule::kV && !Rule::kX && !CARRY),
+                "bf16 state: Adam's m and v, no amsgrad, no carry");
   int64_t seg = 0;
   for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
     while (chunk_prefix[seg + 1] <= c) ++seg;
     const AdamSeg s = segs[seg];
-    const int64_t i = (c - chunk_prefix[seg]) * kThreads + threadIdx.x;
+    const int64_t i0 = (c - chunk_prefix[seg]) * kThreads;  // uniform
+    const int64_t i = i0 + threadIdx.x;
     if (i >= s.n) continue;
     float gs = s.g ? load_g1<GT>(s.g, i) : 0.0f;
     const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
     float p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
                     : glob(s.master)[i];
+    const gptr<unsigned short> mb = glob(reinterpret_cast<unsigned short*>(s.m));
+    const gptr<unsigned short> vb = glob(reinterpret_cast<unsigned short*>(s.v));
     float m = 0.0f, v = 0.0f, vm = 0.0f;
     if constexpr (S16) {
-      m = bf16_to_f32(glob(reinterpret_cast<unsigned short*>(s.m))[i]);
-      v = bf16_to_f32(glob(reinterpret_cast<unsigned short*>(s.v))[i]);
+      m = bf16_to_f32(mb[i]);
+      v = bf16_to_f32(vb[i]);
     } else {
       if constexpr (Rule::kM) m = glob(s.m)[i];
       if constexpr (Rule::kV) v = glob(s.v)[i];
@@ -825,162 +843,18 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
       if (s.master_out) glob(s.master_out)[i] = p;
       if (s.p_out) glob(s.p_out)[i] = f32_to_bf16(p);
     }
-    if constexpr (S16) {
-      glob(reinterpret_cast<unsigned short*>(s.m))[i] = f32_to_bf16(m);
-      glob(reinterpret_cast<unsigned short*>(s.v))[i] = f32_to_bf16(v);
+    if constexpr (kStochastic<ST>) {
+      uint32_t mh, vh;
+      sr_narrow(m, v, sr_bits_at(sr_seg_index(s.m, hp) + uint64_t(i0), threadIdx.x, hp), mh, vh);
+      mb[i] = (unsigned short)(mh >> 16);
+      vb[i] = (unsigned short)(vh >> 16);
+    } else if constexpr (S16) {
+      mb[i] = f32_to_bf16(m);
+      vb[i] = f32_to_bf16(v);
     } else {
       if constexpr (Rule::kM) glob(s.m)[i] = m;
       if constexpr (Rule::kV) glob(s.v)[i] = v;
     }
-    if constexpr (Rule::kX) glob(s.vmax)[i] = vm;
-    if constexpr (CARRY) glob(s.carry)[i] = cr;
-  }
-}
-
-// The bf16-state Adam kernels with stochastic rounding (zs_adamset_run_sr): the two kernels above
-// over AdamSrRule / SrBf16, whose Hyper carries the keys and m_base.  Kernels of their own, so the
-// ones above keep their signature.
-template <typename GT, bool SPLIT, bool LOADS_FIRST, bool CLIP>
-__global__ __launch_bounds__(kThreads) void adam_sr_segments_kernel(
-    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
-    int64_t total_chunks, SrHP hp, const float* __restrict__ coef_ptr) {
-  const float coef = clip_coef<CLIP>(coef_ptr);
-  using Rule = AdamSrRule;
-  int64_t seg = 0;
-  if constexpr (LOADS_FIRST) {
-    int64_t hi = nseg;
-    while (hi - seg > 1) {
-      const int64_t mid = (seg + hi) >> 1;
-      if (chunk_prefix[mid] <= int64_t(blockIdx.x)) seg = mid;
-      else hi = mid;
-    }
-  }
-  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
-    while (chunk_prefix[seg + 1] <= c) ++seg;
-    const AdamSeg s = segs[seg];
-    constexpr int G = adam_groups(SPLIT);
-    const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT);
-    if constexpr (LOADS_FIRST) {
-      if (e0 + adam_chunk(SPLIT) <= s.n) {  // uniform per workgroup
-        if (s.g) update_full_chunk<Rule, GT, false, SPLIT, true, CLIP, SrBf16>(s, e0, hp, coef);
-        else update_full_chunk<Rule, GT, false, SPLIT, false, CLIP, SrBf16>(s, e0, hp, coef);
-      } else {
-#pragma unroll 1
-        for (int u = 0; u < G && e0 + int64_t(u) * kThreads * 4 < s.n; ++u)
-          update_pred_groups<Rule, GT, false, SPLIT, 1, CLIP, SrBf16>(
-              s, e0 + int64_t(u) * kThreads * 4, hp, coef);
-      }
-    } else {
-      update_pred_groups<Rule, GT, false, SPLIT, G, CLIP, SrBf16>(s, e0, hp, coef);
-    }
-  }
-}
-
-template <typename GT, bool SPLIT, bool CLIP>
-__global__ __launch_bounds__(kThreads) void adam_sr_scalar_kernel(
-    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
-    int64_t total_chunks, SrHP hp, const float* __restrict__ coef_ptr) {
-  const float coef = clip_coef<CLIP>(coef_ptr);
-  int64_t seg = 0;
-  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
-    while (chunk_prefix[seg + 1] <= c) ++seg;
-    const AdamSeg s = segs[seg];
-    const int64_t i0 = (c - chunk_prefix[seg]) * kThreads;  // uniform
-    const int64_t i = i0 + threadIdx.x;
-    if (i >= s.n) continue;
-    float gs = s.g ? load_g1<GT>(s.g, i) : 0.0f;
-    const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
-    float p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
-                    : glob(s.master)[i];
-    const gptr<unsigned short> mb = glob(reinterpret_cast<unsigned short*>(s.m));
-    const gptr<unsigned short> vb = glob(reinterpret_cast<unsigned short*>(s.v));
-    float m = bf16_to_f32(mb[i]), v = bf16_to_f32(vb[i]), vm = 0.0f, cr = 0.0f;
-    AdamSrRule::template elem<false, CLIP>(gs, p, m, v, vm, cr, hp, coef);
-    if constexpr (SPLIT) {
-      const unsigned short h = f32_to_bf16(p);
-      glob(s.p_out)[i] = h;
-      lo[i] = (unsigned short)master_residual(p, h);
-    } else {
-      if (s.master_out) glob(s.master_out)[i] = p;
-      if (s.p_out) glob(s.p_out)[i] = f32_to_bf16(p);
-    }
-    uint32_t mh, vh;
-    sr_narrow(m, v, sr_bits_at(sr_seg_index(s.m, hp) + uint64_t(i0), threadIdx.x, hp), mh, vh);
-    mb[i] = (unsigned short)(mh >> 16);
-    vb[i] = (unsigned short)(vh >> 16);
-  }
-}
-
-template <typename GT, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP, bool MOM>
-__global__ __launch_bounds__(kThreads) void sgd_segments_kernel(
-    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
-    int64_t total_chunks, SgdHP hp, const float* __restrict__ coef_ptr) {
-  static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
-  const float coef = clip_coef<CLIP>(coef_ptr);
-  using Rule = SgdRule<MOM>;
-  int64_t seg = 0;
-  if constexpr (LOADS_FIRST) {
-    int64_t hi = nseg;
-    while (hi - seg > 1) {
-      const int64_t mid = (seg + hi) >> 1;
-      if (chunk_prefix[mid] <= int64_t(blockIdx.x)) seg = mid;
-      else hi = mid;
-    }
-  }
-  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
-    while (chunk_prefix[seg + 1] <= c) ++seg;
-    const AdamSeg s = segs[seg];
-    constexpr int G = adam_groups(SPLIT);
-    const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT);
-    if constexpr (LOADS_FIRST) {
-      if (e0 + adam_chunk(SPLIT) <= s.n) {  // uniform per workgroup
-        if (s.g) update_full_chunk<Rule, GT, CARRY, SPLIT, true, CLIP>(s, e0, hp, coef);
-        else update_full_chunk<Rule, GT, CARRY, SPLIT, false, CLIP>(s, e0, hp, coef);
-      } else {
-#pragma unroll 1
-        for (int u = 0; u < G && e0 + int64_t(u) * kThreads * 4 < s.n; ++u)
-          update_pred_groups<Rule, GT, CARRY, SPLIT, 1, CLIP>(s, e0 + int64_t(u) * kThreads * 4, hp,
-                                                              coef);
-      }
-    } else {
-      update_pred_groups<Rule, GT, CARRY, SPLIT, G, CLIP>(s, e0, hp, coef);
-    }
-  }
-}
-
-template <typename GT, bool CARRY, bool SPLIT, bool CLIP, bool MOM>
-__global__ __launch_bounds__(kThreads) void sgd_scalar_kernel(
-    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
-    int64_t total_chunks, SgdHP hp, const float* __restrict__ coef_ptr) {
-  static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
-  const float coef = clip_coef<CLIP>(coef_ptr);
-  using Rule = SgdRule<MOM>;
-  int64_t seg = 0;
-  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
-    while (chunk_prefix[seg + 1] <= c) ++seg;
-    const AdamSeg s = segs[seg];
-    const int64_t i = (c - chunk_prefix[seg]) * kThreads + threadIdx.x;
-    if (i >= s.n) continue;
-    float gs = s.g ? load_g1<GT>(s.g, i) : 0.0f;
-    const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
-    float p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
-                    : glob(s.master)[i];
-    float m = 0.0f, v = 0.0f, vm = 0.0f;
-    if constexpr (Rule::kM) m = glob(s.m)[i];
-    if constexpr (Rule::kV) v = glob(s.v)[i];
-    if constexpr (Rule::kX) vm = glob(s.vmax)[i];
-    float cr = CARRY ? glob(s.carry)[i] : 0.0f;
-    Rule::template elem<CARRY, CLIP>(gs, p, m, v, vm, cr, hp, coef);
-    if constexpr (SPLIT) {
-      const unsigned short h = f32_to_bf16(p);
-      glob(s.p_out)[i] = h;
-      lo[i] = (unsigned short)master_residual(p, h);
-    } else {
-      if (s.master_out) glob(s.master_out)[i] = p;
-      if (s.p_out) glob(s.p_out)[i] = f32_to_bf16(p);
-    }
-    if constexpr (Rule::kM) glob(s.m)[i] = m;
-    if constexpr (Rule::kV) glob(s.v)[i] = v;
     if constexpr (Rule::kX) glob(s.vmax)[i] = vm;
     if constexpr (CARRY) glob(s.carry)[i] = cr;
   }
@@ -1933,39 +1807,24 @@ static HP make_hp(const zs_adam_hparams* h) {
   return hp;
 }
 
-// A family's vector (VEC) or scalar kernel by <grad type, rule flag (amsgrad / momentum), carry,
-// split, loads-first, clip>, whatever order the kernel itself lists them in.
-struct AdamKernels {
-  template <bool VEC, typename GT, bool AMS, bool C, bool S, bool LF, bool CLIP>
-  static auto get() {
-    if constexpr (VEC) return adam_segments_kernel<GT, AMS, C, S, LF, CLIP>;
-    else return adam_scalar_kernel<GT, AMS, C, S, CLIP>;
-  }
+// A family of update kernels: its rule as a function of the one rule flag (amsgrad / momentum
+// buffer), the type m and v are stored as, and whether instances with the flag set or with the
+// ZeRO-1 carry exist at all.  16-bit moments have neither: set_create refuses their vmax and carry
+// and adam_run their amsgrad, so the flag and the carry select nothing there.
+template <template <bool> class RuleOf, typename ST, bool VARIANTS>
+struct UpdateFamily {
+  template <bool FLAG>
+  using Rule = RuleOf<FLAG>;
+  using State = ST;
+  using Hyper = typename RuleOf<false>::Hyper;
+  static constexpr bool kVariants = VARIANTS;
 };
-// bf16 moments (zs_adamset_create_ex, ZS_BF16 state): no amsgrad and no carry instance exists; the
-// entry points refuse both, so whatever the two flags say names the one plain instance
-struct AdamBf16StateKernels {
-  template <bool VEC, typename GT, bool AMS, bool C, bool S, bool LF, bool CLIP>
-  static auto get() {
-    if constexpr (VEC) return adam_segments_kernel<GT, false, false, S, LF, CLIP, unsigned short>;
-    else return adam_scalar_kernel<GT, false, false, S, CLIP, unsigned short>;
-  }
-};
-// ... stored with stochastic rounding (zs_adamset_run_sr): the same 24 instances over SrBf16
-struct AdamSrKernels {
-  template <bool VEC, typename GT, bool AMS, bool C, bool S, bool LF, bool CLIP>
-  static auto get() {
-    if constexpr (VEC) return adam_sr_segments_kernel<GT, S, LF, CLIP>;
-    else return adam_sr_scalar_kernel<GT, S, CLIP>;
-  }
-};
-struct SgdKernels {
-  template <bool VEC, typename GT, bool MOM, bool C, bool S, bool LF, bool CLIP>
-  static auto get() {
-    if constexpr (VEC) return sgd_segments_kernel<GT, C, S, LF, CLIP, MOM>;
-    else return sgd_scalar_kernel<GT, C, S, CLIP, MOM>;
-  }
-};
+template <bool>
+using AdamSrRuleOf = AdamSrRule;
+using AdamFamily = UpdateFamily<AdamRule, float, true>;
+using AdamBf16Family = UpdateFamily<AdamRule, unsigned short, false>;  // zs_adamset_create_ex
+using AdamSrFamily = UpdateFamily<AdamSrRuleOf, SrBf16, false>;        // zs_adamset_run_sr
+using SgdFamily = UpdateFamily<SgdRule, float, true>;
 
 struct UpdateTable {  // a segment array with its chunk prefix
   const AdamSeg* segs;
@@ -1979,34 +1838,66 @@ static UpdateTable sca_table(const zs_adamset* as) {
   return {as->d_sca, as->d_sca_prefix, as->nsca, as->sca_chunks};
 }
 
-// Vector table (aligned, n % 4 == 0) then scalar table (tails, unaligned); the instance of K's
-// kernels (AdamKernels, SgdKernels) is picked by grad dtype, split master, the rule's flag (amsgrad
-// / momentum buffer) and carry.  No instance has the carry with CLIP (the clipped entry points
-// refuse a set with one) or with fp32 gradients over the split master (set_create refuses one).
-template <typename K, bool CLIP, typename HPT>
+// The tail of a segment from element nv on, n elements: what the vector kernel leaves to the scalar
+// one.  gsz, msz, ssz: bytes per element of g, of master / master_out and of m / v / vmax.
+static AdamSeg seg_tail(const AdamSeg& d, int64_t nv, int64_t n, int64_t gsz, int64_t msz,
+                        int64_t ssz) {
+  auto adv = [nv](auto* p, int64_t es) {
+    using P = decltype(p);
+    return p ? reinterpret_cast<P>(reinterpret_cast<uintptr_t>(p) + uintptr_t(nv * es)) : p;
+  };
+  return {adv(d.g, gsz),  adv(d.master, msz), adv(d.master_out, msz), adv(d.p_out, 2),
+          adv(d.m, ssz),  adv(d.v, ssz),      adv(d.vmax, ssz),       adv(d.carry, 4),
+          n};
+}
+
+// a run-time flag as a compile-time one: fn(std::true_type) or fn(std::false_type)
+template <typename Fn>
+static void with_flag(bool b, Fn&& fn) {
+  if (b) fn(std::true_type{});
+  else fn(std::false_type{});
+}
+
+// Vector table (aligned, n % 4 == 0) then scalar table (tails, unaligned); the instance of family
+// F is picked by clip (a coefficient is given), split master, grad dtype, the rule's flag and
+// carry.  No instance has the carry with CLIP (the run paths refuse a set with one) or with fp32
+// gradients over the split master (set_create refuses one), and none is named here that F has not.
+template <typename F>
 static int launch_update_tables(const UpdateTable& vec, const UpdateTable& sca, int g_dtype,
-                                bool split, bool flag, bool carry, const HPT& hp,
+                                bool split, bool flag, bool carry, const typename F::Hyper& hp,
                                 const float* coef, hipStream_t st) {
+  using ST = typename F::State;
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
   auto table = [&](const UpdateTable& t, auto is_vec, auto lf, int64_t cap) {
-    auto launch = [&](auto gt, auto s, auto f, auto c) {
-      hipLaunchKernelGGL((K::template get<decltype(is_vec)::value, decltype(gt), decltype(f)::value,
-                                          decltype(c)::value, decltype(s)::value,
-                                          decltype(lf)::value, CLIP>()),
-                         dim3(int(std::min<int64_t>(t.chunks, cap))), dim3(kThreads), 0, st, t.segs,
-                         t.prefix, t.nseg, t.chunks, hp, coef);
-    };
-    auto flags = [&](auto gt, auto s) {
-      if constexpr (!CLIP && !(sizeof(gt) == 4 && decltype(s)::value)) {
-        if (carry) return flag ? launch(gt, s, yes, yes) : launch(gt, s, no, yes);
-      }
-      return flag ? launch(gt, s, yes, no) : launch(gt, s, no, no);
-    };
-    if (g_dtype == ZS_F32 && split) flags(float(), yes);
-    else if (g_dtype == ZS_F32) flags(float(), no);
-    else if (split) flags((unsigned short)0, yes);
-    else flags((unsigned short)0, no);
+    const dim3 grid(int(std::min<int64_t>(t.chunks, cap)));
+    with_flag(coef != nullptr, [&](auto clip) {
+      with_flag(split, [&](auto s) {
+        with_flag(g_dtype == ZS_F32, [&](auto g32) {
+          using GT = std::conditional_t<decltype(g32)::value, float, unsigned short>;
+          constexpr bool CLIP = decltype(clip)::value, S = decltype(s)::value;
+          auto launch = [&](auto f, auto c) {
+            using Rule = typename F::template Rule<decltype(f)::value>;
+            constexpr bool C = decltype(c)::value;
+            if constexpr (decltype(is_vec)::value)
+              hipLaunchKernelGGL(
+                  (adam_segments_kernel<Rule, GT, C, S, decltype(lf)::value, CLIP, ST>), grid,
+                  dim3(kThreads), 0, st, t.segs, t.prefix, t.nseg, t.chunks, hp, coef);
+            else
+              hipLaunchKernelGGL((adam_scalar_kernel<Rule, GT, C, S, CLIP, ST>), grid,
+                                 dim3(kThreads), 0, st, t.segs, t.prefix, t.nseg, t.chunks, hp, coef);
+          };
+          if constexpr (!F::kVariants) {
+            launch(no, no);
+          } else {
+            if constexpr (!CLIP && !(decltype(g32)::value && S)) {
+              if (carry) return with_flag(flag, [&](auto f) { launch(f, yes); });
+            }
+            with_flag(flag, [&](auto f) { launch(f, no); });
+          }
+        });
+      });
+    });
   };
   if (vec.chunks) {
     const bool lf = adam_loads_first() != 0;
@@ -2021,6 +1912,16 @@ static int launch_update_tables(const UpdateTable& vec, const UpdateTable& sca, 
     ZS_HIP(hipGetLastError());
   }
   return ZS_OK;
+}
+
+// One run of a set's two tables through family F (flag: amsgrad / momentum).  The callers have
+// refused a clipped run of a set with the carry.
+template <typename F>
+static int run_set(const zs_adamset* as, bool flag, const typename F::Hyper& hp, const float* coef,
+                   uintptr_t stream) {
+  return launch_update_tables<F>(vec_table(as), sca_table(as), as->g_dtype,
+                                 as->p_dtype == ZS_BF16_SPLIT, flag, as->has_carry != 0, hp, coef,
+                                 reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" {
@@ -2549,20 +2450,7 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
       vpre.push_back(vpre.back() + (nv + adam_chunk(split) - 1) / adam_chunk(split));
     }
     if (nv < s.n) {  // tail (or the whole unaligned segment) through the scalar kernel
-      AdamSeg t = d;
-      auto adv = [nv](auto* p, int64_t es) {
-        using P = decltype(p);
-        return p ? reinterpret_cast<P>(reinterpret_cast<uintptr_t>(p) + uintptr_t(nv * es)) : p;
-      };
-      t.g = s.g ? reinterpret_cast<const void*>(s.g + uint64_t(nv * gsz)) : nullptr;
-      t.master = adv(d.master, msz);
-      t.master_out = adv(d.master_out, msz);
-      t.p_out = adv(d.p_out, 2);
-      t.m = adv(d.m, ssz);
-      t.v = adv(d.v, ssz);
-      t.vmax = adv(d.vmax, ssz);
-      t.carry = adv(d.carry, 4);
-      t.n = s.n - nv;
+      const AdamSeg t = seg_tail(d, nv, s.n - nv, gsz, msz, ssz);
       sca.push_back(t);
       sca_in.push_back(int32_t(i));
       sca_goff.push_back(nv * gsz);
@@ -2686,81 +2574,60 @@ int zs_sgdset_run(const zs_adamset* as, const zs_sgd_hparams* h, const float* co
   hp.nesterov = h->nesterov ? 1 : 0;
   hp.maximize = h->maximize ? 1 : 0;
   hp.first = h->first ? 1 : 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // torch with momentum == 0 never makes a buffer: a set that has one leaves it alone then
-  const bool mom = as->has_mom != 0 && h->momentum != 0.0f;
-  const bool split = as->p_dtype == ZS_BF16_SPLIT;
-  if (coef)
-    return launch_update_tables<SgdKernels, true>(vec_table(as), sca_table(as), as->g_dtype, split,
-                                                  mom, false, hp, coef, st);
-  return launch_update_tables<SgdKernels, false>(vec_table(as), sca_table(as), as->g_dtype, split,
-                                                 mom, as->has_carry != 0, hp, nullptr, st);
+  return run_set<SgdFamily>(as, as->has_mom != 0 && h->momentum != 0.0f, hp, coef, stream);
+}
+
+// The three Adam entry points (`fn`: the one called, in messages).  need_coef: zs_adamset_run_clipped
+// requires its coefficient; sr: zs_adamset_run_sr's m_base and keys, over a set with bf16 moments.
+struct SrArgs {
+  uint64_t m_base;
+  uint32_t k0, k1;
+};
+static int adam_run(const char* fn, const zs_adamset* as, const zs_adam_hparams* h, bool need_coef,
+                    const float* coef, const SrArgs* sr, uintptr_t stream) {
+  ZS_REQUIRE(as && h && (coef || !need_coef), "%s: NULL argument", fn);
+  ZS_REQUIRE(!sr || (!as->sgd && as->state_dtype == ZS_BF16),
+             "%s: stochastic rounding needs an Adam set with ZS_BF16 state (zs_adamset_create_ex)",
+             fn);
+  ZS_REQUIRE(!as->sgd, "%s: the set was made by zs_sgdset_create (use zs_sgdset_run)", fn);
+  ZS_REQUIRE(!coef || !as->has_carry, "%s: a set with the ZeRO-1 carry cannot be clipped", fn);
+  const bool ams = h->amsgrad != 0;
+  const bool bf16_state = as->state_dtype == ZS_BF16;
+  ZS_REQUIRE(!ams || !bf16_state, "%s: a set with ZS_BF16 state has no amsgrad", fn);
+  ZS_REQUIRE(!ams || as->has_vmax || (as->nvec + as->nsca) == 0, "%s: amsgrad needs vmax segments",
+             fn);
+  if (!sr) {
+    if (bf16_state) return run_set<AdamBf16Family>(as, false, make_hp(h), coef, stream);
+    return run_set<AdamFamily>(as, ams, make_hp(h), coef, stream);
+  }
+  if (as->nvec + as->nsca) {  // every element's index: its m address less m_base, in elements
+    ZS_REQUIRE(as->m_lowest >= sr->m_base, "%s: a segment's m lies below m_base (%#llx < %#llx)", fn,
+               (unsigned long long)as->m_lowest, (unsigned long long)sr->m_base);
+    ZS_REQUIRE(as->m_one_parity && ((as->m_lowest - sr->m_base) & 1) == 0,
+               "%s: a segment's m lies at an odd byte distance from m_base", fn);
+  }
+  SrHP hp;
+  static_cast<HP&>(hp) = make_hp(h);
+  hp.k0 = sr->k0;
+  hp.k1 = sr->k1;
+  hp.m_base = sr->m_base;
+  return run_set<AdamSrFamily>(as, false, hp, coef, stream);
 }
 
 int zs_adamset_run(const zs_adamset* as, const zs_adam_hparams* h, uintptr_t stream) {
-  ZS_REQUIRE(as && h, "zs_adamset_run: NULL argument");
-  ZS_REQUIRE(!as->sgd, "zs_adamset_run: the set was made by zs_sgdset_create (use zs_sgdset_run)");
-  const bool ams = h->amsgrad != 0;
-  ZS_REQUIRE(!ams || as->has_vmax || (as->nvec + as->nsca) == 0,
-             "zs_adamset_run: amsgrad needs vmax segments");
-  if (as->state_dtype == ZS_BF16) {
-    ZS_REQUIRE(!ams, "zs_adamset_run: a set with ZS_BF16 state has no amsgrad");
-    return launch_update_tables<AdamBf16StateKernels, false>(
-        vec_table(as), sca_table(as), as->g_dtype, as->p_dtype == ZS_BF16_SPLIT, false, false,
-        make_hp(h), nullptr, reinterpret_cast<hipStream_t>(stream));
-  }
-  return launch_update_tables<AdamKernels, false>(
-      vec_table(as), sca_table(as), as->g_dtype, as->p_dtype == ZS_BF16_SPLIT, ams,
-      as->has_carry != 0, make_hp(h), nullptr, reinterpret_cast<hipStream_t>(stream));
+  return adam_run("zs_adamset_run", as, h, false, nullptr, nullptr, stream);
 }
 
 int zs_adamset_run_clipped(const zs_adamset* as, const zs_adam_hparams* h, const float* coef,
                            uintptr_t stream) {
-  ZS_REQUIRE(as && h && coef, "zs_adamset_run_clipped: NULL argument");
-  ZS_REQUIRE(!as->sgd,
-             "zs_adamset_run_clipped: the set was made by zs_sgdset_create (use zs_sgdset_run)");
-  ZS_REQUIRE(!as->has_carry,
-             "zs_adamset_run_clipped: a set with the ZeRO-1 carry cannot be clipped");
-  const bool ams = h->amsgrad != 0;
-  ZS_REQUIRE(!ams || as->has_vmax || (as->nvec + as->nsca) == 0,
-             "zs_adamset_run_clipped: amsgrad needs vmax segments");
-  if (as->state_dtype == ZS_BF16) {
-    ZS_REQUIRE(!ams, "zs_adamset_run_clipped: a set with ZS_BF16 state has no amsgrad");
-    return launch_update_tables<AdamBf16StateKernels, true>(
-        vec_table(as), sca_table(as), as->g_dtype, as->p_dtype == ZS_BF16_SPLIT, false, false,
-        make_hp(h), coef, reinterpret_cast<hipStream_t>(stream));
-  }
-  return launch_update_tables<AdamKernels, true>(
-      vec_table(as), sca_table(as), as->g_dtype, as->p_dtype == ZS_BF16_SPLIT, ams, false,
-      make_hp(h), coef, reinterpret_cast<hipStream_t>(stream));
+  return adam_run("zs_adamset_run_clipped", as, h, true, coef, nullptr, stream);
 }
 
 int zs_adamset_run_sr(const zs_adamset* as, const zs_adam_hparams* h, const float* coef,
                       uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream) {
-  ZS_REQUIRE(as && h, "zs_adamset_run_sr: NULL argument");
-  ZS_REQUIRE(!as->sgd && as->state_dtype == ZS_BF16,
-             "zs_adamset_run_sr: stochastic rounding needs an Adam set with ZS_BF16 state "
-             "(zs_adamset_create_ex)");
-  ZS_REQUIRE(!h->amsgrad, "zs_adamset_run_sr: a set with ZS_BF16 state has no amsgrad");
-  if (as->nvec + as->nsca) {  // every element's index: its m address less m_base, in elements
-    ZS_REQUIRE(as->m_lowest >= m_base,
-               "zs_adamset_run_sr: a segment's m lies below m_base (%#llx < %#llx)",
-               (unsigned long long)as->m_lowest, (unsigned long long)m_base);
-    ZS_REQUIRE(as->m_one_parity && ((as->m_lowest - m_base) & 1) == 0,
-               "zs_adamset_run_sr: a segment's m lies at an odd byte distance from m_base");
-  }
-  SrHP hp;
-  static_cast<HP&>(hp) = make_hp(h);
-  hp.k0 = key0;
-  hp.k1 = key1;
-  hp.m_base = m_base;
-  const bool split = as->p_dtype == ZS_BF16_SPLIT;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (coef)
-    return launch_update_tables<AdamSrKernels, true>(vec_table(as), sca_table(as), as->g_dtype,
-                                                     split, false, false, hp, coef, st);
-  return launch_update_tables<AdamSrKernels, false>(vec_table(as), sca_table(as), as->g_dtype,
-                                                    split, false, false, hp, nullptr, st);
+  const SrArgs sr = {m_base, key0, key1};
+  return adam_run("zs_adamset_run_sr", as, h, false, coef, &sr, stream);
 }
 
 int zs_adamset_sqnorm_partials(const zs_adamset* as, int64_t* n) {
@@ -2861,18 +2728,9 @@ int zs_adam_step_ex(float* p, uint16_t* p_bf16, const void* g, int g_dtype, floa
   a.vmax = nullptr;
   a.carry = carry;
   a.n = nv;
-  AdamSeg& b = t.seg[1];
-  b = a;
-  b.g = g ? reinterpret_cast<const void*>(ug + uint64_t(nv * gsz)) : nullptr;
-  b.master = p + nv;
-  b.master_out = p + nv;
-  b.p_out = p_bf16 ? reinterpret_cast<unsigned short*>(p_bf16 + nv) : nullptr;
-  b.m = m + nv;
-  b.v = v + nv;
-  b.carry = carry ? carry + nv : nullptr;
-  b.n = n - nv;
+  t.seg[1] = seg_tail(a, nv, n - nv, gsz, 4, 4);
   const int64_t vch = (nv + adam_chunk(false) - 1) / adam_chunk(false);
-  const int64_t sch = (b.n + kThreads - 1) / kThreads;
+  const int64_t sch = (n - nv + kThreads - 1) / kThreads;
   t.prefix[0] = 0;
   t.prefix[1] = vch;
   t.prefix[2] = 0;
@@ -2883,10 +2741,9 @@ int zs_adam_step_ex(float* p, uint16_t* p_bf16, const void* g, int g_dtype, floa
   hipLaunchKernelGGL(write_tables_kernel, dim3(1), dim3(1), 0, st, d, t);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) {
-    rc = launch_update_tables<AdamKernels, false>({d->seg, d->prefix, 1, vch},
-                                                  {d->seg + 1, d->prefix + 2, 1, sch}, g_dtype,
-                                                  false, false, carry != nullptr, make_hp(&h),
-                                                  nullptr, st);
+    rc = launch_update_tables<AdamFamily>({d->seg, d->prefix, 1, vch},
+                                          {d->seg + 1, d->prefix + 2, 1, sch}, g_dtype, false, false,
+                                          carry != nullptr, make_hp(&h), nullptr, st);
   }
   const hipError_t ef = hipFreeAsync(d, st);  // after the launches, in stream order
   if (e != hipSuccess)

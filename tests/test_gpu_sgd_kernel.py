@@ -1,4 +1,5 @@
-"""The fused SGD kernels (sgd_segments_kernel / sgd_scalar_kernel) through zero_amd.kernels.SgdSet.
+"""The fused SGD kernels (adam_segments_kernel / adam_scalar_kernel over SgdRule) through
+zero_amd.kernels.SgdSet.
 
 Every case runs 3 steps (the first with ``first`` set, so both branches of the momentum buffer
 run) and compares every array the kernels may write, whole (gaps between segments and the slack
