@@ -749,6 +749,10 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
 // when Adam was the only rule (the roofline label, the profiles and the ABI test key on it), so an
 // SGD launch shows under a profiler as adam_segments_kernel<SgdRule<true>, ...> -- like AdamSeg and
 // zs_adamset, which carry SGD sets too.  CLIP instances exist without the carry only.
+// GUARD (zs_adamset_run_guarded, zs_adamset_run_sr_guarded; with CLIP, the Adam families): a NaN
+// coefficient -- zs_clip_coef_guarded's mark of a non-finite gradient norm -- ends the workgroup
+// right after the coefficient's scalar load, so the skipped step changes nothing in memory.  The
+// coefficient is uniform (clip_coef's readfirstlane): one scalar compare and branch.
 //
 // Vector kernel: every segment 16-B aligned (8-B for bf16 arrays) with n % 4 == 0 (the host
 // splits tails off into the scalar table).  adam_groups() float4 groups per thread, lane-contiguous
@@ -763,12 +767,16 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
 // (zs_adamset_run_sr, over AdamSrRule, whose Hyper carries the keys and m_base): the same arrays,
 // stored with stochastic rounding.
 template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP,
-          typename ST = float>
+          typename ST = float, bool GUARD = false>
 __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
     const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
     int64_t total_chunks, typename Rule::Hyper hp, const float* __restrict__ coef_ptr) {
   static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
+  static_assert(CLIP || !GUARD, "the guard tests the clip coefficient");
   const float coef = clip_coef<CLIP>(coef_ptr);
+  if constexpr (GUARD) {
+    if (coef != coef) return;  // uniform: the step is skipped, nothing is loaded or stored
+  }
   int64_t seg = 0;
   if constexpr (LOADS_FIRST) {
     int64_t hi = nseg;
@@ -802,12 +810,17 @@ __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
 // Scalar kernel: one element per lane, 256-element chunks.  m and v as ST stores them: stochastic
 // (one draw for both, the chunk's uniform index i0 plus the lane), bf16 to nearest, or the rule's
 // own fp32 arrays.
-template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool CLIP, typename ST = float>
+template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool CLIP, typename ST = float,
+          bool GUARD = false>
 __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
     int64_t total_chunks, typename Rule::Hyper hp, const float* __restrict__ coef_ptr) {
   static_assert(!(CLIP && CARRY), "the clip coefficient is not defined under the ZeRO-1 carry");
+  static_assert(CLIP || !GUARD, "the guard tests the clip coefficient");
   const float coef = clip_coef<CLIP>(coef_ptr);
+  if constexpr (GUARD) {
+    if (coef != coef) return;  // uniform: the step is skipped, nothing is loaded or stored
+  }
   constexpr bool S16 = sizeof(ST) == 2;
   static_assert(!S16 || (Rule::kM && Rule::kV && !Rule::kX && !CARRY),
                 "bf16 state: Adam's m and v, no amsgrad, no carry");
@@ -989,6 +1002,30 @@ __global__ __launch_bounds__(64) void clip_coef_kernel(const float* __restrict__
   const float c = max_norm / (norm + 1e-6f);
   out2[0] = norm;
   out2[1] = c > 1.0f ? 1.0f : c;
+}
+
+// clip_coef_kernel plus the skip decision (zs_clip_coef_guarded), on the same lane: a norm that is
+// not finite -- NaN or inf, from any non-finite gradient element or from a sum of squares beyond
+// fp32 -- gives the quiet NaN 0x7FC00000 as the coefficient, which the GUARD update instances take
+// as "skip this step", and counts one skipped step (a plain load, add and store: the launches of a
+// stream are ordered).  A finite norm gives clip_coef_kernel's bits, and then the coefficient is
+// never NaN: max_norm is finite or inf and >= 0 and norm + 1e-6f > 0, so the quotient is a
+// number >= 0 or inf and the clamp a number in [0, 1].  NaN therefore means "skipped" and nothing
+// else.
+__global__ __launch_bounds__(64) void clip_coef_guarded_kernel(
+    const float* __restrict__ sumsq, double grad_div, float max_norm, float* __restrict__ out2,
+    unsigned long long* __restrict__ skipped) {
+#pragma clang fp contract(off)
+  if (threadIdx.x != 0) return;
+  const float norm = float(sqrt(double(*sumsq)) / grad_div);
+  const float c = max_norm / (norm + 1e-6f);
+  out2[0] = norm;
+  if ((__float_as_uint(norm) & 0x7F800000u) == 0x7F800000u) {  // NaN or inf
+    out2[1] = __uint_as_float(0x7FC00000u);
+    *skipped = *skipped + 1ull;
+  } else {
+    out2[1] = c > 1.0f ? 1.0f : c;
+  }
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1811,19 +1848,20 @@ static HP make_hp(const zs_adam_hparams* h) {
 // buffer), the type m and v are stored as, and whether instances with the flag set or with the
 // ZeRO-1 carry exist at all.  16-bit moments have neither: set_create refuses their vmax and carry
 // and adam_run their amsgrad, so the flag and the carry select nothing there.
-template <template <bool> class RuleOf, typename ST, bool VARIANTS>
+template <template <bool> class RuleOf, typename ST, bool VARIANTS, bool GUARDED = false>
 struct UpdateFamily {
   template <bool FLAG>
   using Rule = RuleOf<FLAG>;
   using State = ST;
   using Hyper = typename RuleOf<false>::Hyper;
   static constexpr bool kVariants = VARIANTS;
+  static constexpr bool kGuard = GUARDED;  // GUARD instances of its CLIP kernels exist
 };
 template <bool>
 using AdamSrRuleOf = AdamSrRule;
-using AdamFamily = UpdateFamily<AdamRule, float, true>;
-using AdamBf16Family = UpdateFamily<AdamRule, unsigned short, false>;  // zs_adamset_create_ex
-using AdamSrFamily = UpdateFamily<AdamSrRuleOf, SrBf16, false>;        // zs_adamset_run_sr
+using AdamFamily = UpdateFamily<AdamRule, float, true, true>;
+using AdamBf16Family = UpdateFamily<AdamRule, unsigned short, false, true>;  // zs_adamset_create_ex
+using AdamSrFamily = UpdateFamily<AdamSrRuleOf, SrBf16, false, true>;        // zs_adamset_run_sr
 using SgdFamily = UpdateFamily<SgdRule, float, true>;
 
 struct UpdateTable {  // a segment array with its chunk prefix
@@ -1860,12 +1898,13 @@ static void with_flag(bool b, Fn&& fn) {
 
 // Vector table (aligned, n % 4 == 0) then scalar table (tails, unaligned); the instance of family
 // F is picked by clip (a coefficient is given), split master, grad dtype, the rule's flag and
-// carry.  No instance has the carry with CLIP (the run paths refuse a set with one) or with fp32
-// gradients over the split master (set_create refuses one), and none is named here that F has not.
+// carry, and with CLIP by guard (the guarded runs of the Adam families).  No instance has the
+// carry with CLIP (the run paths refuse a set with one) or with fp32 gradients over the split
+// master (set_create refuses one), and none is named here that F has not.
 template <typename F>
 static int launch_update_tables(const UpdateTable& vec, const UpdateTable& sca, int g_dtype,
                                 bool split, bool flag, bool carry, const typename F::Hyper& hp,
-                                const float* coef, hipStream_t st) {
+                                const float* coef, hipStream_t st, bool guard = false) {
   using ST = typename F::State;
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
@@ -1879,13 +1918,21 @@ static int launch_update_tables(const UpdateTable& vec, const UpdateTable& sca, 
           auto launch = [&](auto f, auto c) {
             using Rule = typename F::template Rule<decltype(f)::value>;
             constexpr bool C = decltype(c)::value;
-            if constexpr (decltype(is_vec)::value)
-              hipLaunchKernelGGL(
-                  (adam_segments_kernel<Rule, GT, C, S, decltype(lf)::value, CLIP, ST>), grid,
-                  dim3(kThreads), 0, st, t.segs, t.prefix, t.nseg, t.chunks, hp, coef);
-            else
-              hipLaunchKernelGGL((adam_scalar_kernel<Rule, GT, C, S, CLIP, ST>), grid,
-                                 dim3(kThreads), 0, st, t.segs, t.prefix, t.nseg, t.chunks, hp, coef);
+            auto go = [&](auto gd) {
+              constexpr bool GD = decltype(gd)::value;
+              if constexpr (decltype(is_vec)::value)
+                hipLaunchKernelGGL(
+                    (adam_segments_kernel<Rule, GT, C, S, decltype(lf)::value, CLIP, ST, GD>), grid,
+                    dim3(kThreads), 0, st, t.segs, t.prefix, t.nseg, t.chunks, hp, coef);
+              else
+                hipLaunchKernelGGL((adam_scalar_kernel<Rule, GT, C, S, CLIP, ST, GD>), grid,
+                                   dim3(kThreads), 0, st, t.segs, t.prefix, t.nseg, t.chunks, hp,
+                                   coef);
+            };
+            // GUARD: with CLIP, without the carry, the Adam families only (the callers refuse the
+            // rest), so SGD gets no such instance
+            if constexpr (CLIP && !C && F::kGuard) with_flag(guard, go);
+            else go(no);
           };
           if constexpr (!F::kVariants) {
             launch(no, no);
@@ -1918,10 +1965,10 @@ static int launch_update_tables(const UpdateTable& vec, const UpdateTable& sca, 
 // refused a clipped run of a set with the carry.
 template <typename F>
 static int run_set(const zs_adamset* as, bool flag, const typename F::Hyper& hp, const float* coef,
-                   uintptr_t stream) {
+                   uintptr_t stream, bool guard = false) {
   return launch_update_tables<F>(vec_table(as), sca_table(as), as->g_dtype,
                                  as->p_dtype == ZS_BF16_SPLIT, flag, as->has_carry != 0, hp, coef,
-                                 reinterpret_cast<hipStream_t>(stream));
+                                 reinterpret_cast<hipStream_t>(stream), guard);
 }
 
 extern "C" {
@@ -2585,8 +2632,10 @@ struct SrArgs {
   uint32_t k0, k1;
 };
 static int adam_run(const char* fn, const zs_adamset* as, const zs_adam_hparams* h, bool need_coef,
-                    const float* coef, const SrArgs* sr, uintptr_t stream) {
+                    const float* coef, const SrArgs* sr, uintptr_t stream, bool guard = false) {
   ZS_REQUIRE(as && h && (coef || !need_coef), "%s: NULL argument", fn);
+  ZS_REQUIRE(!guard || !as->sgd, "%s: the guarded update is Adam's (the set was made by "
+             "zs_sgdset_create)", fn);
   ZS_REQUIRE(!sr || (!as->sgd && as->state_dtype == ZS_BF16),
              "%s: stochastic rounding needs an Adam set with ZS_BF16 state (zs_adamset_create_ex)",
              fn);
@@ -2598,8 +2647,8 @@ static int adam_run(const char* fn, const zs_adamset* as, const zs_adam_hparams*
   ZS_REQUIRE(!ams || as->has_vmax || (as->nvec + as->nsca) == 0, "%s: amsgrad needs vmax segments",
              fn);
   if (!sr) {
-    if (bf16_state) return run_set<AdamBf16Family>(as, false, make_hp(h), coef, stream);
-    return run_set<AdamFamily>(as, ams, make_hp(h), coef, stream);
+    if (bf16_state) return run_set<AdamBf16Family>(as, false, make_hp(h), coef, stream, guard);
+    return run_set<AdamFamily>(as, ams, make_hp(h), coef, stream, guard);
   }
   if (as->nvec + as->nsca) {  // every element's index: its m address less m_base, in elements
     ZS_REQUIRE(as->m_lowest >= sr->m_base, "%s: a segment's m lies below m_base (%#llx < %#llx)", fn,
@@ -2612,7 +2661,7 @@ static int adam_run(const char* fn, const zs_adamset* as, const zs_adam_hparams*
   hp.k0 = sr->k0;
   hp.k1 = sr->k1;
   hp.m_base = sr->m_base;
-  return run_set<AdamSrFamily>(as, false, hp, coef, stream);
+  return run_set<AdamSrFamily>(as, false, hp, coef, stream, guard);
 }
 
 int zs_adamset_run(const zs_adamset* as, const zs_adam_hparams* h, uintptr_t stream) {
@@ -2628,6 +2677,17 @@ int zs_adamset_run_sr(const zs_adamset* as, const zs_adam_hparams* h, const floa
                       uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream) {
   const SrArgs sr = {m_base, key0, key1};
   return adam_run("zs_adamset_run_sr", as, h, false, coef, &sr, stream);
+}
+
+int zs_adamset_run_guarded(const zs_adamset* as, const zs_adam_hparams* h, const float* coef,
+                           uintptr_t stream) {
+  return adam_run("zs_adamset_run_guarded", as, h, true, coef, nullptr, stream, true);
+}
+
+int zs_adamset_run_sr_guarded(const zs_adamset* as, const zs_adam_hparams* h, const float* coef,
+                              uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream) {
+  const SrArgs sr = {m_base, key0, key1};
+  return adam_run("zs_adamset_run_sr_guarded", as, h, true, coef, &sr, stream, true);
 }
 
 int zs_adamset_sqnorm_partials(const zs_adamset* as, int64_t* n) {
@@ -2691,6 +2751,19 @@ int zs_clip_coef(const float* sumsq, double grad_div, double max_norm, float* ou
   ZS_REQUIRE(max_norm >= 0.0, "zs_clip_coef: max_norm must be >= 0 (infinity allowed), not NaN");
   hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(64), 0,
                      reinterpret_cast<hipStream_t>(stream), sumsq, grad_div, float(max_norm), out2);
+  ZS_HIP(hipGetLastError());
+  return ZS_OK;
+}
+
+int zs_clip_coef_guarded(const float* sumsq, double grad_div, double max_norm, float* out2,
+                         uint64_t* skipped, uintptr_t stream) {
+  ZS_REQUIRE(sumsq && out2 && skipped, "zs_clip_coef_guarded: NULL argument");
+  ZS_REQUIRE(grad_div > 0.0, "zs_clip_coef_guarded: grad_div must be > 0");
+  ZS_REQUIRE(max_norm >= 0.0,
+             "zs_clip_coef_guarded: max_norm must be >= 0 (infinity allowed), not NaN");
+  hipLaunchKernelGGL(clip_coef_guarded_kernel, dim3(1), dim3(64), 0,
+                     reinterpret_cast<hipStream_t>(stream), sumsq, grad_div, float(max_norm), out2,
+                     reinterpret_cast<unsigned long long*>(skipped));
   ZS_HIP(hipGetLastError());
   return ZS_OK;
 }

@@ -39,6 +39,7 @@ EXPORTED = (
     "zs_adamset_stats", "zs_adam_step", "zs_adam_step_ex",
     "zs_adamset_sqnorm_partials", "zs_adamset_grad_sqnorm", "zs_sqnorm_reduce", "zs_clip_coef",
     "zs_adamset_run_clipped", "zs_adamset_run_sr", "zs_sr_keys", "zs_sr_bits",
+    "zs_clip_coef_guarded", "zs_adamset_run_guarded", "zs_adamset_run_sr_guarded",
     "zs_sgd_hparams_init", "zs_sgdset_create", "zs_sgdset_run",
     "zs_comm_unique_id", "zs_comm_init", "zs_comm_destroy", "zs_reduce_scatter", "zs_all_gather",
     "zs_all_reduce", "zs_reduce", "zs_broadcast", "zs_reduce_group", "zs_broadcast_group", "zs_all_gather_group", "zs_reduce_scatter_group",
@@ -143,6 +144,10 @@ _SIGS = {
     "zs_adamset_run_clipped": ([_P, ctypes.POINTER(AdamHParams), _P, _U], ctypes.c_int),
     "zs_adamset_run_sr": ([_P, ctypes.POINTER(AdamHParams), _P, ctypes.c_uint64, ctypes.c_uint32,
                            ctypes.c_uint32, _U], ctypes.c_int),
+    "zs_clip_coef_guarded": ([_P, ctypes.c_double, ctypes.c_double, _P, _P, _U], ctypes.c_int),
+    "zs_adamset_run_guarded": ([_P, ctypes.POINTER(AdamHParams), _P, _U], ctypes.c_int),
+    "zs_adamset_run_sr_guarded": ([_P, ctypes.POINTER(AdamHParams), _P, ctypes.c_uint64,
+                                   ctypes.c_uint32, ctypes.c_uint32, _U], ctypes.c_int),
     "zs_sr_keys": ([ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32),
                     ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
     "zs_sr_bits": ([ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,

@@ -20,8 +20,8 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import (check_bf16_state_group, check_state_dtype, check_state_rounding,
-                      owner_range)
+from ._update import (check_bf16_state_group, check_max_grad_norm, check_skip_nonfinite,
+                      check_state_dtype, check_state_rounding, owner_range)
 from .engine import ShardEngine
 from .training_utils.utils import get
 
@@ -80,7 +80,8 @@ class ShardedOptimizerBase:
                  overlap: bool = False, overlap_bucket_mb: float = 64.0, master: str = "split",
                  arena: str = "flat", grad_comm: str | None = None,
                  max_grad_norm: float | None = None, state_dtype=None,
-                 state_rounding: str | None = None, state_seed: int = 0):
+                 state_rounding: str | None = None, state_seed: int = 0,
+                 skip_nonfinite: bool = False):
         if arena not in ("flat", "buckets", "auto"):
             raise ValueError(f"arena must be 'flat', 'buckets' or 'auto' (got {arena!r})")
         # the moments' dtype: None / torch.float32, or torch.bfloat16 (opt-in: exp_avg and
@@ -110,6 +111,10 @@ class ShardedOptimizerBase:
             self._clip_unsupported = f"layout={layout!r} (it runs on the bucket arena)"
         self._check_clip()
         self._kind = optimizer_kind(optimizer)
+        # skip_nonfinite (with max_grad_norm; Adam): a step whose gradient norm is not finite is
+        # skipped on the device — nothing in device memory changes, the host proceeds as for any
+        # step; refused here, on every rank and before anything collective
+        self.skip_nonfinite = check_skip_nonfinite(skip_nonfinite, max_grad_norm, self._kind)
         for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
             hpd = group_hparams(self._kind, group, optimizer)
             if bf16_state and self._kind == "adam":
@@ -212,10 +217,11 @@ class ShardedOptimizerBase:
         """``max_grad_norm`` is None or a limit >= 0 (infinity: report the norm, clip nothing) on
         a configuration that supports clipping; ValueError otherwise."""
         m = self.max_grad_norm
+        check_max_grad_norm(m)
         if m is None:
+            if getattr(self, "skip_nonfinite", False):
+                raise ValueError("zero_amd: skip_nonfinite=True needs max_grad_norm")
             return
-        if isinstance(m, bool) or not isinstance(m, (int, float)) or not m >= 0:
-            raise ValueError(f"max_grad_norm must be None or a number >= 0 (got {m!r})")
         if self._clip_unsupported is not None:
             raise ValueError("zero_amd: max_grad_norm is not supported with "
                              + self._clip_unsupported)
@@ -238,6 +244,14 @@ class ShardedOptimizerBase:
     def last_norm_bytes(self) -> int:
         """Gradient bytes the last step's norm pass read (0 without clipping)."""
         return 0 if self.engine is None else self.engine.last_norm_bytes
+
+    @property
+    def skipped_steps(self):
+        """0-d int64 device tensor (``skip_nonfinite``): the steps skipped so far for a non-finite
+        gradient norm; valid in stream order after step(), not checkpointed; None before the
+        first step and without ``skip_nonfinite``."""
+        clip = None if self.engine is None else self.engine.clip
+        return None if clip is None or clip.skipped is None else clip.skipped[0]
 
     def _flat(self) -> bool:
         """The flat parameter arena: the reference layout (the drop-in), or the balanced Layout F
@@ -328,6 +342,7 @@ class ShardedOptimizerBase:
             for gi in range(len(self._groups)):
                 check_bf16_state_group(self._hparams_of(gi), self.state_rounding)
         self.engine.max_grad_norm = self.max_grad_norm
+        self.engine.skip_nonfinite = self.skip_nonfinite
         had_vmax = self.engine.vmax is not None
         grads = [p.grad for p in self.params]
         seen = self._validated

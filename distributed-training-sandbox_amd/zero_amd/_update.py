@@ -7,6 +7,8 @@ of how gradients reach the shard: ``ShardEngine`` (engine.py, flat.py) is a core
 ``zero3.ShardedOptimizer`` holds one over its chunk arena.  Callers hand it ``zs_adam_seg`` rows
 (include/zero_amd.h) whose pointer columns they filled; the core fills the state columns, cuts the
 rows into (group, step key, carry multiplier) parts and launches one AdamSet / SgdSet per part.
+``GradClip`` is global gradient-norm clipping around those launches (and the skip of a step whose
+norm is not finite), shared by the same two callers.
 """
 from __future__ import annotations
 
@@ -281,17 +283,22 @@ class UpdateCore:
         """Free replaced segment tables; call only after the device has been synchronised."""
         self.retired.clear()
 
-    def launch(self, aset, hp, stream, coef=None) -> None:
-        """Run ``aset`` (``coef``: with the clip coefficient, a device scalar's address); with
-        ``timing_events`` on, between two HIP events."""
+    def launch(self, aset, hp, stream, coef=None, guard=False) -> None:
+        """Run ``aset`` (``coef``: with the clip coefficient, a device scalar's address; ``guard``:
+        a NaN coefficient skips the step on the device); with ``timing_events`` on, between two
+        HIP events."""
         ev = self.timing_events
         if ev is not None:
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record(stream)
+        if guard and coef is None:
+            raise ValueError("zero_amd: the guarded update tests the clip coefficient")
         if self.state_rounding == "stochastic":
-            aset.run_sr(hp, self.m.data_ptr(), hp.sr_keys, stream, coef=coef)
+            aset.run_sr(hp, self.m.data_ptr(), hp.sr_keys, stream, coef=coef, guard=guard)
         elif coef is None:
             aset.run(hp, stream)
+        elif guard:
+            aset.run_guarded(hp, coef, stream)
         else:
             aset.run_clipped(hp, coef, stream)
         if ev is not None:
@@ -335,3 +342,111 @@ class UpdateCore:
                 aset.set_grads(g, stream)
             self.launch(aset, hp, stream)
         return parts
+
+
+def check_max_grad_norm(m) -> None:
+    """``max_grad_norm`` is None or a number >= 0 (infinity: report the norm, clip nothing);
+    ValueError otherwise."""
+    if m is None:
+        return
+    if isinstance(m, bool) or not isinstance(m, (int, float)) or not m >= 0:
+        raise ValueError(f"max_grad_norm must be None or a number >= 0 (got {m!r})")
+
+
+def check_skip_nonfinite(skip_nonfinite, max_grad_norm, kind: str) -> bool:
+    """``skip_nonfinite`` as a bool; ValueError for what it cannot be combined with: no
+    ``max_grad_norm`` (the norm is what is tested; infinity gives a pure skip) and SGD (its "first
+    step" is told from the host's count, which a skipped first step would advance: the momentum
+    buffer would be born wrong under dampening)."""
+    if not skip_nonfinite:
+        return False
+    if max_grad_norm is None:
+        raise ValueError("zero_amd: skip_nonfinite=True tests the gradient norm: it needs "
+                         "max_grad_norm (float('inf') skips without clipping)")
+    if kind == "sgd":
+        raise ValueError("zero_amd: skip_nonfinite=True is not supported with torch.optim.SGD "
+                         "(a skipped first step would be taken for the momentum buffer's birth)")
+    return True
+
+
+class GradClip:
+    """Global gradient-norm clipping around an ``UpdateCore``'s launches (clip_grad_norm_ between
+    the reduction and the update): what the ZeRO-1/2 flat arena and ZeRO-3's update
+    mode share.  The caller collects the step's parts as ``(aset, hp, gptr or None)``
+    (``run_parts(defer=)``) and calls, in stream order, ``prepare`` (host only), ``norm`` (each
+    set's sum of squares into its slice of one float64 partials tensor), ``reduce`` (all partials
+    into the fp32 scalar ``sumsq``, which the caller all-reduces at world size > 1), ``coef``
+    ({norm, coefficient} into ``out``) and ``run`` (the update with the coefficient).  How the
+    streams are ordered around the all-reduce is the caller's.  The gradient is never rewritten and
+    the host never waits.
+
+    ``guard`` (``skip_nonfinite``): the coefficient comes from zs_clip_coef_guarded — a non-finite
+    norm gives a NaN coefficient and counts in ``skipped`` — and every launch is the guarded one,
+    which a NaN coefficient ends before its first load."""
+
+    def __init__(self, core: UpdateCore, guard: bool = False):
+        self.core, self.guard = core, bool(guard)
+        dev = core.device
+        self.partials = None  # float64, sized on first use
+        self._key, self._off = None, np.zeros(1, np.int64)
+        self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.out = torch.zeros(2, dtype=torch.float32, device=dev)  # {norm, coef}
+        self.skipped = torch.zeros(1, dtype=torch.int64, device=dev) if guard else None
+        self.norm_events = None  # optional list of (start, end, bytes) per norm pass
+        self.last_norm_bytes = 0
+
+    def prepare(self, deferred) -> None:
+        """Each collected set's slice of the partials tensor: sized on first use, regrown only when
+        the list of sets changes (the old one is retired with the core's tables: queued kernels
+        may still write it)."""
+        key = tuple((id(aset), aset.sqnorm_partials) for aset, _, _ in deferred)
+        if self._key != key:
+            self._off = np.concatenate([[0], np.cumsum([n for _, n in key])]).astype(np.int64)
+            total = int(self._off[-1])
+            buf = self.partials
+            if buf is None or buf.numel() < total:
+                if buf is not None:
+                    self.core.retired.append(buf)
+                self.partials = torch.zeros(max(total, 1), dtype=torch.float64,
+                                            device=self.core.device)
+            self._key = key
+        self.last_norm_bytes = 0
+
+    def norm(self, deferred, first, stream) -> None:
+        """Stage 1 for ``deferred[first:]``: bind the gradients where needed, then the sum of
+        squares into the set's slice."""
+        base = self.partials.data_ptr()
+        for k in range(first, len(deferred)):
+            aset, _, g = deferred[k]
+            if g is not None:
+                aset.set_grads(g, stream)
+            ev = None
+            if self.norm_events is not None:
+                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                ev[0].record(stream)
+            aset.grad_sqnorm(base + int(self._off[k]) * 8, stream)
+            nb = aset.grad_bytes  # what the pass reads
+            if ev is not None:
+                ev[1].record(stream)
+                self.norm_events.append((ev[0], ev[1], nb))
+            self.last_norm_bytes += nb
+
+    def reduce(self, stream) -> None:
+        """Stage 2: one fixed-order reduction of all partials into ``sumsq`` (no sets: 0)."""
+        from .kernels import sqnorm_reduce
+
+        sqnorm_reduce(self.partials, int(self._off[-1]), self.sumsq, stream)
+
+    def coef(self, max_norm, stream) -> None:
+        """Stage 3, after the caller's all-reduce of ``sumsq``: {norm, coefficient} of the gradient
+        averaged over the core's world size."""
+        from .kernels import clip_coef
+
+        clip_coef(self.sumsq, float(self.core.ws), float(max_norm), self.out, stream,
+                  skipped=self.skipped if self.guard else None)
+
+    def run(self, deferred, first, last, stream) -> None:
+        """Stage 4 for ``deferred[first:last]``: the update with the coefficient."""
+        coef = self.out.data_ptr() + 4
+        for aset, hp, _ in deferred[first:last]:
+            self.core.launch(aset, hp, stream, coef, guard=self.guard)

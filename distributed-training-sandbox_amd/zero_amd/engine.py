@@ -354,10 +354,17 @@ class ShardEngine(UpdateCore):
         self.copy_events = None    # optional list of (kind, start, end, bytes) per pack / unpack
         self.capture_reduced = None  # optional tensor (stream-long): the reduced grads, for checks
         # global gradient-norm clipping (flat arena only; flat.py _clip_*): the limit of this step
-        # (None = off), bytes the last step's norm pass read, and the device results
+        # (None = off), bytes the last step's norm pass read, and the stages with their device
+        # results (_update.GradClip, made by the first clipped step; skip_nonfinite: its guard)
         self.max_grad_norm = None
         self.last_norm_bytes = 0
-        self.clip_out = None  # fp32 {norm, coef}, allocated by the first clipped step
+        self.skip_nonfinite = False
+        self.clip = None
+
+    @property
+    def clip_out(self):
+        """fp32 {norm, coef} of the last clipped step (None before the first)."""
+        return None if self.clip is None else self.clip.out
 
     # ------------------------------------------------------------------------------------------
     def _piece_cols(self):

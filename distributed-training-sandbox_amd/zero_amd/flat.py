@@ -48,6 +48,7 @@ import torch
 
 from . import _lib
 from ._hooks import WeakCall
+from ._update import GradClip
 from .comm import StreamEvent
 from .engine import ALIGN_ELEMS, ShardEngine, _ptr
 from .kernels import check_extents, check_extents_enabled, copy_direct
@@ -340,67 +341,40 @@ class FlatEngine(ShardEngine):
     # Global gradient-norm clipping (clip_grad_norm_ between the reduction and the update): one
     # read-only pass over the reduced gradients the collected Adam sets are bound to, a scalar
     # all-reduce, and the coefficient read from device memory by the update.  The gradient is
-    # never rewritten and the host never waits.
+    # never rewritten and the host never waits.  The stages are _update.GradClip's (shared with
+    # ZeRO-3); what stands here is this engine's ordering of them around its rounds.
     def _clip_prepare(self, deferred):
-        """Each collected set's slice of the partials tensor (sized on first use, regrown only
-        when the list of sets changes) and the device scalars."""
-        key = tuple((id(aset), aset.sqnorm_partials) for aset, _, _ in deferred)
-        if getattr(self, "_clip_key", None) != key:
-            counts = [n for _, n in key]
-            self._clip_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-            total = int(self._clip_off[-1])
-            buf = getattr(self, "clip_partials", None)
-            if buf is None or buf.numel() < total:
-                if buf is not None:  # queued kernels may still write it
-                    self.retired.append(buf)
-                self.clip_partials = torch.zeros(max(total, 1), dtype=torch.float64,
-                                                 device=self.device)
-            self._clip_key = key
-        if self.clip_out is None:
-            self.clip_sumsq = torch.zeros(1, dtype=torch.float32, device=self.device)
-            self.clip_out = torch.zeros(2, dtype=torch.float32, device=self.device)
+        """The stages' object (made by the first clipped step) and each collected set's slice of
+        its partials tensor."""
+        if self.clip is None:
+            self.clip = GradClip(self, guard=self.skip_nonfinite)
             self.ev_clip = (StreamEvent(), StreamEvent())  # around the norm's scalar all-reduce
+        self.clip.norm_events = self.norm_events
+        self.clip.prepare(deferred)
 
     def _clip_norm(self, deferred, first, stream):
-        """Stage 1 for ``deferred[first:]``: bind the gradients where needed, then the sum of
-        squares into the set's slice."""
-        base = self.clip_partials.data_ptr()
-        for k in range(first, len(deferred)):
-            aset, _, g = deferred[k]
-            if g is not None:
-                aset.set_grads(g, stream)
-            ev = None
-            if self.norm_events is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record(stream)
-            aset.grad_sqnorm(base + int(self._clip_off[k]) * 8, stream)
-            nb = aset.grad_bytes  # what the pass reads
-            if ev is not None:
-                ev[1].record(stream)
-                self.norm_events.append((ev[0], ev[1], nb))
-            self.last_norm_bytes += nb
+        """Stage 1 for ``deferred[first:]``."""
+        self.clip.norm(deferred, first, stream)
+        self.last_norm_bytes = self.clip.last_norm_bytes
 
     def _clip_coef(self, deferred, stream):
         """Stages 2 and 3: one fixed-order reduction of all partials, the scalar all-reduce on the
         communication stream (ordered by events on both sides; a rank that owns nothing
         contributes 0 and still takes part), the coefficient."""
-        from .kernels import clip_coef, sqnorm_reduce
-
-        sqnorm_reduce(self.clip_partials, int(self._clip_off[-1]), self.clip_sumsq, stream)
+        clip = self.clip
+        clip.reduce(stream)
         if self.ws > 1:
             cs = self.comm_stream
             self.ev_clip[0].record(stream)
             cs.wait_event(self.ev_clip[0])
-            self.comm.all_reduce(self.clip_sumsq, cs)
+            self.comm.all_reduce(clip.sumsq, cs)
             self.ev_clip[1].record(cs)
             stream.wait_event(self.ev_clip[1])
-        clip_coef(self.clip_sumsq, float(self.ws), float(self.max_grad_norm), self.clip_out, stream)
+        clip.coef(self.max_grad_norm, stream)
 
     def _clip_run(self, deferred, first, last, stream):
         """Stage 4 for ``deferred[first:last]``: the update with the coefficient."""
-        coef = self.clip_out.data_ptr() + 4
-        for aset, hp, _ in deferred[first:last]:
-            self.launch(aset, hp, stream, coef)
+        self.clip.run(deferred, first, last, stream)
 
     # ------------------------------------------------------------------------------------------
     def _reduce_round(self, rd: _Round, cs):

@@ -4,7 +4,8 @@
 ``copy_direct`` — the same copy with the segments in the kernel arguments (no table to keep).
 ``AdamSet``  — one launch of the fused Adam/AdamW update over a list of segments; its
 ``grad_sqnorm`` / ``run_clipped`` with ``sqnorm_reduce`` and ``clip_coef`` are global-norm clipping;
-``run_sr`` with ``sr_keys`` stores bf16 moments with stochastic rounding.
+``run_guarded`` (``run_sr(guard=True)``) with ``clip_coef(skipped=)`` skips a step whose norm is not
+finite; ``run_sr`` with ``sr_keys`` stores bf16 moments with stochastic rounding.
 ``SgdSet``   — the same tables with torch.optim.SGD's update (momentum, Nesterov); ``sgd_hparams``.
 ``adam_step`` — the same update over one contiguous range (zs_adam_step_ex; no table to keep).
 
@@ -221,14 +222,22 @@ class AdamSet:
         ptr = coef if isinstance(coef, int) else coef.data_ptr()
         _lib.call("zs_adamset_run_clipped", self._h, ctypes.byref(hp), ptr, stream_handle(stream))
 
-    def run_sr(self, hp: AdamHParams, m_base: int, keys, stream, coef=None) -> None:
+    def run_guarded(self, hp: AdamHParams, coef, stream) -> None:
+        """``run_clipped``, except that a NaN ``coef`` (``clip_coef(..., skipped=)``'s mark of a
+        non-finite norm) skips the step: nothing is read or written (zs_adamset_run_guarded)."""
+        ptr = coef if isinstance(coef, int) else coef.data_ptr()
+        _lib.call("zs_adamset_run_guarded", self._h, ctypes.byref(hp), ptr, stream_handle(stream))
+
+    def run_sr(self, hp: AdamHParams, m_base: int, keys, stream, coef=None, guard=False) -> None:
         """``run`` (``coef`` None) or ``run_clipped`` of a set with ``ZS_BF16`` state, the moments
         stored with stochastic rounding (zs_adamset_run_sr): ``keys`` = ``sr_keys(seed, step)``,
         ``m_base`` the address of element 0 of the moment array the ``m`` column points into (only
-        subtracted from, never read)."""
+        subtracted from, never read).  ``guard``: as ``run_guarded`` (zs_adamset_run_sr_guarded; it
+        needs ``coef``)."""
         ptr = None if coef is None else coef if isinstance(coef, int) else coef.data_ptr()
-        _lib.call("zs_adamset_run_sr", self._h, ctypes.byref(hp), ptr, int(m_base), int(keys[0]),
-                  int(keys[1]), stream_handle(stream))
+        _lib.call("zs_adamset_run_sr_guarded" if guard else "zs_adamset_run_sr", self._h,
+                  ctypes.byref(hp), ptr, int(m_base), int(keys[0]), int(keys[1]),
+                  stream_handle(stream))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -281,6 +290,11 @@ class SgdSet(AdamSet):
     def run_clipped(self, hp, coef, stream) -> None:
         self.run(hp, stream, coef=coef)
 
+    def run_guarded(self, hp, coef, stream) -> None:
+        raise _lib.ZeroAmdError("zs_adamset_run_guarded", _lib.ZS_ERR_INVALID,
+                                "the guarded update is Adam's (SGD tells its first step from the "
+                                "host's count, which a skipped step would advance)")
+
 
 def sqnorm_reduce(partials, n: int, sumsq, stream) -> None:
     """``sumsq`` (one fp32 device element) = the fp32 rounding of the double sum of the first ``n``
@@ -290,13 +304,20 @@ def sqnorm_reduce(partials, n: int, sumsq, stream) -> None:
               stream_handle(stream))
 
 
-def clip_coef(sumsq, grad_div: float, max_norm: float, out2, stream) -> None:
+def clip_coef(sumsq, grad_div: float, max_norm: float, out2, stream, skipped=None) -> None:
     """``out2`` (two fp32 device elements) = {norm, coef}: the L2 norm of the averaged gradient
     from the raw sum of squares ``sumsq`` and clip_grad_norm_'s clamped coefficient
-    (zs_clip_coef)."""
+    (zs_clip_coef).  ``skipped`` (one 8-byte integer device element): a non-finite norm gives the
+    quiet NaN as the coefficient — the guarded runs' "skip this step" — and adds one to
+    ``skipped`` (zs_clip_coef_guarded)."""
     assert out2.numel() >= 2 and out2.dtype.itemsize == 4 and sumsq.dtype.itemsize == 4
-    _lib.call("zs_clip_coef", sumsq.data_ptr(), float(grad_div), float(max_norm), out2.data_ptr(),
-              stream_handle(stream))
+    if skipped is None:
+        _lib.call("zs_clip_coef", sumsq.data_ptr(), float(grad_div), float(max_norm),
+                  out2.data_ptr(), stream_handle(stream))
+        return
+    assert skipped.numel() >= 1 and skipped.dtype.itemsize == 8
+    _lib.call("zs_clip_coef_guarded", sumsq.data_ptr(), float(grad_div), float(max_norm),
+              out2.data_ptr(), skipped.data_ptr(), stream_handle(stream))
 
 
 def adam_step(p, g, m, v, *, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,

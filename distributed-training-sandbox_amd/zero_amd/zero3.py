@@ -69,8 +69,9 @@ from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
 from ._sharded import group_hparams, optimizer_kind
-from ._update import (UpdateCore, check_bf16_state_group, check_params, check_state_dtype,
-                      check_state_rounding, owner_range)
+from ._update import (GradClip, UpdateCore, check_bf16_state_group, check_max_grad_norm,
+                      check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
+                      owner_range)
 from .comm import STREAM_SYNC, RcclComm, Sync, comm_stream, sync_kind, zs_dtype
 from .engine import ALIGN_ELEMS
 from .kernels import AdamSet, SgdSet, stream_handle
@@ -1838,7 +1839,20 @@ class ShardedOptimizer:
                  gather_wave: int = GATHER_WAVE, side_stream: bool = True,
                  stream_sync: str = STREAM_SYNC, grad_accumulation: bool = False,
                  accumulation_dtype=None, state_dtype=None, state_rounding: str | None = None,
-                 state_seed: int = 0):
+                 state_seed: int = 0, max_grad_norm: float | None = None,
+                 skip_nonfinite: bool = False):
+        # global gradient-norm clipping inside step() (update mode; None = off): a plain attribute,
+        # re-checked at every step().  skip_nonfinite (with it; Adam): a step whose gradient norm
+        # is not finite is skipped on the device.  Both are refused here where they
+        # do not apply, on every rank and before anything collective
+        self.update = bool(update)
+        self.max_grad_norm = max_grad_norm
+        self._check_clip()
+        self.skip_nonfinite = check_skip_nonfinite(skip_nonfinite, max_grad_norm,
+                                                   optimizer_kind(optimizer))
+        self._clip = None  # the stages and their device results, made by the first clipped step
+        self._clip_syncs = None
+        self._span_end = None
         # state_dtype=torch.bfloat16 (update mode, Adam without amsgrad): exp_avg and exp_avg_sq are
         # stored in bf16, the arithmetic stays fp32; None / torch.float32: fp32.
         # state_rounding="stochastic" (None / "nearest": as before): they are stored with
@@ -1890,8 +1904,9 @@ class ShardedOptimizer:
         self.local_param_indices = list(range(*owner_range(len(self.params), world_size, rank)))
         self.local_params = set(self.params[i] for i in self.local_param_indices)
         self.world_size, self.rank = world_size, rank
-        self.update = bool(update)
         self._sync = sync
+        self._last_norm_bytes = 0
+        self._norm_events = None
         # grad_comm="bf16" (update mode, fp32 params): full grads are converted to bf16 before the
         # reduce-scatter, so the exchange moves 2 B per element; opt-in
         if grad_comm not in (None, "bf16"):
@@ -1962,6 +1977,54 @@ class ShardedOptimizer:
         self._fast_sig, self._fast_sets = {}, {}
         self._step_shared = self._step_shared_sig = None
         self._expose_state()
+
+    def _check_clip(self):
+        """``max_grad_norm`` is None or a limit >= 0 (infinity: report the norm, clip nothing) in
+        update mode; ValueError otherwise."""
+        m = self.max_grad_norm
+        check_max_grad_norm(m)
+        if m is None:
+            if getattr(self, "skip_nonfinite", False):
+                raise ValueError("zero_amd: skip_nonfinite=True needs max_grad_norm")
+            return
+        if not self.update:
+            raise ValueError("zero_amd: max_grad_norm applies to update mode (reference mode "
+                             "never updates: zero3.py:150-153 drops every gradient)")
+
+    @property
+    def last_grad_norm(self):
+        """0-d fp32 device tensor: the L2 norm of the averaged gradient the last clipped step saw
+        (clip_grad_norm_'s return value; the same bits on every rank); valid in stream order after
+        step(), overwritten by the next step; None before the first clipped step."""
+        return None if self._clip is None else self._clip.out[0]
+
+    @property
+    def last_clip_coef(self):
+        """0-d fp32 device tensor: min(1, max_grad_norm / (last_grad_norm + 1e-6)), as above (NaN:
+        ``skip_nonfinite`` skipped the step)."""
+        return None if self._clip is None else self._clip.out[1]
+
+    @property
+    def last_norm_bytes(self) -> int:
+        """Gradient bytes the last step's norm pass read (0 without clipping)."""
+        return self._last_norm_bytes
+
+    @property
+    def skipped_steps(self):
+        """0-d int64 device tensor (``skip_nonfinite``): the steps skipped so far for a non-finite
+        gradient norm; valid in stream order after step(), not checkpointed; None before the
+        first step and without ``skip_nonfinite``."""
+        clip = self._clip
+        return None if clip is None or clip.skipped is None else clip.skipped[0]
+
+    @property
+    def norm_events(self):
+        """Optional list of (start, end, bytes) around each norm pass (the clip stages')."""
+        return self._norm_events
+
+    @norm_events.setter
+    def norm_events(self, events):
+        self._norm_events = events
 
     @property
     def timing_events(self):
@@ -2170,15 +2233,29 @@ class ShardedOptimizer:
         sig = (idx.tobytes(), core.vmax is None) if self.world_size > 1 else None
         fast = self._fast_sets.get(acc) if uniform and sig is not None \
             and self._fast_sig.get(acc) == sig else None
+        # gradient clipping: both paths collect their launches as (aset, hp, None) instead
+        deferred = None if self.max_grad_norm is None else []
         if fast is not None:  # the same parameters as last step, one step count: cached sets
             for gi, aset in fast:
-                core.launch(aset, core.make_hp(hps[gi], int(steps[0])), cur)
+                hp = core.make_hp(hps[gi], int(steps[0]))
+                if deferred is None:
+                    core.launch(aset, hp, cur)
+                else:
+                    deferred.append((aset, hp, None))
         elif len(idx):
             used = core.run_parts(acc, self._adam_rows(idx, acc), idx, hps.__getitem__, cur,
-                                  new_set=lambda rows: self._new_set(rows, acc))
+                                  new_set=lambda rows: self._new_set(rows, acc), defer=deferred)
             # one set per param group and one step count: next step takes the cached sets
             self._fast_sig[acc] = sig if uniform else None
             self._fast_sets[acc] = used if uniform else None
+        self._last_norm_bytes = 0
+        if deferred is not None:  # (every rank, also one that updates nothing: the all-reduce)
+            if done is not None and self.runtime.stream is not None:
+                # the communication_time span ends behind the last gradient collective, not
+                # behind the norm's all-reduce (which waits for the norm pass)
+                self._span_end = torch.cuda.Event(enable_timing=True)
+                self._span_end.record(self.runtime.stream)
+            self._clip_update(deferred, cur)
         if self._kind == "sgd":  # torch's SGD keeps no step: the buffer appears after the first
             self._expose_sgd(idx)
         elif uniform:  # torch's state['step'] (a CPU tensor): one shared tensor, updated in place
@@ -2205,12 +2282,51 @@ class ShardedOptimizer:
         red.reset()
         return done
 
+    def _clip_update(self, deferred, cur):
+        """The collected launches of a clipped step (the four stages of
+        _update.GradClip): the norm over the chunks this rank updates — whatever the sets are
+        bound to: _G, the fp32 accumulation arena, the local grads at ws == 1; a slot's ``ln``
+        elements only — one scalar all-reduce, the coefficient, the update.
+
+        The all-reduce goes where this optimizer's other collectives go: the side stream, between
+        a record on the compute stream (behind the reduction of the partials) and a wait on it
+        (before the coefficient), or, in single-stream mode, the compute stream itself.  On that
+        stream it follows the step's last gradient reduce-scatter, which the compute stream has
+        waited for before the norm pass, and precedes every all-gather of the next iteration,
+        which end_iteration and the forward enqueue after step() has enqueued this.  Every rank
+        calls it on every clipped step, with sumsq == 0 when it updates nothing."""
+        clip = self._clip
+        if clip is None:
+            clip = self._clip = GradClip(self._core, guard=self.skip_nonfinite)
+        clip.norm_events = self._norm_events
+        clip.prepare(deferred)
+        clip.norm(deferred, 0, cur)
+        clip.reduce(cur)
+        if self.world_size > 1:
+            side = self.runtime.stream
+            if side is None:
+                self.comm.all_reduce(clip.sumsq, cur)
+            else:
+                if self._clip_syncs is None:  # (ready, done): reused every step
+                    kind = self.runtime.sync_kind
+                    self._clip_syncs = (Sync(kind), Sync(kind))
+                ready, done = self._clip_syncs
+                ready.record(cur.cuda_stream)
+                ready.wait(side.cuda_stream)
+                self.comm.all_reduce(clip.sumsq, side)
+                done.record(side.cuda_stream)
+                done.wait(cur.cuda_stream)
+        clip.coef(self.max_grad_norm, cur)
+        clip.run(deferred, 0, len(deferred), cur)
+        self._last_norm_bytes = clip.last_norm_bytes
+
     @on_param_device
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._check_clip()
         step_start = time.perf_counter()
         e0 = torch.cuda.Event(enable_timing=True)
         e0.record(torch.cuda.current_stream(self.params[0].device))
@@ -2219,6 +2335,8 @@ class ShardedOptimizer:
         if done is not None and self.world_size > 1:
             if self.runtime.stream is None:  # single stream: `done` follows the last collective
                 e1 = done
+            elif self._span_end is not None:  # (a clipped step recorded it before its all-reduce)
+                e1, self._span_end = self._span_end, None
             else:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record(self.runtime.stream)  # after the last gradient collective

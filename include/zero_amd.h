@@ -379,6 +379,30 @@ int zs_adamset_run_sr(const zs_adamset* as, const zs_adam_hparams* hp, const flo
 int zs_sr_keys(uint64_t seed, uint64_t step, uint32_t* key0, uint32_t* key1);
 int zs_sr_bits(uint64_t e, uint32_t key0, uint32_t key1, uint32_t* r);
 
+/* The guarded update: a step whose gradient norm is not finite is skipped on the device (additive
+ * in ABI v13).  The host never learns of it and never waits.
+ *
+ * zs_clip_coef_guarded is zs_clip_coef plus the decision: out2[0] = the norm as computed; if that
+ * norm is NaN or +-inf (some gradient element is not finite, or the sum of squares left fp32's
+ * range), out2[1] = the quiet NaN 0x7FC00000 and *skipped (a uint64_t in device memory) is
+ * incremented, by a plain load, add and store in stream order; otherwise out2[1] has zs_clip_coef's
+ * bits, which are then never a NaN (max_norm is finite or inf and >= 0, norm + 1e-6f > 0).
+ * ZS_ERR_INVALID as zs_clip_coef, and for skipped == NULL.
+ *
+ * zs_adamset_run_guarded / zs_adamset_run_sr_guarded are zs_adamset_run_clipped / zs_adamset_run_sr
+ * with a coefficient (required here), except that a NaN *coef ends every workgroup right after the
+ * coefficient's uniform load: no parameter, master residual, moment or vmax element is read or
+ * written.  With any other coefficient every output has the unguarded run's bits.
+ * ZS_ERR_INVALID, nothing launched: what the unguarded run refuses, coef == NULL, a set with the
+ * ZeRO-1 carry, an SGD set (its "first step" is the host's count, which a skipped step would
+ * advance). */
+int zs_clip_coef_guarded(const float* sumsq, double grad_div, double max_norm, float* out2,
+                         uint64_t* skipped, uintptr_t stream);
+int zs_adamset_run_guarded(const zs_adamset* as, const zs_adam_hparams* hp, const float* coef,
+                           uintptr_t stream);
+int zs_adamset_run_sr_guarded(const zs_adamset* as, const zs_adam_hparams* hp, const float* coef,
+                              uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Fused SGD (momentum, Nesterov), additive in ABI v13.  Replaces torch.optim.SGD.step on the    */
 /* owned shard where the reference's ShardedOptimizer wraps an SGD (zero1.py:88, zero2.py:120,  */
