@@ -1,6 +1,7 @@
 // CDNA4 (gfx950) kernels of the ZeRO step and the C entry points that launch them: segment copy
 // (pack / unpack), the fused optimizer update (one vector and one scalar kernel, instantiated over
-// the element rules: Adam, Adam with bf16 moments rounded to nearest or stochastically, SGD), the
+// the element rules: Adam, Adam with bf16 moments rounded to nearest or stochastically, Adam over
+// master-free bf16 parameters rounded stochastically, SGD), the
 // gradient sum of squares and clip coefficient, scale, accumulate, convert, the fp8 row quantizer
 // and gather, and the flag kernels.
 //
@@ -318,6 +319,7 @@ template <bool AMS>
 struct AdamRule {
   using Hyper = HP;
   static constexpr bool kM = true, kV = true, kX = AMS, kGradOffset2 = true;
+  static constexpr bool kPsr = false;  // AdamPsrRule: no master, the bf16 parameter in place
 
   // One element of torch.optim.Adam's single-tensor update (adam.py:394-547), one fp32 operation
   // per operation of torch's CPU kernels: lerp = fma(w, end-self, self) or fma(w-1, end-self, end)
@@ -402,6 +404,40 @@ __device__ __forceinline__ void sr_pack_bf16x4(const float* mp, const float* vp,
   vr = make_uint2(sr_pack2(vw[0], vw[1]), sr_pack2(vw[2], vw[3]));
 }
 
+// Master-free bf16 parameters (zs_adamset_run_psr over a ZS_BF16_SR set; DESIGN.md §4, "Master-free
+// bf16 parameters").  AdamPsrRule names the instances: the third storage mode beside SPLIT and the
+// fp32 master.  A segment's `master` is the bf16 parameter, read, widened (exact), run through the
+// unchanged fp32 rule and stored in place through p_out with zs_sr::round_bf16 and the low 16 bits
+// of zs_sr::bits(e, kp0, kp1), (kp0, kp1) = zs_sr::pkeys(k0, k1) derived on the host; there is no
+// master_out and no residual.  The geometry (groups, chunk, alignment) is the split master's, so
+// such an instance has SPLIT set.  e counts elements of the m array as ST stores it (fp32 or bf16).
+struct PsrHP : SrHP {
+  uint32_t kp0, kp1;
+};
+struct AdamPsrRule : AdamRule<false> {
+  using Hyper = PsrHP;
+  static constexpr bool kPsr = true;
+};
+template <typename ST>
+__device__ __forceinline__ uint64_t psr_seg_index(const float* m, const PsrHP& hp) {
+  return (uint64_t(reinterpret_cast<uintptr_t>(m)) - hp.m_base) >> (sizeof(ST) == 2 ? 1 : 2);
+}
+// sr_bits_at under the parameter's keys, its low 16 bits: the index's high word stays scalar
+__device__ __forceinline__ uint32_t psr_r16_at(uint64_t eu, uint32_t off, const PsrHP& hp) {
+  const uint32_t lo0 = uint32_t(eu), hi = uint32_t(eu >> 32);
+  const uint32_t lo = lo0 + off;
+  const uint32_t ka = hp.kp0 ^ (hi * 0x9E3779B9u), kb = hp.kp0 ^ ((hi + 1u) * 0x9E3779B9u);
+  return (zs_sr::lowbias32(lo ^ (lo < lo0 ? kb : ka)) ^ hp.kp1) & 0xFFFFu;
+}
+// four parameters from index eu + off on as their stochastically rounded bf16 codes, 8 bytes
+__device__ __forceinline__ uint2 psr_pack_bf16x4(const float* pp, uint64_t eu, uint32_t off,
+                                                 const PsrHP& hp) {
+  uint32_t w[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) w[j] = sr_word(pp[j], psr_r16_at(eu, off + j, hp));
+  return make_uint2(sr_pack2(w[0], w[1]), sr_pack2(w[2], w[3]));
+}
+
 // torch.optim.SGD over the same tables: field `m` of a segment is the momentum buffer (MOM: the
 // set has one), `v` and `vmax` are unused.  Without MOM no state array is touched.
 struct SgdHP {
@@ -413,6 +449,7 @@ template <bool MOM>
 struct SgdRule {
   using Hyper = SgdHP;
   static constexpr bool kM = MOM, kV = false, kX = false, kGradOffset2 = false;
+  static constexpr bool kPsr = false;
 
   // One element of torch.optim.SGD's single-tensor update (sgd.py _single_tensor_sgd), in the
   // rounding order of torch's CPU kernels: add(x, alpha=a) = fma(a, x, self), so
@@ -522,7 +559,8 @@ struct NoStream {
 // group.  ST: the element type of m and v in memory, float or unsigned short (bf16 moments: 8 bytes
 // per lane per access through the 16-bit streams, widened before the rule and rounded to nearest
 // even after it — SrBf16: stochastically, sr_pack_bf16x4; the rule itself and the parameter it
-// leaves see fp32 moments only).
+// leaves see fp32 moments only).  Rule::kPsr (AdamPsrRule, with SPLIT): the parameter is the one
+// 16-bit stream `hi` / `pb`, read, widened and stored back through psr_pack_bf16x4; no `lo`.
 template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool HASG, bool CLIP,
           typename ST = float>
 __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
@@ -530,8 +568,11 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
   constexpr int G = adam_groups(SPLIT);
   constexpr bool G32 = sizeof(GT) == 4;
   constexpr bool S16 = sizeof(ST) == 2;
+  constexpr bool PSR = Rule::kPsr;
   static_assert(!S16 || (Rule::kM && Rule::kV && !Rule::kX && !CARRY),
                 "bf16 state: Adam's m and v, no amsgrad, no carry");
+  static_assert(!PSR || (SPLIT && !Rule::kX && !CARRY),
+                "master-free: the split master's geometry, no amsgrad, no carry");
   uint32_t o4 = threadIdx.x * 16u;                   // lane byte offset in an fp32 stream
   uint32_t o2 = threadIdx.x * 8u;                    // ... in a bf16 stream
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -551,7 +592,7 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
   const S4 sc(CARRY ? s.carry + e0 : nullptr);
   const S2 gh(HASG && !G32 ? (unsigned short*)s.g + e0 : nullptr);
   const S2 hi(SPLIT ? (unsigned short*)s.master + e0 : nullptr);
-  const S2 lo(SPLIT ? (unsigned short*)s.master_out + e0 : nullptr), pb(s.p_out + e0);
+  const S2 lo(SPLIT && !PSR ? (unsigned short*)s.master_out + e0 : nullptr), pb(s.p_out + e0);
   const SH mh((unsigned short*)s.m + e0), vh((unsigned short*)s.v + e0);
   uint4 gq[G], pq[G], mq[G], vq[G], xq[G], cq[G];
   uint2 gd[G], hd[G], ld[G], md[G], vd[G];
@@ -575,7 +616,7 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
     }
     if constexpr (SPLIT) {
       hd[u] = nt_ld8(hi.at(u, o2));
-      ld[u] = nt_ld8(lo.at(u, o2));
+      if constexpr (!PSR) ld[u] = nt_ld8(lo.at(u, o2));
     } else {
       pq[u] = nt_ld16(pm.at(u, o4));
     }
@@ -594,7 +635,8 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
     float gp[4] = {0.f, 0.f, 0.f, 0.f}, pp[4];
     if constexpr (HASG && G32) unpack4(gq[u], gp);
     else if constexpr (HASG) unpack_bf16x4(gd[u], gp);
-    if constexpr (SPLIT) join_master4(hd[u], ld[u], pp);
+    if constexpr (PSR) unpack_bf16x4(hd[u], pp);
+    else if constexpr (SPLIT) join_master4(hd[u], ld[u], pp);
     else unpack4(pq[u], pp);
     float mp[4] = {0.f, 0.f, 0.f, 0.f}, vp[4] = {0.f, 0.f, 0.f, 0.f};
     float xp[4] = {0.f, 0.f, 0.f, 0.f}, cp[4] = {0.f, 0.f, 0.f, 0.f};
@@ -613,7 +655,11 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(o4), "+v"(o2));  // as above, for the block the stores are in
 #endif
-    if constexpr (SPLIT) {
+    if constexpr (PSR) {
+      const uint2 r = psr_pack_bf16x4(pp, psr_seg_index<ST>(s.m, hp) + uint64_t(e0),
+                                      (uint32_t(u) * kThreads + threadIdx.x) * 4u, hp);
+      nt_st8(pb.at(u, o2), r);
+    } else if constexpr (SPLIT) {
       uint32_t h[4], l[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {  // split_master4, in place: through the call 16 instances
@@ -657,8 +703,11 @@ template <typename Rule, typename GT, bool CARRY, bool SPLIT, int G, bool CLIP,
 __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
                                                    const typename Rule::Hyper& hp, float coef) {
   constexpr bool S16 = sizeof(ST) == 2;
+  constexpr bool PSR = Rule::kPsr;
   static_assert(!S16 || (Rule::kM && Rule::kV && !Rule::kX && !CARRY),
                 "bf16 state: Adam's m and v, no amsgrad, no carry");
+  static_assert(!PSR || (SPLIT && !Rule::kX && !CARRY),
+                "master-free: the split master's geometry, no amsgrad, no carry");
   float4 g4[G], p4[G], m4[G], v4[G];
   float4 x4[G], c4[G];
 #pragma unroll
@@ -666,7 +715,10 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
     const int64_t i = e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
     if (i < s.n) {
       g4[u] = s.g ? load_g4<GT>(s.g, i) : make_float4(0.f, 0.f, 0.f, 0.f);
-      if constexpr (SPLIT) {
+      if constexpr (PSR) {
+        const uint2 h = nt_ld8(reinterpret_cast<const unsigned short*>(s.master) + i);
+        unpack_bf16x4(h, reinterpret_cast<float*>(&p4[u]));
+      } else if constexpr (SPLIT) {
         const uint2 h = nt_ld8(reinterpret_cast<const unsigned short*>(s.master) + i);
         const uint2 l = nt_ld8(reinterpret_cast<const unsigned short*>(s.master_out) + i);
         join_master4(h, l, reinterpret_cast<float*>(&p4[u]));
@@ -708,7 +760,11 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
         if constexpr (Rule::kX) xp[j] = xv;
         if constexpr (CARRY) cp[j] = cv;
       }
-      if constexpr (SPLIT) {
+      if constexpr (PSR) {
+        const uint2 r = psr_pack_bf16x4(pp, psr_seg_index<ST>(s.m, hp) + uint64_t(e0),
+                                        (uint32_t(u) * kThreads + threadIdx.x) * 4u, hp);
+        nt_st8(s.p_out + i, r);
+      } else if constexpr (SPLIT) {
         uint32_t h[4], l[4];
         split_master4(pp, h, l);
         nt_st8(s.p_out + i, pack_u16x4(h));
@@ -765,7 +821,8 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
 // ST = unsigned short (zs_adamset_create_ex with ZS_BF16 state): m and v are bf16 arrays, 8-B
 // aligned like the other 16-bit ones; the chunk geometry is the fp32-state instance's.  ST = SrBf16
 // (zs_adamset_run_sr, over AdamSrRule, whose Hyper carries the keys and m_base): the same arrays,
-// stored with stochastic rounding.
+// stored with stochastic rounding.  Rule = AdamPsrRule (zs_adamset_run_psr, a ZS_BF16_SR set;
+// SPLIT names its geometry): no master, the bf16 parameter in place, any of the three ST.
 template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP,
           typename ST = float, bool GUARD = false>
 __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
@@ -822,8 +879,11 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     if (coef != coef) return;  // uniform: the step is skipped, nothing is loaded or stored
   }
   constexpr bool S16 = sizeof(ST) == 2;
+  constexpr bool PSR = Rule::kPsr;
   static_assert(!S16 || (Rule::kM && Rule::kV && !Rule::kX && !CARRY),
                 "bf16 state: Adam's m and v, no amsgrad, no carry");
+  static_assert(!PSR || (SPLIT && !Rule::kX && !CARRY),
+                "master-free: the split master's geometry, no amsgrad, no carry");
   int64_t seg = 0;
   for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
     while (chunk_prefix[seg + 1] <= c) ++seg;
@@ -833,8 +893,11 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     if (i >= s.n) continue;
     float gs = s.g ? load_g1<GT>(s.g, i) : 0.0f;
     const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
-    float p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
-                    : glob(s.master)[i];
+    float p;
+    if constexpr (PSR) p = bf16_to_f32(glob(reinterpret_cast<const unsigned short*>(s.master))[i]);
+    else
+      p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
+                : glob(s.master)[i];
     const gptr<unsigned short> mb = glob(reinterpret_cast<unsigned short*>(s.m));
     const gptr<unsigned short> vb = glob(reinterpret_cast<unsigned short*>(s.v));
     float m = 0.0f, v = 0.0f, vm = 0.0f;
@@ -848,7 +911,10 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     if constexpr (Rule::kX) vm = glob(s.vmax)[i];
     float cr = CARRY ? glob(s.carry)[i] : 0.0f;
     Rule::template elem<CARRY, CLIP>(gs, p, m, v, vm, cr, hp, coef);
-    if constexpr (SPLIT) {
+    if constexpr (PSR) {
+      const uint32_t r16 = psr_r16_at(psr_seg_index<ST>(s.m, hp) + uint64_t(i0), threadIdx.x, hp);
+      glob(s.p_out)[i] = (unsigned short)(sr_word(p, r16) >> 16);
+    } else if constexpr (SPLIT) {
       const unsigned short h = f32_to_bf16(p);
       glob(s.p_out)[i] = h;
       lo[i] = (unsigned short)master_residual(p, h);
@@ -1743,7 +1809,16 @@ struct zs_adamset {
   // its parity (an element index is a whole number of bf16 elements from m_base)
   uint64_t m_lowest = ~uint64_t(0);
   int m_one_parity = 1;
+  // zs_adamset_run_psr over fp32 moments: whether all inputs' m share m_lowest's low two bits
+  int m_one_mod4 = 1;
+  // zs_adamset_set_state_rounding: a ZS_BF16_SR set's bf16 moments round stochastically
+  int state_sr = 0;
 };
+
+// ZS_BF16_SR (master-free) sets have the split master's geometry: 16-bit parameter stream, 4 groups
+static bool split_geometry(const zs_adamset* as) {
+  return as->p_dtype == ZS_BF16_SPLIT || as->p_dtype == ZS_BF16_SR;
+}
 
 namespace {
 // zs_adamset_set_grads: new gradient pointers for inputs [k0, k0 + n) of a set, in the kernel
@@ -1863,6 +1938,12 @@ using AdamFamily = UpdateFamily<AdamRule, float, true, true>;
 using AdamBf16Family = UpdateFamily<AdamRule, unsigned short, false, true>;  // zs_adamset_create_ex
 using AdamSrFamily = UpdateFamily<AdamSrRuleOf, SrBf16, false, true>;        // zs_adamset_run_sr
 using SgdFamily = UpdateFamily<SgdRule, float, true>;
+template <bool>
+using AdamPsrRuleOf = AdamPsrRule;
+// zs_adamset_run_psr: the master-free instances, by how m and v are stored
+using AdamPsrFamily = UpdateFamily<AdamPsrRuleOf, float, false, true>;
+using AdamPsrBf16Family = UpdateFamily<AdamPsrRuleOf, unsigned short, false, true>;
+using AdamPsrSrFamily = UpdateFamily<AdamPsrRuleOf, SrBf16, false, true>;
 
 struct UpdateTable {  // a segment array with its chunk prefix
   const AdamSeg* segs;
@@ -1920,7 +2001,10 @@ static int launch_update_tables(const UpdateTable& vec, const UpdateTable& sca, 
             constexpr bool C = decltype(c)::value;
             auto go = [&](auto gd) {
               constexpr bool GD = decltype(gd)::value;
-              if constexpr (decltype(is_vec)::value)
+              // the master-free families exist over the split geometry only (run_set passes it)
+              if constexpr (Rule::kPsr && !S)
+                return;
+              else if constexpr (decltype(is_vec)::value)
                 hipLaunchKernelGGL(
                     (adam_segments_kernel<Rule, GT, C, S, decltype(lf)::value, CLIP, ST, GD>), grid,
                     dim3(kThreads), 0, st, t.segs, t.prefix, t.nseg, t.chunks, hp, coef);
@@ -1966,8 +2050,8 @@ static int launch_update_tables(const UpdateTable& vec, const UpdateTable& sca, 
 template <typename F>
 static int run_set(const zs_adamset* as, bool flag, const typename F::Hyper& hp, const float* coef,
                    uintptr_t stream, bool guard = false) {
-  return launch_update_tables<F>(vec_table(as), sca_table(as), as->g_dtype,
-                                 as->p_dtype == ZS_BF16_SPLIT, flag, as->has_carry != 0, hp, coef,
+  return launch_update_tables<F>(vec_table(as), sca_table(as), as->g_dtype, split_geometry(as),
+                                 flag, as->has_carry != 0, hp, coef,
                                  reinterpret_cast<hipStream_t>(stream), guard);
 }
 
@@ -2419,12 +2503,15 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   *out = nullptr;
   ZS_REQUIRE(n >= 0 && (n == 0 || in), "%s: bad table", fn);
   ZS_REQUIRE(g_dtype == ZS_F32 || g_dtype == ZS_BF16, "%s: bad g_dtype %d", fn, g_dtype);
-  ZS_REQUIRE(p_dtype == ZS_BF16 || p_dtype == ZS_BF16_SPLIT,
-             "%s: p_dtype must be ZS_BF16 or ZS_BF16_SPLIT (got %d)", fn, p_dtype);
+  const bool psr = p_dtype == ZS_BF16_SR;  // master-free: zs_adamset_run_psr
+  ZS_REQUIRE(p_dtype == ZS_BF16 || p_dtype == ZS_BF16_SPLIT || (psr && !sgd),
+             "%s: p_dtype must be ZS_BF16 or ZS_BF16_SPLIT%s (got %d)", fn,
+             sgd ? "" : " or ZS_BF16_SR", p_dtype);
   ZS_REQUIRE(state_dtype == ZS_F32 || (state_dtype == ZS_BF16 && !sgd),
              "%s: state_dtype must be ZS_F32 or ZS_BF16 (got %d)", fn, state_dtype);
   const bool split = p_dtype == ZS_BF16_SPLIT;
-  const int64_t msz = split ? 2 : 4;  // bytes per element of master / master_out
+  const bool geo = split || psr;      // 16-bit parameter stream, the split master's chunks
+  const int64_t msz = geo ? 2 : 4;    // bytes per element of master / master_out
   const int64_t ssz = state_dtype == ZS_BF16 ? 2 : 4;  // ... of m, v (and vmax)
   const int64_t gsz = g_dtype == ZS_F32 ? 4 : 2;
   ZS_REQUIRE(n < (int64_t(1) << 31), "%s: %lld segments (max 2^31 - 1)", fn,
@@ -2436,7 +2523,7 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   std::vector<uint64_t> in_g(size_t(n), 0);
   std::vector<int64_t> in_n(size_t(n), 0);
   std::vector<unsigned char> in_vec(size_t(n), 0);
-  int carry_state = -1, vmax_state = -1, mom_state = -1, m_one_parity = 1;
+  int carry_state = -1, vmax_state = -1, mom_state = -1, m_one_parity = 1, m_one_mod4 = 1;
   uint64_t m_lowest = ~uint64_t(0);
   int64_t elems = 0, bytes = 0, bytes_no_g = 0;
   for (int64_t i = 0; i < n; ++i) {
@@ -2459,6 +2546,9 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
     ZS_REQUIRE(!split || (s.master_out && s.p_out),
                "%s: seg %lld: a split master needs master_out (residual) and p_out", fn,
                (long long)i);
+    ZS_REQUIRE(!psr || (s.p_out == s.master && !s.master_out && !s.vmax && !s.carry),
+               "%s: seg %lld: a ZS_BF16_SR set takes master = p_out (the bf16 param, updated in "
+               "place) and no master_out, vmax or carry", fn, (long long)i);
     // fp32 gradients over a split master: ZeRO-3's fp32 accumulation arena; ZeRO-1 (the carry)
     // never has such a set, so no CARRY instance of it exists
     ZS_REQUIRE(!(split && g_dtype == ZS_F32 && s.carry),
@@ -2494,7 +2584,7 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
       vec.push_back(d);
       vec_in.push_back(int32_t(i));
       in_vec[size_t(i)] = 1;
-      vpre.push_back(vpre.back() + (nv + adam_chunk(split) - 1) / adam_chunk(split));
+      vpre.push_back(vpre.back() + (nv + adam_chunk(geo) - 1) / adam_chunk(geo));
     }
     if (nv < s.n) {  // tail (or the whole unaligned segment) through the scalar kernel
       const AdamSeg t = seg_tail(d, nv, s.n - nv, gsz, msz, ssz);
@@ -2504,6 +2594,7 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
       spre.push_back(spre.back() + (t.n + kThreads - 1) / kThreads);
     }
     if (m_lowest != ~uint64_t(0) && ((s.m ^ m_lowest) & 1)) m_one_parity = 0;
+    if (m_lowest != ~uint64_t(0) && ((s.m ^ m_lowest) & 3)) m_one_mod4 = 0;
     m_lowest = std::min<uint64_t>(m_lowest, s.m);
     elems += s.n;
     int64_t b = msz /*master*/ + (sgd ? (s.m ? 8 : 0) /*buffer*/ : 2 * ssz /*m*/ + 2 * ssz /*v*/);
@@ -2537,6 +2628,7 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   as->bytes_no_g = bytes_no_g;
   as->m_lowest = m_lowest;
   as->m_one_parity = m_one_parity;
+  as->m_one_mod4 = m_one_mod4;
   int rc = ZS_OK;
   if (as->nvec) {
     rc = upload(vec, &as->d_vec);
@@ -2640,6 +2732,7 @@ static int adam_run(const char* fn, const zs_adamset* as, const zs_adam_hparams*
              "%s: stochastic rounding needs an Adam set with ZS_BF16 state (zs_adamset_create_ex)",
              fn);
   ZS_REQUIRE(!as->sgd, "%s: the set was made by zs_sgdset_create (use zs_sgdset_run)", fn);
+  ZS_REQUIRE(as->p_dtype != ZS_BF16_SR, "%s: a ZS_BF16_SR set runs through zs_adamset_run_psr", fn);
   ZS_REQUIRE(!coef || !as->has_carry, "%s: a set with the ZeRO-1 carry cannot be clipped", fn);
   const bool ams = h->amsgrad != 0;
   const bool bf16_state = as->state_dtype == ZS_BF16;
@@ -2690,6 +2783,43 @@ int zs_adamset_run_sr_guarded(const zs_adamset* as, const zs_adam_hparams* h, co
   return adam_run("zs_adamset_run_sr_guarded", as, h, true, coef, &sr, stream, true);
 }
 
+int zs_adamset_run_psr(const zs_adamset* as, const zs_adam_hparams* h, const float* coef, int guard,
+                       uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream) {
+  const char* fn = "zs_adamset_run_psr";
+  ZS_REQUIRE(as && h, "%s: NULL argument", fn);
+  ZS_REQUIRE(as->p_dtype == ZS_BF16_SR && !as->sgd,
+             "%s: the set was not made with p_dtype ZS_BF16_SR (zs_adamset_create_ex)", fn);
+  ZS_REQUIRE(!guard || coef, "%s: the guard tests the clip coefficient, which is NULL", fn);
+  ZS_REQUIRE(h->amsgrad == 0, "%s: a ZS_BF16_SR set has no amsgrad", fn);
+  const bool bf16_state = as->state_dtype == ZS_BF16;
+  if (as->nvec + as->nsca) {  // every element's index: its m address less m_base, in elements
+    ZS_REQUIRE(as->m_lowest >= m_base, "%s: a segment's m lies below m_base (%#llx < %#llx)", fn,
+               (unsigned long long)as->m_lowest, (unsigned long long)m_base);
+    const uint64_t mask = bf16_state ? 1 : 3;
+    ZS_REQUIRE((bf16_state ? as->m_one_parity : as->m_one_mod4) &&
+                   ((as->m_lowest - m_base) & mask) == 0,
+               "%s: a segment's m is not a whole number of elements from m_base", fn);
+  }
+  PsrHP hp;
+  static_cast<HP&>(hp) = make_hp(h);
+  hp.k0 = key0;
+  hp.k1 = key1;
+  hp.m_base = m_base;
+  zs_sr::pkeys(key0, key1, &hp.kp0, &hp.kp1);
+  if (!bf16_state) return run_set<AdamPsrFamily>(as, false, hp, coef, stream, guard != 0);
+  if (!as->state_sr) return run_set<AdamPsrBf16Family>(as, false, hp, coef, stream, guard != 0);
+  return run_set<AdamPsrSrFamily>(as, false, hp, coef, stream, guard != 0);
+}
+
+int zs_adamset_set_state_rounding(zs_adamset* as, int stochastic) {
+  ZS_REQUIRE(as != nullptr, "zs_adamset_set_state_rounding: NULL set");
+  ZS_REQUIRE(as->p_dtype == ZS_BF16_SR && as->state_dtype == ZS_BF16,
+             "zs_adamset_set_state_rounding: a ZS_BF16_SR set with ZS_BF16 state only (other sets "
+             "choose by entry point: zs_adamset_run / zs_adamset_run_sr)");
+  as->state_sr = stochastic ? 1 : 0;
+  return ZS_OK;
+}
+
 int zs_adamset_sqnorm_partials(const zs_adamset* as, int64_t* n) {
   ZS_REQUIRE(as && n, "zs_adamset_sqnorm_partials: NULL argument");
   *n = as->sq_vec + as->sq_sca;
@@ -2701,7 +2831,7 @@ int zs_adamset_grad_sqnorm(const zs_adamset* as, double* partials, uintptr_t str
   ZS_REQUIRE(partials != nullptr || as->sq_vec + as->sq_sca == 0,
              "zs_adamset_grad_sqnorm: partials is NULL");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool f32 = as->g_dtype == ZS_F32, split = as->p_dtype == ZS_BF16_SPLIT;
+  const bool f32 = as->g_dtype == ZS_F32, split = split_geometry(as);
   if (as->sq_vec) {
 #define ZS_SQ(GT, S, NT)                                                                      \
   hipLaunchKernelGGL((grad_sqnorm_kernel<GT, S, NT>), dim3(int(as->sq_vec)), dim3(kThreads), 0, \

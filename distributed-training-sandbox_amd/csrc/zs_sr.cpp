@@ -17,4 +17,10 @@ int zs_sr_bits(uint64_t e, uint32_t key0, uint32_t key1, uint32_t* r) {
   return ZS_OK;
 }
 
+int zs_sr_pkeys(uint32_t key0, uint32_t key1, uint32_t* pkey0, uint32_t* pkey1) {
+  ZS_REQUIRE(pkey0 && pkey1, "zs_sr_pkeys: NULL argument");
+  zs_sr::pkeys(key0, key1, pkey0, pkey1);
+  return ZS_OK;
+}
+
 }  // extern "C"

@@ -40,6 +40,14 @@ ZS_SR_FN uint32_t bits(uint64_t e, uint32_t k0, uint32_t k1) {
   return lowbias32(uint32_t(e) ^ k0 ^ (uint32_t(e >> 32) * 0x9E3779B9u)) ^ k1;
 }
 
+// The keys of the parameter's draw in a master-free launch (zs_adamset_run_psr), from the launch's
+// keys: r16p = bits(e, kp0, kp1) & 0xFFFF.  Each goes through a hash round of its own, so the draw
+// is independent of the m and v halves of bits(e, k0, k1) of the same element.
+ZS_SR_FN void pkeys(uint32_t k0, uint32_t k1, uint32_t* kp0, uint32_t* kp1) {
+  *kp0 = lowbias32(k0 ^ 0x85EBCA6Bu);
+  *kp1 = lowbias32(k1 + 0xC2B2AE35u);
+}
+
 // fp32 bits u -> bf16 code, r16 in [0, 65535].  Sign-magnitude: away from zero with probability
 // low16(u) / 65536, exact when low16(u) == 0; a carry out of the largest finite value is Inf (a
 // finite u + 0xFFFF stays below 2^32, and Inf + r16 keeps its high half).  A NaN takes `nan_code`,

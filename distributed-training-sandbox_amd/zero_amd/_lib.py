@@ -17,7 +17,7 @@ from torch.profiler import record_function
 LIB_PATH = Path(os.environ.get("ZERO_AMD_LIB", Path(__file__).resolve().parent / "libzero_amd.so"))
 
 ZS_OK, ZS_ERR_INVALID, ZS_ERR_HIP, ZS_ERR_RCCL, ZS_ERR_NOMEM = 0, 1, 2, 3, 4
-ZS_F32, ZS_BF16, ZS_U8, ZS_BF16_SPLIT = 0, 1, 2, 3
+ZS_F32, ZS_BF16, ZS_U8, ZS_BF16_SPLIT, ZS_BF16_SR = 0, 1, 2, 3, 4
 ZS_LAYOUT_R, ZS_LAYOUT_Z, ZS_LAYOUT_F = 0, 1, 2
 ZS_BUCKETS_RAGGED, ZS_BUCKETS_PADDED = 0, 1
 ZS_SYNC_EVENT, ZS_SYNC_FLAG = 0, 1
@@ -40,6 +40,7 @@ EXPORTED = (
     "zs_adamset_sqnorm_partials", "zs_adamset_grad_sqnorm", "zs_sqnorm_reduce", "zs_clip_coef",
     "zs_adamset_run_clipped", "zs_adamset_run_sr", "zs_sr_keys", "zs_sr_bits",
     "zs_clip_coef_guarded", "zs_adamset_run_guarded", "zs_adamset_run_sr_guarded",
+    "zs_adamset_run_psr", "zs_adamset_set_state_rounding", "zs_sr_pkeys",
     "zs_sgd_hparams_init", "zs_sgdset_create", "zs_sgdset_run",
     "zs_comm_unique_id", "zs_comm_init", "zs_comm_destroy", "zs_reduce_scatter", "zs_all_gather",
     "zs_all_reduce", "zs_reduce", "zs_broadcast", "zs_reduce_group", "zs_broadcast_group", "zs_all_gather_group", "zs_reduce_scatter_group",
@@ -148,6 +149,11 @@ _SIGS = {
     "zs_adamset_run_guarded": ([_P, ctypes.POINTER(AdamHParams), _P, _U], ctypes.c_int),
     "zs_adamset_run_sr_guarded": ([_P, ctypes.POINTER(AdamHParams), _P, ctypes.c_uint64,
                                    ctypes.c_uint32, ctypes.c_uint32, _U], ctypes.c_int),
+    "zs_adamset_run_psr": ([_P, ctypes.POINTER(AdamHParams), _P, ctypes.c_int, ctypes.c_uint64,
+                            ctypes.c_uint32, ctypes.c_uint32, _U], ctypes.c_int),
+    "zs_adamset_set_state_rounding": ([_P, ctypes.c_int], ctypes.c_int),
+    "zs_sr_pkeys": ([ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                     ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
     "zs_sr_keys": ([ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32),
                     ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
     "zs_sr_bits": ([ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,

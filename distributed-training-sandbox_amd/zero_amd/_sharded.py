@@ -21,7 +21,8 @@ from torch.optim import Optimizer
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
 from ._update import (check_bf16_state_group, check_max_grad_norm, check_skip_nonfinite,
-                      check_state_dtype, check_state_rounding, owner_range)
+                      check_master_free, check_master_free_group, check_state_dtype,
+                      check_state_rounding, owner_range)
 from .engine import ShardEngine
 from .training_utils.utils import get
 
@@ -115,10 +116,27 @@ class ShardedOptimizerBase:
         # skipped on the device — nothing in device memory changes, the host proceeds as for any
         # step; refused here, on every rank and before anything collective
         self.skip_nonfinite = check_skip_nonfinite(skip_nonfinite, max_grad_norm, self._kind)
+        # master="none": bf16 parameters without any master, updated in place and rounded
+        # stochastically from the same generator (state_seed).  What it cannot be
+        # combined with is refused here, on every rank and before anything collective
+        if master not in ("split", "fp32", "none"):
+            raise ValueError(f"master must be 'split', 'fp32' or 'none' (got {master!r})")
+        master_free = master == "none"
+        if master_free:
+            check_master_free(self._kind, self._carry and get("ws") > 1,
+                              all(p.dtype == torch.bfloat16 for g in optimizer.param_groups
+                                  for p in g["params"]))
+            if arena == "buckets" or overlap or \
+                    (layout != "reference" and (layout != "flat" or self._carry)):
+                raise ValueError("zero_amd: master='none' is not supported with the bucket arena "
+                                 f"or overlap=True (arena={arena!r}, layout={layout!r}, "
+                                 f"overlap={bool(overlap)}); use the flat arena")
         for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
             hpd = group_hparams(self._kind, group, optimizer)
             if bf16_state and self._kind == "adam":
                 check_bf16_state_group(hpd, self.state_rounding)
+            if master_free:
+                check_master_free_group(hpd)
         if bf16_state:
             if self._kind == "sgd":
                 raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with "
@@ -178,6 +196,9 @@ class ShardedOptimizerBase:
                     if bf16_state:
                         raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported "
                                          "with arena='auto' that resolved to the bucket arena")
+                    if master_free:
+                        raise ValueError("zero_amd: master='none' is not supported with "
+                                         "arena='auto' that resolved to the bucket arena")
         # bytes per bucket (bucket arena) / per round (flat arena, all owners' windows together);
         # default 256 MiB / 1 GiB: a flat round has no pack to pipeline, so fewer, larger rounds
         # cost only the last round's Adam as exposed tail and cut the launches per step
@@ -185,7 +206,8 @@ class ShardedOptimizerBase:
             bucket_mb = 1024.0 if arena == "flat" else 256.0
         self._bucket_bytes = int(bucket_mb * (1 << 20))
         self._sync = sync
-        self._master = master  # bf16 params: "split" (bf16 param + int16 residual) or "fp32"
+        # bf16 params: "split" (bf16 param + int16 residual), "fp32", or "none" (no master)
+        self._master = master
         # ws > 1 exchange: "flat" = params and grads are views of one owner-major arena, rounds of
         # grouped reduce / broadcast, no pack / unpack (flat.py); "buckets" = the rank-major
         # bucket arena with pack / reduce-scatter / all-gather / unpack (engine.py)
@@ -341,6 +363,9 @@ class ShardedOptimizerBase:
         if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
             for gi in range(len(self._groups)):
                 check_bf16_state_group(self._hparams_of(gi), self.state_rounding)
+        if self._master == "none":
+            for gi in range(len(self._groups)):
+                check_master_free_group(self._hparams_of(gi))
         self.engine.max_grad_norm = self.max_grad_norm
         self.engine.skip_nonfinite = self.skip_nonfinite
         had_vmax = self.engine.vmax is not None
@@ -411,9 +436,9 @@ class ShardedOptimizerBase:
 
     # checkpointing (zero_amd/checkpoint.py) -------------------------------------------------------
     def _ckpt_header(self):
-        seed = self.state_seed if self.state_rounding == "stochastic" else None
+        keyed = self.state_rounding == "stochastic" or self._master == "none"
         return ckpt.header(self._variant, self.world_size, self.rank, self.local_param_indices,
-                           state_seed=seed)
+                           state_seed=self.state_seed if keyed else None, master=self._master)
 
     def _ckpt_views(self, i: int) -> dict:
         """name -> live view of param i's flat state (the owned params of Layout R)."""
@@ -449,12 +474,14 @@ class ShardedOptimizerBase:
         owned parameters): hyper-parameters through torch's loader, state copied into the flat
         buffers.  Parameters are the model's (load them with the model's own state dict)."""
         ckpt.check_header(state_dict, self._ckpt_header())
+        if self._master == "none":
+            ckpt.check_master_free_load(state_dict.get("state", {}))
         if self.engine is None:
             self._build_engine()
         eng = self.engine
         torch.cuda.synchronize(eng.device)
         seed = ckpt.saved_state_seed(state_dict)
-        if seed is not None and self.state_rounding == "stochastic":
+        if seed is not None and (self.state_rounding == "stochastic" or self._master == "none"):
             self.state_seed = eng.state_seed = seed  # the saved run's bits continue
         ckpt.load_param_groups(self.optimizer, state_dict)
         self.original_param_groups = self.optimizer.param_groups

@@ -18,6 +18,11 @@ import torch
 from .checkpoint import step_of
 from .kernels import adam_hparams, sgd_hparams, sr_keys
 
+# master="none": bf16 parameters without any master — the fused update reads the bf16 parameter,
+# runs the fp32 rule and stores it back rounded stochastically ("Master-free bf16
+# parameters").  Adam without amsgrad or the ZeRO-1 carry only.
+MASTERS = ("split", "fp32", "none")
+
 
 def owner_range(n: int, ws: int, rank: int):
     """(start, end) of the parameter indices ``rank`` owns out of ``n`` (zero1.py:55-62: equal
@@ -89,14 +94,37 @@ def check_bf16_state_group(hpd: dict, state_rounding=None) -> None:
                 "bits and a smaller decay is rounded away, so the moment could never shrink")
 
 
-def state_layout(kind: str, L: int, *, split: bool, fp32_master: bool, carry: bool,
-                 momentum: bool = True, state_dtype=None):
+def check_master_free(kind: str, carry: bool, bf16_params: bool = True) -> None:
+    """What ``master="none"`` cannot be combined with, as ValueError."""
+    if kind != "adam":
+        raise ValueError("zero_amd: master='none' is not supported with torch.optim.SGD")
+    if not bf16_params:
+        raise ValueError("zero_amd: master='none' rounds bf16 parameters stochastically: it needs "
+                         "bf16 parameters (fp32 parameters are their own master)")
+    if carry:
+        raise ValueError("zero_amd: master='none' is not supported with the ZeRO-1 gradient carry")
+
+
+def check_master_free_group(hpd: dict) -> None:
+    if hpd.get("amsgrad"):
+        raise ValueError("zero_amd: master='none' does not support amsgrad")
+
+
+def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = False,
+                 carry: bool = False, momentum: bool = True, state_dtype=None, master=None):
     """(total fp32 words, {name: (word offset, dtype)}) of the flat state of an ``L``-element
     shard: ``m``, ``v`` (Adam; SGD: ``m`` alone, the momentum buffer, and only with ``momentum``),
     ``carry`` (ZeRO-1), ``master`` (fp32 master of bf16 params), each ``L`` fp32, then ``lo``:
     ``L`` int16 residuals of the split master in ``(L + 1) // 2`` words.  ``state_dtype``
     torch.bfloat16 (Adam without carry): ``m`` and ``v`` are ``L`` bf16 each, every array from
-    ``master`` on starting at a multiple of 4 words (16 bytes)."""
+    ``master`` on starting at a multiple of 4 words (16 bytes).  ``master="none"`` (Adam without
+    carry): the moments alone, neither ``master`` nor ``lo``."""
+    if master == "none":
+        check_master_free(kind, carry)
+        if split or fp32_master:
+            raise ValueError("state_layout: master='none' has neither a split nor an fp32 master")
+    elif master is not None and master not in MASTERS:
+        raise ValueError(f"state_layout: master must be one of {MASTERS} (got {master!r})")
     if check_state_dtype(state_dtype) == torch.bfloat16:
         if kind != "adam" or carry:
             raise ValueError("state_layout: bf16 state is Adam's, without the ZeRO-1 carry")
@@ -125,7 +153,7 @@ class UpdateCore:
     def __init__(self, kind: str, L: int, device, ws: int, group_of, n_params: int, *,
                  split: bool = False, fp32_master: bool = False, carry: bool = False,
                  momentum: bool = True, placement_tries: int = 8, state_dtype=None,
-                 state_rounding=None, state_seed: int = 0):
+                 state_rounding=None, state_seed: int = 0, master=None):
         from .engine import probed_zeros  # (engine.py builds on this module)
 
         if kind not in ("adam", "sgd"):
@@ -145,8 +173,11 @@ class UpdateCore:
         # counter-based generator keyed by (state_seed, the part's step, the element's shard index)
         self.state_rounding, self.state_seed = check_state_rounding(state_rounding, state_seed,
                                                                     self.state_dtype)
+        # master="none": no master and no residual; the launches go through run_psr and every one
+        # is keyed by (state_seed, step), whatever the moments' dtype
+        self.master_free = master == "none"
         total, lay = state_layout(kind, self.L, split=split, fp32_master=fp32_master, carry=carry,
-                                  momentum=momentum, state_dtype=self.state_dtype)
+                                  momentum=momentum, state_dtype=self.state_dtype, master=master)
         self.state, self.placement = probed_zeros(total, torch.float32, device, placement_tries)
         for name in ("m", "v", "carry", "master", "lo"):  # residual 0: master = the bf16 param
             off, dt = lay.get(name, (0, None))
@@ -179,6 +210,8 @@ class UpdateCore:
         return views
 
     def ensure_vmax(self):
+        if self.master_free:
+            raise ValueError("zero_amd: master='none' does not support amsgrad")
         if self.state_dtype == torch.bfloat16:
             raise ValueError("zero_amd: state_dtype=torch.bfloat16 does not support amsgrad")
         if self.vmax is None:
@@ -251,10 +284,13 @@ class UpdateCore:
                                grad_div=float(self.ws), carry_mul=carry_mul)
         if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
             check_bf16_state_group(hpd, self.state_rounding)
+        if self.master_free:
+            check_master_free_group(hpd)
         if hpd["amsgrad"] and self.vmax is None:
             raise RuntimeError("amsgrad state buffer missing")
         hp = self._adam_hp(hpd, key, carry_mul)
-        if self.state_rounding == "stochastic":  # the launch's keys travel with its struct
+        # the launch's keys travel with its struct
+        if self.state_rounding == "stochastic" or self.master_free:
             hp.sr_keys = sr_keys(self.state_seed, int(key))
         return hp
 
@@ -293,7 +329,9 @@ class UpdateCore:
             e0.record(stream)
         if guard and coef is None:
             raise ValueError("zero_amd: the guarded update tests the clip coefficient")
-        if self.state_rounding == "stochastic":
+        if self.master_free:
+            aset.run_psr(hp, self.m.data_ptr(), hp.sr_keys, stream, coef=coef, guard=guard)
+        elif self.state_rounding == "stochastic":
             aset.run_sr(hp, self.m.data_ptr(), hp.sr_keys, stream, coef=coef, guard=guard)
         elif coef is None:
             aset.run(hp, stream)

@@ -14,8 +14,9 @@ Per-parameter entries: ``step`` (fp32 CPU scalar, torch's convention), ``exp_avg
 (+ ``max_exp_avg_sq``) and, beyond torch's Adam, what the engine needs to continue bit for bit:
 ``master_residual`` (int16; bf16 params, split master: master = bf16 param bits << 16 + residual),
 ``master_param`` (fp32 master), ``zero1_carry`` (ZeRO-1's A_{t-1}).  A
-``zero_amd`` header names the variant, world size, rank and ownership (and, with stochastic rounding
-of bf16 moments, the generator's ``state_seed``, which a loading optimizer adopts); loading a dict written at a
+``zero_amd`` header names the variant, world size, rank and ownership, how bf16 parameters keep
+their master (``master``; not compared) and, with stochastic rounding of bf16 moments or of the
+parameters (``master="none"``), the generator's ``state_seed``, which a loading optimizer adopts; loading a dict written at a
 different world size or rank raises instead of silently mis-assigning shards.  A dict without the
 header (a plain torch Adam state dict, e.g. the reference's ``opt.optimizer.state_dict()``) loads
 by index; missing extras start from the parameter as it is (residual 0 / master = param, carry 0).
@@ -28,14 +29,32 @@ from torch.optim import Optimizer
 FORMAT = 1
 
 
-def header(variant: int, ws: int, rank: int, owned, update=None, state_seed=None) -> dict:
+def header(variant: int, ws: int, rank: int, owned, update=None, state_seed=None,
+           master=None) -> dict:
     h = {"format": FORMAT, "variant": int(variant), "world_size": int(ws), "rank": int(rank),
          "local_param_indices": [int(i) for i in owned]}
     if update is not None:
         h["update"] = bool(update)
     if state_seed is not None:  # stochastic rounding of bf16 moments: the generator's seed
         h["state_seed"] = int(state_seed)
+    if master is not None:  # how bf16 parameters keep their master: "split", "fp32" or "none"
+        h["master"] = str(master)
     return h
+
+
+MASTER_KEYS = ("master_residual", "master_param")
+
+
+def check_master_free_load(saved: dict) -> None:
+    """A ``master="none"`` optimizer keeps no master: an entry that carries one (a checkpoint of a
+    split or fp32 master) would lose it without a word, so it is refused.  (The other way round
+    loads: the missing residual starts at 0.)"""
+    for k, entry in saved.items():
+        held = [name for name in MASTER_KEYS if isinstance(entry, dict) and name in entry]
+        if held:
+            raise ValueError(f"zero_amd: state entry {k} carries {held[0]!r}, which an optimizer "
+                             "with master='none' cannot keep: loading it would silently drop the "
+                             "master's precision (load it into master='split' or 'fp32')")
 
 
 def saved_state_seed(sd: dict):

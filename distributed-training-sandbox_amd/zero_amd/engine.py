@@ -37,7 +37,7 @@ import torch
 
 from . import _lib
 from .comm import StreamEvent, comm_stream, zs_dtype
-from ._update import UpdateCore, check_params
+from ._update import MASTERS, UpdateCore, check_master_free, check_params
 from .kernels import AdamSet, CopySet, SgdSet
 from .plan import Plan
 
@@ -313,12 +313,17 @@ class ShardEngine(UpdateCore):
         self.rank, self.dtype = rank, dtype
         self.es = params[0].element_size()
         self.mixed = dtype == torch.bfloat16  # bf16 params → an fp32 master in the shard
-        if master not in ("split", "fp32"):
-            raise ValueError(f"master must be 'split' or 'fp32' (got {master!r})")
+        if master not in MASTERS:
+            raise ValueError(f"master must be 'split', 'fp32' or 'none' (got {master!r})")
+        if master == "none":
+            check_master_free(kind, bool(carry), self.mixed)
         # split: the master is the bf16 param + an int16 residual (include/zero_amd.h
-        # ZS_BF16_SPLIT, 26 instead of 28 B/element per update); fp32: a separate fp32 array
+        # ZS_BF16_SPLIT, 26 instead of 28 B/element per update); fp32: a separate fp32 array;
+        # none: no master, the bf16 param is updated in place and rounded stochastically
+        # (ZS_BF16_SR, 22 B/element, 14 with bf16 moments)
         self.split = self.mixed and master == "split"
-        self.p_dtype = _lib.ZS_BF16_SPLIT if self.split else _lib.ZS_BF16
+        self.p_dtype = _lib.ZS_BF16_SR if master == "none" else \
+            _lib.ZS_BF16_SPLIT if self.split else _lib.ZS_BF16
         self.has_carry = bool(carry)
         self.comm = comm
         if ws > 1 and comm is None:
@@ -333,8 +338,9 @@ class ShardEngine(UpdateCore):
         self.pieces = self.plan.pieces(rank)
         # exp_avg, exp_avg_sq (+ ZeRO-1 carry, + fp32 master or its int16 residual) of the stream
         UpdateCore.__init__(self, kind, self.plan.stream_len(rank), dev, ws, group_of, len(params),
-                            split=self.split, fp32_master=self.mixed and not self.split,
-                            carry=carry, momentum=momentum, placement_tries=placement_tries,
+                            split=self.split, fp32_master=self.mixed and master == "fp32",
+                            master=master if master == "none" else None, carry=carry,
+                            momentum=momentum, placement_tries=placement_tries,
                             state_dtype=state_dtype, state_rounding=state_rounding,
                             state_seed=state_seed)
         if self.master is not None:
@@ -416,6 +422,8 @@ class ShardEngine(UpdateCore):
         """Rows of a bf16-param update: master read from the bf16 param ``hi`` + its residual
         (split) or from the fp32 master array; the updated bf16 param written to ``p_out``."""
         so64 = so.astype(np.uint64)
+        if self.master_free:  # the bf16 param is the only copy: read at ``hi``, written in place
+            return self._adam_rows(idx, g, hi, 0, p_out, so, n)
         if self.split:
             lo = np.uint64(self.lo.data_ptr()) + so64 * np.uint64(2)
             return self._adam_rows(idx, g, hi, lo, p_out, so, n)
@@ -427,6 +435,9 @@ class ShardEngine(UpdateCore):
         gz = getattr(self, "czdtype", self.zdtype)  # dtype of the reduced grad the update reads
         if self.kind == "sgd":
             return SgdSet(rows, gz, self.p_dtype)
+        if self.master_free:
+            return AdamSet(rows, gz, self.p_dtype, state_dtype=zs_dtype(self.state_dtype),
+                           wide_grads=gz == _lib.ZS_F32, state_rounding=self.state_rounding)
         return AdamSet(rows, gz, self.p_dtype, state_dtype=zs_dtype(self.state_dtype))
 
     # ------------------------------------------------------------------------------------------
@@ -524,6 +535,8 @@ class ShardEngine(UpdateCore):
     def _step_buckets(self, gptr, has, hparams_of, stream, grads=()):
         from .kernels import CHECK_EXTENTS
 
+        if self.master_free:
+            raise ValueError("zero_amd: master='none' needs the flat arena")
         if self.arena is None:
             self.arena, self.arena_placement = probed_zeros(self.plan.arena_elems, self.dtype,
                                                             self.device, self.placement_tries)

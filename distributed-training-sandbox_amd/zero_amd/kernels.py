@@ -5,7 +5,8 @@
 ``AdamSet``  — one launch of the fused Adam/AdamW update over a list of segments; its
 ``grad_sqnorm`` / ``run_clipped`` with ``sqnorm_reduce`` and ``clip_coef`` are global-norm clipping;
 ``run_guarded`` (``run_sr(guard=True)``) with ``clip_coef(skipped=)`` skips a step whose norm is not
-finite; ``run_sr`` with ``sr_keys`` stores bf16 moments with stochastic rounding.
+finite; ``run_sr`` with ``sr_keys`` stores bf16 moments with stochastic rounding; a set with
+``p_dtype=ZS_BF16_SR`` keeps no master and ``run_psr`` rounds its bf16 parameters stochastically.
 ``SgdSet``   — the same tables with torch.optim.SGD's update (momentum, Nesterov); ``sgd_hparams``.
 ``adam_step`` — the same update over one contiguous range (zs_adam_step_ex; no table to keep).
 
@@ -141,24 +142,38 @@ class AdamSet:
 
     ``state_dtype``: None / ``ZS_F32`` — the ``m`` and ``v`` columns point at fp32 arrays — or
     ``ZS_BF16``: at bf16 arrays (zs_adamset_create_ex: bf16 moments; no vmax, no carry, no
-    amsgrad)."""
+    amsgrad).
+
+    ``p_dtype=ZS_BF16_SR`` — master-free: row i's ``master`` and ``p_out`` are both the bf16
+    parameter, updated in place; ``master_out``, ``vmax`` and ``carry`` are 0; ``g`` is bf16, or
+    fp32 with ``wide_grads=True``.  ``run_psr`` is the only way to run it.  ``state_rounding``
+    ("nearest" / "stochastic") says how its ``ZS_BF16`` moments are stored."""
 
     FIELDS = ("g", "master", "master_out", "p_out", "m", "v", "vmax", "carry", "n")
 
     _CREATE = "zs_adamset_create"
 
     def __init__(self, segs: np.ndarray, g_dtype: int, p_dtype: int = _lib.ZS_BF16, *,
-                 wide_grads: bool = False, state_dtype: int | None = None):
+                 wide_grads: bool = False, state_dtype: int | None = None,
+                 state_rounding: str = "nearest"):
         state_dtype = _lib.ZS_F32 if state_dtype is None else int(state_dtype)
-        if int(p_dtype) == _lib.ZS_BF16_SPLIT and int(g_dtype) == _lib.ZS_F32 and not wide_grads:
+        psr = int(p_dtype) == _lib.ZS_BF16_SR
+        if state_rounding not in ("nearest", "stochastic"):
+            raise ValueError(f"zero_amd: state_rounding must be 'nearest' or 'stochastic', got "
+                             f"{state_rounding!r}")
+        if state_rounding == "stochastic" and not (psr and state_dtype == _lib.ZS_BF16):
             raise _lib.ZeroAmdError(self._CREATE, _lib.ZS_ERR_INVALID,
-                                    "ZS_BF16_SPLIT needs bf16 grads (fp32 gradient buffers: "
-                                    "wide_grads=True)")
+                                    "state_rounding is a ZS_BF16_SR set's with ZS_BF16 state (other "
+                                    "sets choose by run / run_sr)")
+        if int(p_dtype) in (_lib.ZS_BF16_SPLIT, _lib.ZS_BF16_SR) and int(g_dtype) == _lib.ZS_F32 and not wide_grads:
+            raise _lib.ZeroAmdError(self._CREATE, _lib.ZS_ERR_INVALID,
+                                    "ZS_BF16_SPLIT / ZS_BF16_SR need bf16 grads (fp32 gradient "
+                                    "buffers: wide_grads=True)")
         segs = np.ascontiguousarray(np.asarray(segs, dtype=np.uint64).reshape(-1, 9))
         arr = (AdamSeg * max(len(segs), 1))()
         ctypes.memmove(arr, segs.ctypes.data, segs.nbytes)
         h = ctypes.c_void_p()
-        if state_dtype == _lib.ZS_F32:
+        if state_dtype == _lib.ZS_F32 and not (psr and self._CREATE == "zs_adamset_create"):
             _lib.call(self._CREATE, arr, len(segs), int(g_dtype), int(p_dtype), ctypes.byref(h))
         elif self._CREATE != "zs_adamset_create":
             raise _lib.ZeroAmdError(self._CREATE, _lib.ZS_ERR_INVALID,
@@ -168,6 +183,9 @@ class AdamSet:
                       state_dtype, ctypes.byref(h))
         self.state_dtype = state_dtype
         self._h = h
+        if state_rounding == "stochastic":
+            _lib.call("zs_adamset_set_state_rounding", h, 1)
+        self.state_rounding = state_rounding
         self.nseg = len(segs)
         self._g = np.ascontiguousarray(segs[:, 0])  # the gradients bound now, per input row
         self._n = segs[:, 8].astype(np.int64)
@@ -239,6 +257,15 @@ class AdamSet:
                   ctypes.byref(hp), ptr, int(m_base), int(keys[0]), int(keys[1]),
                   stream_handle(stream))
 
+    def run_psr(self, hp: AdamHParams, m_base: int, keys, stream, coef=None, guard=False) -> None:
+        """One step of a ``ZS_BF16_SR`` set (zs_adamset_run_psr): the bf16 parameters are updated
+        in place and rounded stochastically, their draws keyed by ``sr_pkeys(keys)``; ``keys``,
+        ``m_base``, ``coef`` and ``guard`` as ``run_sr`` (``m_base`` counts elements of the moment
+        array's own type, fp32 or bf16)."""
+        ptr = None if coef is None else coef if isinstance(coef, int) else coef.data_ptr()
+        _lib.call("zs_adamset_run_psr", self._h, ctypes.byref(hp), ptr, int(bool(guard)),
+                  int(m_base), int(keys[0]), int(keys[1]), stream_handle(stream))
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib is not None:
@@ -254,6 +281,15 @@ def sr_keys(seed: int, step: int):
     of the launched part (zs_sr_keys; a host function)."""
     k0, k1 = ctypes.c_uint32(), ctypes.c_uint32()
     _lib.call("zs_sr_keys", int(seed), int(step), ctypes.byref(k0), ctypes.byref(k1))
+    return k0.value, k1.value
+
+
+def sr_pkeys(keys):
+    """(pkey0, pkey1): the keys of the parameter's draw in a master-free launch, from the
+    launch's ``keys`` (zs_sr_pkeys; a host function).  The parameter of element ``e`` rounds with
+    ``sr_bits(e, sr_pkeys(keys)) & 0xFFFF``."""
+    k0, k1 = ctypes.c_uint32(), ctypes.c_uint32()
+    _lib.call("zs_sr_pkeys", int(keys[0]), int(keys[1]), ctypes.byref(k0), ctypes.byref(k1))
     return k0.value, k1.value
 
 

@@ -65,12 +65,12 @@ from torch.optim import Optimizer
 from torch.utils.weak import WeakIdKeyDictionary
 
 from . import _lib
-from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_F32
+from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_BF16_SR, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
 from ._sharded import group_hparams, optimizer_kind
-from ._update import (GradClip, UpdateCore, check_bf16_state_group, check_max_grad_norm,
-                      check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
+from ._update import (GradClip, UpdateCore, check_bf16_state_group, check_master_free,
+                      check_master_free_group, check_max_grad_norm, check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
                       owner_range)
 from .comm import STREAM_SYNC, RcclComm, Sync, comm_stream, sync_kind, zs_dtype
 from .engine import ALIGN_ELEMS
@@ -1840,7 +1840,7 @@ class ShardedOptimizer:
                  stream_sync: str = STREAM_SYNC, grad_accumulation: bool = False,
                  accumulation_dtype=None, state_dtype=None, state_rounding: str | None = None,
                  state_seed: int = 0, max_grad_norm: float | None = None,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, master: str = "split"):
         # global gradient-norm clipping inside step() (update mode; None = off): a plain attribute,
         # re-checked at every step().  skip_nonfinite (with it; Adam): a step whose gradient norm
         # is not finite is skipped on the device.  Both are refused here where they
@@ -1886,10 +1886,25 @@ class ShardedOptimizer:
         self._A = None
         # "adam" or "sgd" (TypeError for anything else); reference mode never updates either
         self._kind = optimizer_kind(optimizer)
+        # master (update mode, bf16 chunks): "split" — the fp32 master is the bf16 chunk + an int16
+        # residual — or "none": no master at all, the bf16 chunk is updated in place and rounded
+        # stochastically, keyed by state_seed.  Refused here where it does not apply
+        if master not in ("split", "none"):
+            raise ValueError(f"master must be 'split' or 'none' (got {master!r})")
+        self._master = master
+        if master == "none":
+            if not update:
+                raise ValueError("zero_amd: master='none' applies to update mode (reference mode "
+                                 "never updates and holds no master)")
+            check_master_free(self._kind, False,
+                              all(p.dtype == torch.bfloat16 for g in optimizer.param_groups
+                                  for p in g["params"]))
         for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
             hpd = group_hparams(self._kind, group, optimizer)
             if self.state_dtype == torch.bfloat16 and self._kind == "adam":
                 check_bf16_state_group(hpd, self.state_rounding)
+            if master == "none":
+                check_master_free_group(hpd)
         if self.state_dtype == torch.bfloat16 and self._kind == "sgd":
             raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with "
                              "torch.optim.SGD (bf16 moments are Adam's)")
@@ -1961,9 +1976,11 @@ class ShardedOptimizer:
         # the update core over the chunk arena: exp_avg, exp_avg_sq (SGD: one momentum buffer if
         # any group has a momentum) + for bf16 params the split master's int16 residual (the fp32
         # master is the bf16 chunk + residual, include/zero_amd.h ZS_BF16_SPLIT; starts at 0)
-        self._split = ar.dtype == torch.bfloat16
+        self._master_free = self._master == "none"
+        self._split = ar.dtype == torch.bfloat16 and not self._master_free
         self._core = UpdateCore(self._kind, ar.total, ar.device, self.world_size, self._group_of,
                                 len(self.params), split=self._split,
+                                master="none" if self._master_free else None,
                                 state_dtype=self.state_dtype,
                                 state_rounding=self.state_rounding, state_seed=self.state_seed,
                                 momentum=any(g.get("momentum", 0) != 0 for g in self._groups))
@@ -2177,7 +2194,9 @@ class ShardedOptimizer:
         else:
             rows[:, 0] = [red.local_grads[i].data_ptr() for i in idx]
         pp = np.uint64(ar.P.data_ptr()) + so * np.uint64(es)
-        if self._split:  # master = bf16 chunk (in and out) + int16 residual
+        if self._master_free:  # the bf16 chunk is the only copy: read and written in place
+            rows[:, 1], rows[:, 3] = pp, pp
+        elif self._split:  # master = bf16 chunk (in and out) + int16 residual
             rows[:, 1], rows[:, 3] = pp, pp
             rows[:, 2] = np.uint64(self._core.lo.data_ptr()) + so * np.uint64(2)
         else:
@@ -2189,9 +2208,11 @@ class ShardedOptimizer:
     def _new_set(self, rows, acc: bool):
         """The update's kernel set over ``rows``; ``acc``: fp32 gradients (the accumulation arena)."""
         gz = ZS_F32 if acc else ZS_BF16 if (
-            self._split or (self._grad_comm and self.world_size > 1)) else ZS_F32
+            self._split or self._master_free or (self._grad_comm and self.world_size > 1)) else ZS_F32
         kw = {} if self._kind == "sgd" else dict(state_dtype=zs_dtype(self.state_dtype))
         mk = SgdSet if self._kind == "sgd" else AdamSet
+        if self._master_free:
+            return mk(rows, gz, ZS_BF16_SR, wide_grads=acc, state_rounding=self.state_rounding, **kw)
         if self._split:
             return mk(rows, gz, ZS_BF16_SPLIT, wide_grads=acc, **kw)
         return mk(rows, gz, **kw)
@@ -2202,6 +2223,9 @@ class ShardedOptimizer:
             for group in self._groups:
                 check_bf16_state_group(group_hparams(self._kind, group, self.optimizer),
                                        self.state_rounding)
+        if self._master_free:
+            for group in self._groups:
+                check_master_free_group(group_hparams(self._kind, group, self.optimizer))
         if red.incomplete():
             raise RuntimeError(
                 "zero_amd ZeRO-3: a backward did not finish (it raised), so the accumulated "
@@ -2393,9 +2417,10 @@ class ShardedOptimizer:
 
     # checkpointing (zero_amd/checkpoint.py) -------------------------------------------------------
     def _ckpt_header(self):
-        seed = self.state_seed if self.state_rounding == "stochastic" else None
+        keyed = self.state_rounding == "stochastic" or self._master == "none"
         return ckpt.header(3, self.world_size, self.rank, self.local_param_indices,
-                           update=self.update, state_seed=seed)
+                           update=self.update, state_seed=self.state_seed if keyed else None,
+                           master=self._master if self.update else None)
 
     @on_param_device
     def state_dict(self):
@@ -2424,6 +2449,8 @@ class ShardedOptimizer:
         the next gather is ordered after that copy; a caller that edits the shards at any other
         time between two steps (after an eval forward, say) calls ``mark_params_changed()``."""
         ckpt.check_header(state_dict, self._ckpt_header())
+        if self._master == "none":
+            ckpt.check_master_free_load(state_dict.get("state", {}))
         self.mark_params_changed()
         torch.cuda.synchronize(self._arena.device)
         ckpt.load_param_groups(self.optimizer, state_dict)
@@ -2433,7 +2460,7 @@ class ShardedOptimizer:
         if not self.update:
             return
         seed = ckpt.saved_state_seed(state_dict)
-        if seed is not None and self.state_rounding == "stochastic":
+        if seed is not None and (self.state_rounding == "stochastic" or self._master == "none"):
             self.state_seed = self._core.state_seed = seed  # the saved run's bits continue
         saved = state_dict.get("state", {})
         params = ckpt.inner_params(self.optimizer)

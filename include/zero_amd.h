@@ -43,8 +43,10 @@ enum zs_dtype {
   ZS_F32 = 0,
   ZS_BF16 = 1,
   ZS_U8 = 2,        /* raw bytes (fp8 payloads); collectives only */
-  ZS_BF16_SPLIT = 3 /* zs_adamset_create p_dtype only: the fp32 master stored as the bf16 param
-                       (its round-to-nearest-even high half) + a 16-bit residual, see zs_adam_seg */
+  ZS_BF16_SPLIT = 3, /* zs_adamset_create p_dtype only: the fp32 master stored as the bf16 param
+                        (its round-to-nearest-even high half) + a 16-bit residual, see zs_adam_seg */
+  ZS_BF16_SR = 4     /* zs_adamset_create_ex p_dtype only: no master at all, the bf16 param updated
+                        in place with stochastic rounding, see zs_adamset_run_psr */
 };
 
 /* Shard layouts (SURVEY.md §7 "Two shard layouts"). */
@@ -402,6 +404,34 @@ int zs_adamset_run_guarded(const zs_adamset* as, const zs_adam_hparams* hp, cons
                            uintptr_t stream);
 int zs_adamset_run_sr_guarded(const zs_adamset* as, const zs_adam_hparams* hp, const float* coef,
                               uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream);
+
+/* Master-free bf16 parameters (additive in ABI v13).  A set made by zs_adamset_create_ex with
+ * p_dtype ZS_BF16_SR keeps no master and no residual: a seg's `master` is the bf16 param (read),
+ * `p_out` the same address (written), master_out = vmax = carry = 0; g is bf16 or fp32; anything
+ * else, and zs_sgdset_create, is ZS_ERR_INVALID.  One element: p, g, m and v as stored are widened
+ * to fp32 (exact), zs_adamset_run's fp32 rule runs unchanged (clip coefficient, maximize, coupled
+ * and decoupled weight decay), m and v are stored as the set's state says (fp32; ZS_BF16 rounded to
+ * nearest, or stochastically with the draws of zs_adamset_run_sr after
+ * zs_adamset_set_state_rounding(as, 1)), and the new parameter with bits u is stored as the bf16
+ * code (u + r16p) >> 16 (a NaN as zs_adamset_run stores it): unbiased, so updates below half a bf16
+ * ulp move the parameter in expectation instead of being lost.  14 B/element with bf16 moments and
+ * gradients (18 with the split master), 22 with fp32 moments (26).
+ *   r16p = zs_sr_bits(e, pkey0, pkey1) & 0xFFFF, (pkey0, pkey1) = zs_sr_pkeys(key0, key1):
+ *   pkey0 = lowbias32(key0 ^ 0x85EBCA6B), pkey1 = lowbias32(key1 + 0xC2B2AE35)
+ * — independent of the m and v halves of zs_sr_bits(e, key0, key1).  e = (the element's address in
+ * m - m_base) / the element size of m (4 or 2).
+ * zs_adamset_run_psr is the only way to run such a set: coef NULL = unclipped, otherwise as
+ * zs_adamset_run_clipped, and with guard != 0 as zs_adamset_run_guarded (a NaN coefficient: nothing
+ * is read or written; the step's keys are consumed all the same).  ZS_ERR_INVALID, nothing
+ * launched: any other set, guard without coef, hp->amsgrad, a segment whose m lies below m_base or
+ * not a whole number of elements from it.  zs_adamset_run, _run_clipped, _run_guarded, _run_sr and
+ * _run_sr_guarded return ZS_ERR_INVALID on a ZS_BF16_SR set.  zs_adamset_set_grads,
+ * zs_adamset_sqnorm_partials, zs_adamset_grad_sqnorm, zs_adamset_stats and zs_adamset_destroy work
+ * on it.  zs_sr_pkeys is a host function. */
+int zs_adamset_run_psr(const zs_adamset* as, const zs_adam_hparams* hp, const float* coef, int guard,
+                       uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream);
+int zs_adamset_set_state_rounding(zs_adamset* as, int stochastic);
+int zs_sr_pkeys(uint32_t key0, uint32_t key1, uint32_t* pkey0, uint32_t* pkey1);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Fused SGD (momentum, Nesterov), additive in ABI v13.  Replaces torch.optim.SGD.step on the    */

@@ -55,6 +55,18 @@ const struct {
     {4294979641ull, 4294967297ull, 1099511627783ull, 3020340486u, 130576045u, 230462222u},
 };
 
+// the parameter's draw of a master-free launch (tests/_psr_oracle.py):
+// key0, key1, pkey0, pkey1, e, bits(e, pkey0, pkey1) & 0xFFFF
+const struct {
+  uint32_t k0, k1, kp0, kp1;
+  uint64_t e;
+  uint32_t r16;
+} kPkat[] = {
+    {1753845952u, 2988215890u, 3114669924u, 324057975u, 0ull, 30234u},
+    {1753845952u, 2988215890u, 3114669924u, 324057975u, 4294967296ull, 42996u},
+    {3020340486u, 130576045u, 3101105534u, 2236145741u, 1099511627783ull, 22266u},
+};
+
 }  // namespace
 
 int main() {
@@ -67,7 +79,15 @@ int main() {
     CHECK(zs_sr_bits(k.e, k0, k1, &r) == ZS_OK, "zs_sr_bits failed");
     CHECK(r == k.r, "bits(%llu) = %u, expected %u", (unsigned long long)k.e, r, k.r);
   }
+  for (const auto& k : kPkat) {
+    uint32_t kp0 = 0, kp1 = 0, r = 0;
+    CHECK(zs_sr_pkeys(k.k0, k.k1, &kp0, &kp1) == ZS_OK, "zs_sr_pkeys failed");
+    CHECK(kp0 == k.kp0 && kp1 == k.kp1, "pkeys(%u, %u) = %u, %u", k.k0, k.k1, kp0, kp1);
+    CHECK(zs_sr_bits(k.e, kp0, kp1, &r) == ZS_OK && (r & 0xFFFFu) == k.r16,
+          "the parameter's bits(%llu) = %u, expected %u", (unsigned long long)k.e, r & 0xFFFFu, k.r16);
+  }
   uint32_t x = 0;
+  CHECK(zs_sr_pkeys(0, 0, nullptr, &x) == ZS_ERR_INVALID, "zs_sr_pkeys(NULL) was accepted");
   CHECK(zs_sr_keys(0, 1, nullptr, &x) == ZS_ERR_INVALID, "zs_sr_keys(NULL) was accepted");
   CHECK(zs_sr_bits(0, 0, 0, nullptr) == ZS_ERR_INVALID, "zs_sr_bits(NULL) was accepted");
 

@@ -17,8 +17,15 @@ run through zs_adamset_run_sr with torch's default betas; the verdict: is the st
 than the fp32-state step in every round, and what is its ratio to the nearest one beside the spread
 of the two equal nearest sets?
 
+``--psr`` (master-free bf16 parameters, ``master="none"``; --kind split): the split-master sets with
+bf16-stochastic moments (18 B/element, twice: the A/B's own spread) and with fp32 moments (26)
+against master-free sets over the same rows — the same parameter arena and moment arrays, no
+residual — with bf16-stochastic moments (14) and with fp32 moments (22), interleaved; the verdict:
+is each master-free step faster than its split twin in every round by more than the spread of the
+two equal split sets, and what are the time and byte ratios?
+
 Usage: python tools/state_dtype_ab.py [--rounds 7] [--steps 30] [--kind split|fp32]
-                                      [--config C4] [--sr] [--out FILE.json]
+                                      [--config C4] [--sr | --psr] [--out FILE.json]
 ``--kind split``: bf16 parameters with the split master, bf16 gradients (26 against 18 B/element);
 ``--kind fp32``: fp32 parameters and gradients (28 against 20).
 """
@@ -35,6 +42,7 @@ sys.path.insert(0, str(REPO / "distributed-training-sandbox_amd"))
 PEAK_GBS = 8000.0
 SETTINGS = ("f32", "f32_again", "bf16")
 SR_SETTINGS = ("f32", "bf16", "bf16_again", "bf16_sr")
+PSR_SETTINGS = ("split_sr", "none_sr", "split_sr_again", "split_f32", "none_f32")
 
 
 def main():
@@ -45,9 +53,11 @@ def main():
     ap.add_argument("--config", default="C4", choices=["C2", "C3", "C4", "C5"])
     ap.add_argument("--port", type=int, default=29551)
     ap.add_argument("--sr", action="store_true")
+    ap.add_argument("--psr", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    SETTINGS = SR_SETTINGS if args.sr else globals()["SETTINGS"]
+    SETTINGS = SR_SETTINGS if args.sr else PSR_SETTINGS if args.psr else globals()["SETTINGS"]
+    assert not (args.sr and args.psr) and (not args.psr or args.kind == "split")
     assert args.rounds >= 5 and args.steps >= 20, "at least 5 rounds of at least 20 steps"
 
     import numpy as np
@@ -86,7 +96,17 @@ def main():
         half[:, col] = base + (rows[:, col] - base) // np.uint64(2)
     mk16 = lambda: AdamSet(half, eng.zdtype, eng.p_dtype, state_dtype=_lib.ZS_BF16)  # noqa: E731
     sets = {"f32": AdamSet(rows, eng.zdtype, eng.p_dtype)}
-    if args.sr:
+    if args.psr:
+        def free(r, **kw):  # the same rows without a master: the bf16 parameter in and out
+            r = r.copy()
+            r[:, 2] = 0
+            assert np.array_equal(r[:, 1], r[:, 3])
+            return AdamSet(r, eng.zdtype, _lib.ZS_BF16_SR, **kw)
+
+        sets = {"split_sr": mk16(), "split_sr_again": mk16(), "split_f32": sets["f32"],
+                "none_sr": free(half, state_dtype=_lib.ZS_BF16, state_rounding="stochastic"),
+                "none_f32": free(rows)}
+    elif args.sr:
         sets.update(bf16=mk16(), bf16_again=mk16(), bf16_sr=mk16())
     else:
         sets.update(f32_again=AdamSet(rows, eng.zdtype, eng.p_dtype), bf16=mk16())
@@ -97,11 +117,14 @@ def main():
         ev = []
         for _ in range(n):
             count[s] += 1
-            h = adam_hparams(1e-3, 0.9, 0.999 if s == "bf16_sr" else 0.95, 1e-8, 0.0, count[s])
-            keys = sr_keys(0, count[s]) if s == "bf16_sr" else None
+            sr_state = s in ("bf16_sr", "split_sr", "split_sr_again", "none_sr")
+            h = adam_hparams(1e-3, 0.9, 0.999 if sr_state else 0.95, 1e-8, 0.0, count[s])
+            keys = sr_keys(0, count[s]) if sr_state or s == "none_f32" else None
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
-            if keys is None:
+            if s.startswith("none"):
+                sets[s].run_psr(h, m_base, keys, stream)
+            elif keys is None:
                 sets[s].run(h, stream)
             else:
                 sets[s].run_sr(h, m_base, keys, stream)
@@ -133,6 +156,30 @@ def main():
             "bytes_per_element": nbytes / n_el, "gbs": gbs, "frac_of_8tbs": gbs / PEAK_GBS,
             "frac_round_min_max": [nbytes / m / 1e6 / PEAK_GBS
                                    for m in (max(rounds[s]), min(rounds[s]))]})
+    if args.psr:
+        by = {x["setting"]: x for x in summary["settings"]}
+        same = [abs(a - b) for a, b in zip(rounds["split_sr"], rounds["split_sr_again"])]
+        split_ms = float(np.median(rounds["split_sr"] + rounds["split_sr_again"]))
+        gain_sr = [min(a, b) - c for a, b, c in zip(rounds["split_sr"], rounds["split_sr_again"],
+                                                    rounds["none_sr"])]
+        gain_f32 = [a - c for a, c in zip(rounds["split_f32"], rounds["none_f32"])]
+        summary["verdict"] = {
+            "split_vs_split_abs_diff_ms_per_round": same, "ab_spread_ms": max(same),
+            "spread_over_split": max(same) / split_ms,
+            "none_sr_gain_ms_per_round": gain_sr, "none_f32_gain_ms_per_round": gain_f32,
+            "none_sr_faster_in_every_round_by_more_than_the_spread": bool(min(gain_sr) > max(same)),
+            "none_f32_faster_in_every_round_by_more_than_the_spread": bool(min(gain_f32) > max(same)),
+            "time_ratio_none_sr_over_split_sr": by["none_sr"]["median_ms"] / split_ms,
+            "bytes_ratio_none_sr_over_split_sr": by["none_sr"]["bytes"] / by["split_sr"]["bytes"],
+            "time_ratio_none_f32_over_split_f32":
+                by["none_f32"]["median_ms"] / by["split_f32"]["median_ms"],
+            "bytes_ratio_none_f32_over_split_f32": by["none_f32"]["bytes"] / by["split_f32"]["bytes"]}
+        print(json.dumps(summary), flush=True)
+        if args.out:
+            Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.out).write_text(json.dumps(summary, indent=1) + "\n")
+        dist.destroy_process_group()
+        return
     if args.sr:
         by = {x["setting"]: x for x in summary["settings"]}
         same = [abs(a - b) for a, b in zip(rounds["bf16"], rounds["bf16_again"])]
