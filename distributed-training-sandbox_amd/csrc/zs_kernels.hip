@@ -1056,6 +1056,146 @@ __global__ __launch_bounds__(kThreads) void sqnorm_reduce_kernel(
   if (threadIdx.x == 0) *sumsq = float(b);
 }
 
+// ----------------------------------------------------------------------------------------------
+// the same pass keyed by segment (per-parameter gradient norms)
+// ----------------------------------------------------------------------------------------------
+// grad_sqnorm_kernel's reads and arithmetic with another reduction shape: a table entry (the vector
+// or the scalar part of one input segment) has slots = min(its chunks, cap) partials of its own,
+// and the workgroup of slot j sums chunks j, j + slots, ... of that entry alone.  slot_prefix
+// (entries + 1) maps a workgroup to (entry, j); slot_out[entry] is where the entry's slots start
+// in the set's partials (input order; a segment's vector part, then its scalar part).  An entry's
+// slot count and every slot's value depend on that segment alone: neither its neighbours, the
+// device nor zs_tune enter.  An entry without a gradient is not read: its slots get +0.0.
+constexpr int64_t kSqnormSegVecSlots = 128, kSqnormSegScaSlots = 16;
+
+// grad_sqnorm_kernel's chunk body (kept apart from it, so that the instances of that kernel stay
+// the parent's instruction for instruction): one lane's fp32 sum of squares over the chunk at
+// element e0 of a vector-table segment (g, n) — all of the chunk's loads, then fmaf(x, x, acc) over
+// its 4 * adam_groups() terms; groups past n contribute +0.  NT: the loads' cache policy
+template <typename GT, bool SPLIT, bool NT>
+__device__ __forceinline__ float chunk_sumsq(const GT* __restrict__ g, int64_t n, int64_t e0) {
+  constexpr int G = adam_groups(SPLIT);
+  constexpr bool G32 = sizeof(GT) == 4;
+  uint4 r[G];  // bf16: x, y hold the four elements
+  if (e0 + adam_chunk(SPLIT) <= n) {
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const GT* p = g + e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
+      if constexpr (G32) {
+        r[u] = ld16<NT>(p);
+      } else {
+        const uint2 d = ld8<NT>(p);
+        r[u] = make_uint4(d.x, d.y, 0u, 0u);
+      }
+    }
+  } else {  // the segment's last chunk: groups past n contribute +0
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const int64_t i = e0 + (int64_t(u) * kThreads + threadIdx.x) * 4;
+      r[u] = make_uint4(0u, 0u, 0u, 0u);
+      if (i < n) {
+        if constexpr (G32) {
+          r[u] = ld16<NT>(g + i);
+        } else {
+          const uint2 d = ld8<NT>(g + i);
+          r[u] = make_uint4(d.x, d.y, 0u, 0u);
+        }
+      }
+    }
+  }
+  float acc = 0.0f;
+#pragma unroll
+  for (int u = 0; u < G; ++u) {
+    float x[4];
+    if constexpr (G32) unpack4(r[u], x);
+    else unpack_bf16x4(make_uint2(r[u].x, r[u].y), x);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc = fmaf(x[j], x[j], acc);
+  }
+  return acc;
+}
+
+// the entry of workgroup b: slot_prefix[entry] <= b < slot_prefix[entry + 1]
+__device__ __forceinline__ int64_t slot_entry(const int64_t* __restrict__ slot_prefix,
+                                              int64_t nent, int64_t b) {
+  int64_t e = 0, hi = nent;
+  while (hi - e > 1) {
+    const int64_t mid = (e + hi) >> 1;
+    if (slot_prefix[mid] <= b) e = mid;
+    else hi = mid;
+  }
+  return e;
+}
+
+template <typename GT, bool SPLIT, bool NT>
+__global__ __launch_bounds__(kThreads) void grad_sqnorm_segs_kernel(
+    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ slot_prefix,
+    const int64_t* __restrict__ slot_out, int64_t nent, double* __restrict__ partials) {
+  const int64_t e = slot_entry(slot_prefix, nent, blockIdx.x);
+  const int64_t j = int64_t(blockIdx.x) - slot_prefix[e];
+  const int64_t slots = slot_prefix[e + 1] - slot_prefix[e];
+  const GT* g = static_cast<const GT*>(segs[e].g);
+  const int64_t n = segs[e].n;
+  double total = 0.0;
+  if (g) {  // (uniform per workgroup)
+    const int64_t chunks = (n + adam_chunk(SPLIT) - 1) / adam_chunk(SPLIT);
+    for (int64_t c = j; c < chunks; c += slots)
+      total += double(chunk_sumsq<GT, SPLIT, NT>(g, n, c * adam_chunk(SPLIT)));
+  }
+  const double b = block_sum(total);
+  if (threadIdx.x == 0) partials[slot_out[e] + j] = b;
+}
+
+template <typename GT>
+__global__ __launch_bounds__(kThreads) void grad_sqnorm_segs_scalar_kernel(
+    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ slot_prefix,
+    const int64_t* __restrict__ slot_out, int64_t nent, double* __restrict__ partials) {
+  const int64_t e = slot_entry(slot_prefix, nent, blockIdx.x);
+  const int64_t j = int64_t(blockIdx.x) - slot_prefix[e];
+  const int64_t slots = slot_prefix[e + 1] - slot_prefix[e];
+  const void* g = segs[e].g;
+  const int64_t n = segs[e].n;
+  double total = 0.0;
+  if (g) {
+    const int64_t chunks = (n + kThreads - 1) / kThreads;
+    for (int64_t c = j; c < chunks; c += slots) {
+      const int64_t i = c * kThreads + threadIdx.x;
+      if (i < n) {
+        const float x = load_g1<GT>(g, i);
+        total += double(fmaf(x, x, 0.0f));
+      }
+    }
+  }
+  const double b = block_sum(total);
+  if (threadIdx.x == 0) partials[slot_out[e] + j] = b;
+}
+
+// Per-parameter sums over a CSR of slot ranges: workgroup i adds parameter i's ranges
+// row_ptr[i] .. row_ptr[i + 1] in that order, thread t taking slots t, t + 256, ... of each range
+// into one running double, then block_sum; out[i] is the fp32 rounding.  No range: +0.0.
+__global__ __launch_bounds__(kThreads) void sqnorm_reduce_params_kernel(
+    const double* __restrict__ partials, const int64_t* __restrict__ row_ptr,
+    const int64_t* __restrict__ slot_lo, const int64_t* __restrict__ slot_n,
+    float* __restrict__ out) {
+  double t = 0.0;
+  for (int64_t r = row_ptr[blockIdx.x]; r < row_ptr[blockIdx.x + 1]; ++r) {
+    const double* p = partials + slot_lo[r];
+    for (int64_t i = threadIdx.x; i < slot_n[r]; i += kThreads) t += p[i];
+  }
+  const double b = block_sum(t);
+  if (threadIdx.x == 0) out[blockIdx.x] = float(b);
+}
+
+// clip_coef_kernel's norm line per element: norms[i] = float(sqrt(double(sumsq[i])) / grad_div)
+__global__ __launch_bounds__(kThreads) void param_norms_kernel(const float* __restrict__ sumsq,
+                                                               int64_t n, double grad_div,
+                                                               float* __restrict__ norms) {
+#pragma clang fp contract(off)
+  for (int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x; i < n;
+       i += int64_t(gridDim.x) * kThreads)
+    norms[i] = float(sqrt(double(sumsq[i])) / grad_div);
+}
+
 // clip_grad_norm_'s coefficient (error_if_nonfinite=False): norm = sqrt(sumsq) / grad_div in
 // double, rounded once; coef = min(1, max_norm / (norm + 1e-6)) in fp32, a NaN norm giving a NaN
 // coefficient as torch's clamp does.  One lane.
@@ -1789,6 +1929,12 @@ struct zs_adamset {
   int64_t nvec = 0, vec_chunks = 0, nsca = 0, sca_chunks = 0, elems = 0, bytes = 0;
   // zs_adamset_grad_sqnorm: partials (= workgroups) of the vector and of the scalar table
   int64_t sq_vec = 0, sq_sca = 0;
+  // zs_adamset_grad_sqnorm_segs: per table, entries + 1 slot prefixes followed by each entry's
+  // first slot in the set's partials (one upload); the slots of each table; seg_off (inputs + 1)
+  int64_t* d_vec_slots = nullptr;
+  int64_t* d_sca_slots = nullptr;
+  int64_t sqs_vec = 0, sqs_sca = 0;
+  std::vector<int64_t> seg_off;
   int g_dtype = ZS_F32, p_dtype = ZS_BF16, has_carry = 0, has_vmax = 0;
   // zs_sgdset_create: an SGD set (field m is the momentum buffer, has_mom: it has one)
   int sgd = 0, has_mom = 0;
@@ -2613,6 +2759,28 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   as->sca_chunks = spre.back();
   as->sq_vec = std::min(as->vec_chunks, kSqnormVecPartials);
   as->sq_sca = std::min(as->sca_chunks, kSqnormScaPartials);
+  // the segmented pass: slots per entry from the entry's own chunks, laid out by input segment
+  // (vector part, then scalar part)
+  std::vector<int64_t> seg_off(size_t(n) + 1, 0);
+  std::vector<int64_t> vslots(2 * vec.size() + 1, 0), sslots(2 * sca.size() + 1, 0);
+  for (size_t e = 0; e < vec.size(); ++e) {
+    const int64_t k = std::min(vpre[e + 1] - vpre[e], kSqnormSegVecSlots);
+    vslots[e + 1] = vslots[e] + k;
+    seg_off[size_t(vec_in[e]) + 1] += k;
+  }
+  for (size_t e = 0; e < sca.size(); ++e) {
+    const int64_t k = std::min(spre[e + 1] - spre[e], kSqnormSegScaSlots);
+    sslots[e + 1] = sslots[e] + k;
+    seg_off[size_t(sca_in[e]) + 1] += k;
+  }
+  for (size_t i = 0; i < size_t(n); ++i) seg_off[i + 1] += seg_off[i];
+  for (size_t e = 0; e < vec.size(); ++e)
+    vslots[vec.size() + 1 + e] = seg_off[size_t(vec_in[e])];
+  for (size_t e = 0; e < sca.size(); ++e)  // behind the segment's vector slots, if it has any
+    sslots[sca.size() + 1 + e] = seg_off[size_t(sca_in[e]) + 1] - (sslots[e + 1] - sslots[e]);
+  as->sqs_vec = vslots[vec.size()];
+  as->sqs_sca = sslots[sca.size()];
+  as->seg_off = std::move(seg_off);
   as->elems = elems;
   as->bytes = bytes;
   as->g_dtype = g_dtype;
@@ -2634,12 +2802,14 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
     rc = upload(vec, &as->d_vec);
     if (rc == ZS_OK) rc = upload(vpre, &as->d_vec_prefix);
     if (rc == ZS_OK) rc = upload(vec_in, &as->d_vec_in);
+    if (rc == ZS_OK) rc = upload(vslots, &as->d_vec_slots);
   }
   if (rc == ZS_OK && as->nsca) {
     rc = upload(sca, &as->d_sca);
     if (rc == ZS_OK) rc = upload(spre, &as->d_sca_prefix);
     if (rc == ZS_OK) rc = upload(sca_in, &as->d_sca_in);
     if (rc == ZS_OK) rc = upload(sca_goff, &as->d_sca_goff);
+    if (rc == ZS_OK) rc = upload(sslots, &as->d_sca_slots);
   }
   if (rc != ZS_OK) {
     zs_adamset_destroy(as);
@@ -2874,6 +3044,82 @@ int zs_sqnorm_reduce(const double* partials, int64_t n, float* sumsq, uintptr_t 
   return ZS_OK;
 }
 
+int zs_adamset_sqnorm_seg_partials(const zs_adamset* as, int64_t* n, int64_t* seg_off) {
+  ZS_REQUIRE(as && n && seg_off, "zs_adamset_sqnorm_seg_partials: NULL argument");
+  *n = as->sqs_vec + as->sqs_sca;
+  std::copy(as->seg_off.begin(), as->seg_off.end(), seg_off);
+  return ZS_OK;
+}
+
+int zs_adamset_grad_sqnorm_segs(const zs_adamset* as, double* partials, uintptr_t stream) {
+  ZS_REQUIRE(as != nullptr, "zs_adamset_grad_sqnorm_segs: NULL set");
+  ZS_REQUIRE(partials != nullptr || as->sqs_vec + as->sqs_sca == 0,
+             "zs_adamset_grad_sqnorm_segs: partials is NULL");
+  ZS_REQUIRE(as->sqs_vec < (int64_t(1) << 31) && as->sqs_sca < (int64_t(1) << 31),
+             "zs_adamset_grad_sqnorm_segs: more than 2^31 - 1 slots in one table");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool f32 = as->g_dtype == ZS_F32, split = split_geometry(as);
+  if (as->sqs_vec) {
+#define ZS_SQ(GT, S, NT)                                                                   \
+  hipLaunchKernelGGL((grad_sqnorm_segs_kernel<GT, S, NT>), dim3(int(as->sqs_vec)),         \
+                     dim3(kThreads), 0, st, as->d_vec, as->d_vec_slots,                    \
+                     as->d_vec_slots + as->nvec + 1, as->nvec, partials)
+    if (sqnorm_nt()) {
+      if (f32 && split) ZS_SQ(float, true, true);
+      else if (f32) ZS_SQ(float, false, true);
+      else if (split) ZS_SQ(unsigned short, true, true);
+      else ZS_SQ(unsigned short, false, true);
+    } else {
+      if (f32 && split) ZS_SQ(float, true, false);
+      else if (f32) ZS_SQ(float, false, false);
+      else if (split) ZS_SQ(unsigned short, true, false);
+      else ZS_SQ(unsigned short, false, false);
+    }
+#undef ZS_SQ
+    ZS_HIP(hipGetLastError());
+  }
+  if (as->sqs_sca) {
+    if (f32)
+      hipLaunchKernelGGL(grad_sqnorm_segs_scalar_kernel<float>, dim3(int(as->sqs_sca)),
+                         dim3(kThreads), 0, st, as->d_sca, as->d_sca_slots,
+                         as->d_sca_slots + as->nsca + 1, as->nsca, partials);
+    else
+      hipLaunchKernelGGL(grad_sqnorm_segs_scalar_kernel<unsigned short>, dim3(int(as->sqs_sca)),
+                         dim3(kThreads), 0, st, as->d_sca, as->d_sca_slots,
+                         as->d_sca_slots + as->nsca + 1, as->nsca, partials);
+    ZS_HIP(hipGetLastError());
+  }
+  return ZS_OK;
+}
+
+int zs_sqnorm_reduce_params(const double* partials, const int64_t* row_ptr, const int64_t* slot_lo,
+                            const int64_t* slot_n, int64_t n_params, float* out,
+                            uintptr_t stream) {
+  ZS_REQUIRE(n_params >= 0 && n_params < (int64_t(1) << 31),
+             "zs_sqnorm_reduce_params: %lld parameters", (long long)n_params);
+  // (partials, slot_lo and slot_n may be NULL when no parameter has a range)
+  ZS_REQUIRE(row_ptr && out, "zs_sqnorm_reduce_params: NULL argument");
+  if (n_params == 0) return ZS_OK;
+  hipLaunchKernelGGL(sqnorm_reduce_params_kernel, dim3(int(n_params)), dim3(kThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), partials, row_ptr, slot_lo, slot_n,
+                     out);
+  ZS_HIP(hipGetLastError());
+  return ZS_OK;
+}
+
+int zs_param_norms(const float* sumsq_vec, int64_t n, double grad_div, float* norms,
+                   uintptr_t stream) {
+  ZS_REQUIRE(n >= 0 && (n == 0 || (sumsq_vec && norms)), "zs_param_norms: %lld elements at NULL",
+             (long long)n);
+  ZS_REQUIRE(grad_div > 0.0, "zs_param_norms: grad_div must be > 0");
+  if (n == 0) return ZS_OK;
+  const int grid = int(std::min<int64_t>((n + kThreads - 1) / kThreads, 1024));
+  hipLaunchKernelGGL(param_norms_kernel, dim3(grid), dim3(kThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), sumsq_vec, n, grad_div, norms);
+  ZS_HIP(hipGetLastError());
+  return ZS_OK;
+}
+
 int zs_clip_coef(const float* sumsq, double grad_div, double max_norm, float* out2,
                  uintptr_t stream) {
   ZS_REQUIRE(sumsq && out2, "zs_clip_coef: NULL argument");
@@ -3022,6 +3268,8 @@ int zs_adamset_destroy(zs_adamset* as) {
   if (as->d_vec_in) (void)hipFree(as->d_vec_in);
   if (as->d_sca_in) (void)hipFree(as->d_sca_in);
   if (as->d_sca_goff) (void)hipFree(as->d_sca_goff);
+  if (as->d_vec_slots) (void)hipFree(as->d_vec_slots);
+  if (as->d_sca_slots) (void)hipFree(as->d_sca_slots);
   delete as;
   return ZS_OK;
 }

@@ -41,6 +41,8 @@ EXPORTED = (
     "zs_adamset_run_clipped", "zs_adamset_run_sr", "zs_sr_keys", "zs_sr_bits",
     "zs_clip_coef_guarded", "zs_adamset_run_guarded", "zs_adamset_run_sr_guarded",
     "zs_adamset_run_psr", "zs_adamset_set_state_rounding", "zs_sr_pkeys",
+    "zs_adamset_sqnorm_seg_partials", "zs_adamset_grad_sqnorm_segs", "zs_sqnorm_reduce_params",
+    "zs_param_norms",
     "zs_sgd_hparams_init", "zs_sgdset_create", "zs_sgdset_run",
     "zs_comm_unique_id", "zs_comm_init", "zs_comm_destroy", "zs_reduce_scatter", "zs_all_gather",
     "zs_all_reduce", "zs_reduce", "zs_broadcast", "zs_reduce_group", "zs_broadcast_group", "zs_all_gather_group", "zs_reduce_scatter_group",
@@ -146,6 +148,10 @@ _SIGS = {
     "zs_adamset_run_sr": ([_P, ctypes.POINTER(AdamHParams), _P, ctypes.c_uint64, ctypes.c_uint32,
                            ctypes.c_uint32, _U], ctypes.c_int),
     "zs_clip_coef_guarded": ([_P, ctypes.c_double, ctypes.c_double, _P, _P, _U], ctypes.c_int),
+    "zs_adamset_sqnorm_seg_partials": ([_P, _PI64, _PI64], ctypes.c_int),
+    "zs_adamset_grad_sqnorm_segs": ([_P, _P, _U], ctypes.c_int),
+    "zs_sqnorm_reduce_params": ([_P, _P, _P, _P, _I64, _P, _U], ctypes.c_int),
+    "zs_param_norms": ([_P, _I64, ctypes.c_double, _P, _U], ctypes.c_int),
     "zs_adamset_run_guarded": ([_P, ctypes.POINTER(AdamHParams), _P, _U], ctypes.c_int),
     "zs_adamset_run_sr_guarded": ([_P, ctypes.POINTER(AdamHParams), _P, ctypes.c_uint64,
                                    ctypes.c_uint32, ctypes.c_uint32, _U], ctypes.c_int),

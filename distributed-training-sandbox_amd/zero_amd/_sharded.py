@@ -20,9 +20,9 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import (check_bf16_state_group, check_max_grad_norm, check_skip_nonfinite,
-                      check_master_free, check_master_free_group, check_state_dtype,
-                      check_state_rounding, owner_range)
+from ._update import (check_bf16_state_group, check_max_grad_norm, check_param_grad_norms,
+                      check_skip_nonfinite, check_master_free, check_master_free_group,
+                      check_state_dtype, check_state_rounding, owner_range)
 from .engine import ShardEngine
 from .training_utils.utils import get
 
@@ -82,7 +82,7 @@ class ShardedOptimizerBase:
                  arena: str = "flat", grad_comm: str | None = None,
                  max_grad_norm: float | None = None, state_dtype=None,
                  state_rounding: str | None = None, state_seed: int = 0,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, param_grad_norms: bool = False):
         if arena not in ("flat", "buckets", "auto"):
             raise ValueError(f"arena must be 'flat', 'buckets' or 'auto' (got {arena!r})")
         # the moments' dtype: None / torch.float32, or torch.bfloat16 (opt-in: exp_avg and
@@ -116,6 +116,10 @@ class ShardedOptimizerBase:
         # skipped on the device — nothing in device memory changes, the host proceeds as for any
         # step; refused here, on every rank and before anything collective
         self.skip_nonfinite = check_skip_nonfinite(skip_nonfinite, max_grad_norm, self._kind)
+        # param_grad_norms (with max_grad_norm): the norm pass also reports the L2 norm of every
+        # parameter's averaged gradient, last_param_grad_norms; a reporting switch,
+        # fixed at construction and not checkpointed
+        self.param_grad_norms = check_param_grad_norms(param_grad_norms, max_grad_norm)
         # master="none": bf16 parameters without any master, updated in place and rounded
         # stochastically from the same generator (state_seed).  What it cannot be
         # combined with is refused here, on every rank and before anything collective
@@ -243,6 +247,7 @@ class ShardedOptimizerBase:
         if m is None:
             if getattr(self, "skip_nonfinite", False):
                 raise ValueError("zero_amd: skip_nonfinite=True needs max_grad_norm")
+            check_param_grad_norms(getattr(self, "param_grad_norms", False), m)
             return
         if self._clip_unsupported is not None:
             raise ValueError("zero_amd: max_grad_norm is not supported with "
@@ -261,6 +266,16 @@ class ShardedOptimizerBase:
         """0-d fp32 device tensor: min(1, max_grad_norm / (last_grad_norm + 1e-6)), as above."""
         out = None if self.engine is None else self.engine.clip_out
         return None if out is None else out[1]
+
+    @property
+    def last_param_grad_norms(self):
+        """1-D fp32 device tensor of ``len(params)`` (``param_grad_norms``): entry i is the L2 norm
+        of parameter i's averaged gradient in the last clipped step, +0.0 for a parameter without
+        a gradient; the same bits on every rank, valid in stream order after step(), overwritten
+        (the same tensor) by the next step; None before the first such step and without the
+        option."""
+        clip = None if self.engine is None else self.engine.clip
+        return None if clip is None else clip.param_norms
 
     @property
     def last_norm_bytes(self) -> int:
@@ -368,6 +383,7 @@ class ShardedOptimizerBase:
                 check_master_free_group(self._hparams_of(gi))
         self.engine.max_grad_norm = self.max_grad_norm
         self.engine.skip_nonfinite = self.skip_nonfinite
+        self.engine.param_grad_norms = self.param_grad_norms
         had_vmax = self.engine.vmax is not None
         grads = [p.grad for p in self.params]
         seen = self._validated

@@ -355,6 +355,7 @@ class UpdateCore:
         the sets before they run (AdamSet.set_grads; the rows then carry g = 0).  ``defer`` (a
         list; gradient clipping): nothing is launched, every part is appended as ``(aset, hp, gptr
         of its rows or None)`` for the caller to run once the clip coefficient exists.
+        Every set carries the parameter index of each of its rows as ``seg_params``.
         Returns the parts as ``(group, aset)``."""
         parts = []
         if len(rows) == 0:
@@ -370,6 +371,7 @@ class UpdateCore:
             gidx, step, cmul = int(key[0]), int(key[1]), int(key[2])
             aset = self.cached((gidx, len(sel), int(sel[0]), tag), sub.tobytes(),
                                lambda: new_set(sub))
+            aset.seg_params = np.asarray(param_idx, np.int64)[sel]  # (GradClip per_param)
             parts.append((gidx, aset))
             g = None if gptr is None else np.asarray(gptr, np.uint64)[sel]
             hp = self.make_hp(hparams_of(gidx), step, cmul)
@@ -407,6 +409,17 @@ def check_skip_nonfinite(skip_nonfinite, max_grad_norm, kind: str) -> bool:
     return True
 
 
+def check_param_grad_norms(param_grad_norms, max_grad_norm) -> bool:
+    """``param_grad_norms`` as a bool; ValueError without ``max_grad_norm`` (the norms come out of
+    the clipping pass; infinity reports them without clipping)."""
+    if not param_grad_norms:
+        return False
+    if max_grad_norm is None:
+        raise ValueError("zero_amd: param_grad_norms=True reports from the clipping pass: it needs "
+                         "max_grad_norm (float('inf') reports without clipping)")
+    return True
+
+
 class GradClip:
     """Global gradient-norm clipping around an ``UpdateCore``'s launches (clip_grad_norm_ between
     the reduction and the update): what the ZeRO-1/2 flat arena and ZeRO-3's update
@@ -418,28 +431,54 @@ class GradClip:
     streams are ordered around the all-reduce is the caller's.  The gradient is never rewritten and
     the host never waits.
 
+    ``per_param`` (``param_grad_norms``): ``norm`` runs the pass keyed by segment, ``reduce`` also
+    sums each parameter's slots into its element of ``reduced`` — ``len(core.steps) + 1`` floats
+    whose last element is ``sumsq``; the caller all-reduces ``reduced``, whatever the mode — and
+    ``coef`` also writes ``param_norms``, the L2 norm of each parameter's averaged gradient.
+
     ``guard`` (``skip_nonfinite``): the coefficient comes from zs_clip_coef_guarded — a non-finite
     norm gives a NaN coefficient and counts in ``skipped`` — and every launch is the guarded one,
     which a NaN coefficient ends before its first load."""
 
-    def __init__(self, core: UpdateCore, guard: bool = False):
-        self.core, self.guard = core, bool(guard)
+    def __init__(self, core: UpdateCore, guard: bool = False, per_param: bool = False):
+        self.core, self.guard, self.per_param = core, bool(guard), bool(per_param)
         dev = core.device
         self.partials = None  # float64, sized on first use
         self._key, self._off = None, np.zeros(1, np.int64)
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
+        # what the caller all-reduces at world size > 1: the scalar, or (``per_param``) the
+        # per-parameter sums of squares with the scalar as their last element
+        self.reduced = self.sumsq
+        self.param_norms = None
+        if self.per_param:
+            n = self.n_params = len(core.steps)
+            self.reduced = torch.zeros(n + 1, dtype=torch.float32, device=dev)
+            self.sumsq = self.reduced[n:]
+            self.param_norms = torch.zeros(n, dtype=torch.float32, device=dev)
+            # the CSR of slot ranges per parameter, [row_ptr | slot_lo | slot_n] in one device
+            # tensor; uploaded on a stream of its own, which the host waits for, so that an
+            # upload never waits for the work queued on the caller's streams
+            self._csr, self._upload_stream = None, torch.cuda.Stream(dev)
         self.out = torch.zeros(2, dtype=torch.float32, device=dev)  # {norm, coef}
         self.skipped = torch.zeros(1, dtype=torch.int64, device=dev) if guard else None
         self.norm_events = None  # optional list of (start, end, bytes) per norm pass
         self.last_norm_bytes = 0
 
-    def prepare(self, deferred) -> None:
+    def prepare(self, deferred, seg_params=None) -> None:
         """Each collected set's slice of the partials tensor: sized on first use, regrown only when
         the list of sets changes (the old one is retired with the core's tables: queued kernels
-        may still write it)."""
-        key = tuple((id(aset), aset.sqnorm_partials) for aset, _, _ in deferred)
+        may still write it).  ``per_param``: ``seg_params[k]`` is the parameter index of each
+        segment of ``deferred[k]``'s set; the slices hold the sets' per-segment slots, and the
+        slot ranges of every parameter — several for one cut across sets — become a CSR in the
+        order the sets were collected, rebuilt under the same rule."""
+        if self.per_param:
+            key = tuple((id(aset), int(aset.sqnorm_seg_offsets[-1]),
+                         np.asarray(idx, np.int64).tobytes())
+                        for (aset, _, _), idx in zip(deferred, seg_params))
+        else:
+            key = tuple((id(aset), aset.sqnorm_partials) for aset, _, _ in deferred)
         if self._key != key:
-            self._off = np.concatenate([[0], np.cumsum([n for _, n in key])]).astype(np.int64)
+            self._off = np.concatenate([[0], np.cumsum([k[1] for k in key])]).astype(np.int64)
             total = int(self._off[-1])
             buf = self.partials
             if buf is None or buf.numel() < total:
@@ -447,8 +486,30 @@ class GradClip:
                     self.core.retired.append(buf)
                 self.partials = torch.zeros(max(total, 1), dtype=torch.float64,
                                             device=self.core.device)
+            if self.per_param:
+                if self._csr is not None:
+                    self.core.retired.append(self._csr)
+                with torch.cuda.stream(self._upload_stream):
+                    self._csr = torch.from_numpy(self._build_csr(deferred, seg_params)).to(
+                        self.core.device)
+                self._upload_stream.synchronize()
             self._key = key
         self.last_norm_bytes = 0
+
+    def _build_csr(self, deferred, seg_params) -> np.ndarray:
+        par, lo, cnt = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+        for k, ((aset, _, _), idx) in enumerate(zip(deferred, seg_params)):
+            so = aset.sqnorm_seg_offsets
+            assert len(idx) == aset.nseg
+            par.append(np.asarray(idx, np.int64))
+            lo.append(self._off[k] + so[:-1])
+            cnt.append(np.diff(so))
+        par, lo, cnt = np.concatenate(par), np.concatenate(lo), np.concatenate(cnt)
+        keep = cnt > 0
+        par, lo, cnt = par[keep], lo[keep], cnt[keep]
+        order = np.argsort(par, kind="stable")  # per parameter: the order the sets were collected
+        row_ptr = np.concatenate([[0], np.cumsum(np.bincount(par, minlength=self.n_params))])
+        return np.concatenate([row_ptr, lo[order], cnt[order]]).astype(np.int64)
 
     def norm(self, deferred, first, stream) -> None:
         """Stage 1 for ``deferred[first:]``: bind the gradients where needed, then the sum of
@@ -462,7 +523,10 @@ class GradClip:
             if self.norm_events is not None:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record(stream)
-            aset.grad_sqnorm(base + int(self._off[k]) * 8, stream)
+            if self.per_param:
+                aset.grad_sqnorm_segs(base + int(self._off[k]) * 8, stream)
+            else:
+                aset.grad_sqnorm(base + int(self._off[k]) * 8, stream)
             nb = aset.grad_bytes  # what the pass reads
             if ev is not None:
                 ev[1].record(stream)
@@ -470,18 +534,26 @@ class GradClip:
             self.last_norm_bytes += nb
 
     def reduce(self, stream) -> None:
-        """Stage 2: one fixed-order reduction of all partials into ``sumsq`` (no sets: 0)."""
-        from .kernels import sqnorm_reduce
+        """Stage 2: one fixed-order reduction of all partials into ``sumsq`` (no sets: 0);
+        ``per_param``: before it, each parameter's slots into its element of ``reduced``."""
+        from .kernels import sqnorm_reduce, sqnorm_reduce_params
 
+        if self.per_param:
+            n, t = self.n_params, self._csr
+            nr = (t.numel() - (n + 1)) // 2
+            sqnorm_reduce_params(self.partials, t[:n + 1], t[n + 1:n + 1 + nr], t[n + 1 + nr:], n,
+                                 self.reduced, stream)
         sqnorm_reduce(self.partials, int(self._off[-1]), self.sumsq, stream)
 
     def coef(self, max_norm, stream) -> None:
         """Stage 3, after the caller's all-reduce of ``sumsq``: {norm, coefficient} of the gradient
         averaged over the core's world size."""
-        from .kernels import clip_coef
+        from .kernels import clip_coef, param_norms
 
         clip_coef(self.sumsq, float(self.core.ws), float(max_norm), self.out, stream,
                   skipped=self.skipped if self.guard else None)
+        if self.per_param:
+            param_norms(self.reduced, self.n_params, float(self.core.ws), self.param_norms, stream)
 
     def run(self, deferred, first, last, stream) -> None:
         """Stage 4 for ``deferred[first:last]``: the update with the coefficient."""

@@ -365,6 +365,7 @@ class ShardEngine(UpdateCore):
         self.max_grad_norm = None
         self.last_norm_bytes = 0
         self.skip_nonfinite = False
+        self.param_grad_norms = False  # the pass also reports per-parameter norms (GradClip)
         self.clip = None
 
     @property

@@ -304,6 +304,7 @@ class FlatEngine(ShardEngine):
             for gi in np.unique(groups):
                 sel = np.nonzero(groups == gi)[0]
                 sets.append((int(gi), rd.idx[sel], self.new_set(np.ascontiguousarray(rd.rows[sel]))))
+                sets[-1][2].seg_params = rd.idx[sel].astype(np.int64)
             rd.sets = sets
         return sets
 
@@ -347,10 +348,11 @@ class FlatEngine(ShardEngine):
         """The stages' object (made by the first clipped step) and each collected set's slice of
         its partials tensor."""
         if self.clip is None:
-            self.clip = GradClip(self, guard=self.skip_nonfinite)
-            self.ev_clip = (StreamEvent(), StreamEvent())  # around the norm's scalar all-reduce
+            self.clip = GradClip(self, guard=self.skip_nonfinite, per_param=self.param_grad_norms)
+            self.ev_clip = (StreamEvent(), StreamEvent())  # around the norm's all-reduce
         self.clip.norm_events = self.norm_events
-        self.clip.prepare(deferred)
+        self.clip.prepare(deferred, [aset.seg_params for aset, _, _ in deferred]
+                          if self.clip.per_param else None)
 
     def _clip_norm(self, deferred, first, stream):
         """Stage 1 for ``deferred[first:]``."""
@@ -360,14 +362,16 @@ class FlatEngine(ShardEngine):
     def _clip_coef(self, deferred, stream):
         """Stages 2 and 3: one fixed-order reduction of all partials, the scalar all-reduce on the
         communication stream (ordered by events on both sides; a rank that owns nothing
-        contributes 0 and still takes part), the coefficient."""
+        contributes 0 and still takes part), the coefficient.  ``param_grad_norms``: the one
+        all-reduce carries the per-parameter sums of squares in front of the scalar (every
+        parameter has one owner, the others add 0: the sum is exact)."""
         clip = self.clip
         clip.reduce(stream)
         if self.ws > 1:
             cs = self.comm_stream
             self.ev_clip[0].record(stream)
             cs.wait_event(self.ev_clip[0])
-            self.comm.all_reduce(clip.sumsq, cs)
+            self.comm.all_reduce(clip.reduced, cs)
             self.ev_clip[1].record(cs)
             stream.wait_event(self.ev_clip[1])
         clip.coef(self.max_grad_norm, stream)

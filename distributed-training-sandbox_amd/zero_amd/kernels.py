@@ -234,6 +234,30 @@ class AdamSet:
             partials = partials.data_ptr()
         _lib.call("zs_adamset_grad_sqnorm", self._h, partials, stream_handle(stream))
 
+    @property
+    def sqnorm_seg_offsets(self) -> np.ndarray:
+        """``nseg + 1`` int64 offsets: row i's slots in what ``grad_sqnorm_segs`` writes are
+        ``[off[i], off[i + 1])``, ``off[-1]`` the set's slot count (fixed when the set was created:
+        zs_adamset_sqnorm_seg_partials)."""
+        off = getattr(self, "_sq_seg_off", None)
+        if off is None:
+            c = ctypes.c_int64()
+            off = np.zeros(self.nseg + 1, np.int64)
+            _lib.call("zs_adamset_sqnorm_seg_partials", self._h, ctypes.byref(c),
+                      off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+            assert int(off[-1]) == c.value
+            self._sq_seg_off = off
+        return off
+
+    def grad_sqnorm_segs(self, partials, stream) -> None:
+        """``grad_sqnorm`` keyed by row: the sums of squares of each row's gradient into its slots
+        of ``partials`` (a float64 device tensor of at least ``sqnorm_seg_offsets[-1]`` elements, or
+        its address): zs_adamset_grad_sqnorm_segs."""
+        if not isinstance(partials, int):
+            assert partials.dtype.itemsize == 8 and partials.numel() >= self.sqnorm_seg_offsets[-1]
+            partials = partials.data_ptr()
+        _lib.call("zs_adamset_grad_sqnorm_segs", self._h, partials, stream_handle(stream))
+
     def run_clipped(self, hp: AdamHParams, coef, stream) -> None:
         """``run`` with every averaged gradient times the fp32 device scalar ``coef`` (a tensor or
         its address), read when the kernel runs: zs_adamset_run_clipped."""
@@ -337,6 +361,28 @@ def sqnorm_reduce(partials, n: int, sumsq, stream) -> None:
     float64 ``partials``, added in a fixed order (zs_sqnorm_reduce)."""
     assert n == 0 or (partials.dtype.itemsize == 8 and partials.numel() >= n)
     _lib.call("zs_sqnorm_reduce", partials.data_ptr() if n else None, int(n), sumsq.data_ptr(),
+              stream_handle(stream))
+
+
+def sqnorm_reduce_params(partials, row_ptr, slot_lo, slot_n, n_params: int, out, stream) -> None:
+    """``out[i]`` (fp32 device elements) = the fp32 rounding of the double sum of parameter i's
+    slots of the float64 ``partials``: the ranges ``row_ptr[i] .. row_ptr[i + 1]`` of the CSR
+    (``row_ptr``, ``slot_lo``, ``slot_n``: int64 device tensors), added in a fixed order; +0.0
+    without a range (zs_sqnorm_reduce_params)."""
+    assert row_ptr.dtype.itemsize == 8 and row_ptr.numel() >= n_params + 1
+    assert slot_lo.dtype.itemsize == 8 and slot_n.dtype.itemsize == 8
+    assert out.dtype.itemsize == 4 and out.numel() >= n_params
+    _lib.call("zs_sqnorm_reduce_params", partials.data_ptr(), row_ptr.data_ptr(),
+              slot_lo.data_ptr(), slot_n.data_ptr(), int(n_params), out.data_ptr(),
+              stream_handle(stream))
+
+
+def param_norms(sumsq_vec, n: int, grad_div: float, norms, stream) -> None:
+    """``norms[i] = float32(sqrt(float64(sumsq_vec[i])) / grad_div)`` for the first ``n`` fp32
+    device elements: ``clip_coef``'s norm per element (zs_param_norms)."""
+    assert sumsq_vec.dtype.itemsize == 4 and norms.dtype.itemsize == 4
+    assert sumsq_vec.numel() >= n and norms.numel() >= n
+    _lib.call("zs_param_norms", sumsq_vec.data_ptr(), int(n), float(grad_div), norms.data_ptr(),
               stream_handle(stream))
 
 

@@ -70,7 +70,7 @@ from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
 from ._sharded import group_hparams, optimizer_kind
 from ._update import (GradClip, UpdateCore, check_bf16_state_group, check_master_free,
-                      check_master_free_group, check_max_grad_norm, check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
+                      check_master_free_group, check_max_grad_norm, check_param_grad_norms, check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
                       owner_range)
 from .comm import STREAM_SYNC, RcclComm, Sync, comm_stream, sync_kind, zs_dtype
 from .engine import ALIGN_ELEMS
@@ -1840,7 +1840,8 @@ class ShardedOptimizer:
                  stream_sync: str = STREAM_SYNC, grad_accumulation: bool = False,
                  accumulation_dtype=None, state_dtype=None, state_rounding: str | None = None,
                  state_seed: int = 0, max_grad_norm: float | None = None,
-                 skip_nonfinite: bool = False, master: str = "split"):
+                 skip_nonfinite: bool = False, master: str = "split",
+                 param_grad_norms: bool = False):
         # global gradient-norm clipping inside step() (update mode; None = off): a plain attribute,
         # re-checked at every step().  skip_nonfinite (with it; Adam): a step whose gradient norm
         # is not finite is skipped on the device.  Both are refused here where they
@@ -1850,6 +1851,9 @@ class ShardedOptimizer:
         self._check_clip()
         self.skip_nonfinite = check_skip_nonfinite(skip_nonfinite, max_grad_norm,
                                                    optimizer_kind(optimizer))
+        # param_grad_norms (with max_grad_norm): the norm pass also reports the L2 norm of every
+        # parameter's averaged gradient, last_param_grad_norms; fixed at construction
+        self.param_grad_norms = check_param_grad_norms(param_grad_norms, max_grad_norm)
         self._clip = None  # the stages and their device results, made by the first clipped step
         self._clip_syncs = None
         self._span_end = None
@@ -2003,6 +2007,7 @@ class ShardedOptimizer:
         if m is None:
             if getattr(self, "skip_nonfinite", False):
                 raise ValueError("zero_amd: skip_nonfinite=True needs max_grad_norm")
+            check_param_grad_norms(getattr(self, "param_grad_norms", False), m)
             return
         if not self.update:
             raise ValueError("zero_amd: max_grad_norm applies to update mode (reference mode "
@@ -2020,6 +2025,15 @@ class ShardedOptimizer:
         """0-d fp32 device tensor: min(1, max_grad_norm / (last_grad_norm + 1e-6)), as above (NaN:
         ``skip_nonfinite`` skipped the step)."""
         return None if self._clip is None else self._clip.out[1]
+
+    @property
+    def last_param_grad_norms(self):
+        """1-D fp32 device tensor of ``len(params)`` (``param_grad_norms``): entry i is the L2 norm
+        of parameter i's averaged gradient in the last clipped step — over all ranks' chunks —
+        and +0.0 for a parameter without a gradient; the same bits on every rank, valid in stream
+        order after step(), overwritten (the same tensor) by the next step; None before the first
+        such step and without the option."""
+        return None if self._clip is None else self._clip.param_norms
 
     @property
     def last_norm_bytes(self) -> int:
@@ -2321,15 +2335,17 @@ class ShardedOptimizer:
         calls it on every clipped step, with sumsq == 0 when it updates nothing."""
         clip = self._clip
         if clip is None:
-            clip = self._clip = GradClip(self._core, guard=self.skip_nonfinite)
+            clip = self._clip = GradClip(self._core, guard=self.skip_nonfinite,
+                                         per_param=self.param_grad_norms)
         clip.norm_events = self._norm_events
-        clip.prepare(deferred)
+        clip.prepare(deferred, [aset.seg_params for aset, _, _ in deferred]
+                     if clip.per_param else None)
         clip.norm(deferred, 0, cur)
         clip.reduce(cur)
         if self.world_size > 1:
             side = self.runtime.stream
             if side is None:
-                self.comm.all_reduce(clip.sumsq, cur)
+                self.comm.all_reduce(clip.reduced, cur)
             else:
                 if self._clip_syncs is None:  # (ready, done): reused every step
                     kind = self.runtime.sync_kind
@@ -2337,7 +2353,7 @@ class ShardedOptimizer:
                 ready, done = self._clip_syncs
                 ready.record(cur.cuda_stream)
                 ready.wait(side.cuda_stream)
-                self.comm.all_reduce(clip.sumsq, side)
+                self.comm.all_reduce(clip.reduced, side)
                 done.record(side.cuda_stream)
                 done.wait(cur.cuda_stream)
         clip.coef(self.max_grad_norm, cur)

@@ -405,6 +405,48 @@ int zs_adamset_run_guarded(const zs_adamset* as, const zs_adam_hparams* hp, cons
 int zs_adamset_run_sr_guarded(const zs_adamset* as, const zs_adam_hparams* hp, const float* coef,
                               uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream);
 
+/* Per-parameter gradient norms from the clipping pass (additive in ABI v13): the same read-only
+ * pass with its partials keyed by segment, so that the per-segment sums of squares, and from them
+ * the global one, come out of one read of the gradients.
+ *
+ * zs_adamset_sqnorm_seg_partials: *n = the double partials ("slots")
+ * zs_adamset_grad_sqnorm_segs writes for this set; seg_off[0 .. nseg] (nseg = the segments given to
+ * *_create, in that order; the caller's array of nseg + 1) = where each segment's slots start,
+ * seg_off[nseg] == *n.  A segment's slots are those of its vector part (the 4-aligned prefix of an
+ * aligned segment, in chunks of 2,048 elements, 4,096 for ZS_BF16_SPLIT / ZS_BF16_SR) followed by
+ * those of its scalar part (the tail of up to 3 elements, or a whole unaligned segment, in chunks
+ * of 256): min(chunks, 128) for a vector part, min(chunks, 16) for a scalar part, none for an
+ * empty segment.  The count depends on that segment's length, its alignment class and the set's
+ * dtypes alone — not on the device, zs_tune or the other segments.  (A set of 326 segments has at
+ * most 326 * 144 slots: 376 KB.)
+ *
+ * zs_adamset_grad_sqnorm_segs: zs_adamset_grad_sqnorm's pass — the gradients bound now, the same
+ * loads, fp32 only inside one lane's terms of one chunk, double above, plain stores, no atomics —
+ * where slot j of a part with s slots is the sum over chunks j, j + s, ... of that part.  A
+ * segment with g == 0 is not read and its slots are +0.0.  Every slot is written; nothing else
+ * is.  A slot's bits depend on its own segment alone.  Works on every kind of set.
+ *
+ * zs_sqnorm_reduce_params: out[i] = (float) of the double sum of parameter i's slots, for i in
+ * [0, n_params).  row_ptr (n_params + 1), slot_lo and slot_n are device arrays: parameter i owns
+ * the ranges r in [row_ptr[i], row_ptr[i + 1]), range r being partials[slot_lo[r] .. slot_lo[r] +
+ * slot_n[r]) — several when the parameter is cut across sets.  One workgroup per parameter adds
+ * its ranges in that order, thread t taking slots t, t + 256, ... of each range into one running
+ * double; then the 64 lanes of each wave by shuffles (offsets 32, 16, .. 1) and the four waves in
+ * order.  A parameter without a range gets +0.0.
+ *
+ * zs_param_norms: norms[i] = (float)(sqrt((double)sumsq_vec[i]) / grad_div) for i in [0, n):
+ * zs_clip_coef's norm, per element (no contraction).
+ *
+ * ZS_ERR_INVALID, nothing launched: a NULL set, n, seg_off, row_ptr or out; NULL partials for a
+ * set that has slots; n_params or n < 0; sumsq_vec or norms NULL with n > 0; grad_div <= 0. */
+int zs_adamset_sqnorm_seg_partials(const zs_adamset* as, int64_t* n, int64_t* seg_off);
+int zs_adamset_grad_sqnorm_segs(const zs_adamset* as, double* partials, uintptr_t stream);
+int zs_sqnorm_reduce_params(const double* partials, const int64_t* row_ptr, const int64_t* slot_lo,
+                            const int64_t* slot_n, int64_t n_params, float* out,
+                            uintptr_t stream);
+int zs_param_norms(const float* sumsq_vec, int64_t n, double grad_div, float* norms,
+                   uintptr_t stream);
+
 /* Master-free bf16 parameters (additive in ABI v13).  A set made by zs_adamset_create_ex with
  * p_dtype ZS_BF16_SR keeps no master and no residual: a seg's `master` is the bf16 param (read),
  * `p_out` the same address (written), master_out = vmax = carry = 0; g is bf16 or fp32; anything
