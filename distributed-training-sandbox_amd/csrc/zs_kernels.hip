@@ -320,6 +320,7 @@ struct AdamRule {
   using Hyper = HP;
   static constexpr bool kM = true, kV = true, kX = AMS, kGradOffset2 = true;
   static constexpr bool kPsr = false;  // AdamPsrRule: no master, the bf16 parameter in place
+  static constexpr bool kEma = false;  // AdamEmaRule: the vmax stream is an EMA of the stored master
 
   // One element of torch.optim.Adam's single-tensor update (adam.py:394-547), one fp32 operation
   // per operation of torch's CPU kernels: lerp = fma(w, end-self, self) or fma(w-1, end-self, end)
@@ -438,6 +439,26 @@ __device__ __forceinline__ uint2 psr_pack_bf16x4(const float* pp, uint64_t eu, u
   return make_uint2(sr_pack2(w[0], w[1]), sr_pack2(w[2], w[3]));
 }
 
+// Sharded EMA of the master weights (zs_adamset_run_ema; DESIGN.md §4, "Sharded EMA").  AdamEmaRule
+// names the instances: the unchanged amsgrad-free fp32 rule, with the segment's `vmax` column as the
+// EMA array -- the stream slot amsgrad uses, so kX is set and elem leaves the value alone.  After the
+// storage step the skeleton calls ema(stored, e, hp): e = lerp(e, stored, w), ATen's lerp like
+// exp_avg's, where `stored` is the fp32 master as memory now holds it (for the split master the
+// re-joined (hi << 16) + sext(lo), 1 ulp off the computed value at an exact tie).  ema_w / ema_hi:
+// the fma's coefficient and which operand it adds to, made on the host like lerp_w / lerp_hi.
+struct EmaHP : HP {
+  float ema_w;
+  int ema_hi;
+};
+struct AdamEmaRule : AdamRule<false> {
+  using Hyper = EmaHP;
+  static constexpr bool kX = true, kEma = true;
+  static __device__ __forceinline__ void ema(float stored, float& e, const EmaHP& hp) {
+#pragma clang fp contract(off)
+    e = fmaf(hp.ema_w, stored - e, hp.ema_hi ? stored : e);
+  }
+};
+
 // torch.optim.SGD over the same tables: field `m` of a segment is the momentum buffer (MOM: the
 // set has one), `v` and `vmax` are unused.  Without MOM no state array is touched.
 struct SgdHP {
@@ -450,6 +471,7 @@ struct SgdRule {
   using Hyper = SgdHP;
   static constexpr bool kM = MOM, kV = false, kX = false, kGradOffset2 = false;
   static constexpr bool kPsr = false;
+  static constexpr bool kEma = false;
 
   // One element of torch.optim.SGD's single-tensor update (sgd.py _single_tensor_sgd), in the
   // rounding order of torch's CPU kernels: add(x, alpha=a) = fma(a, x, self), so
@@ -668,11 +690,19 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
       }
       nt_st8(pb.at(u, o2), pack_u16x4(h));
       nt_st8(lo.at(u, o2), pack_u16x4(l));
+      if constexpr (Rule::kEma) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Rule::ema(join_master(h[j], l[j]), xp[j], hp);
+      }
     } else {
       if (s.master_out) nt_st16(po.at(u, o4), pack4(pp));
       if (s.p_out) {
         const uint2 r = pack_bf16x4(pp);
         nt_st8(pb.at(u, o2), r);
+      }
+      if constexpr (Rule::kEma) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Rule::ema(pp[j], xp[j], hp);
       }
     }
     if constexpr (kStochastic<ST>) {
@@ -769,11 +799,19 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
         split_master4(pp, h, l);
         nt_st8(s.p_out + i, pack_u16x4(h));
         nt_st8(reinterpret_cast<unsigned short*>(s.master_out) + i, pack_u16x4(l));
+        if constexpr (Rule::kEma) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) Rule::ema(join_master(h[j], l[j]), xp[j], hp);
+        }
       } else {
         if (s.master_out) st4(s.master_out, i, p4[u]);
         if (s.p_out) {
           const uint2 r = pack_bf16x4(pp);
           nt_st8(s.p_out + i, r);
+        }
+        if constexpr (Rule::kEma) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) Rule::ema(pp[j], xp[j], hp);
         }
       }
       if constexpr (kStochastic<ST>) {
@@ -823,6 +861,8 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
 // (zs_adamset_run_sr, over AdamSrRule, whose Hyper carries the keys and m_base): the same arrays,
 // stored with stochastic rounding.  Rule = AdamPsrRule (zs_adamset_run_psr, a ZS_BF16_SR set;
 // SPLIT names its geometry): no master, the bf16 parameter in place, any of the three ST.
+// Rule = AdamEmaRule (zs_adamset_run_ema; fp32 moments, no carry): the vmax stream is an EMA of the
+// master, moved by Rule::ema right after the storage step of each body, on the value as stored.
 template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP,
           typename ST = float, bool GUARD = false>
 __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
@@ -917,10 +957,13 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     } else if constexpr (SPLIT) {
       const unsigned short h = f32_to_bf16(p);
       glob(s.p_out)[i] = h;
-      lo[i] = (unsigned short)master_residual(p, h);
+      const uint32_t l = master_residual(p, h);
+      lo[i] = (unsigned short)l;
+      if constexpr (Rule::kEma) Rule::ema(join_master(h, l), vm, hp);
     } else {
       if (s.master_out) glob(s.master_out)[i] = p;
       if (s.p_out) glob(s.p_out)[i] = f32_to_bf16(p);
+      if constexpr (Rule::kEma) Rule::ema(p, vm, hp);
     }
     if constexpr (kStochastic<ST>) {
       uint32_t mh, vh;
@@ -2090,6 +2133,10 @@ using AdamPsrRuleOf = AdamPsrRule;
 using AdamPsrFamily = UpdateFamily<AdamPsrRuleOf, float, false, true>;
 using AdamPsrBf16Family = UpdateFamily<AdamPsrRuleOf, unsigned short, false, true>;
 using AdamPsrSrFamily = UpdateFamily<AdamPsrRuleOf, SrBf16, false, true>;
+template <bool>
+using AdamEmaRuleOf = AdamEmaRule;
+// zs_adamset_run_ema: fp32 moments, no carry; every (gradient dtype, master storage) pair
+using AdamEmaFamily = UpdateFamily<AdamEmaRuleOf, float, false, true>;
 
 struct UpdateTable {  // a segment array with its chunk prefix
   const AdamSeg* segs;
@@ -2979,6 +3026,28 @@ int zs_adamset_run_psr(const zs_adamset* as, const zs_adam_hparams* h, const flo
   if (!bf16_state) return run_set<AdamPsrFamily>(as, false, hp, coef, stream, guard != 0);
   if (!as->state_sr) return run_set<AdamPsrBf16Family>(as, false, hp, coef, stream, guard != 0);
   return run_set<AdamPsrSrFamily>(as, false, hp, coef, stream, guard != 0);
+}
+
+int zs_adamset_run_ema(const zs_adamset* as, const zs_adam_hparams* h, const float* coef, int guard,
+                       float ema_weight, uintptr_t stream) {
+  const char* fn = "zs_adamset_run_ema";
+  ZS_REQUIRE(as && h, "%s: NULL argument", fn);
+  ZS_REQUIRE(!as->sgd, "%s: the EMA rides on Adam's update (the set was made by zs_sgdset_create)",
+             fn);
+  ZS_REQUIRE(as->state_dtype == ZS_F32, "%s: a set with ZS_BF16 state has no EMA column", fn);
+  ZS_REQUIRE(as->p_dtype != ZS_BF16_SR, "%s: a ZS_BF16_SR set has no master to average", fn);
+  ZS_REQUIRE(!as->has_carry, "%s: a set with the ZeRO-1 carry has no EMA instances", fn);
+  ZS_REQUIRE(as->has_vmax || (as->nvec + as->nsca) == 0,
+             "%s: the EMA array is the segments' vmax column, which this set lacks", fn);
+  ZS_REQUIRE(h->amsgrad == 0, "%s: amsgrad and the EMA share the vmax column", fn);
+  ZS_REQUIRE(!guard || coef, "%s: the guard tests the clip coefficient, which is NULL", fn);
+  ZS_REQUIRE(ema_weight >= 0.0f && ema_weight <= 1.0f,  // false for a NaN
+             "%s: ema_weight must lie in [0, 1]", fn);
+  EmaHP hp;
+  static_cast<HP&>(hp) = make_hp(h);
+  hp.ema_hi = ema_weight < 0.5f ? 0 : 1;  // ATen's lerp, as make_hp for exp_avg
+  hp.ema_w = hp.ema_hi ? ema_weight - 1.0f : ema_weight;
+  return run_set<AdamEmaFamily>(as, false, hp, coef, stream, guard != 0);
 }
 
 int zs_adamset_set_state_rounding(zs_adamset* as, int stochastic) {

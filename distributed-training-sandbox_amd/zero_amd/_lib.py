@@ -40,7 +40,7 @@ EXPORTED = (
     "zs_adamset_sqnorm_partials", "zs_adamset_grad_sqnorm", "zs_sqnorm_reduce", "zs_clip_coef",
     "zs_adamset_run_clipped", "zs_adamset_run_sr", "zs_sr_keys", "zs_sr_bits",
     "zs_clip_coef_guarded", "zs_adamset_run_guarded", "zs_adamset_run_sr_guarded",
-    "zs_adamset_run_psr", "zs_adamset_set_state_rounding", "zs_sr_pkeys",
+    "zs_adamset_run_psr", "zs_adamset_set_state_rounding", "zs_sr_pkeys", "zs_adamset_run_ema",
     "zs_adamset_sqnorm_seg_partials", "zs_adamset_grad_sqnorm_segs", "zs_sqnorm_reduce_params",
     "zs_param_norms",
     "zs_sgd_hparams_init", "zs_sgdset_create", "zs_sgdset_run",
@@ -157,6 +157,8 @@ _SIGS = {
                                    ctypes.c_uint32, ctypes.c_uint32, _U], ctypes.c_int),
     "zs_adamset_run_psr": ([_P, ctypes.POINTER(AdamHParams), _P, ctypes.c_int, ctypes.c_uint64,
                             ctypes.c_uint32, ctypes.c_uint32, _U], ctypes.c_int),
+    "zs_adamset_run_ema": ([_P, ctypes.POINTER(AdamHParams), _P, ctypes.c_int, ctypes.c_float, _U],
+                           ctypes.c_int),
     "zs_adamset_set_state_rounding": ([_P, ctypes.c_int], ctypes.c_int),
     "zs_sr_pkeys": ([ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
                      ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),

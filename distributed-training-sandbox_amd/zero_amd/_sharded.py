@@ -11,6 +11,7 @@ engine (engine.py → libzero_amd.so); the inner torch optimizer's own ``step`` 
 """
 from __future__ import annotations
 
+import contextlib
 import time
 import weakref
 
@@ -20,7 +21,8 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import (check_bf16_state_group, check_max_grad_norm, check_param_grad_norms,
+from ._update import (check_bf16_state_group, check_ema, check_ema_decay, check_ema_group,
+                      check_max_grad_norm, check_param_grad_norms,
                       check_skip_nonfinite, check_master_free, check_master_free_group,
                       check_state_dtype, check_state_rounding, owner_range)
 from .engine import ShardEngine
@@ -82,7 +84,8 @@ class ShardedOptimizerBase:
                  arena: str = "flat", grad_comm: str | None = None,
                  max_grad_norm: float | None = None, state_dtype=None,
                  state_rounding: str | None = None, state_seed: int = 0,
-                 skip_nonfinite: bool = False, param_grad_norms: bool = False):
+                 skip_nonfinite: bool = False, param_grad_norms: bool = False,
+                 ema_decay: float | None = None):
         if arena not in ("flat", "buckets", "auto"):
             raise ValueError(f"arena must be 'flat', 'buckets' or 'auto' (got {arena!r})")
         # the moments' dtype: None / torch.float32, or torch.bfloat16 (opt-in: exp_avg and
@@ -135,12 +138,27 @@ class ShardedOptimizerBase:
                 raise ValueError("zero_amd: master='none' is not supported with the bucket arena "
                                  f"or overlap=True (arena={arena!r}, layout={layout!r}, "
                                  f"overlap={bool(overlap)}); use the flat arena")
+        # ema_decay: an fp32 EMA of the master weights, sharded like exp_avg and updated inside
+        # the fused Adam step ("Sharded EMA"); None: off.  What it cannot be combined
+        # with is refused here, on every rank and before anything collective
+        self._ema_decay = check_ema_decay(ema_decay)
+        self._ema_swapped = False  # inside ema_parameters()
+        has_ema = self._ema_decay is not None
+        if has_ema:
+            check_ema(self._kind, self._carry and get("ws") > 1, self.state_dtype, master)
+            if arena == "buckets" or overlap or \
+                    (layout != "reference" and (layout != "flat" or self._carry)):
+                raise ValueError("zero_amd: ema_decay is not supported with the bucket arena or "
+                                 f"overlap=True (arena={arena!r}, layout={layout!r}, "
+                                 f"overlap={bool(overlap)}); use the flat arena")
         for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
             hpd = group_hparams(self._kind, group, optimizer)
             if bf16_state and self._kind == "adam":
                 check_bf16_state_group(hpd, self.state_rounding)
             if master_free:
                 check_master_free_group(hpd)
+            if has_ema:
+                check_ema_group(hpd)
         if bf16_state:
             if self._kind == "sgd":
                 raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with "
@@ -203,6 +221,9 @@ class ShardedOptimizerBase:
                     if master_free:
                         raise ValueError("zero_amd: master='none' is not supported with "
                                          "arena='auto' that resolved to the bucket arena")
+                    if has_ema:
+                        raise ValueError("zero_amd: ema_decay is not supported with "
+                                         "arena='auto' that resolved to the bucket arena")
         # bytes per bucket (bucket arena) / per round (flat arena, all owners' windows together);
         # default 256 MiB / 1 GiB: a flat round has no pack to pipeline, so fewer, larger rounds
         # cost only the last round's Adam as exposed tail and cut the launches per step
@@ -238,6 +259,67 @@ class ShardedOptimizerBase:
             # before the first step (every rank builds it: the communicator is a collective)
             self._build_engine()
             self._overlap_hooks = self.engine.register_marks()
+
+    @property
+    def ema_decay(self):
+        """The EMA's decay (None: the optimizer keeps no EMA): ``ema = lerp(ema, master, 1 - d)``
+        after every update.  It may be changed between steps (a warm-up schedule) and is checked
+        when set and at every step; whether there is an EMA is fixed at construction.  Not
+        checkpointed."""
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, d):
+        if (d is None) != (self._ema_decay is None):
+            raise ValueError("zero_amd: whether the optimizer keeps an EMA is fixed at construction "
+                             "(ShardedOptimizer(..., ema_decay=d))")
+        self._ema_decay = check_ema_decay(d)
+
+    def _check_not_swapped(self, what: str):
+        if self._ema_swapped:
+            raise RuntimeError(f"zero_amd: {what} inside ema_parameters(): the parameters hold the "
+                               "EMA, not the weights training continues from")
+
+    @contextlib.contextmanager
+    def ema_parameters(self):
+        """Inside the ``with`` block every rank's parameters hold the EMA rounded to the parameter
+        dtype (to nearest even); on exit they are restored bit for bit.  Collective at world size
+        > 1: each rank stashes its own window of the parameter arena (in the parameter dtype,
+        freed on exit), writes its EMA there and the step's broadcast groups send every owner's
+        window round; exit copies the stash back and broadcasts again.  ``step()``,
+        ``state_dict()``, ``load_state_dict()`` and a nested entry raise RuntimeError inside."""
+        if self._ema_decay is None:
+            raise RuntimeError("zero_amd: ema_parameters() needs ShardedOptimizer(..., ema_decay=d)")
+        self._check_not_swapped("ema_parameters()")
+        with contextlib.ExitStack() as es:
+            dev = self._param_device
+            if dev is not None and dev.type == "cuda" and dev.index is not None:
+                es.enter_context(torch.cuda.device(dev))
+            if self.engine is None:
+                self._build_engine()
+            eng = self.engine
+            stream = torch.cuda.current_stream(eng.device)
+            win = eng.own_window()
+            with torch.no_grad():
+                stash = win.clone()
+                if win.numel():
+                    if win.dtype == torch.float32:
+                        win.copy_(eng.ema)
+                    else:
+                        from .kernels import convert
+
+                        convert(eng.ema, win, stream)
+                eng.broadcast_params(stream)
+            self._ema_swapped = True
+            try:
+                yield self
+            finally:
+                stream = torch.cuda.current_stream(eng.device)
+                with torch.no_grad():
+                    win.copy_(stash)
+                    eng.broadcast_params(stream)
+                self._ema_swapped = False
+                del stash
 
     def _check_clip(self):
         """``max_grad_norm`` is None or a limit >= 0 (infinity: report the norm, clip nothing) on
@@ -321,6 +403,7 @@ class ShardedOptimizerBase:
                                      state_dtype=self.state_dtype,
                                      state_rounding=self.state_rounding,
                                      state_seed=self.state_seed,
+                                     ema=self._ema_decay is not None,
                                      momentum=self._kind == "sgd" and any(
                                          g.get("momentum", 0) != 0 for g in self._groups))
         else:
@@ -372,9 +455,15 @@ class ShardedOptimizerBase:
             with torch.enable_grad():
                 loss = closure()
         step_start = time.perf_counter()
+        self._check_not_swapped("step()")
         if self.engine is None:
             self._build_engine()
         self._check_clip()
+        if self._ema_decay is not None:  # (the decay and the groups are mutable between steps)
+            check_ema_decay(self._ema_decay)
+            for gi in range(len(self._groups)):
+                check_ema_group(self._hparams_of(gi))
+            self.engine.ema_decay = self._ema_decay
         if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
             for gi in range(len(self._groups)):
                 check_bf16_state_group(self._hparams_of(gi), self.state_rounding)
@@ -469,6 +558,7 @@ class ShardedOptimizerBase:
         as the reference's ``opt.optimizer.state_dict()``), every tensor a copy of the engine's
         flat state, plus the split master's residual / fp32 master and ZeRO-1's carry
         (zero_amd/checkpoint.py)."""
+        self._check_not_swapped("state_dict()")
         torch.cuda.synchronize(self.params[0].device)  # the state of every enqueued step
         sd = Optimizer.state_dict(self.optimizer)
         index = {id(p): k for k, p in enumerate(ckpt.inner_params(self.optimizer))}
@@ -489,7 +579,10 @@ class ShardedOptimizerBase:
         """Restore a ``state_dict()`` of this rank (or a plain torch Adam state dict over the same
         owned parameters): hyper-parameters through torch's loader, state copied into the flat
         buffers.  Parameters are the model's (load them with the model's own state dict)."""
+        self._check_not_swapped("load_state_dict()")
         ckpt.check_header(state_dict, self._ckpt_header())
+        if self._ema_decay is None:
+            ckpt.check_ema_load(state_dict.get("state", {}))
         if self._master == "none":
             ckpt.check_master_free_load(state_dict.get("state", {}))
         if self.engine is None:

@@ -110,6 +110,52 @@ def check_master_free_group(hpd: dict) -> None:
         raise ValueError("zero_amd: master='none' does not support amsgrad")
 
 
+def check_ema_decay(ema_decay):
+    """``ema_decay`` as None (no EMA) or a float in [0, 1]; ValueError for anything else, a bool
+    included (torch's ``get_ema_multi_avg_fn`` refuses a decay outside that range alike)."""
+    if ema_decay is None:
+        return None
+    if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(ema_decay) <= 1.0:
+        raise ValueError(f"zero_amd: ema_decay must be None or a number in [0, 1] (got {ema_decay!r})")
+    return float(ema_decay)
+
+
+def ema_weight(ema_decay) -> float:
+    """The lerp weight of one EMA step: 1 - decay in double, rounded to fp32 once (torch's
+    ``lerp_(p, 1 - decay)`` hands its kernels the same number)."""
+    return float(np.float32(1.0 - check_ema_decay(ema_decay)))
+
+
+def check_ema(kind: str, carry: bool, state_dtype=None, master=None) -> None:
+    """What ``ema_decay`` cannot be combined with on an update core, as ValueError."""
+    if kind != "adam":
+        raise ValueError("zero_amd: ema_decay is not supported with torch.optim.SGD (the EMA is "
+                         "fused into the Adam update)")
+    if check_state_dtype(state_dtype) == torch.bfloat16:
+        raise ValueError("zero_amd: ema_decay is not supported with state_dtype=torch.bfloat16 (the "
+                         "fp32 EMA would add back the bytes the bf16 moments save)")
+    if master == "none":
+        raise ValueError("zero_amd: ema_decay is not supported with master='none' (there is no "
+                         "master to average)")
+    if carry:
+        raise ValueError("zero_amd: ema_decay is not supported with the ZeRO-1 gradient carry "
+                         "(ZeRO-1 at world size > 1)")
+
+
+def check_ema_group(hpd: dict) -> None:
+    if hpd.get("amsgrad"):
+        raise ValueError("zero_amd: ema_decay is not supported with amsgrad (the EMA streams "
+                         "through the slot of max_exp_avg_sq)")
+
+
+def join_split_master(param: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
+    """The fp32 split master of bf16 ``param`` and its int16 ``residual``:
+    (bits << 16) + sext(residual), as the kernel joins them."""
+    hi = param.detach().contiguous().view(torch.int16).to(torch.int32) << 16
+    return (hi + residual.reshape(hi.shape).to(torch.int32)).view(torch.float32)
+
+
 def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = False,
                  carry: bool = False, momentum: bool = True, state_dtype=None, master=None):
     """(total fp32 words, {name: (word offset, dtype)}) of the flat state of an ``L``-element
@@ -153,7 +199,7 @@ class UpdateCore:
     def __init__(self, kind: str, L: int, device, ws: int, group_of, n_params: int, *,
                  split: bool = False, fp32_master: bool = False, carry: bool = False,
                  momentum: bool = True, placement_tries: int = 8, state_dtype=None,
-                 state_rounding=None, state_seed: int = 0, master=None):
+                 state_rounding=None, state_seed: int = 0, master=None, ema: bool = False):
         from .engine import probed_zeros  # (engine.py builds on this module)
 
         if kind not in ("adam", "sgd"):
@@ -183,6 +229,14 @@ class UpdateCore:
             off, dt = lay.get(name, (0, None))
             setattr(self, name, None if dt is None else self.state[off:].view(dt)[:self.L])
         self.vmax = None
+        # ema (ema_decay): an fp32 EMA of the master per element, sharded like m, allocated like
+        # vmax, whose column of the rows it takes; every launch then goes through run_ema with the
+        # weight of the decay as it is at that step (the owner initialises the array from the
+        # master once the parameters are in place)
+        self.ema, self.ema_decay = None, None
+        if ema:
+            check_ema(kind, bool(carry), self.state_dtype, master)
+            self.ema = torch.zeros(self.L, dtype=torch.float32, device=device)
         self.steps = np.zeros(n_params, np.int64)  # torch's per-param state['step']
         self._cache = {}
         self.retired = []
@@ -205,11 +259,16 @@ class UpdateCore:
             views["master_residual"] = cut(self.lo)
         if self.vmax is not None:
             views["max_exp_avg_sq"] = cut(self.vmax)
+        if self.ema is not None:
+            views["ema_param"] = cut(self.ema)
         if ckpt and self.carry is not None:
             views["zero1_carry"] = cut(self.carry)
         return views
 
     def ensure_vmax(self):
+        if self.ema is not None:
+            raise ValueError("zero_amd: ema_decay is not supported with amsgrad (the EMA streams "
+                             "through the slot of max_exp_avg_sq)")
         if self.master_free:
             raise ValueError("zero_amd: master='none' does not support amsgrad")
         if self.state_dtype == torch.bfloat16:
@@ -219,9 +278,11 @@ class UpdateCore:
         return self.vmax
 
     def state_cols(self, rows, so) -> None:
-        """Columns 4-7 (m, v, vmax, carry) of zs_adam_seg ``rows`` at shard offsets ``so``."""
+        """Columns 4-7 (m, v, vmax -- an EMA core: the EMA array --, carry) of zs_adam_seg ``rows``
+        at shard offsets ``so``."""
         so = np.asarray(so).astype(np.uint64)
-        for col, t in ((4, self.m), (5, self.v), (6, self.vmax), (7, self.carry)):
+        x = self.vmax if self.ema is None else self.ema
+        for col, t in ((4, self.m), (5, self.v), (6, x), (7, self.carry)):
             if t is not None:
                 rows[:, col] = np.uint64(t.data_ptr()) + so * np.uint64(t.element_size())
 
@@ -251,15 +312,25 @@ class UpdateCore:
 
     def load_entry(self, i: int, views: dict, entry: dict, param) -> None:
         """``entry`` into parameter i's ``views`` and step count.  What it lacks starts fresh:
-        moments and carry 0 (torch's new Adam), the master = ``param`` as it is (residual 0)."""
+        moments and carry 0 (torch's new Adam), the master = ``param`` as it is (residual 0), the
+        EMA = the master as loaded."""
         for name, view in views.items():
             src = entry.get(name)
             if src is not None:
                 view.copy_(src.reshape(view.shape))
             elif name == "master_param":
                 view.copy_(param.detach().reshape(view.shape))
-            else:
+            elif name != "ema_param":
                 view.zero_()
+        if "ema_param" in views and entry.get("ema_param") is None:
+            view = views["ema_param"]
+            if "master_param" in views:
+                view.copy_(views["master_param"])
+            elif "master_residual" in views:
+                view.copy_(join_split_master(param.detach().reshape(view.shape),
+                                             views["master_residual"]))
+            else:
+                view.copy_(param.detach().reshape(view.shape))
         if self.kind == "sgd":  # no buffer saved: the parameter's next step is its first
             self.steps[i] = int(entry.get("momentum_buffer") is not None)
         else:
@@ -286,6 +357,8 @@ class UpdateCore:
             check_bf16_state_group(hpd, self.state_rounding)
         if self.master_free:
             check_master_free_group(hpd)
+        if self.ema is not None:
+            check_ema_group(hpd)
         if hpd["amsgrad"] and self.vmax is None:
             raise RuntimeError("amsgrad state buffer missing")
         hp = self._adam_hp(hpd, key, carry_mul)
@@ -329,7 +402,9 @@ class UpdateCore:
             e0.record(stream)
         if guard and coef is None:
             raise ValueError("zero_amd: the guarded update tests the clip coefficient")
-        if self.master_free:
+        if self.ema is not None:
+            aset.run_ema(hp, ema_weight(self.ema_decay), stream, coef=coef, guard=guard)
+        elif self.master_free:
             aset.run_psr(hp, self.m.data_ptr(), hp.sr_keys, stream, coef=coef, guard=guard)
         elif self.state_rounding == "stochastic":
             aset.run_sr(hp, self.m.data_ptr(), hp.sr_keys, stream, coef=coef, guard=guard)

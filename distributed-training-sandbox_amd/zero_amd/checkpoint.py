@@ -13,7 +13,8 @@ optimizer's parameters in group order — and the tensors are copied into and ou
 Per-parameter entries: ``step`` (fp32 CPU scalar, torch's convention), ``exp_avg``, ``exp_avg_sq``
 (+ ``max_exp_avg_sq``) and, beyond torch's Adam, what the engine needs to continue bit for bit:
 ``master_residual`` (int16; bf16 params, split master: master = bf16 param bits << 16 + residual),
-``master_param`` (fp32 master), ``zero1_carry`` (ZeRO-1's A_{t-1}).  A
+``master_param`` (fp32 master), ``zero1_carry`` (ZeRO-1's A_{t-1}),
+``ema_param`` (the fp32 EMA of an optimizer with ``ema_decay``; the decay itself is not saved).  A
 ``zero_amd`` header names the variant, world size, rank and ownership, how bf16 parameters keep
 their master (``master``; not compared) and, with stochastic rounding of bf16 moments or of the
 parameters (``master="none"``), the generator's ``state_seed``, which a loading optimizer adopts; loading a dict written at a
@@ -55,6 +56,17 @@ def check_master_free_load(saved: dict) -> None:
             raise ValueError(f"zero_amd: state entry {k} carries {held[0]!r}, which an optimizer "
                              "with master='none' cannot keep: loading it would silently drop the "
                              "master's precision (load it into master='split' or 'fp32')")
+
+
+def check_ema_load(saved: dict) -> None:
+    """An optimizer without ``ema_decay`` keeps no EMA: an entry that carries ``ema_param`` would
+    lose it without a word, so it is refused.  (The other way round loads: the missing EMA starts
+    from the loaded master.)"""
+    for k, entry in saved.items():
+        if isinstance(entry, dict) and "ema_param" in entry:
+            raise ValueError(f"zero_amd: state entry {k} carries 'ema_param', which an optimizer "
+                             "without ema_decay cannot keep: loading it would silently drop the "
+                             "EMA (construct the optimizer with ema_decay=d)")
 
 
 def saved_state_seed(sd: dict):

@@ -84,7 +84,7 @@ class FlatEngine(ShardEngine):
                  bucket_bytes: int = 256 << 20, master: str = "split", placement_tries: int = 8,
                  grad_comm: str | None = None, layout: str = "reference", kind: str = "adam",
                  momentum: bool = True, state_dtype=None, state_rounding=None,
-                 state_seed: int = 0):
+                 state_seed: int = 0, ema: bool = False):
         if layout not in ("reference", "flat"):
             raise ValueError(f"the flat arena takes layout 'reference' or 'flat' (got {layout!r})")
         if layout == "flat" and carry:
@@ -95,7 +95,7 @@ class FlatEngine(ShardEngine):
         super().__init__(params, group_of, ws, rank, layout=layout, carry=carry, comm=comm,
                          bucket_bytes=1 << 62, buckets="ragged", placement_tries=placement_tries,
                          master=master, kind=kind, momentum=momentum, state_dtype=state_dtype,
-                         state_rounding=state_rounding, state_seed=state_seed)
+                         state_rounding=state_rounding, state_seed=state_seed, ema=ema)
         self.arena_kind = "flat"
         self.layout = layout
         plan, es, dev, dt = self.plan, self.es, self.device, self.dtype
@@ -124,6 +124,8 @@ class FlatEngine(ShardEngine):
                 s = int(self.slot[i])
                 self.P[s:s + int(self.numel[i])].copy_(p.detach().reshape(-1))
                 p.data = self.P[s:s + int(self.numel[i])].view(p.shape)
+            if self.ema is not None:  # the EMA starts at the master: the own window of P, widened
+                self.ema.copy_(self.own_window())
         # bf16 gradient exchange for fp32 parameters: G is converted into Gc
         # (bf16, same layout) before the reduces, which then move and sum 2 B per element; Adam
         # reads the bf16 sum (its fp32 master is the fp32 parameter itself)
@@ -237,6 +239,25 @@ class FlatEngine(ShardEngine):
         else:  # fp32: P is the master, updated in place
             rows = self._adam_rows(idx, g, pslot, pslot, 0, so, ln)
         return _Round(j, send, recv, count, bcast, rows, idx)
+
+    def own_window(self) -> torch.Tensor:
+        """This rank's stream in P: the parameters its shard's state (and EMA) belongs to."""
+        b = int(self.base[self.rank])
+        return self.P[b:b + self.L]
+
+    def broadcast_params(self, stream) -> None:
+        """Every owner's window of P to all ranks, round by round on the communication stream
+        (the step's own broadcast groups), ``stream`` ordered before and after; nothing at
+        world size 1."""
+        if self.ws == 1:
+            return
+        cs = self.comm_stream
+        self.ev_grads.record(stream)
+        cs.wait_event(self.ev_grads)
+        for rd in self.rounds:
+            self._bcast_round(rd, cs)
+        self.ev_bc[self.K - 1].record(cs)
+        stream.wait_event(self.ev_bc[self.K - 1])
 
     def slot_view(self, buf: torch.Tensor, i: int) -> torch.Tensor:
         s, n = int(self.slot[i]), int(self.numel[i])

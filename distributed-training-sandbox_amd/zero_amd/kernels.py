@@ -290,6 +290,15 @@ class AdamSet:
         _lib.call("zs_adamset_run_psr", self._h, ctypes.byref(hp), ptr, int(bool(guard)),
                   int(m_base), int(keys[0]), int(keys[1]), stream_handle(stream))
 
+    def run_ema(self, hp: AdamHParams, ema_w: float, stream, coef=None, guard=False) -> None:
+        """``run`` (``coef`` None), ``run_clipped`` or, with ``guard``, ``run_guarded`` of a set
+        whose ``vmax`` column points at fp32 EMA arrays, followed per element by
+        ``ema = lerp(ema, master as stored, ema_w)`` in the same kernel (zs_adamset_run_ema);
+        ``ema_w`` = fp32(1 - decay)."""
+        ptr = None if coef is None else coef if isinstance(coef, int) else coef.data_ptr()
+        _lib.call("zs_adamset_run_ema", self._h, ctypes.byref(hp), ptr, int(bool(guard)),
+                  float(ema_w), stream_handle(stream))
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib is not None:

@@ -69,12 +69,13 @@ from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_BF16_SR, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
 from ._sharded import group_hparams, optimizer_kind
-from ._update import (GradClip, UpdateCore, check_bf16_state_group, check_master_free,
+from ._update import (GradClip, UpdateCore, check_bf16_state_group, check_ema, check_ema_decay,
+                      check_ema_group, check_master_free,
                       check_master_free_group, check_max_grad_norm, check_param_grad_norms, check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
                       owner_range)
 from .comm import STREAM_SYNC, RcclComm, Sync, comm_stream, sync_kind, zs_dtype
 from .engine import ALIGN_ELEMS
-from .kernels import AdamSet, SgdSet, stream_handle
+from .kernels import AdamSet, SgdSet, convert, stream_handle
 from .training_utils.utils import get
 
 try:  # the hooks' per-module install / release in C++ (csrc/zs_host_ext.cpp, built with the library)
@@ -1841,7 +1842,7 @@ class ShardedOptimizer:
                  accumulation_dtype=None, state_dtype=None, state_rounding: str | None = None,
                  state_seed: int = 0, max_grad_norm: float | None = None,
                  skip_nonfinite: bool = False, master: str = "split",
-                 param_grad_norms: bool = False):
+                 param_grad_norms: bool = False, ema_decay: float | None = None):
         # global gradient-norm clipping inside step() (update mode; None = off): a plain attribute,
         # re-checked at every step().  skip_nonfinite (with it; Adam): a step whose gradient norm
         # is not finite is skipped on the device.  Both are refused here where they
@@ -1903,12 +1904,24 @@ class ShardedOptimizer:
             check_master_free(self._kind, False,
                               all(p.dtype == torch.bfloat16 for g in optimizer.param_groups
                                   for p in g["params"]))
+        # ema_decay (update mode, Adam): an fp32 EMA of the master weights on this rank's chunks,
+        # updated inside the fused step ("Sharded EMA"); None: off.  Refused here
+        # where it does not apply, on every rank and before anything collective
+        self._ema_decay = check_ema_decay(ema_decay)
+        self._ema_swapped = False  # inside ema_parameters()
+        if self._ema_decay is not None:
+            if not update:
+                raise ValueError("zero_amd: ema_decay applies to update mode (reference mode never "
+                                 "updates: there is nothing to average)")
+            check_ema(self._kind, False, self.state_dtype, master)
         for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
             hpd = group_hparams(self._kind, group, optimizer)
             if self.state_dtype == torch.bfloat16 and self._kind == "adam":
                 check_bf16_state_group(hpd, self.state_rounding)
             if master == "none":
                 check_master_free_group(hpd)
+            if self._ema_decay is not None:
+                check_ema_group(hpd)
         if self.state_dtype == torch.bfloat16 and self._kind == "sgd":
             raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with "
                              "torch.optim.SGD (bf16 moments are Adam's)")
@@ -1987,7 +2000,10 @@ class ShardedOptimizer:
                                 master="none" if self._master_free else None,
                                 state_dtype=self.state_dtype,
                                 state_rounding=self.state_rounding, state_seed=self.state_seed,
-                                momentum=any(g.get("momentum", 0) != 0 for g in self._groups))
+                                momentum=any(g.get("momentum", 0) != 0 for g in self._groups),
+                                ema=self._ema_decay is not None)
+        if self._core.ema is not None:  # the EMA starts at the master: the chunks, widened
+            self._core.ema.copy_(ar.P)
         self._core.timing_events = self._timing_events
         self.placement = self._core.placement
         gdt = torch.bfloat16 if self._grad_comm else ar.dtype
@@ -2012,6 +2028,56 @@ class ShardedOptimizer:
         if not self.update:
             raise ValueError("zero_amd: max_grad_norm applies to update mode (reference mode "
                              "never updates: zero3.py:150-153 drops every gradient)")
+
+    @property
+    def ema_decay(self):
+        """The EMA's decay (None: the optimizer keeps no EMA): ``ema = lerp(ema, master, 1 - d)``
+        after every update.  It may be changed between steps (a warm-up schedule) and is checked
+        when set and at every step; whether there is an EMA is fixed at construction.  Not
+        checkpointed."""
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, d):
+        if (d is None) != (self._ema_decay is None):
+            raise ValueError("zero_amd: whether the optimizer keeps an EMA is fixed at construction "
+                             "(ShardedOptimizer(..., ema_decay=d))")
+        self._ema_decay = check_ema_decay(d)
+
+    def _check_not_swapped(self, what: str):
+        if self.__dict__.get("_ema_swapped"):
+            raise RuntimeError(f"zero_amd: {what} inside ema_parameters(): the parameters hold the "
+                               "EMA, not the weights training continues from")
+
+    @contextlib.contextmanager
+    def ema_parameters(self):
+        """Inside the ``with`` block this rank's chunks hold the EMA rounded to the parameter dtype
+        (to nearest even), so the gathers of a forward hand every rank the EMA weights; on exit
+        the chunks are restored bit for bit.  The chunk arena is stashed in the parameter dtype
+        (freed on exit) and the shards are marked changed on entry and on exit
+        (``mark_params_changed``); every rank enters and leaves together.  ``step()``,
+        ``state_dict()``, ``load_state_dict()`` and a nested entry raise RuntimeError inside."""
+        if self._ema_decay is None:
+            raise RuntimeError("zero_amd: ema_parameters() needs ShardedOptimizer(..., update=True, "
+                               "ema_decay=d)")
+        self._check_not_swapped("ema_parameters()")
+        P, ema = self._arena.P, self._core.ema
+        with torch.cuda.device(P.device), torch.no_grad():
+            stash = P.clone()
+            if P.dtype == torch.float32:
+                P.copy_(ema)
+            else:
+                convert(ema, P, torch.cuda.current_stream(P.device))
+        self.mark_params_changed()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            with torch.cuda.device(P.device), torch.no_grad():
+                P.copy_(stash)
+            self.mark_params_changed()
+            self._ema_swapped = False
+            del stash
 
     @property
     def last_grad_norm(self):
@@ -2240,6 +2306,11 @@ class ShardedOptimizer:
         if self._master_free:
             for group in self._groups:
                 check_master_free_group(group_hparams(self._kind, group, self.optimizer))
+        if self._ema_decay is not None:  # (the decay and the groups are mutable between steps)
+            check_ema_decay(self._ema_decay)
+            for group in self._groups:
+                check_ema_group(group_hparams(self._kind, group, self.optimizer))
+            self._core.ema_decay = self._ema_decay
         if red.incomplete():
             raise RuntimeError(
                 "zero_amd ZeRO-3: a backward did not finish (it raised), so the accumulated "
@@ -2366,6 +2437,7 @@ class ShardedOptimizer:
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._check_not_swapped("step()")
         self._check_clip()
         step_start = time.perf_counter()
         e0 = torch.cuda.Event(enable_timing=True)
@@ -2444,6 +2516,7 @@ class ShardedOptimizer:
         entry is this rank's dim-0 chunk of its state (copies of the flat state, incl. the split
         master's residual), so each rank saves its own shard.  Reference mode keeps no state
         (zero3.py:150-153), like the reference."""
+        self._check_not_swapped("state_dict()")
         torch.cuda.synchronize(self._arena.device)
         sd = Optimizer.state_dict(self.optimizer)
         state = {}
@@ -2464,7 +2537,10 @@ class ShardedOptimizer:
         before the next forward.  Loading marks the shards changed (``mark_params_changed``), so
         the next gather is ordered after that copy; a caller that edits the shards at any other
         time between two steps (after an eval forward, say) calls ``mark_params_changed()``."""
+        self._check_not_swapped("load_state_dict()")
         ckpt.check_header(state_dict, self._ckpt_header())
+        if self._ema_decay is None:
+            ckpt.check_ema_load(state_dict.get("state", {}))
         if self._master == "none":
             ckpt.check_master_free_load(state_dict.get("state", {}))
         self.mark_params_changed()

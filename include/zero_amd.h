@@ -475,6 +475,24 @@ int zs_adamset_run_psr(const zs_adamset* as, const zs_adam_hparams* hp, const fl
 int zs_adamset_set_state_rounding(zs_adamset* as, int stochastic);
 int zs_sr_pkeys(uint32_t key0, uint32_t key1, uint32_t* pkey0, uint32_t* pkey1);
 
+/* Sharded EMA of the master weights, fused into the Adam update (additive in ABI v13).  Over a set
+ * made by zs_adamset_create / _create_ex with fp32 state and any master storage but ZS_BF16_SR,
+ * whose segments' `vmax` column points at an fp32 EMA array (the stream slot amsgrad uses, so the
+ * two exclude each other): zs_adamset_run's update runs unchanged (coef NULL), or
+ * zs_adamset_run_clipped's (coef given), or zs_adamset_run_guarded's (coef and guard != 0: a NaN
+ * coefficient, nothing is read or written, the EMA included).  Then, per element,
+ *   ema = lerp(ema, master_after, ema_weight)
+ * with ATen's lerp -- fma(w, end - start, start) for w < 0.5, fma(w - 1, end - start, end)
+ * otherwise -- and master_after the fp32 master as this call stored it: the fp32 parameter or master,
+ * or for ZS_BF16_SPLIT (hi << 16) + sext(lo) of the two words just written.  ema_weight is
+ * 1 - decay, rounded to fp32 by the caller.  A segment without a gradient runs like any other (its
+ * gradient reads as zero), as in zs_adamset_run.  Bytes per element: those of the amsgrad run.
+ * ZS_ERR_INVALID, nothing launched: a NULL set or hparams; a set made by zs_sgdset_create; ZS_BF16
+ * state; a ZS_BF16_SR set; a set with the carry; a non-empty set without the vmax column;
+ * hp->amsgrad; guard without coef; an ema_weight that is NaN or outside [0, 1]. */
+int zs_adamset_run_ema(const zs_adamset* as, const zs_adam_hparams* hp, const float* coef, int guard,
+                       float ema_weight, uintptr_t stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Fused SGD (momentum, Nesterov), additive in ABI v13.  Replaces torch.optim.SGD.step on the    */
 /* owned shard where the reference's ShardedOptimizer wraps an SGD (zero1.py:88, zero2.py:120,  */
