@@ -307,6 +307,13 @@ __device__ __forceinline__ float prep_grad(float gsum, float& carry, const HPT& 
 // one element, elem<CARRY, CLIP>(gsum, p, m, v, vmax, carry, hp, coef); state it does not touch is
 // passed as a dummy.  kGradOffset2: see update_full_chunk.
 
+// Rule::Stats: what a lane carries through the bodies of one chunk beside the update -- nothing
+// (NoStats), or AdamStatsRule's two running sums.
+struct NoStats {};
+struct LaneStats {
+  float d = 0.0f, w = 0.0f;
+};
+
 // lerp_w / lerp_hi: ATen's lerp (Lerp.h) with weight w = 1-beta1 is self + w*(end-self) for
 // |w| < 0.5 and end - (end-self)*(1-w) otherwise; make_hp holds the fma's coefficient (w, or w-1 in
 // one fp32 subtraction) and which operand it adds to, so the choice is uniform.
@@ -321,6 +328,8 @@ struct AdamRule {
   static constexpr bool kM = true, kV = true, kX = AMS, kGradOffset2 = true;
   static constexpr bool kPsr = false;  // AdamPsrRule: no master, the bf16 parameter in place
   static constexpr bool kEma = false;  // AdamEmaRule: the vmax stream is an EMA of the stored master
+  static constexpr bool kStats = false;  // AdamStatsRule: per-chunk sums of (p1 - p0)^2 and p1^2
+  using Stats = NoStats;
 
   // One element of torch.optim.Adam's single-tensor update (adam.py:394-547), one fp32 operation
   // per operation of torch's CPU kernels: lerp = fma(w, end-self, self) or fma(w-1, end-self, end)
@@ -459,6 +468,48 @@ struct AdamEmaRule : AdamRule<false> {
   }
 };
 
+// Per-parameter update and weight norms (zs_adamset_run_stats; DESIGN.md §4, "Per-parameter update
+// and weight norms").  AdamStatsRule names the instances: the unchanged amsgrad-free fp32 rule, whose
+// bodies keep the master as loaded (p0) and, right after the storage step, add per element
+//   d = p1 - p0 (one fp32 subtraction), accd = fmaf(d, d, accd), accw = fmaf(p1, p1, accw)
+// with p1 the fp32 master as stored (the split master: the re-joined words, as AdamEmaRule::ema
+// sees it).  A lane's two sums cover its elements of one chunk, in the order the body visits them;
+// stats_store widens them to double, sums the wave's 64 lanes (block_sum's first stage) and lane 0
+// stores the pair with plain stores: one slot per wave per chunk, so the four waves of a workgroup
+// stay independent (no LDS, no barrier, no atomics).  The slot of a chunk: off[entry] +
+// 4 * (chunk in entry) + wave, off the table's per-entry offsets (vec_off in the vector kernel,
+// sca_off in the scalar one); plane 0 (sum d^2) at planes, plane 1 (sum p1^2) nslots doubles on.
+struct StatsHP : HP {
+  double* planes;
+  int64_t nslots;
+  const int64_t* vec_off;
+  const int64_t* sca_off;
+};
+struct AdamStatsRule : AdamRule<false> {
+  using Hyper = StatsHP;
+  using Stats = LaneStats;
+  static constexpr bool kStats = true;
+  static __device__ __forceinline__ void stat(float p0, float p1, LaneStats& a) {
+#pragma clang fp contract(off)
+    const float d = p1 - p0;
+    a.d = fmaf(d, d, a.d);
+    a.w = fmaf(p1, p1, a.w);
+  }
+};
+// The wave's sums of one chunk into its slot (every lane of the wave arrives here).
+__device__ __forceinline__ void stats_store(const LaneStats& a, const StatsHP& hp, int64_t slot) {
+  double d = double(a.d), w = double(a.w);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    d += __shfl_down(d, o, 64);
+    w += __shfl_down(w, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    glob(hp.planes)[slot] = d;
+    glob(hp.planes)[hp.nslots + slot] = w;
+  }
+}
+
 // torch.optim.SGD over the same tables: field `m` of a segment is the momentum buffer (MOM: the
 // set has one), `v` and `vmax` are unused.  Without MOM no state array is touched.
 struct SgdHP {
@@ -472,6 +523,8 @@ struct SgdRule {
   static constexpr bool kM = MOM, kV = false, kX = false, kGradOffset2 = false;
   static constexpr bool kPsr = false;
   static constexpr bool kEma = false;
+  static constexpr bool kStats = false;
+  using Stats = NoStats;
 
   // One element of torch.optim.SGD's single-tensor update (sgd.py _single_tensor_sgd), in the
   // rounding order of torch's CPU kernels: add(x, alpha=a) = fma(a, x, self), so
@@ -586,7 +639,8 @@ struct NoStream {
 template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool HASG, bool CLIP,
           typename ST = float>
 __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
-                                                  const typename Rule::Hyper& hp, float coef) {
+                                                  const typename Rule::Hyper& hp, float coef,
+                                                  typename Rule::Stats& acc) {
   constexpr int G = adam_groups(SPLIT);
   constexpr bool G32 = sizeof(GT) == 4;
   constexpr bool S16 = sizeof(ST) == 2;
@@ -671,6 +725,11 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
     }
     if constexpr (Rule::kX) unpack4(xq[u], xp);
     if constexpr (CARRY) unpack4(cq[u], cp);
+    float p0[4] = {0.f, 0.f, 0.f, 0.f};  // the master as loaded (kStats)
+    if constexpr (Rule::kStats) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) p0[j] = pp[j];
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       Rule::template elem<CARRY, CLIP>(gp[j], pp[j], mp[j], vp[j], xp[j], cp[j], hp, coef);
@@ -694,6 +753,10 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
 #pragma unroll
         for (int j = 0; j < 4; ++j) Rule::ema(join_master(h[j], l[j]), xp[j], hp);
       }
+      if constexpr (Rule::kStats) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Rule::stat(p0[j], join_master(h[j], l[j]), acc);
+      }
     } else {
       if (s.master_out) nt_st16(po.at(u, o4), pack4(pp));
       if (s.p_out) {
@@ -703,6 +766,10 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
       if constexpr (Rule::kEma) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) Rule::ema(pp[j], xp[j], hp);
+      }
+      if constexpr (Rule::kStats) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Rule::stat(p0[j], pp[j], acc);
       }
     }
     if constexpr (kStochastic<ST>) {
@@ -731,7 +798,8 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
 template <typename Rule, typename GT, bool CARRY, bool SPLIT, int G, bool CLIP,
           typename ST = float>
 __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
-                                                   const typename Rule::Hyper& hp, float coef) {
+                                                   const typename Rule::Hyper& hp, float coef,
+                                                   typename Rule::Stats& acc) {
   constexpr bool S16 = sizeof(ST) == 2;
   constexpr bool PSR = Rule::kPsr;
   static_assert(!S16 || (Rule::kM && Rule::kV && !Rule::kX && !CARRY),
@@ -778,6 +846,11 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
       float* vp = reinterpret_cast<float*>(&v4[u]);
       float* xp = reinterpret_cast<float*>(&x4[u]);
       float* cp = reinterpret_cast<float*>(&c4[u]);
+      float p0[4] = {0.f, 0.f, 0.f, 0.f};  // the master as loaded (kStats)
+      if constexpr (Rule::kStats) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p0[j] = pp[j];
+      }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float mv = Rule::kM ? mp[j] : 0.0f;
@@ -803,6 +876,10 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
 #pragma unroll
           for (int j = 0; j < 4; ++j) Rule::ema(join_master(h[j], l[j]), xp[j], hp);
         }
+        if constexpr (Rule::kStats) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) Rule::stat(p0[j], join_master(h[j], l[j]), acc);
+        }
       } else {
         if (s.master_out) st4(s.master_out, i, p4[u]);
         if (s.p_out) {
@@ -812,6 +889,10 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
         if constexpr (Rule::kEma) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) Rule::ema(pp[j], xp[j], hp);
+        }
+        if constexpr (Rule::kStats) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) Rule::stat(p0[j], pp[j], acc);
         }
       }
       if constexpr (kStochastic<ST>) {
@@ -863,6 +944,9 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
 // SPLIT names its geometry): no master, the bf16 parameter in place, any of the three ST.
 // Rule = AdamEmaRule (zs_adamset_run_ema; fp32 moments, no carry): the vmax stream is an EMA of the
 // master, moved by Rule::ema right after the storage step of each body, on the value as stored.
+// Rule = AdamStatsRule (zs_adamset_run_stats; fp32 moments, no carry): each body also adds the
+// element's (stored - loaded)^2 and stored^2 to the lane's Rule::Stats, which stats_store sums per
+// wave into the chunk's slots once the chunk is done.
 template <typename Rule, typename GT, bool CARRY, bool SPLIT, bool LOADS_FIRST, bool CLIP,
           typename ST = float, bool GUARD = false>
 __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
@@ -888,19 +972,22 @@ __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
     const AdamSeg s = segs[seg];
     constexpr int G = adam_groups(SPLIT);
     const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT);
+    typename Rule::Stats acc;  // kStats: this lane's sums over the chunk, +0 at its start
     if constexpr (LOADS_FIRST) {
       if (e0 + adam_chunk(SPLIT) <= s.n) {  // uniform per workgroup
-        if (s.g) update_full_chunk<Rule, GT, CARRY, SPLIT, true, CLIP, ST>(s, e0, hp, coef);
-        else update_full_chunk<Rule, GT, CARRY, SPLIT, false, CLIP, ST>(s, e0, hp, coef);
+        if (s.g) update_full_chunk<Rule, GT, CARRY, SPLIT, true, CLIP, ST>(s, e0, hp, coef, acc);
+        else update_full_chunk<Rule, GT, CARRY, SPLIT, false, CLIP, ST>(s, e0, hp, coef, acc);
       } else {
 #pragma unroll 1
         for (int u = 0; u < G && e0 + int64_t(u) * kThreads * 4 < s.n; ++u)
           update_pred_groups<Rule, GT, CARRY, SPLIT, 1, CLIP, ST>(
-              s, e0 + int64_t(u) * kThreads * 4, hp, coef);
+              s, e0 + int64_t(u) * kThreads * 4, hp, coef, acc);
       }
     } else {
-      update_pred_groups<Rule, GT, CARRY, SPLIT, G, CLIP, ST>(s, e0, hp, coef);
+      update_pred_groups<Rule, GT, CARRY, SPLIT, G, CLIP, ST>(s, e0, hp, coef, acc);
     }
+    if constexpr (Rule::kStats)
+      stats_store(acc, hp, hp.vec_off[seg] + 4 * (c - chunk_prefix[seg]) + (threadIdx.x >> 6));
   }
 }
 
@@ -930,55 +1017,63 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     const AdamSeg s = segs[seg];
     const int64_t i0 = (c - chunk_prefix[seg]) * kThreads;  // uniform
     const int64_t i = i0 + threadIdx.x;
-    if (i >= s.n) continue;
-    float gs = s.g ? load_g1<GT>(s.g, i) : 0.0f;
-    const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
-    float p;
-    if constexpr (PSR) p = bf16_to_f32(glob(reinterpret_cast<const unsigned short*>(s.master))[i]);
-    else
-      p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
-                : glob(s.master)[i];
-    const gptr<unsigned short> mb = glob(reinterpret_cast<unsigned short*>(s.m));
-    const gptr<unsigned short> vb = glob(reinterpret_cast<unsigned short*>(s.v));
-    float m = 0.0f, v = 0.0f, vm = 0.0f;
-    if constexpr (S16) {
-      m = bf16_to_f32(mb[i]);
-      v = bf16_to_f32(vb[i]);
-    } else {
-      if constexpr (Rule::kM) m = glob(s.m)[i];
-      if constexpr (Rule::kV) v = glob(s.v)[i];
+    typename Rule::Stats acc;  // kStats: a lane past n adds nothing and still joins the wave's sum
+    if (i < s.n) {
+      float gs = s.g ? load_g1<GT>(s.g, i) : 0.0f;
+      const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
+      float p;
+      if constexpr (PSR)
+        p = bf16_to_f32(glob(reinterpret_cast<const unsigned short*>(s.master))[i]);
+      else
+        p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
+                  : glob(s.master)[i];
+      const gptr<unsigned short> mb = glob(reinterpret_cast<unsigned short*>(s.m));
+      const gptr<unsigned short> vb = glob(reinterpret_cast<unsigned short*>(s.v));
+      float m = 0.0f, v = 0.0f, vm = 0.0f;
+      if constexpr (S16) {
+        m = bf16_to_f32(mb[i]);
+        v = bf16_to_f32(vb[i]);
+      } else {
+        if constexpr (Rule::kM) m = glob(s.m)[i];
+        if constexpr (Rule::kV) v = glob(s.v)[i];
+      }
+      if constexpr (Rule::kX) vm = glob(s.vmax)[i];
+      float cr = CARRY ? glob(s.carry)[i] : 0.0f;
+      const float p0 = p;  // the master as loaded (kStats)
+      Rule::template elem<CARRY, CLIP>(gs, p, m, v, vm, cr, hp, coef);
+      if constexpr (PSR) {
+        const uint32_t r16 = psr_r16_at(psr_seg_index<ST>(s.m, hp) + uint64_t(i0), threadIdx.x, hp);
+        glob(s.p_out)[i] = (unsigned short)(sr_word(p, r16) >> 16);
+      } else if constexpr (SPLIT) {
+        const unsigned short h = f32_to_bf16(p);
+        glob(s.p_out)[i] = h;
+        const uint32_t l = master_residual(p, h);
+        lo[i] = (unsigned short)l;
+        if constexpr (Rule::kEma) Rule::ema(join_master(h, l), vm, hp);
+        if constexpr (Rule::kStats) Rule::stat(p0, join_master(h, l), acc);
+      } else {
+        if (s.master_out) glob(s.master_out)[i] = p;
+        if (s.p_out) glob(s.p_out)[i] = f32_to_bf16(p);
+        if constexpr (Rule::kEma) Rule::ema(p, vm, hp);
+        if constexpr (Rule::kStats) Rule::stat(p0, p, acc);
+      }
+      if constexpr (kStochastic<ST>) {
+        uint32_t mh, vh;
+        sr_narrow(m, v, sr_bits_at(sr_seg_index(s.m, hp) + uint64_t(i0), threadIdx.x, hp), mh, vh);
+        mb[i] = (unsigned short)(mh >> 16);
+        vb[i] = (unsigned short)(vh >> 16);
+      } else if constexpr (S16) {
+        mb[i] = f32_to_bf16(m);
+        vb[i] = f32_to_bf16(v);
+      } else {
+        if constexpr (Rule::kM) glob(s.m)[i] = m;
+        if constexpr (Rule::kV) glob(s.v)[i] = v;
+      }
+      if constexpr (Rule::kX) glob(s.vmax)[i] = vm;
+      if constexpr (CARRY) glob(s.carry)[i] = cr;
     }
-    if constexpr (Rule::kX) vm = glob(s.vmax)[i];
-    float cr = CARRY ? glob(s.carry)[i] : 0.0f;
-    Rule::template elem<CARRY, CLIP>(gs, p, m, v, vm, cr, hp, coef);
-    if constexpr (PSR) {
-      const uint32_t r16 = psr_r16_at(psr_seg_index<ST>(s.m, hp) + uint64_t(i0), threadIdx.x, hp);
-      glob(s.p_out)[i] = (unsigned short)(sr_word(p, r16) >> 16);
-    } else if constexpr (SPLIT) {
-      const unsigned short h = f32_to_bf16(p);
-      glob(s.p_out)[i] = h;
-      const uint32_t l = master_residual(p, h);
-      lo[i] = (unsigned short)l;
-      if constexpr (Rule::kEma) Rule::ema(join_master(h, l), vm, hp);
-    } else {
-      if (s.master_out) glob(s.master_out)[i] = p;
-      if (s.p_out) glob(s.p_out)[i] = f32_to_bf16(p);
-      if constexpr (Rule::kEma) Rule::ema(p, vm, hp);
-    }
-    if constexpr (kStochastic<ST>) {
-      uint32_t mh, vh;
-      sr_narrow(m, v, sr_bits_at(sr_seg_index(s.m, hp) + uint64_t(i0), threadIdx.x, hp), mh, vh);
-      mb[i] = (unsigned short)(mh >> 16);
-      vb[i] = (unsigned short)(vh >> 16);
-    } else if constexpr (S16) {
-      mb[i] = f32_to_bf16(m);
-      vb[i] = f32_to_bf16(v);
-    } else {
-      if constexpr (Rule::kM) glob(s.m)[i] = m;
-      if constexpr (Rule::kV) glob(s.v)[i] = v;
-    }
-    if constexpr (Rule::kX) glob(s.vmax)[i] = vm;
-    if constexpr (CARRY) glob(s.carry)[i] = cr;
+    if constexpr (Rule::kStats)
+      stats_store(acc, hp, hp.sca_off[seg] + 4 * (c - chunk_prefix[seg]) + (threadIdx.x >> 6));
   }
 }
 
@@ -1237,6 +1332,29 @@ __global__ __launch_bounds__(kThreads) void param_norms_kernel(const float* __re
   for (int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x; i < n;
        i += int64_t(gridDim.x) * kThreads)
     norms[i] = float(sqrt(double(sumsq[i])) / grad_div);
+}
+
+// zs_update_norms: parameter i of sums3 = [sum d^2 | sum p1^2 | touched], n floats each.  A step
+// that measured nothing for i -- the coefficient is NaN (the guarded update skipped the step) or no
+// rank has a range for i -- gives the update norm +0.0 and leaves the weight norm as it is.
+__global__ __launch_bounds__(kThreads) void update_norms_kernel(
+    const float* __restrict__ sums3, int64_t n, const float* __restrict__ coef,
+    float* __restrict__ update_norms, float* __restrict__ weight_norms) {
+#pragma clang fp contract(off)
+  bool skipped = false;
+  if (coef) {
+    const float c = *coef;
+    skipped = c != c;
+  }
+  for (int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x; i < n;
+       i += int64_t(gridDim.x) * kThreads) {
+    if (skipped || sums3[2 * n + i] == 0.0f) {
+      update_norms[i] = 0.0f;
+    } else {
+      update_norms[i] = float(sqrt(double(sums3[i])));
+      weight_norms[i] = float(sqrt(double(sums3[n + i])));
+    }
+  }
 }
 
 // clip_grad_norm_'s coefficient (error_if_nonfinite=False): norm = sqrt(sumsq) / grad_div in
@@ -1978,6 +2096,11 @@ struct zs_adamset {
   int64_t* d_sca_slots = nullptr;
   int64_t sqs_vec = 0, sqs_sca = 0;
   std::vector<int64_t> seg_off;
+  // zs_adamset_run_stats: 4 slots per chunk of either table, by input segment (vector part, then
+  // scalar part); each table entry's first slot (un_vec, then un_sca), on the device from the first
+  // such run on (d_un_off: nvec + nsca offsets); un_seg_off (inputs + 1)
+  std::vector<int64_t> un_off, un_seg_off;
+  mutable int64_t* d_un_off = nullptr;
   int g_dtype = ZS_F32, p_dtype = ZS_BF16, has_carry = 0, has_vmax = 0;
   // zs_sgdset_create: an SGD set (field m is the momentum buffer, has_mom: it has one)
   int sgd = 0, has_mom = 0;
@@ -2137,6 +2260,10 @@ template <bool>
 using AdamEmaRuleOf = AdamEmaRule;
 // zs_adamset_run_ema: fp32 moments, no carry; every (gradient dtype, master storage) pair
 using AdamEmaFamily = UpdateFamily<AdamEmaRuleOf, float, false, true>;
+template <bool>
+using AdamStatsRuleOf = AdamStatsRule;
+// zs_adamset_run_stats: the same pairs, 24 vector + 12 scalar instances
+using AdamStatsFamily = UpdateFamily<AdamStatsRuleOf, float, false, true>;
 
 struct UpdateTable {  // a segment array with its chunk prefix
   const AdamSeg* segs;
@@ -2828,6 +2955,16 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   as->sqs_vec = vslots[vec.size()];
   as->sqs_sca = sslots[sca.size()];
   as->seg_off = std::move(seg_off);
+  // the update-norm slots: 4 per chunk (one per wave), laid out the same way
+  std::vector<int64_t> un_seg(size_t(n) + 1, 0), un_off(vec.size() + sca.size(), 0);
+  for (size_t e = 0; e < vec.size(); ++e) un_seg[size_t(vec_in[e]) + 1] += 4 * (vpre[e + 1] - vpre[e]);
+  for (size_t e = 0; e < sca.size(); ++e) un_seg[size_t(sca_in[e]) + 1] += 4 * (spre[e + 1] - spre[e]);
+  for (size_t i = 0; i < size_t(n); ++i) un_seg[i + 1] += un_seg[i];
+  for (size_t e = 0; e < vec.size(); ++e) un_off[e] = un_seg[size_t(vec_in[e])];
+  for (size_t e = 0; e < sca.size(); ++e)
+    un_off[vec.size() + e] = un_seg[size_t(sca_in[e]) + 1] - 4 * (spre[e + 1] - spre[e]);
+  as->un_off = std::move(un_off);
+  as->un_seg_off = std::move(un_seg);
   as->elems = elems;
   as->bytes = bytes;
   as->g_dtype = g_dtype;
@@ -3048,6 +3185,58 @@ int zs_adamset_run_ema(const zs_adamset* as, const zs_adam_hparams* h, const flo
   hp.ema_hi = ema_weight < 0.5f ? 0 : 1;  // ATen's lerp, as make_hp for exp_avg
   hp.ema_w = hp.ema_hi ? ema_weight - 1.0f : ema_weight;
   return run_set<AdamEmaFamily>(as, false, hp, coef, stream, guard != 0);
+}
+
+int zs_adamset_update_norm_slots(const zs_adamset* as, int64_t* n, int64_t* seg_off) {
+  ZS_REQUIRE(as && n && seg_off, "zs_adamset_update_norm_slots: NULL argument");
+  *n = as->un_seg_off.back();
+  std::copy(as->un_seg_off.begin(), as->un_seg_off.end(), seg_off);
+  return ZS_OK;
+}
+
+int zs_adamset_run_stats(const zs_adamset* as, const zs_adam_hparams* h, const float* coef,
+                         int guard, double* partials, uintptr_t stream) {
+  const char* fn = "zs_adamset_run_stats";
+  ZS_REQUIRE(as && h, "%s: NULL argument", fn);
+  ZS_REQUIRE(!as->sgd, "%s: the norms ride on Adam's update (the set was made by zs_sgdset_create)",
+             fn);
+  ZS_REQUIRE(as->state_dtype == ZS_F32, "%s: a set with ZS_BF16 state has no stats instances", fn);
+  ZS_REQUIRE(as->p_dtype != ZS_BF16_SR, "%s: a ZS_BF16_SR set has no master to measure", fn);
+  ZS_REQUIRE(!as->has_carry, "%s: a set with the ZeRO-1 carry has no stats instances", fn);
+  ZS_REQUIRE(!as->has_vmax, "%s: a set with the vmax column (amsgrad, EMA) has no stats instances",
+             fn);
+  ZS_REQUIRE(h->amsgrad == 0, "%s: amsgrad has no stats instances", fn);
+  ZS_REQUIRE(!guard || coef, "%s: the guard tests the clip coefficient, which is NULL", fn);
+  const int64_t nslots = as->un_seg_off.back();
+  ZS_REQUIRE(partials != nullptr || nslots == 0, "%s: partials is NULL", fn);
+  if (nslots && !as->d_un_off) {  // first use: the per-entry slot offsets
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!as->d_un_off) {
+      const int rc = upload(as->un_off, &as->d_un_off);
+      if (rc != ZS_OK) return rc;
+    }
+  }
+  StatsHP hp;
+  static_cast<HP&>(hp) = make_hp(h);
+  hp.planes = partials;
+  hp.nslots = nslots;
+  hp.vec_off = as->d_un_off;
+  hp.sca_off = as->d_un_off ? as->d_un_off + as->nvec : nullptr;
+  return run_set<AdamStatsFamily>(as, false, hp, coef, stream, guard != 0);
+}
+
+int zs_update_norms(const float* sums3, int64_t n_params, const float* coef, float* update_norms,
+                    float* weight_norms, uintptr_t stream) {
+  ZS_REQUIRE(n_params >= 0 && (n_params == 0 || (sums3 && update_norms && weight_norms)),
+             "zs_update_norms: %lld parameters at NULL", (long long)n_params);
+  if (n_params == 0) return ZS_OK;
+  const int grid = int(std::min<int64_t>((n_params + kThreads - 1) / kThreads, 1024));
+  hipLaunchKernelGGL(update_norms_kernel, dim3(grid), dim3(kThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), sums3, n_params, coef, update_norms,
+                     weight_norms);
+  ZS_HIP(hipGetLastError());
+  return ZS_OK;
 }
 
 int zs_adamset_set_state_rounding(zs_adamset* as, int stochastic) {
@@ -3339,6 +3528,7 @@ int zs_adamset_destroy(zs_adamset* as) {
   if (as->d_sca_goff) (void)hipFree(as->d_sca_goff);
   if (as->d_vec_slots) (void)hipFree(as->d_vec_slots);
   if (as->d_sca_slots) (void)hipFree(as->d_sca_slots);
+  if (as->d_un_off) (void)hipFree(as->d_un_off);
   delete as;
   return ZS_OK;
 }

@@ -43,6 +43,7 @@ EXPORTED = (
     "zs_adamset_run_psr", "zs_adamset_set_state_rounding", "zs_sr_pkeys", "zs_adamset_run_ema",
     "zs_adamset_sqnorm_seg_partials", "zs_adamset_grad_sqnorm_segs", "zs_sqnorm_reduce_params",
     "zs_param_norms",
+    "zs_adamset_update_norm_slots", "zs_adamset_run_stats", "zs_update_norms",
     "zs_sgd_hparams_init", "zs_sgdset_create", "zs_sgdset_run",
     "zs_comm_unique_id", "zs_comm_init", "zs_comm_destroy", "zs_reduce_scatter", "zs_all_gather",
     "zs_all_reduce", "zs_reduce", "zs_broadcast", "zs_reduce_group", "zs_broadcast_group", "zs_all_gather_group", "zs_reduce_scatter_group",
@@ -159,6 +160,10 @@ _SIGS = {
                             ctypes.c_uint32, ctypes.c_uint32, _U], ctypes.c_int),
     "zs_adamset_run_ema": ([_P, ctypes.POINTER(AdamHParams), _P, ctypes.c_int, ctypes.c_float, _U],
                            ctypes.c_int),
+    "zs_adamset_update_norm_slots": ([_P, _PI64, _PI64], ctypes.c_int),
+    "zs_adamset_run_stats": ([_P, ctypes.POINTER(AdamHParams), _P, ctypes.c_int, _P, _U],
+                             ctypes.c_int),
+    "zs_update_norms": ([_P, _I64, _P, _P, _P, _U], ctypes.c_int),
     "zs_adamset_set_state_rounding": ([_P, ctypes.c_int], ctypes.c_int),
     "zs_sr_pkeys": ([ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
                      ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),

@@ -22,7 +22,8 @@ from torch.optim import Optimizer
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
 from ._update import (check_bf16_state_group, check_ema, check_ema_decay, check_ema_group,
-                      check_max_grad_norm, check_param_grad_norms,
+                      check_max_grad_norm, check_param_grad_norms, check_update_norms,
+                      check_update_norms_group,
                       check_skip_nonfinite, check_master_free, check_master_free_group,
                       check_state_dtype, check_state_rounding, owner_range)
 from .engine import ShardEngine
@@ -85,7 +86,7 @@ class ShardedOptimizerBase:
                  max_grad_norm: float | None = None, state_dtype=None,
                  state_rounding: str | None = None, state_seed: int = 0,
                  skip_nonfinite: bool = False, param_grad_norms: bool = False,
-                 ema_decay: float | None = None):
+                 ema_decay: float | None = None, param_update_norms: bool = False):
         if arena not in ("flat", "buckets", "auto"):
             raise ValueError(f"arena must be 'flat', 'buckets' or 'auto' (got {arena!r})")
         # the moments' dtype: None / torch.float32, or torch.bfloat16 (opt-in: exp_avg and
@@ -151,6 +152,19 @@ class ShardedOptimizerBase:
                 raise ValueError("zero_amd: ema_decay is not supported with the bucket arena or "
                                  f"overlap=True (arena={arena!r}, layout={layout!r}, "
                                  f"overlap={bool(overlap)}); use the flat arena")
+        # param_update_norms: the fused update also reports the L2 norm of every parameter's
+        # update and of its weights, on the fp32 master (last_param_update_norms,
+        # last_param_weight_norms); a reporting switch, fixed at construction and not
+        # checkpointed.  Refused here where it does not apply, before anything collective
+        self.param_update_norms = bool(param_update_norms)
+        if self.param_update_norms:
+            check_update_norms(self._kind, self._carry and get("ws") > 1, self.state_dtype, master,
+                               ema=has_ema)
+            if arena == "buckets" or overlap or \
+                    (layout != "reference" and (layout != "flat" or self._carry)):
+                raise ValueError("zero_amd: param_update_norms is not supported with the bucket "
+                                 f"arena or overlap=True (arena={arena!r}, layout={layout!r}, "
+                                 f"overlap={bool(overlap)}); use the flat arena")
         for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
             hpd = group_hparams(self._kind, group, optimizer)
             if bf16_state and self._kind == "adam":
@@ -159,6 +173,8 @@ class ShardedOptimizerBase:
                 check_master_free_group(hpd)
             if has_ema:
                 check_ema_group(hpd)
+            if self.param_update_norms:
+                check_update_norms_group(hpd)
         if bf16_state:
             if self._kind == "sgd":
                 raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with "
@@ -223,6 +239,9 @@ class ShardedOptimizerBase:
                                          "arena='auto' that resolved to the bucket arena")
                     if has_ema:
                         raise ValueError("zero_amd: ema_decay is not supported with "
+                                         "arena='auto' that resolved to the bucket arena")
+                    if self.param_update_norms:
+                        raise ValueError("zero_amd: param_update_norms is not supported with "
                                          "arena='auto' that resolved to the bucket arena")
         # bytes per bucket (bucket arena) / per round (flat arena, all owners' windows together);
         # default 256 MiB / 1 GiB: a flat round has no pack to pipeline, so fewer, larger rounds
@@ -360,6 +379,24 @@ class ShardedOptimizerBase:
         return None if clip is None else clip.param_norms
 
     @property
+    def last_param_update_norms(self):
+        """1-D fp32 device tensor of ``len(params)`` (``param_update_norms``): entry i is the L2
+        norm of (fp32 master after - fp32 master before) of parameter i in the last step; +0.0 for
+        a parameter that step did not update and for a step ``skip_nonfinite`` skipped; NaN before
+        the first step.  The same bits on every rank, valid in stream order after step(),
+        overwritten (the same tensor) by the next step; None without the option."""
+        un = None if self.engine is None else getattr(self.engine, "stats", None)
+        return None if un is None else un.update
+
+    @property
+    def last_param_weight_norms(self):
+        """As ``last_param_update_norms``: entry i is the L2 norm of parameter i's fp32 master
+        after the last step that updated it (a parameter not updated and a skipped step keep the
+        entry); NaN until then."""
+        un = None if self.engine is None else getattr(self.engine, "stats", None)
+        return None if un is None else un.weight
+
+    @property
     def last_norm_bytes(self) -> int:
         """Gradient bytes the last step's norm pass read (0 without clipping)."""
         return 0 if self.engine is None else self.engine.last_norm_bytes
@@ -404,6 +441,7 @@ class ShardedOptimizerBase:
                                      state_rounding=self.state_rounding,
                                      state_seed=self.state_seed,
                                      ema=self._ema_decay is not None,
+                                     update_norms=self.param_update_norms,
                                      momentum=self._kind == "sgd" and any(
                                          g.get("momentum", 0) != 0 for g in self._groups))
         else:
@@ -464,6 +502,9 @@ class ShardedOptimizerBase:
             for gi in range(len(self._groups)):
                 check_ema_group(self._hparams_of(gi))
             self.engine.ema_decay = self._ema_decay
+        if self.param_update_norms:  # (groups are mutable between steps)
+            for gi in range(len(self._groups)):
+                check_update_norms_group(self._hparams_of(gi))
         if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
             for gi in range(len(self._groups)):
                 check_bf16_state_group(self._hparams_of(gi), self.state_rounding)

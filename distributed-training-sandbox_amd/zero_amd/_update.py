@@ -149,6 +149,31 @@ def check_ema_group(hpd: dict) -> None:
                          "through the slot of max_exp_avg_sq)")
 
 
+def check_update_norms(kind: str, carry: bool, state_dtype=None, master=None, ema=False) -> None:
+    """What ``param_update_norms`` cannot be combined with on an update core, as ValueError."""
+    if kind != "adam":
+        raise ValueError("zero_amd: param_update_norms is not supported with torch.optim.SGD (the "
+                         "norms are summed inside the fused Adam update)")
+    if check_state_dtype(state_dtype) == torch.bfloat16:
+        raise ValueError("zero_amd: param_update_norms is not supported with "
+                         "state_dtype=torch.bfloat16 (the stats instances keep fp32 moments)")
+    if master == "none":
+        raise ValueError("zero_amd: param_update_norms is not supported with master='none' (there "
+                         "is no master to measure)")
+    if ema:
+        raise ValueError("zero_amd: param_update_norms is not supported with ema_decay (the EMA "
+                         "has a rule family of its own)")
+    if carry:
+        raise ValueError("zero_amd: param_update_norms is not supported with the ZeRO-1 gradient "
+                         "carry (ZeRO-1 at world size > 1)")
+
+
+def check_update_norms_group(hpd: dict) -> None:
+    if hpd.get("amsgrad"):
+        raise ValueError("zero_amd: param_update_norms is not supported with amsgrad (the stats "
+                         "instances have no max_exp_avg_sq stream)")
+
+
 def join_split_master(param: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
     """The fp32 split master of bf16 ``param`` and its int16 ``residual``:
     (bits << 16) + sext(residual), as the kernel joins them."""
@@ -196,10 +221,13 @@ def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = 
 
 
 class UpdateCore:
+    update_norms = False  # (param_update_norms; set by the constructor)
+
     def __init__(self, kind: str, L: int, device, ws: int, group_of, n_params: int, *,
                  split: bool = False, fp32_master: bool = False, carry: bool = False,
                  momentum: bool = True, placement_tries: int = 8, state_dtype=None,
-                 state_rounding=None, state_seed: int = 0, master=None, ema: bool = False):
+                 state_rounding=None, state_seed: int = 0, master=None, ema: bool = False,
+                 update_norms: bool = False):
         from .engine import probed_zeros  # (engine.py builds on this module)
 
         if kind not in ("adam", "sgd"):
@@ -237,6 +265,11 @@ class UpdateCore:
         if ema:
             check_ema(kind, bool(carry), self.state_dtype, master)
             self.ema = torch.zeros(self.L, dtype=torch.float32, device=device)
+        # update_norms (param_update_norms): every launch goes through run_stats, which also sums
+        # each chunk's (master after - master before)^2 and master after^2 (UpdateNorms below)
+        self.update_norms = bool(update_norms)
+        if self.update_norms:
+            check_update_norms(kind, bool(carry), self.state_dtype, master, ema=bool(ema))
         self.steps = np.zeros(n_params, np.int64)  # torch's per-param state['step']
         self._cache = {}
         self.retired = []
@@ -266,6 +299,8 @@ class UpdateCore:
         return views
 
     def ensure_vmax(self):
+        if self.update_norms:
+            check_update_norms_group({"amsgrad": True})
         if self.ema is not None:
             raise ValueError("zero_amd: ema_decay is not supported with amsgrad (the EMA streams "
                              "through the slot of max_exp_avg_sq)")
@@ -359,6 +394,8 @@ class UpdateCore:
             check_master_free_group(hpd)
         if self.ema is not None:
             check_ema_group(hpd)
+        if self.update_norms:
+            check_update_norms_group(hpd)
         if hpd["amsgrad"] and self.vmax is None:
             raise RuntimeError("amsgrad state buffer missing")
         hp = self._adam_hp(hpd, key, carry_mul)
@@ -392,17 +429,22 @@ class UpdateCore:
         """Free replaced segment tables; call only after the device has been synchronised."""
         self.retired.clear()
 
-    def launch(self, aset, hp, stream, coef=None, guard=False) -> None:
+    def launch(self, aset, hp, stream, coef=None, guard=False, stats=None) -> None:
         """Run ``aset`` (``coef``: with the clip coefficient, a device scalar's address; ``guard``:
-        a NaN coefficient skips the step on the device); with ``timing_events`` on, between two
-        HIP events."""
+        a NaN coefficient skips the step on the device; ``stats``, an ``update_norms`` core: the
+        address of the set's two planes of partials); with ``timing_events`` on, between two HIP
+        events."""
         ev = self.timing_events
         if ev is not None:
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record(stream)
         if guard and coef is None:
             raise ValueError("zero_amd: the guarded update tests the clip coefficient")
-        if self.ema is not None:
+        if self.update_norms:
+            if stats is None:
+                raise ValueError("zero_amd: param_update_norms: a launch without its partials")
+            aset.run_stats(hp, int(stats), stream, coef=coef, guard=guard)
+        elif self.ema is not None:
             aset.run_ema(hp, ema_weight(self.ema_decay), stream, coef=coef, guard=guard)
         elif self.master_free:
             aset.run_psr(hp, self.m.data_ptr(), hp.sr_keys, stream, coef=coef, guard=guard)
@@ -495,6 +537,26 @@ def check_param_grad_norms(param_grad_norms, max_grad_norm) -> bool:
     return True
 
 
+def slot_csr(base, seg_offsets, seg_params, n_params: int):
+    """(row_ptr, slot_lo, slot_n) of the slot ranges per parameter over sets collected in order:
+    set k's row i -- parameter ``seg_params[k][i]`` -- owns the slots ``base[k] + seg_offsets[k][i]
+    .. base[k] + seg_offsets[k][i + 1]`` of one partials tensor.  Empty ranges are dropped; a
+    parameter's ranges -- several for one cut across sets -- stand in the order the sets were
+    collected; one without a range has an empty row."""
+    par, lo, cnt = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for b, so, idx in zip(base, seg_offsets, seg_params):
+        assert len(idx) == len(so) - 1
+        par.append(np.asarray(idx, np.int64))
+        lo.append(int(b) + so[:-1])
+        cnt.append(np.diff(so))
+    par, lo, cnt = np.concatenate(par), np.concatenate(lo), np.concatenate(cnt)
+    keep = cnt > 0
+    par, lo, cnt = par[keep], lo[keep], cnt[keep]
+    order = np.argsort(par, kind="stable")  # per parameter: the order the sets were collected
+    row_ptr = np.concatenate([[0], np.cumsum(np.bincount(par, minlength=n_params))])
+    return row_ptr.astype(np.int64), lo[order].astype(np.int64), cnt[order].astype(np.int64)
+
+
 class GradClip:
     """Global gradient-norm clipping around an ``UpdateCore``'s launches (clip_grad_norm_ between
     the reduction and the update): what the ZeRO-1/2 flat arena and ZeRO-3's update
@@ -572,19 +634,9 @@ class GradClip:
         self.last_norm_bytes = 0
 
     def _build_csr(self, deferred, seg_params) -> np.ndarray:
-        par, lo, cnt = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
-        for k, ((aset, _, _), idx) in enumerate(zip(deferred, seg_params)):
-            so = aset.sqnorm_seg_offsets
-            assert len(idx) == aset.nseg
-            par.append(np.asarray(idx, np.int64))
-            lo.append(self._off[k] + so[:-1])
-            cnt.append(np.diff(so))
-        par, lo, cnt = np.concatenate(par), np.concatenate(lo), np.concatenate(cnt)
-        keep = cnt > 0
-        par, lo, cnt = par[keep], lo[keep], cnt[keep]
-        order = np.argsort(par, kind="stable")  # per parameter: the order the sets were collected
-        row_ptr = np.concatenate([[0], np.cumsum(np.bincount(par, minlength=self.n_params))])
-        return np.concatenate([row_ptr, lo[order], cnt[order]]).astype(np.int64)
+        row_ptr, lo, cnt = slot_csr(self._off[:-1], [aset.sqnorm_seg_offsets for aset, _, _ in deferred],
+                                    seg_params, self.n_params)
+        return np.concatenate([row_ptr, lo, cnt]).astype(np.int64)
 
     def norm(self, deferred, first, stream) -> None:
         """Stage 1 for ``deferred[first:]``: bind the gradients where needed, then the sum of
@@ -630,8 +682,97 @@ class GradClip:
         if self.per_param:
             param_norms(self.reduced, self.n_params, float(self.core.ws), self.param_norms, stream)
 
-    def run(self, deferred, first, last, stream) -> None:
-        """Stage 4 for ``deferred[first:last]``: the update with the coefficient."""
+    def run(self, deferred, first, last, stream, stats=None) -> None:
+        """Stage 4 for ``deferred[first:last]``: the update with the coefficient (``stats``: the
+        step's ``UpdateNorms``, prepared over the same list)."""
         coef = self.out.data_ptr() + 4
-        for aset, hp, _ in deferred[first:last]:
-            self.core.launch(aset, hp, stream, coef, guard=self.guard)
+        for k in range(first, min(last, len(deferred))):
+            aset, hp, _ = deferred[k]
+            self.core.launch(aset, hp, stream, coef, guard=self.guard,
+                             stats=None if stats is None else stats.planes(k))
+
+
+class UpdateNorms:
+    """Per-parameter update and weight norms out of an ``update_norms`` core's launches (DESIGN.md
+    §4): a stage beside ``GradClip``, shared by the ZeRO-1/2 flat arena and ZeRO-3's update mode.
+    The caller collects the step's parts as ``(aset, hp, gptr or None)`` and calls ``prepare`` (host
+    only), launches set k with ``stats=planes(k)`` (``UpdateCore.launch`` / ``GradClip.run``), then
+    in stream order ``reduce`` (each parameter's slots of both planes into ``sums3`` =
+    [sum d^2 | sum p1^2 | touched], which the caller all-reduces at world size > 1) and ``finish``
+    (the square roots into ``update`` and ``weight``; a skipped step or an untouched parameter:
+    update +0.0, weight kept).  The host never waits for the step's work."""
+
+    def __init__(self, core: UpdateCore):
+        self.core = core
+        dev = core.device
+        n = self.n_params = len(core.steps)
+        self.partials = None  # float64, sized on first use: per set two planes of its slots
+        self._key, self._off = None, np.zeros(1, np.int64)
+        self.sums3 = torch.zeros(3 * n, dtype=torch.float32, device=dev)
+        self.update = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
+        self.weight = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
+        # [row_ptr | slot_lo of plane 0 | slot_lo of plane 1 | slot_n] and the touched mask, uploaded
+        # like GradClip's CSR on a stream of its own, which the host waits for
+        self._csr, self._touched = None, None
+        self._upload_stream = torch.cuda.Stream(dev)
+
+    @staticmethod
+    def tables(base, seg_offsets, seg_params, n_params: int):
+        """(csr, touched) on the host for sets whose two planes start at ``base[k]``: the CSR as
+        [row_ptr | slot_lo of the update plane | slot_lo of the weight plane | slot_n] and the 0/1
+        mark "a set has a range for parameter i" as float32."""
+        row_ptr, lo_d, cnt = slot_csr(base, seg_offsets, seg_params, n_params)
+        base_w = [int(b) + int(so[-1]) for b, so in zip(base, seg_offsets)]
+        _, lo_w, _ = slot_csr(base_w, seg_offsets, seg_params, n_params)
+        touched = (np.diff(row_ptr) > 0).astype(np.float32)
+        return np.concatenate([row_ptr, lo_d, lo_w, cnt]).astype(np.int64), touched
+
+    def prepare(self, deferred, seg_params) -> None:
+        """Each collected set's slice (two planes) of the partials tensor, the CSR and the touched
+        mask, under ``GradClip.prepare``'s rules: sized on first use, rebuilt only when the list of
+        sets or their parameters change, what they replace retired with the core's tables."""
+        key = tuple((id(aset), int(aset.update_norm_offsets[-1]), np.asarray(idx, np.int64).tobytes())
+                    for (aset, _, _), idx in zip(deferred, seg_params))
+        if self._key == key:
+            return
+        self._off = np.concatenate([[0], np.cumsum([2 * k[1] for k in key])]).astype(np.int64)
+        total = int(self._off[-1])
+        buf = self.partials
+        if buf is None or buf.numel() < total:
+            if buf is not None:
+                self.core.retired.append(buf)
+            self.partials = torch.zeros(max(total, 1), dtype=torch.float64, device=self.core.device)
+        csr, touched = self.tables(self._off[:-1], [aset.update_norm_offsets for aset, _, _ in deferred],
+                                   seg_params, self.n_params)
+        if self._csr is not None:
+            self.core.retired.extend([self._csr, self._touched])
+        with torch.cuda.stream(self._upload_stream):
+            self._csr = torch.from_numpy(csr).to(self.core.device)
+            self._touched = torch.from_numpy(touched).to(self.core.device)
+        self._upload_stream.synchronize()
+        self._key = key
+
+    def planes(self, k: int) -> int:
+        """The address of set k's two planes."""
+        return self.partials.data_ptr() + int(self._off[k]) * 8
+
+    def reduce(self, stream) -> None:
+        """Each parameter's slots of the two planes into ``sums3``, and this rank's touched mask
+        behind them."""
+        from .kernels import sqnorm_reduce_params
+
+        n, t = self.n_params, self._csr
+        nr = (t.numel() - (n + 1)) // 3
+        row_ptr, cnt = t[:n + 1], t[n + 1 + 2 * nr:]
+        for plane in (0, 1):
+            sqnorm_reduce_params(self.partials, row_ptr, t[n + 1 + plane * nr:n + 1 + (plane + 1) * nr],
+                                 cnt, n, self.sums3[plane * n:], stream)
+        with torch.cuda.stream(stream):
+            self.sums3[2 * n:].copy_(self._touched)
+
+    def finish(self, coef_ptr, stream) -> None:
+        """After the caller's all-reduce of ``sums3``: the norms (``coef_ptr``: the clip coefficient
+        of a guarded step, whose NaN marks the step as skipped; None otherwise)."""
+        from .kernels import update_norms
+
+        update_norms(self.sums3, self.n_params, coef_ptr, self.update, self.weight, stream)

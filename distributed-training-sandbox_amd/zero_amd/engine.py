@@ -300,7 +300,8 @@ class ShardEngine(UpdateCore):
                  comm=None, bucket_bytes: int = 256 << 20, align: int = ALIGN_ELEMS,
                  buckets: str = "ragged", placement_tries: int = 8, master: str = "split",
                  kind: str = "adam", momentum: bool = True, state_dtype=None,
-                 state_rounding=None, state_seed: int = 0, ema: bool = False):
+                 state_rounding=None, state_seed: int = 0, ema: bool = False,
+                 update_norms: bool = False):
         if kind not in ("adam", "sgd"):
             raise ValueError(f"ShardEngine: kind must be 'adam' or 'sgd' (got {kind!r})")
         if not params:
@@ -342,7 +343,7 @@ class ShardEngine(UpdateCore):
                             master=master if master == "none" else None, carry=carry,
                             momentum=momentum, placement_tries=placement_tries,
                             state_dtype=state_dtype, state_rounding=state_rounding,
-                            state_seed=state_seed, ema=ema)
+                            state_seed=state_seed, ema=ema, update_norms=update_norms)
         if self.master is not None:
             for i, po, so, n in zip(*self._piece_cols()):
                 self.master[so:so + n].copy_(params[i].detach().reshape(-1)[po:po + n])
@@ -367,6 +368,8 @@ class ShardEngine(UpdateCore):
         self.skip_nonfinite = False
         self.param_grad_norms = False  # the pass also reports per-parameter norms (GradClip)
         self.clip = None
+        # param_update_norms (flat arena only): _update.UpdateNorms, made with the engine
+        self.stats = None
 
     @property
     def clip_out(self):

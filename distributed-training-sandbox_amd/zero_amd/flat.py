@@ -48,7 +48,7 @@ import torch
 
 from . import _lib
 from ._hooks import WeakCall
-from ._update import GradClip
+from ._update import GradClip, UpdateNorms
 from .comm import StreamEvent
 from .engine import ALIGN_ELEMS, ShardEngine, _ptr
 from .kernels import check_extents, check_extents_enabled, copy_direct
@@ -84,7 +84,7 @@ class FlatEngine(ShardEngine):
                  bucket_bytes: int = 256 << 20, master: str = "split", placement_tries: int = 8,
                  grad_comm: str | None = None, layout: str = "reference", kind: str = "adam",
                  momentum: bool = True, state_dtype=None, state_rounding=None,
-                 state_seed: int = 0, ema: bool = False):
+                 state_seed: int = 0, ema: bool = False, update_norms: bool = False):
         if layout not in ("reference", "flat"):
             raise ValueError(f"the flat arena takes layout 'reference' or 'flat' (got {layout!r})")
         if layout == "flat" and carry:
@@ -95,7 +95,11 @@ class FlatEngine(ShardEngine):
         super().__init__(params, group_of, ws, rank, layout=layout, carry=carry, comm=comm,
                          bucket_bytes=1 << 62, buckets="ragged", placement_tries=placement_tries,
                          master=master, kind=kind, momentum=momentum, state_dtype=state_dtype,
-                         state_rounding=state_rounding, state_seed=state_seed, ema=ema)
+                         state_rounding=state_rounding, state_seed=state_seed, ema=ema,
+                         update_norms=update_norms)
+        if self.update_norms:  # the stage and its NaN-filled results exist from construction on
+            self.stats = UpdateNorms(self)
+            self.ev_stats = (StreamEvent(), StreamEvent())  # around the sums' all-reduce
         self.arena_kind = "flat"
         self.layout = layout
         plan, es, dev, dt = self.plan, self.es, self.device, self.dtype
@@ -399,7 +403,37 @@ class FlatEngine(ShardEngine):
 
     def _clip_run(self, deferred, first, last, stream):
         """Stage 4 for ``deferred[first:last]``: the update with the coefficient."""
-        self.clip.run(deferred, first, last, stream)
+        self.clip.run(deferred, first, last, stream, stats=self.stats)
+
+    # ------------------------------------------------------------------------------------------
+    # Per-parameter update and weight norms (``param_update_norms``; _update.UpdateNorms, shared
+    # with ZeRO-3): every update of the step is collected first, as for clipping, so that each set
+    # knows its planes of partials; after the last round's update the partials are reduced per
+    # parameter, summed over the ranks and finished.  The host never waits.
+    def _stats_run(self, deferred, first, last, stream):
+        """The unclipped update of ``deferred[first:last]`` with its partials."""
+        for k in range(first, last):
+            aset, hp, g = deferred[k]
+            if g is not None:
+                aset.set_grads(g, stream)
+            self.launch(aset, hp, stream, stats=self.stats.planes(k))
+
+    def _stats_finish(self, stream):
+        """After the step's last update: [sum d^2 | sum p1^2 | touched] per parameter, one
+        all-reduce of the 3 n floats on the communication stream (ordered by events on both
+        sides; every parameter has one owner and the others add 0: the sum is exact), the norms.
+        A guarded step hands its coefficient on: NaN means the step was skipped."""
+        st = self.stats
+        st.reduce(stream)
+        if self.ws > 1:
+            cs = self.comm_stream
+            self.ev_stats[0].record(stream)
+            cs.wait_event(self.ev_stats[0])
+            self.comm.all_reduce(st.sums3, cs)
+            self.ev_stats[1].record(cs)
+            stream.wait_event(self.ev_stats[1])
+        guarded = self.max_grad_norm is not None and self.skip_nonfinite
+        st.finish(self.clip.out.data_ptr() + 4 if guarded else None, stream)
 
     # ------------------------------------------------------------------------------------------
     def _reduce_round(self, rd: _Round, cs):
@@ -747,9 +781,10 @@ class FlatEngine(ShardEngine):
 
             convert(self.G, self.Gc, stream)
         clip = self.max_grad_norm is not None
+        stats = self.stats is not None
         self.last_norm_bytes = 0
-        if clip:
-            if self.overlap or self.carry is not None:
+        if clip or stats:
+            if clip and (self.overlap or self.carry is not None):
                 raise ValueError("zero_amd: max_grad_norm is not supported with backward overlap "
                                  "or the ZeRO-1 gradient carry")
             # every Adam launch of the step is collected first (host only): the sets' slices of
@@ -758,16 +793,23 @@ class FlatEngine(ShardEngine):
             for rd in self.rounds:
                 self._adam_round(rd, has, cmul, hps, hparams_of, stream, gptr, deferred)
                 ends.append(len(deferred))
-            self._clip_prepare(deferred)
+            if clip:
+                self._clip_prepare(deferred)
+            if stats:
+                self.stats.prepare(deferred, [aset.seg_params for aset, _, _ in deferred])
         if self.ws == 1:  # zero1.py:107-108 / zero2.py:120 at ws=1: Adam on the local grads
             with _lib.phase_range("optimizer_step"):
                 if clip:
                     self._clip_norm(deferred, 0, stream)
                     self._clip_coef(deferred, stream)
                     self._clip_run(deferred, 0, len(deferred), stream)
+                elif stats:
+                    self._stats_run(deferred, 0, len(deferred), stream)
                 else:
                     for rd in self.rounds:
                         self._adam_round(rd, has, cmul, hps, hparams_of, stream, gptr)
+                if stats:
+                    self._stats_finish(stream)
             if self.inplace:
                 if self.overlap:
                     self.launched_in_backward = self.ov_launched
@@ -799,6 +841,9 @@ class FlatEngine(ShardEngine):
             for k, rd in enumerate(self.rounds):
                 if clip:
                     self._clip_run(deferred, ends[k - 1] if k else 0, ends[k], stream)
+                elif stats:
+                    stream.wait_event(self.ev_red[rd.j])
+                    self._stats_run(deferred, ends[k - 1] if k else 0, ends[k], stream)
                 else:
                     stream.wait_event(self.ev_red[rd.j])
                     self._adam_round(rd, has, cmul, hps, hparams_of, stream)
@@ -810,6 +855,8 @@ class FlatEngine(ShardEngine):
                 self._bcast_round(rd, cs)
                 self.ev_bc[rd.j].record(cs)
                 self._timed_end(e0, cs, "ag", int(rd.count.sum()))
+        if stats:  # (behind the broadcasts on the communication stream: they do not wait for it)
+            self._stats_finish(stream)
         stream.wait_event(self.ev_bc[self.K - 1])  # the parameters are P: next forward reads it
         self._reinstall(has, view)
 

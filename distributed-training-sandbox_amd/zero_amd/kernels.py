@@ -299,6 +299,35 @@ class AdamSet:
         _lib.call("zs_adamset_run_ema", self._h, ctypes.byref(hp), ptr, int(bool(guard)),
                   float(ema_w), stream_handle(stream))
 
+    @property
+    def update_norm_offsets(self) -> np.ndarray:
+        """``nseg + 1`` int64 offsets: row i's slots in each plane ``run_stats`` writes are
+        ``[off[i], off[i + 1])``, ``off[-1]`` the slots per plane — 4 per chunk of the row's vector
+        part, then 4 per 256-element chunk of its scalar part (fixed when the set was created:
+        zs_adamset_update_norm_slots)."""
+        off = getattr(self, "_un_off", None)
+        if off is None:
+            c = ctypes.c_int64()
+            off = np.zeros(self.nseg + 1, np.int64)
+            _lib.call("zs_adamset_update_norm_slots", self._h, ctypes.byref(c),
+                      off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+            assert int(off[-1]) == c.value
+            self._un_off = off
+        return off
+
+    def run_stats(self, hp: AdamHParams, partials, stream, coef=None, guard=False) -> None:
+        """``run`` (``coef`` None), ``run_clipped`` or, with ``guard``, ``run_guarded`` with the same
+        bits, and per slot the sums of (master after - master before)^2 and of master after^2 into
+        the two planes of ``partials`` (a float64 device tensor of at least
+        ``2 * update_norm_offsets[-1]`` elements, or its address): zs_adamset_run_stats."""
+        if not isinstance(partials, int):
+            assert partials.dtype.itemsize == 8
+            assert partials.numel() >= 2 * self.update_norm_offsets[-1]
+            partials = partials.data_ptr()
+        ptr = None if coef is None else coef if isinstance(coef, int) else coef.data_ptr()
+        _lib.call("zs_adamset_run_stats", self._h, ctypes.byref(hp), ptr, int(bool(guard)),
+                  partials or None, stream_handle(stream))
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib is not None:
@@ -393,6 +422,20 @@ def param_norms(sumsq_vec, n: int, grad_div: float, norms, stream) -> None:
     assert sumsq_vec.numel() >= n and norms.numel() >= n
     _lib.call("zs_param_norms", sumsq_vec.data_ptr(), int(n), float(grad_div), norms.data_ptr(),
               stream_handle(stream))
+
+
+def update_norms(sums3, n: int, coef, update, weight, stream) -> None:
+    """The finishing step of the per-parameter update and weight norms (zs_update_norms) over
+    ``sums3`` = [sum d^2 | sum p1^2 | touched], ``n`` fp32 device elements each: where
+    ``touched[i] != 0`` and the fp32 device scalar ``coef`` (a tensor, its address or None) is not
+    NaN, ``update[i]`` and ``weight[i]`` become the square roots (in double, rounded once);
+    elsewhere ``update[i]`` = +0.0 and ``weight[i]`` stays."""
+    assert sums3.dtype.itemsize == 4 and sums3.numel() >= 3 * n
+    assert update.dtype.itemsize == 4 and weight.dtype.itemsize == 4
+    assert update.numel() >= n and weight.numel() >= n
+    ptr = None if coef is None else coef if isinstance(coef, int) else coef.data_ptr()
+    _lib.call("zs_update_norms", sums3.data_ptr(), int(n), ptr, update.data_ptr(),
+              weight.data_ptr(), stream_handle(stream))
 
 
 def clip_coef(sumsq, grad_div: float, max_norm: float, out2, stream, skipped=None) -> None:

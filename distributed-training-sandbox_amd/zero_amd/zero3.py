@@ -69,8 +69,9 @@ from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_BF16_SR, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
 from ._sharded import group_hparams, optimizer_kind
-from ._update import (GradClip, UpdateCore, check_bf16_state_group, check_ema, check_ema_decay,
-                      check_ema_group, check_master_free,
+from ._update import (GradClip, UpdateCore, UpdateNorms, check_bf16_state_group, check_ema,
+                      check_ema_decay, check_ema_group, check_master_free, check_update_norms,
+                      check_update_norms_group,
                       check_master_free_group, check_max_grad_norm, check_param_grad_norms, check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
                       owner_range)
 from .comm import STREAM_SYNC, RcclComm, Sync, comm_stream, sync_kind, zs_dtype
@@ -1842,7 +1843,8 @@ class ShardedOptimizer:
                  accumulation_dtype=None, state_dtype=None, state_rounding: str | None = None,
                  state_seed: int = 0, max_grad_norm: float | None = None,
                  skip_nonfinite: bool = False, master: str = "split",
-                 param_grad_norms: bool = False, ema_decay: float | None = None):
+                 param_grad_norms: bool = False, ema_decay: float | None = None,
+                 param_update_norms: bool = False):
         # global gradient-norm clipping inside step() (update mode; None = off): a plain attribute,
         # re-checked at every step().  skip_nonfinite (with it; Adam): a step whose gradient norm
         # is not finite is skipped on the device.  Both are refused here where they
@@ -1914,6 +1916,19 @@ class ShardedOptimizer:
                 raise ValueError("zero_amd: ema_decay applies to update mode (reference mode never "
                                  "updates: there is nothing to average)")
             check_ema(self._kind, False, self.state_dtype, master)
+        # param_update_norms (update mode, Adam): the fused update also reports the L2 norm of every
+        # parameter's update and of its weights on the fp32 master (last_param_update_norms,
+        # last_param_weight_norms); fixed at construction, not checkpointed.  Refused
+        # here where it does not apply, on every rank and before anything collective
+        self.param_update_norms = bool(param_update_norms)
+        self._stats = None  # _update.UpdateNorms, made with the core
+        self._stats_syncs = None
+        if self.param_update_norms:
+            if not update:
+                raise ValueError("zero_amd: param_update_norms applies to update mode (reference "
+                                 "mode never updates: there is nothing to measure)")
+            check_update_norms(self._kind, False, self.state_dtype, master,
+                               ema=self._ema_decay is not None)
         for group in optimizer.param_groups:  # (what a group cannot ask for is refused here)
             hpd = group_hparams(self._kind, group, optimizer)
             if self.state_dtype == torch.bfloat16 and self._kind == "adam":
@@ -1922,6 +1937,8 @@ class ShardedOptimizer:
                 check_master_free_group(hpd)
             if self._ema_decay is not None:
                 check_ema_group(hpd)
+            if self.param_update_norms:
+                check_update_norms_group(hpd)
         if self.state_dtype == torch.bfloat16 and self._kind == "sgd":
             raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with "
                              "torch.optim.SGD (bf16 moments are Adam's)")
@@ -2001,7 +2018,10 @@ class ShardedOptimizer:
                                 state_dtype=self.state_dtype,
                                 state_rounding=self.state_rounding, state_seed=self.state_seed,
                                 momentum=any(g.get("momentum", 0) != 0 for g in self._groups),
-                                ema=self._ema_decay is not None)
+                                ema=self._ema_decay is not None,
+                                update_norms=self.param_update_norms)
+        if self.param_update_norms:  # the stage and its NaN-filled results exist from here on
+            self._stats = UpdateNorms(self._core)
         if self._core.ema is not None:  # the EMA starts at the master: the chunks, widened
             self._core.ema.copy_(ar.P)
         self._core.timing_events = self._timing_events
@@ -2091,6 +2111,22 @@ class ShardedOptimizer:
         """0-d fp32 device tensor: min(1, max_grad_norm / (last_grad_norm + 1e-6)), as above (NaN:
         ``skip_nonfinite`` skipped the step)."""
         return None if self._clip is None else self._clip.out[1]
+
+    @property
+    def last_param_update_norms(self):
+        """1-D fp32 device tensor of ``len(params)`` (``param_update_norms``): entry i is the L2
+        norm of (fp32 master after - fp32 master before) of the whole parameter i in the last
+        step; +0.0 for a parameter that step did not update and for a step ``skip_nonfinite``
+        skipped; NaN before the first step.  The same bits on every rank, valid in stream order
+        after step(), overwritten (the same tensor) by the next step; None without the option."""
+        return None if self._stats is None else self._stats.update
+
+    @property
+    def last_param_weight_norms(self):
+        """As ``last_param_update_norms``: entry i is the L2 norm of parameter i's fp32 master
+        after the last step that updated it (a parameter not updated and a skipped step keep the
+        entry); NaN until then."""
+        return None if self._stats is None else self._stats.weight
 
     @property
     def last_param_grad_norms(self):
@@ -2311,6 +2347,9 @@ class ShardedOptimizer:
             for group in self._groups:
                 check_ema_group(group_hparams(self._kind, group, self.optimizer))
             self._core.ema_decay = self._ema_decay
+        if self.param_update_norms:  # (groups are mutable between steps)
+            for group in self._groups:
+                check_update_norms_group(group_hparams(self._kind, group, self.optimizer))
         if red.incomplete():
             raise RuntimeError(
                 "zero_amd ZeRO-3: a backward did not finish (it raised), so the accumulated "
@@ -2343,7 +2382,10 @@ class ShardedOptimizer:
         fast = self._fast_sets.get(acc) if uniform and sig is not None \
             and self._fast_sig.get(acc) == sig else None
         # gradient clipping: both paths collect their launches as (aset, hp, None) instead
-        deferred = None if self.max_grad_norm is None else []
+        # (param_update_norms: too, so that every set knows its planes of partials)
+        stats = self._stats
+        clip = self.max_grad_norm is not None
+        deferred = [] if clip or stats is not None else None
         if fast is not None:  # the same parameters as last step, one step count: cached sets
             for gi, aset in fast:
                 hp = core.make_hp(hps[gi], int(steps[0]))
@@ -2358,13 +2400,20 @@ class ShardedOptimizer:
             self._fast_sig[acc] = sig if uniform else None
             self._fast_sets[acc] = used if uniform else None
         self._last_norm_bytes = 0
-        if deferred is not None:  # (every rank, also one that updates nothing: the all-reduce)
-            if done is not None and self.runtime.stream is not None:
-                # the communication_time span ends behind the last gradient collective, not
-                # behind the norm's all-reduce (which waits for the norm pass)
-                self._span_end = torch.cuda.Event(enable_timing=True)
-                self._span_end.record(self.runtime.stream)
+        if stats is not None:
+            stats.prepare(deferred, [aset.seg_params for aset, _, _ in deferred])
+        if deferred is not None and done is not None and self.runtime.stream is not None:
+            # the communication_time span ends behind the last gradient collective, not behind
+            # the all-reduce of the norm (which waits for the norm pass) or of the update norms
+            self._span_end = torch.cuda.Event(enable_timing=True)
+            self._span_end.record(self.runtime.stream)
+        if clip:  # (every rank, also one that updates nothing: the all-reduce)
             self._clip_update(deferred, cur)
+        elif stats is not None:
+            for k, (aset, hp, _) in enumerate(deferred):
+                core.launch(aset, hp, cur, stats=stats.planes(k))
+        if stats is not None:  # (every rank, also one that updates nothing: the all-reduce)
+            self._stats_finish(cur)
         if self._kind == "sgd":  # torch's SGD keeps no step: the buffer appears after the first
             self._expose_sgd(idx)
         elif uniform:  # torch's state['step'] (a CPU tensor): one shared tensor, updated in place
@@ -2428,8 +2477,33 @@ class ShardedOptimizer:
                 done.record(side.cuda_stream)
                 done.wait(cur.cuda_stream)
         clip.coef(self.max_grad_norm, cur)
-        clip.run(deferred, 0, len(deferred), cur)
+        clip.run(deferred, 0, len(deferred), cur, stats=self._stats)
         self._last_norm_bytes = clip.last_norm_bytes
+
+    def _stats_finish(self, cur):
+        """After the step's one fused update (``param_update_norms``; _update.UpdateNorms): each
+        parameter's [sum d^2 | sum p1^2 | touched] over this rank's chunks, one all-reduce of the
+        3 n floats where ``_clip_update`` sends its own (every rank holds a chunk of a parameter,
+        so the sums add up in the communicator's order), the norms.  A guarded step hands its
+        coefficient on: NaN means the step was skipped."""
+        st = self._stats
+        st.reduce(cur)
+        if self.world_size > 1:
+            side = self.runtime.stream
+            if side is None:
+                self.comm.all_reduce(st.sums3, cur)
+            else:
+                if self._stats_syncs is None:  # (ready, done): reused every step
+                    kind = self.runtime.sync_kind
+                    self._stats_syncs = (Sync(kind), Sync(kind))
+                ready, done = self._stats_syncs
+                ready.record(cur.cuda_stream)
+                ready.wait(side.cuda_stream)
+                self.comm.all_reduce(st.sums3, side)
+                done.record(side.cuda_stream)
+                done.wait(cur.cuda_stream)
+        guarded = self.max_grad_norm is not None and self.skip_nonfinite
+        st.finish(self._clip.out.data_ptr() + 4 if guarded else None, cur)
 
     @on_param_device
     def step(self, closure=None):

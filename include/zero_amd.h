@@ -493,6 +493,46 @@ int zs_sr_pkeys(uint32_t key0, uint32_t key1, uint32_t* pkey0, uint32_t* pkey1);
 int zs_adamset_run_ema(const zs_adamset* as, const zs_adam_hparams* hp, const float* coef, int guard,
                        float ema_weight, uintptr_t stream);
 
+/* Per-parameter update and weight norms out of the fused Adam update (additive in ABI v13).  Over a
+ * set made by zs_adamset_create / _create_ex with fp32 state, any master storage but ZS_BF16_SR, no
+ * carry and no vmax column, zs_adamset_run_stats runs zs_adamset_run's update unchanged (coef NULL),
+ * zs_adamset_run_clipped's (coef given) or zs_adamset_run_guarded's (coef and guard != 0), with the
+ * same bits in every parameter, residual and moment, and sums per element, in the same kernel,
+ *   d = p1 - p0 (one fp32 subtraction),  sum d * d  and  sum p1 * p1,
+ * p0 the fp32 master as the update loaded it and p1 the fp32 master as it stored it (ZS_BF16_SPLIT:
+ * (hi << 16) + sext(lo) of the words read / just written).  fp32 (fmaf) covers one lane's terms of
+ * one chunk -- 16 for ZS_BF16_SPLIT, 8 otherwise, 1 in the scalar part --, double the wave's 64 lanes
+ * (shuffles, offsets 32 .. 1); each wave stores its pair with plain stores, no atomics.
+ *
+ * zs_adamset_update_norm_slots: *n = the slots per plane; seg_off[0 .. nseg] = where each input
+ * segment's slots start, seg_off[nseg] == *n (the shape of zs_adamset_sqnorm_seg_partials).  A
+ * segment's slots: 4 per chunk of its vector part (chunks of 2,048 elements, 4,096 for
+ * ZS_BF16_SPLIT), one per wave, chunk-major, then 4 per 256-element chunk of its scalar part; none
+ * for an empty segment.  A slot's value depends on its own chunk alone: not on the grid, zs_tune,
+ * the device or the other segments.
+ *
+ * partials: two planes of *n doubles, sum d^2 first, sum p1^2 second (16 B per 512 or 1,024
+ * elements: 1.5 G elements of a split-master set take 2 * 24 MB).  Every slot of both planes is
+ * written by a run that is not skipped (a wave without an element in range stores +0.0); a guarded
+ * run with a NaN coefficient writes none.  A segment with g == 0 runs like any other.
+ * zs_sqnorm_reduce_params sums a plane's slots per parameter.
+ *
+ * zs_update_norms: sums3 = [sum d^2 | sum p1^2 | touched], n_params floats each.  For parameter i
+ * with touched[i] != 0, and *coef not NaN where coef is given:
+ *   update_norms[i] = (float)sqrt((double)sums3[i]),
+ *   weight_norms[i] = (float)sqrt((double)sums3[n_params + i]);
+ * otherwise update_norms[i] = +0.0 and weight_norms[i] is left as it is.
+ *
+ * ZS_ERR_INVALID, nothing launched: a NULL set, hparams, n or seg_off; a set made by
+ * zs_sgdset_create; ZS_BF16 state; a ZS_BF16_SR set; a set with the carry or the vmax column;
+ * hp->amsgrad; guard without coef; NULL partials for a set that has slots; n_params < 0; sums3,
+ * update_norms or weight_norms NULL with n_params > 0. */
+int zs_adamset_update_norm_slots(const zs_adamset* as, int64_t* n, int64_t* seg_off);
+int zs_adamset_run_stats(const zs_adamset* as, const zs_adam_hparams* hp, const float* coef,
+                         int guard, double* partials, uintptr_t stream);
+int zs_update_norms(const float* sums3, int64_t n_params, const float* coef, float* update_norms,
+                    float* weight_norms, uintptr_t stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Fused SGD (momentum, Nesterov), additive in ABI v13.  Replaces torch.optim.SGD.step on the    */
 /* owned shard where the reference's ShardedOptimizer wraps an SGD (zero1.py:88, zero2.py:120,  */
