@@ -207,7 +207,7 @@ __global__ __launch_bounds__(kThreads) void copy_direct_kernel(const DirectSet s
 }
 
 // ----------------------------------------------------------------------------------------------
-// fused optimizer update: one chunk-streaming skeleton, two element rules (Adam, SGD)
+// fused optimizer update: one chunk-streaming skeleton, three element rules (Adam, SGD, Lion)
 // ----------------------------------------------------------------------------------------------
 struct AdamSeg {
   const void* g;
@@ -377,12 +377,15 @@ template <typename ST>
 inline constexpr bool kStochastic = std::is_same_v<ST, SrBf16>;
 
 // index of a segment's element 0 in the shard's m array (uniform: scalar registers)
-__device__ __forceinline__ uint64_t sr_seg_index(const float* m, const SrHP& hp) {
+template <typename HPT>
+__device__ __forceinline__ uint64_t sr_seg_index(const float* m, const HPT& hp) {
   return (uint64_t(reinterpret_cast<uintptr_t>(m)) - hp.m_base) >> 1;
 }
 // zs_sr::bits(eu + off, k0, k1) for a uniform eu and a per-lane off: the high word of the sum is
 // eu's or one more, so its multiply and the xor with k0 stay scalar and a lane selects
-__device__ __forceinline__ uint32_t sr_bits_at(uint64_t eu, uint32_t off, const SrHP& hp) {
+// (HPT: SrHP or LionSrHP, which name k0, k1 and m_base alike)
+template <typename HPT>
+__device__ __forceinline__ uint32_t sr_bits_at(uint64_t eu, uint32_t off, const HPT& hp) {
   const uint32_t lo0 = uint32_t(eu), hi = uint32_t(eu >> 32);
   const uint32_t lo = lo0 + off;
   const uint32_t ka = hp.k0 ^ (hi * 0x9E3779B9u), kb = hp.k0 ^ ((hi + 1u) * 0x9E3779B9u);
@@ -412,6 +415,16 @@ __device__ __forceinline__ void sr_pack_bf16x4(const float* mp, const float* vp,
   for (int j = 0; j < 4; ++j) sr_narrow(mp[j], vp[j], sr_bits_at(eu, off + j, hp), mw[j], vw[j]);
   mr = make_uint2(sr_pack2(mw[0], mw[1]), sr_pack2(mw[2], mw[3]));
   vr = make_uint2(sr_pack2(vw[0], vw[1]), sr_pack2(vw[2], vw[3]));
+}
+// The same for a rule whose only 16-bit state is m (LionSrRule): the low half of each element's
+// draw, the one Adam's exp_avg takes; the high half is not used.
+template <typename HPT>
+__device__ __forceinline__ uint2 sr_pack_m_bf16x4(const float* mp, uint64_t eu, uint32_t off,
+                                                  const HPT& hp) {
+  uint32_t mw[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) mw[j] = sr_word(mp[j], sr_bits_at(eu, off + j, hp) & 0xFFFFu);
+  return make_uint2(sr_pack2(mw[0], mw[1]), sr_pack2(mw[2], mw[3]));
 }
 
 // Master-free bf16 parameters (zs_adamset_run_psr over a ZS_BF16_SR set; DESIGN.md §4, "Master-free
@@ -546,6 +559,49 @@ struct SgdRule {
   }
 };
 
+// Lion (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms") over the same tables:
+// field `m` of a segment is exp_avg, the one moment; `v` and `vmax` are unused.  No bias correction,
+// so nothing in the struct depends on the step count.  LionSrHP: the keys and m_base of the
+// stochastically rounded bf16 momentum ride behind it, as SrHP's behind HP.
+struct LionHP {
+  float beta1, omb1, beta2, omb2, neg_lr, decay_mul, grad_div, inv_div, carry_mul;
+  int div_pow2, maximize;
+};
+struct LionSrHP : LionHP {
+  uint32_t k0, k1;
+  uint64_t m_base;
+};
+
+template <typename HPT>
+struct LionRuleT {
+  using Hyper = HPT;
+  static constexpr bool kM = true, kV = false, kX = false, kGradOffset2 = false;
+  static constexpr bool kPsr = false;
+  static constexpr bool kEma = false;
+  static constexpr bool kStats = false;
+  using Stats = NoStats;
+
+  // One element of zero_amd.optim.Lion's step, in the rounding order of torch's CPU kernels:
+  // p.mul_(1 - lr*wd); c = m.mul(b1).add_(g, alpha=1-b1) = fma(1-b1, g, m*b1); u = sign(c) (torch's:
+  // +-0 -> +0, NaN -> 0); p.add_(u, alpha=-lr) = fma(-lr, u, p); m.mul_(b2).add_(g, alpha=1-b2) =
+  // fma(1-b2, g, m*b2).  Only explicit fmaf() fuse.
+  template <bool CARRY, bool CLIP>
+  static __device__ __forceinline__ void elem(float gsum, float& p, float& m, float&, float&,
+                                              float& carry, const HPT& hp, float coef) {
+#pragma clang fp contract(off)
+    const float g = prep_grad<CARRY, CLIP>(gsum, carry, hp, coef);
+    p = p * hp.decay_mul;
+    const float c = fmaf(hp.omb1, g, m * hp.beta1);
+    const float u = (c > 0.0f ? 1.0f : 0.0f) - (c < 0.0f ? 1.0f : 0.0f);
+    p = fmaf(hp.neg_lr, u, p);
+    m = fmaf(hp.omb2, g, m * hp.beta2);
+  }
+};
+template <bool>
+using LionRule = LionRuleT<LionHP>;
+template <bool>
+using LionSrRule = LionRuleT<LionSrHP>;
+
 template <typename GT>
 __device__ __forceinline__ float load_g1(const void* g, int64_t i) {
   if constexpr (sizeof(GT) == 4) return glob(static_cast<const float*>(g))[i];
@@ -645,8 +701,8 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
   constexpr bool G32 = sizeof(GT) == 4;
   constexpr bool S16 = sizeof(ST) == 2;
   constexpr bool PSR = Rule::kPsr;
-  static_assert(!S16 || (Rule::kM && Rule::kV && !Rule::kX && !CARRY),
-                "bf16 state: Adam's m and v, no amsgrad, no carry");
+  static_assert(!S16 || (Rule::kM && !Rule::kX && !CARRY),
+                "bf16 state: m (and Adam's v), no amsgrad, no carry");
   static_assert(!PSR || (SPLIT && !Rule::kX && !CARRY),
                 "master-free: the split master's geometry, no amsgrad, no carry");
   uint32_t o4 = threadIdx.x * 16u;                   // lane byte offset in an fp32 stream
@@ -660,7 +716,8 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
   typedef ChunkStream<unsigned short, G> S2;
   typedef std::conditional_t<Rule::kV && !S16, S4, NoStream> SV;  // v and its running maximum vmax
   typedef std::conditional_t<S16, NoStream, S4> SM;                // m as fp32
-  typedef std::conditional_t<S16, S2, NoStream> SH;                // m and v as bf16
+  typedef std::conditional_t<S16, S2, NoStream> SH;                // m as bf16
+  typedef std::conditional_t<S16 && Rule::kV, S2, NoStream> SHV;   // v as bf16 (Lion: none)
   const S4 gf(HASG && G32 ? (float*)s.g + e0 : nullptr), pm(SPLIT ? nullptr : (float*)s.master + e0);
   const S4 po(SPLIT ? nullptr : s.master_out + e0);
   const SM sm(Rule::kM ? s.m + e0 : nullptr);
@@ -669,7 +726,8 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
   const S2 gh(HASG && !G32 ? (unsigned short*)s.g + e0 : nullptr);
   const S2 hi(SPLIT ? (unsigned short*)s.master + e0 : nullptr);
   const S2 lo(SPLIT && !PSR ? (unsigned short*)s.master_out + e0 : nullptr), pb(s.p_out + e0);
-  const SH mh((unsigned short*)s.m + e0), vh((unsigned short*)s.v + e0);
+  const SH mh((unsigned short*)s.m + e0);
+  const SHV vh((unsigned short*)s.v + e0);
   uint4 gq[G], pq[G], mq[G], vq[G], xq[G], cq[G];
   uint2 gd[G], hd[G], ld[G], md[G], vd[G];
   // kGradOffset2 (Adam), fp32 gradients over the split master (G = 4): the gradient's groups 2 and
@@ -698,7 +756,7 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
     }
     if constexpr (S16) {
       md[u] = nt_ld8(mh.at(u, o2));
-      vd[u] = nt_ld8(vh.at(u, o2));
+      if constexpr (Rule::kV) vd[u] = nt_ld8(vh.at(u, o2));
     } else {
       if constexpr (Rule::kM) mq[u] = nt_ld16(sm.at(u, o4));
       if constexpr (Rule::kV) vq[u] = nt_ld16(sv.at(u, o4));
@@ -718,7 +776,7 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
     float xp[4] = {0.f, 0.f, 0.f, 0.f}, cp[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (S16) {
       unpack_bf16x4(md[u], mp);
-      unpack_bf16x4(vd[u], vp);
+      if constexpr (Rule::kV) unpack_bf16x4(vd[u], vp);
     } else {
       if constexpr (Rule::kM) unpack4(mq[u], mp);
       if constexpr (Rule::kV) unpack4(vq[u], vp);
@@ -772,7 +830,15 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
         for (int j = 0; j < 4; ++j) Rule::stat(p0[j], pp[j], acc);
       }
     }
-    if constexpr (kStochastic<ST>) {
+    if constexpr (S16 && !Rule::kV) {  // a 16-bit m alone (Lion): no v stream at all
+      uint2 mr;
+      if constexpr (kStochastic<ST>)
+        mr = sr_pack_m_bf16x4(mp, sr_seg_index(s.m, hp) + uint64_t(e0),
+                              (uint32_t(u) * kThreads + threadIdx.x) * 4u, hp);
+      else
+        mr = pack_bf16x4(mp);
+      nt_st8(mh.at(u, o2), mr);
+    } else if constexpr (kStochastic<ST>) {
       uint2 mr, vr;
       // (one uniform index per chunk: the group's offset rides in the lane's part, an immediate)
       sr_pack_bf16x4(mp, vp, sr_seg_index(s.m, hp) + uint64_t(e0),
@@ -802,8 +868,8 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
                                                    typename Rule::Stats& acc) {
   constexpr bool S16 = sizeof(ST) == 2;
   constexpr bool PSR = Rule::kPsr;
-  static_assert(!S16 || (Rule::kM && Rule::kV && !Rule::kX && !CARRY),
-                "bf16 state: Adam's m and v, no amsgrad, no carry");
+  static_assert(!S16 || (Rule::kM && !Rule::kX && !CARRY),
+                "bf16 state: m (and Adam's v), no amsgrad, no carry");
   static_assert(!PSR || (SPLIT && !Rule::kX && !CARRY),
                 "master-free: the split master's geometry, no amsgrad, no carry");
   float4 g4[G], p4[G], m4[G], v4[G];
@@ -825,9 +891,13 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
       }
       if constexpr (S16) {
         const uint2 mr = nt_ld8(reinterpret_cast<const unsigned short*>(s.m) + i);
-        const uint2 vr = nt_ld8(reinterpret_cast<const unsigned short*>(s.v) + i);
-        unpack_bf16x4(mr, reinterpret_cast<float*>(&m4[u]));
-        unpack_bf16x4(vr, reinterpret_cast<float*>(&v4[u]));
+        if constexpr (Rule::kV) {
+          const uint2 vr = nt_ld8(reinterpret_cast<const unsigned short*>(s.v) + i);
+          unpack_bf16x4(mr, reinterpret_cast<float*>(&m4[u]));
+          unpack_bf16x4(vr, reinterpret_cast<float*>(&v4[u]));
+        } else {  // a 16-bit m alone (Lion)
+          unpack_bf16x4(mr, reinterpret_cast<float*>(&m4[u]));
+        }
       } else {
         if constexpr (Rule::kM) m4[u] = ld4(s.m, i);
         if constexpr (Rule::kV) v4[u] = ld4(s.v, i);
@@ -895,7 +965,15 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
           for (int j = 0; j < 4; ++j) Rule::stat(p0[j], pp[j], acc);
         }
       }
-      if constexpr (kStochastic<ST>) {
+      if constexpr (S16 && !Rule::kV) {  // a 16-bit m alone (Lion)
+        uint2 mr;
+        if constexpr (kStochastic<ST>)
+          mr = sr_pack_m_bf16x4(mp, sr_seg_index(s.m, hp) + uint64_t(e0),
+                                (uint32_t(u) * kThreads + threadIdx.x) * 4u, hp);
+        else
+          mr = pack_bf16x4(mp);
+        nt_st8(reinterpret_cast<unsigned short*>(s.m) + i, mr);
+      } else if constexpr (kStochastic<ST>) {
         uint2 mr, vr;
         sr_pack_bf16x4(mp, vp, sr_seg_index(s.m, hp) + uint64_t(e0),
                        (uint32_t(u) * kThreads + threadIdx.x) * 4u, hp, mr, vr);
@@ -1007,8 +1085,8 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
   }
   constexpr bool S16 = sizeof(ST) == 2;
   constexpr bool PSR = Rule::kPsr;
-  static_assert(!S16 || (Rule::kM && Rule::kV && !Rule::kX && !CARRY),
-                "bf16 state: Adam's m and v, no amsgrad, no carry");
+  static_assert(!S16 || (Rule::kM && !Rule::kX && !CARRY),
+                "bf16 state: m (and Adam's v), no amsgrad, no carry");
   static_assert(!PSR || (SPLIT && !Rule::kX && !CARRY),
                 "master-free: the split master's geometry, no amsgrad, no carry");
   int64_t seg = 0;
@@ -1032,7 +1110,7 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
       float m = 0.0f, v = 0.0f, vm = 0.0f;
       if constexpr (S16) {
         m = bf16_to_f32(mb[i]);
-        v = bf16_to_f32(vb[i]);
+        if constexpr (Rule::kV) v = bf16_to_f32(vb[i]);
       } else {
         if constexpr (Rule::kM) m = glob(s.m)[i];
         if constexpr (Rule::kV) v = glob(s.v)[i];
@@ -1057,7 +1135,14 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
         if constexpr (Rule::kEma) Rule::ema(p, vm, hp);
         if constexpr (Rule::kStats) Rule::stat(p0, p, acc);
       }
-      if constexpr (kStochastic<ST>) {
+      if constexpr (S16 && !Rule::kV) {  // a 16-bit m alone (Lion)
+        if constexpr (kStochastic<ST>) {
+          const uint32_t r = sr_bits_at(sr_seg_index(s.m, hp) + uint64_t(i0), threadIdx.x, hp);
+          mb[i] = (unsigned short)(sr_word(m, r & 0xFFFFu) >> 16);
+        } else {
+          mb[i] = f32_to_bf16(m);
+        }
+      } else if constexpr (kStochastic<ST>) {
         uint32_t mh, vh;
         sr_narrow(m, v, sr_bits_at(sr_seg_index(s.m, hp) + uint64_t(i0), threadIdx.x, hp), mh, vh);
         mb[i] = (unsigned short)(mh >> 16);
@@ -2104,6 +2189,8 @@ struct zs_adamset {
   int g_dtype = ZS_F32, p_dtype = ZS_BF16, has_carry = 0, has_vmax = 0;
   // zs_sgdset_create: an SGD set (field m is the momentum buffer, has_mom: it has one)
   int sgd = 0, has_mom = 0;
+  // zs_lionset_create: a Lion set (field m is exp_avg, fp32 or bf16 by state_dtype; no v)
+  int lion = 0;
   // zs_adamset_create_ex: the element type of m and v, ZS_F32 or ZS_BF16
   int state_dtype = ZS_F32;
   // zs_adamset_set_grads: which input segment each table entry came from (the scalar entries with
@@ -2250,6 +2337,11 @@ using AdamFamily = UpdateFamily<AdamRule, float, true, true>;
 using AdamBf16Family = UpdateFamily<AdamRule, unsigned short, false, true>;  // zs_adamset_create_ex
 using AdamSrFamily = UpdateFamily<AdamSrRuleOf, SrBf16, false, true>;        // zs_adamset_run_sr
 using SgdFamily = UpdateFamily<SgdRule, float, true>;
+// zs_lionset_run: fp32 momentum (with the carry instances; the rule has no flag), bf16 momentum to
+// nearest, bf16 momentum rounded stochastically
+using LionFamily = UpdateFamily<LionRule, float, true, true>;
+using LionBf16Family = UpdateFamily<LionRule, unsigned short, false, true>;
+using LionSrFamily = UpdateFamily<LionSrRule, SrBf16, false, true>;
 template <bool>
 using AdamPsrRuleOf = AdamPsrRule;
 // zs_adamset_run_psr: the master-free instances, by how m and v are stored
@@ -2814,19 +2906,21 @@ int zs_adam_hparams_init(double lr, double beta1, double beta2, double eps, doub
   return ZS_OK;
 }
 
-// zs_adamset_create (sgd = false) and zs_sgdset_create (sgd = true: field m is the momentum buffer,
-// on all segments or on none; v and vmax must be 0); `fn` names the entry point in messages.
-// state_dtype: the element type of m and v (ZS_BF16: zs_adamset_create_ex's bf16 moments).
+// zs_adamset_create (sgd = false), zs_sgdset_create (sgd = true: field m is the momentum buffer,
+// on all segments or on none; v and vmax must be 0) and zs_lionset_create (lion = true: m on every
+// segment, v and vmax 0); `fn` names the entry point in messages.
+// state_dtype: the element type of m and v (ZS_BF16: zs_adamset_create_ex's bf16 moments, Lion's
+// bf16 momentum).
 static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n, int g_dtype,
-                      int p_dtype, int state_dtype, zs_adamset** out) {
+                      int p_dtype, int state_dtype, zs_adamset** out, bool lion = false) {
   ZS_REQUIRE(out != nullptr, "%s: out is NULL", fn);
   *out = nullptr;
   ZS_REQUIRE(n >= 0 && (n == 0 || in), "%s: bad table", fn);
   ZS_REQUIRE(g_dtype == ZS_F32 || g_dtype == ZS_BF16, "%s: bad g_dtype %d", fn, g_dtype);
   const bool psr = p_dtype == ZS_BF16_SR;  // master-free: zs_adamset_run_psr
-  ZS_REQUIRE(p_dtype == ZS_BF16 || p_dtype == ZS_BF16_SPLIT || (psr && !sgd),
+  ZS_REQUIRE(p_dtype == ZS_BF16 || p_dtype == ZS_BF16_SPLIT || (psr && !sgd && !lion),
              "%s: p_dtype must be ZS_BF16 or ZS_BF16_SPLIT%s (got %d)", fn,
-             sgd ? "" : " or ZS_BF16_SR", p_dtype);
+             sgd || lion ? "" : " or ZS_BF16_SR", p_dtype);
   ZS_REQUIRE(state_dtype == ZS_F32 || (state_dtype == ZS_BF16 && !sgd),
              "%s: state_dtype must be ZS_F32 or ZS_BF16 (got %d)", fn, state_dtype);
   const bool split = p_dtype == ZS_BF16_SPLIT;
@@ -2860,6 +2954,10 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
       ZS_REQUIRE(mom_state < 0 || mom_state == b,
                  "%s: m (the momentum buffer) must be set on all segments or none", fn);
       mom_state = b;
+    } else if (lion) {
+      ZS_REQUIRE(s.master && s.m, "%s: seg %lld missing master/m", fn, (long long)i);
+      ZS_REQUIRE(!s.v && !s.vmax, "%s: seg %lld: v and vmax must be 0 in a Lion set", fn,
+                 (long long)i);
     } else {
       ZS_REQUIRE(s.master && s.m && s.v, "%s: seg %lld missing master/m/v", fn, (long long)i);
     }
@@ -2917,7 +3015,9 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
     if (m_lowest != ~uint64_t(0) && ((s.m ^ m_lowest) & 3)) m_one_mod4 = 0;
     m_lowest = std::min<uint64_t>(m_lowest, s.m);
     elems += s.n;
-    int64_t b = msz /*master*/ + (sgd ? (s.m ? 8 : 0) /*buffer*/ : 2 * ssz /*m*/ + 2 * ssz /*v*/);
+    int64_t b = msz /*master*/ + (sgd    ? (s.m ? 8 : 0) /*buffer*/
+                                  : lion ? 2 * ssz /*m*/
+                                         : 2 * ssz /*m*/ + 2 * ssz /*v*/);
     if (s.master_out) b += split ? 4 /*residual read + write*/ : 4;
     if (s.p_out) b += 2;
     if (s.vmax) b += 2 * ssz;
@@ -2973,6 +3073,7 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   as->has_vmax = vmax_state > 0 ? 1 : 0;
   as->sgd = sgd ? 1 : 0;
   as->has_mom = mom_state > 0 ? 1 : 0;
+  as->lion = lion ? 1 : 0;
   as->state_dtype = state_dtype;
   as->in_g = std::move(in_g);
   as->in_n = std::move(in_n);
@@ -3044,6 +3145,7 @@ int zs_sgd_hparams_init(double lr, double momentum, double dampening, double wei
 int zs_sgdset_run(const zs_adamset* as, const zs_sgd_hparams* h, const float* coef,
                   uintptr_t stream) {
   ZS_REQUIRE(as && h, "zs_sgdset_run: NULL argument");
+  ZS_REQUIRE(!as->lion, "zs_sgdset_run: the set was made by zs_lionset_create (use zs_lionset_run)");
   ZS_REQUIRE(as->sgd, "zs_sgdset_run: the set was made by zs_adamset_create (use zs_adamset_run)");
   // a struct filled by hand gets zs_sgd_hparams_init's rules too (-0.0f is lr = 0)
   ZS_REQUIRE(h->neg_lr <= 0.0f, "zs_sgdset_run: negative learning rate");
@@ -3071,6 +3173,71 @@ int zs_sgdset_run(const zs_adamset* as, const zs_sgd_hparams* h, const float* co
   return run_set<SgdFamily>(as, as->has_mom != 0 && h->momentum != 0.0f, hp, coef, stream);
 }
 
+int zs_lionset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype, int state_dtype,
+                      zs_adamset** out) {
+  return set_create("zs_lionset_create", false, in, n, g_dtype, p_dtype, state_dtype, out, true);
+}
+
+int zs_lion_hparams_init(double lr, double beta1, double beta2, double weight_decay, int maximize,
+                         double grad_div, double carry_mul, zs_lion_hparams* hp) {
+  ZS_REQUIRE(hp != nullptr, "zs_lion_hparams_init: hp is NULL");
+  ZS_REQUIRE(grad_div > 0.0, "zs_lion_hparams_init: grad_div must be > 0");
+  // zero_amd.optim.Lion.__init__'s rules
+  ZS_REQUIRE(lr >= 0.0, "zs_lion_hparams_init: invalid learning rate %g", lr);
+  ZS_REQUIRE(beta1 >= 0.0 && beta1 < 1.0, "zs_lion_hparams_init: invalid beta1 %g", beta1);
+  ZS_REQUIRE(beta2 >= 0.0 && beta2 < 1.0, "zs_lion_hparams_init: invalid beta2 %g", beta2);
+  ZS_REQUIRE(weight_decay >= 0.0, "zs_lion_hparams_init: invalid weight_decay %g", weight_decay);
+  hp->neg_lr = float(-lr);
+  hp->beta1 = float(beta1);
+  hp->one_minus_beta1 = float(1.0 - beta1);
+  hp->beta2 = float(beta2);
+  hp->one_minus_beta2 = float(1.0 - beta2);
+  hp->decay_mul = weight_decay != 0.0 ? float(1.0 - lr * weight_decay) : 1.0f;
+  hp->grad_div = float(grad_div);
+  hp->carry_mul = float(carry_mul);
+  hp->maximize = maximize ? 1 : 0;
+  return ZS_OK;
+}
+
+int zs_lionset_run(const zs_adamset* as, const zs_lion_hparams* h, const float* coef, int guard,
+                   uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream) {
+  const char* fn = "zs_lionset_run";
+  ZS_REQUIRE(as && h, "%s: NULL argument", fn);
+  ZS_REQUIRE(as->lion, "%s: the set was not made by zs_lionset_create", fn);
+  ZS_REQUIRE(!guard || coef, "%s: the guard tests the clip coefficient, which is NULL", fn);
+  // a struct filled by hand gets zs_lion_hparams_init's rules too (-0.0f is lr = 0)
+  ZS_REQUIRE(h->neg_lr <= 0.0f, "%s: negative learning rate", fn);
+  ZS_REQUIRE(h->beta1 >= 0.0f && h->beta1 <= 1.0f && h->beta2 >= 0.0f && h->beta2 <= 1.0f,
+             "%s: invalid betas (%g, %g)", fn, double(h->beta1), double(h->beta2));
+  ZS_REQUIRE(h->grad_div > 0.0f, "%s: grad_div must be > 0", fn);
+  ZS_REQUIRE(!coef || !as->has_carry, "%s: a set with the ZeRO-1 carry cannot be clipped", fn);
+  LionSrHP hp;
+  hp.beta1 = h->beta1;
+  hp.omb1 = h->one_minus_beta1;
+  hp.beta2 = h->beta2;
+  hp.omb2 = h->one_minus_beta2;
+  hp.neg_lr = h->neg_lr;
+  hp.decay_mul = h->decay_mul;
+  hp.carry_mul = h->carry_mul;
+  set_grad_div(&hp, h->grad_div);
+  hp.maximize = h->maximize ? 1 : 0;
+  hp.k0 = key0;
+  hp.k1 = key1;
+  hp.m_base = m_base;
+  const bool g = guard != 0;
+  if (as->state_dtype != ZS_BF16)
+    return run_set<LionFamily>(as, false, static_cast<const LionHP&>(hp), coef, stream, g);
+  if (!as->state_sr)
+    return run_set<LionBf16Family>(as, false, static_cast<const LionHP&>(hp), coef, stream, g);
+  if (as->nvec + as->nsca) {  // every element's index: its m address less m_base, in elements
+    ZS_REQUIRE(as->m_lowest >= m_base, "%s: a segment's m lies below m_base (%#llx < %#llx)", fn,
+               (unsigned long long)as->m_lowest, (unsigned long long)m_base);
+    ZS_REQUIRE(as->m_one_parity && ((as->m_lowest - m_base) & 1) == 0,
+               "%s: a segment's m lies at an odd byte distance from m_base", fn);
+  }
+  return run_set<LionSrFamily>(as, false, hp, coef, stream, g);
+}
+
 // The three Adam entry points (`fn`: the one called, in messages).  need_coef: zs_adamset_run_clipped
 // requires its coefficient; sr: zs_adamset_run_sr's m_base and keys, over a set with bf16 moments.
 struct SrArgs {
@@ -3080,6 +3247,7 @@ struct SrArgs {
 static int adam_run(const char* fn, const zs_adamset* as, const zs_adam_hparams* h, bool need_coef,
                     const float* coef, const SrArgs* sr, uintptr_t stream, bool guard = false) {
   ZS_REQUIRE(as && h && (coef || !need_coef), "%s: NULL argument", fn);
+  ZS_REQUIRE(!as->lion, "%s: the set was made by zs_lionset_create (use zs_lionset_run)", fn);
   ZS_REQUIRE(!guard || !as->sgd, "%s: the guarded update is Adam's (the set was made by "
              "zs_sgdset_create)", fn);
   ZS_REQUIRE(!sr || (!as->sgd && as->state_dtype == ZS_BF16),
@@ -3141,7 +3309,7 @@ int zs_adamset_run_psr(const zs_adamset* as, const zs_adam_hparams* h, const flo
                        uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream) {
   const char* fn = "zs_adamset_run_psr";
   ZS_REQUIRE(as && h, "%s: NULL argument", fn);
-  ZS_REQUIRE(as->p_dtype == ZS_BF16_SR && !as->sgd,
+  ZS_REQUIRE(as->p_dtype == ZS_BF16_SR && !as->sgd && !as->lion,
              "%s: the set was not made with p_dtype ZS_BF16_SR (zs_adamset_create_ex)", fn);
   ZS_REQUIRE(!guard || coef, "%s: the guard tests the clip coefficient, which is NULL", fn);
   ZS_REQUIRE(h->amsgrad == 0, "%s: a ZS_BF16_SR set has no amsgrad", fn);
@@ -3171,6 +3339,8 @@ int zs_adamset_run_ema(const zs_adamset* as, const zs_adam_hparams* h, const flo
   ZS_REQUIRE(as && h, "%s: NULL argument", fn);
   ZS_REQUIRE(!as->sgd, "%s: the EMA rides on Adam's update (the set was made by zs_sgdset_create)",
              fn);
+  ZS_REQUIRE(!as->lion, "%s: the EMA rides on Adam's update (the set was made by "
+             "zs_lionset_create)", fn);
   ZS_REQUIRE(as->state_dtype == ZS_F32, "%s: a set with ZS_BF16 state has no EMA column", fn);
   ZS_REQUIRE(as->p_dtype != ZS_BF16_SR, "%s: a ZS_BF16_SR set has no master to average", fn);
   ZS_REQUIRE(!as->has_carry, "%s: a set with the ZeRO-1 carry has no EMA instances", fn);
@@ -3200,6 +3370,8 @@ int zs_adamset_run_stats(const zs_adamset* as, const zs_adam_hparams* h, const f
   ZS_REQUIRE(as && h, "%s: NULL argument", fn);
   ZS_REQUIRE(!as->sgd, "%s: the norms ride on Adam's update (the set was made by zs_sgdset_create)",
              fn);
+  ZS_REQUIRE(!as->lion, "%s: the norms ride on Adam's update (the set was made by "
+             "zs_lionset_create)", fn);
   ZS_REQUIRE(as->state_dtype == ZS_F32, "%s: a set with ZS_BF16 state has no stats instances", fn);
   ZS_REQUIRE(as->p_dtype != ZS_BF16_SR, "%s: a ZS_BF16_SR set has no master to measure", fn);
   ZS_REQUIRE(!as->has_carry, "%s: a set with the ZeRO-1 carry has no stats instances", fn);
@@ -3241,9 +3413,9 @@ int zs_update_norms(const float* sums3, int64_t n_params, const float* coef, flo
 
 int zs_adamset_set_state_rounding(zs_adamset* as, int stochastic) {
   ZS_REQUIRE(as != nullptr, "zs_adamset_set_state_rounding: NULL set");
-  ZS_REQUIRE(as->p_dtype == ZS_BF16_SR && as->state_dtype == ZS_BF16,
-             "zs_adamset_set_state_rounding: a ZS_BF16_SR set with ZS_BF16 state only (other sets "
-             "choose by entry point: zs_adamset_run / zs_adamset_run_sr)");
+  ZS_REQUIRE((as->p_dtype == ZS_BF16_SR || as->lion) && as->state_dtype == ZS_BF16,
+             "zs_adamset_set_state_rounding: a ZS_BF16_SR set or a Lion set, with ZS_BF16 state "
+             "only (other sets choose by entry point: zs_adamset_run / zs_adamset_run_sr)");
   as->state_sr = stochastic ? 1 : 0;
   return ZS_OK;
 }

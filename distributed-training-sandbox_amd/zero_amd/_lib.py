@@ -45,6 +45,7 @@ EXPORTED = (
     "zs_param_norms",
     "zs_adamset_update_norm_slots", "zs_adamset_run_stats", "zs_update_norms",
     "zs_sgd_hparams_init", "zs_sgdset_create", "zs_sgdset_run",
+    "zs_lion_hparams_init", "zs_lionset_create", "zs_lionset_run",
     "zs_comm_unique_id", "zs_comm_init", "zs_comm_destroy", "zs_reduce_scatter", "zs_all_gather",
     "zs_all_reduce", "zs_reduce", "zs_broadcast", "zs_reduce_group", "zs_broadcast_group", "zs_all_gather_group", "zs_reduce_scatter_group",
     "zs_all_gather_group_ordered", "zs_reduce_scatter_group_ordered", "zs_stream_wait_event",
@@ -85,6 +86,14 @@ class SgdHParams(ctypes.Structure):
                 ("grad_div", ctypes.c_float), ("carry_mul", ctypes.c_float),
                 ("nesterov", ctypes.c_int32), ("maximize", ctypes.c_int32),
                 ("first", ctypes.c_int32)]
+
+
+class LionHParams(ctypes.Structure):
+    _fields_ = [("neg_lr", ctypes.c_float), ("beta1", ctypes.c_float),
+                ("one_minus_beta1", ctypes.c_float), ("beta2", ctypes.c_float),
+                ("one_minus_beta2", ctypes.c_float), ("decay_mul", ctypes.c_float),
+                ("grad_div", ctypes.c_float), ("carry_mul", ctypes.c_float),
+                ("maximize", ctypes.c_int32)]
 
 
 _P = ctypes.c_void_p
@@ -177,6 +186,13 @@ _SIGS = {
     "zs_sgdset_create": ([ctypes.POINTER(AdamSeg), _I64, ctypes.c_int, ctypes.c_int,
                           ctypes.POINTER(_P)], ctypes.c_int),
     "zs_sgdset_run": ([_P, ctypes.POINTER(SgdHParams), _P, _U], ctypes.c_int),
+    "zs_lion_hparams_init": ([ctypes.c_double] * 4 + [ctypes.c_int] +
+                             [ctypes.c_double, ctypes.c_double, ctypes.POINTER(LionHParams)],
+                             ctypes.c_int),
+    "zs_lionset_create": ([ctypes.POINTER(AdamSeg), _I64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                           ctypes.POINTER(_P)], ctypes.c_int),
+    "zs_lionset_run": ([_P, ctypes.POINTER(LionHParams), _P, ctypes.c_int, ctypes.c_uint64,
+                        ctypes.c_uint32, ctypes.c_uint32, _U], ctypes.c_int),
     "zs_adam_step": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_float] * 5 +
                      [ctypes.c_int, _I64, ctypes.c_float, _P, ctypes.c_float, _U], ctypes.c_int),
     "zs_adam_step_ex": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_double] * 5 +

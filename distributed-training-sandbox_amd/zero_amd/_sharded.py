@@ -21,11 +21,11 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import (check_bf16_state_group, check_ema, check_ema_decay, check_ema_group,
+from ._update import (check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
                       check_max_grad_norm, check_param_grad_norms, check_update_norms,
                       check_update_norms_group,
                       check_skip_nonfinite, check_master_free, check_master_free_group,
-                      check_state_dtype, check_state_rounding, owner_range)
+                      check_state_dtype, check_state_rounding, owner_range, KIND_NAMES)
 from .engine import ShardEngine
 from .training_utils.utils import get
 
@@ -57,19 +57,36 @@ def sgd_group_hparams(group: dict) -> dict:
                 maximize=bool(group.get("maximize", False)), amsgrad=False)
 
 
+def lion_group_hparams(group: dict) -> dict:
+    """Hyper-parameters of one zero_amd.optim.Lion param group."""
+    lr = group["lr"]
+    lr = float(lr.item()) if torch.is_tensor(lr) else float(lr)
+    beta1, beta2 = group["betas"]
+    return dict(lr=lr, beta1=float(beta1), beta2=float(beta2),
+                weight_decay=float(group.get("weight_decay", 0.0)),
+                maximize=bool(group.get("maximize", False)), amsgrad=False)
+
+
 def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
-    """One param group's hyper-parameters for the ``kind`` ("adam" / "sgd") update."""
+    """One param group's hyper-parameters for the ``kind`` ("adam" / "sgd" / "lion") update."""
+    if kind == "lion":
+        return lion_group_hparams(group)
     return sgd_group_hparams(group) if kind == "sgd" else adam_group_hparams(group, optimizer)
 
 
 def optimizer_kind(optimizer: Optimizer) -> str:
-    """"adam" (torch.optim.Adam / AdamW) or "sgd" (torch.optim.SGD); TypeError for anything else."""
+    """"adam" (torch.optim.Adam / AdamW), "sgd" (torch.optim.SGD) or "lion"
+    (zero_amd.optim.Lion); TypeError for anything else."""
+    from .optim import Lion
+
     if isinstance(optimizer, torch.optim.Adam):
         return "adam"
     if isinstance(optimizer, torch.optim.SGD):
         return "sgd"
-    raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD "
-                    f"(got {type(optimizer).__name__})")
+    if isinstance(optimizer, Lion):
+        return "lion"
+    raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD or "
+                    f"zero_amd.optim.Lion (got {type(optimizer).__name__})")
 
 
 class ShardedOptimizerBase:
@@ -169,6 +186,8 @@ class ShardedOptimizerBase:
             hpd = group_hparams(self._kind, group, optimizer)
             if bf16_state and self._kind == "adam":
                 check_bf16_state_group(hpd, self.state_rounding)
+            if bf16_state and self._kind == "lion":
+                check_bf16_state_lion_group(hpd, self.state_rounding)
             if master_free:
                 check_master_free_group(hpd)
             if has_ema:
@@ -186,13 +205,14 @@ class ShardedOptimizerBase:
                 raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with the "
                                  f"bucket arena (arena={arena!r}, layout={layout!r}); use the "
                                  "flat arena")
-        if self._kind == "sgd":
-            # the SGD update runs on the flat arena (and its rounds) only
+        if self._kind in ("sgd", "lion"):
+            # the SGD and Lion updates run on the flat arena (and its rounds) only
+            name = KIND_NAMES[self._kind]
             if arena == "buckets":
-                raise ValueError("zero_amd: torch.optim.SGD is not supported with arena='buckets' "
+                raise ValueError(f"zero_amd: {name} is not supported with arena='buckets' "
                                  "(the bucket arena); use the flat arena")
             if layout != "reference" and (layout != "flat" or self._carry):
-                raise ValueError(f"zero_amd: torch.optim.SGD is not supported with layout={layout!r} "
+                raise ValueError(f"zero_amd: {name} is not supported with layout={layout!r} "
                                  "(it runs on the bucket arena, arena='buckets')")
             arena = "flat"  # arena='auto' would time the bucket arena as a candidate
         self.optimizer = optimizer
@@ -506,8 +526,9 @@ class ShardedOptimizerBase:
             for gi in range(len(self._groups)):
                 check_update_norms_group(self._hparams_of(gi))
         if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
+            check = check_bf16_state_lion_group if self._kind == "lion" else check_bf16_state_group
             for gi in range(len(self._groups)):
-                check_bf16_state_group(self._hparams_of(gi), self.state_rounding)
+                check(self._hparams_of(gi), self.state_rounding)
         if self._master == "none":
             for gi in range(len(self._groups)):
                 check_master_free_group(self._hparams_of(gi))

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .checkpoint import step_of
-from .kernels import adam_hparams, sgd_hparams, sr_keys
+from .kernels import adam_hparams, lion_hparams, sgd_hparams, sr_keys
 
 # master="none": bf16 parameters without any master — the fused update reads the bf16 parameter,
 # runs the fp32 rule and stores it back rounded stochastically ("Master-free bf16
@@ -47,6 +47,11 @@ def check_params(params):
 # bf16 moments keep 8 significant bits: a pure decay x <- beta * x moves every stored value only
 # while 1 - beta >= 2^-8 ("bf16 moments"); below that exp_avg_sq could never shrink
 BF16_STATE_MIN_ONE_MINUS_BETA = 2.0 ** -8
+
+
+KINDS = ("adam", "sgd", "lion")
+# what the messages call the optimizer of a kind that an option does not support
+KIND_NAMES = {"sgd": "torch.optim.SGD", "lion": "zero_amd.optim.Lion"}
 
 
 def check_state_dtype(state_dtype):
@@ -94,10 +99,20 @@ def check_bf16_state_group(hpd: dict, state_rounding=None) -> None:
                 "bits and a smaller decay is rounded away, so the moment could never shrink")
 
 
+def check_bf16_state_lion_group(hpd: dict, state_rounding=None) -> None:
+    """Lion's bf16 momentum rounded to nearest: only beta2 is bounded (beta2 <= 0.99609375), since
+    beta1 never reaches a stored value; ValueError otherwise.  "stochastic": any beta."""
+    if state_rounding != "stochastic" and 1.0 - float(hpd["beta2"]) < BF16_STATE_MIN_ONE_MINUS_BETA:
+        raise ValueError(
+            "zero_amd: state_dtype=torch.bfloat16 needs 1 - beta2 >= 2^-8 = 0.00390625, that is "
+            f"beta2 <= 0.99609375 (got beta2 = {hpd['beta2']!r}): bf16 keeps 8 significant bits and "
+            "a smaller decay is rounded away, so the momentum could never shrink")
+
+
 def check_master_free(kind: str, carry: bool, bf16_params: bool = True) -> None:
     """What ``master="none"`` cannot be combined with, as ValueError."""
     if kind != "adam":
-        raise ValueError("zero_amd: master='none' is not supported with torch.optim.SGD")
+        raise ValueError(f"zero_amd: master='none' is not supported with {KIND_NAMES[kind]}")
     if not bf16_params:
         raise ValueError("zero_amd: master='none' rounds bf16 parameters stochastically: it needs "
                          "bf16 parameters (fp32 parameters are their own master)")
@@ -130,8 +145,8 @@ def ema_weight(ema_decay) -> float:
 def check_ema(kind: str, carry: bool, state_dtype=None, master=None) -> None:
     """What ``ema_decay`` cannot be combined with on an update core, as ValueError."""
     if kind != "adam":
-        raise ValueError("zero_amd: ema_decay is not supported with torch.optim.SGD (the EMA is "
-                         "fused into the Adam update)")
+        raise ValueError(f"zero_amd: ema_decay is not supported with {KIND_NAMES[kind]} (the EMA "
+                         "is fused into the Adam update)")
     if check_state_dtype(state_dtype) == torch.bfloat16:
         raise ValueError("zero_amd: ema_decay is not supported with state_dtype=torch.bfloat16 (the "
                          "fp32 EMA would add back the bytes the bf16 moments save)")
@@ -152,8 +167,8 @@ def check_ema_group(hpd: dict) -> None:
 def check_update_norms(kind: str, carry: bool, state_dtype=None, master=None, ema=False) -> None:
     """What ``param_update_norms`` cannot be combined with on an update core, as ValueError."""
     if kind != "adam":
-        raise ValueError("zero_amd: param_update_norms is not supported with torch.optim.SGD (the "
-                         "norms are summed inside the fused Adam update)")
+        raise ValueError(f"zero_amd: param_update_norms is not supported with {KIND_NAMES[kind]} "
+                         "(the norms are summed inside the fused Adam update)")
     if check_state_dtype(state_dtype) == torch.bfloat16:
         raise ValueError("zero_amd: param_update_norms is not supported with "
                          "state_dtype=torch.bfloat16 (the stats instances keep fp32 moments)")
@@ -184,11 +199,12 @@ def join_split_master(param: torch.Tensor, residual: torch.Tensor) -> torch.Tens
 def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = False,
                  carry: bool = False, momentum: bool = True, state_dtype=None, master=None):
     """(total fp32 words, {name: (word offset, dtype)}) of the flat state of an ``L``-element
-    shard: ``m``, ``v`` (Adam; SGD: ``m`` alone, the momentum buffer, and only with ``momentum``),
+    shard: ``m``, ``v`` (Adam; SGD: ``m`` alone, the momentum buffer, and only with ``momentum``;
+    Lion: ``m`` alone, always),
     ``carry`` (ZeRO-1), ``master`` (fp32 master of bf16 params), each ``L`` fp32, then ``lo``:
     ``L`` int16 residuals of the split master in ``(L + 1) // 2`` words.  ``state_dtype``
-    torch.bfloat16 (Adam without carry): ``m`` and ``v`` are ``L`` bf16 each, every array from
-    ``master`` on starting at a multiple of 4 words (16 bytes).  ``master="none"`` (Adam without
+    torch.bfloat16 (Adam or Lion, without carry): ``m`` and ``v`` (Lion: ``m`` alone) are ``L``
+    bf16 each, every array from ``v`` on starting at a multiple of 4 words (16 bytes).  ``master="none"`` (Adam without
     carry): the moments alone, neither ``master`` nor ``lo``."""
     if master == "none":
         check_master_free(kind, carry)
@@ -197,12 +213,15 @@ def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = 
     elif master is not None and master not in MASTERS:
         raise ValueError(f"state_layout: master must be one of {MASTERS} (got {master!r})")
     if check_state_dtype(state_dtype) == torch.bfloat16:
-        if kind != "adam" or carry:
-            raise ValueError("state_layout: bf16 state is Adam's, without the ZeRO-1 carry")
+        if kind not in ("adam", "lion") or carry:
+            raise ValueError("state_layout: bf16 state is Adam's or Lion's, without the ZeRO-1 "
+                             "carry")
         words = (L + 1) // 2  # of one bf16 array
         pad = lambda w: (w + 3) // 4 * 4  # noqa: E731
-        lay = {"m": (0, torch.bfloat16), "v": (pad(words), torch.bfloat16)}
-        total = pad(words) + words
+        lay, total = {"m": (0, torch.bfloat16)}, words
+        if kind == "adam":
+            lay["v"] = (pad(words), torch.bfloat16)
+            total = pad(words) + words
         if fp32_master:
             lay["master"] = (pad(total), torch.float32)
             total = pad(total) + L
@@ -210,7 +229,7 @@ def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = 
             lay["lo"] = (pad(total), torch.int16)
             total = pad(total) + words
         return total, lay
-    names = ["m", "v"][:2 if kind == "adam" else int(bool(momentum))]
+    names = ["m", "v"][:2 if kind == "adam" else 1 if kind == "lion" else int(bool(momentum))]
     names += ["carry"] * bool(carry) + ["master"] * bool(fp32_master)
     lay = {name: (k * L, torch.float32) for k, name in enumerate(names)}
     total = len(names) * L
@@ -230,19 +249,20 @@ class UpdateCore:
                  update_norms: bool = False):
         from .engine import probed_zeros  # (engine.py builds on this module)
 
-        if kind not in ("adam", "sgd"):
-            raise ValueError(f"UpdateCore: kind must be 'adam' or 'sgd' (got {kind!r})")
-        # the update: torch.optim.Adam's, or torch.optim.SGD's (`momentum`: some group has a
+        if kind not in KINDS:
+            raise ValueError(f"UpdateCore: kind must be 'adam', 'sgd' or 'lion' (got {kind!r})")
+        # the update: torch.optim.Adam's, torch.optim.SGD's (`momentum`: some group has a
         # momentum, so the shard holds a momentum buffer; none of them: no optimizer state at all)
+        # or zero_amd.optim.Lion's (one moment, exp_avg, always)
         self.kind, self.L, self.device, self.ws = kind, int(L), device, ws
         self.group_of = list(group_of)
         # the moments' dtype: torch.float32, or torch.bfloat16 (Adam without amsgrad or carry; one
         # step widens them, runs the fp32 update and stores them rounded to nearest even, or
         # stochastically: state_rounding below)
         self.state_dtype = check_state_dtype(state_dtype)
-        if self.state_dtype == torch.bfloat16 and (kind != "adam" or carry):
+        if self.state_dtype == torch.bfloat16 and (kind == "sgd" or carry):
             raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with " +
-                             ("torch.optim.SGD" if kind != "adam" else "the ZeRO-1 gradient carry"))
+                             ("torch.optim.SGD" if kind == "sgd" else "the ZeRO-1 gradient carry"))
         # how the bf16 moments are rounded when stored: "nearest", or "stochastic" from the
         # counter-based generator keyed by (state_seed, the part's step, the element's shard index)
         self.state_rounding, self.state_seed = check_state_rounding(state_rounding, state_seed,
@@ -284,6 +304,8 @@ class UpdateCore:
         cut = lambda t: t[so:so + n].view(shape)  # noqa: E731
         if self.kind == "sgd":  # torch's SGD state: the buffer alone (absent without momentum)
             views = {} if self.m is None else {"momentum_buffer": cut(self.m)}
+        elif self.kind == "lion":
+            views = {"exp_avg": cut(self.m)}
         else:
             views = {"exp_avg": cut(self.m), "exp_avg_sq": cut(self.v)}
         if self.master is not None:
@@ -374,8 +396,11 @@ class UpdateCore:
     # hyper-parameters ---------------------------------------------------------------------------
     def hp_key(self, steps):
         """What of a parameter's step count the hyper-parameter struct depends on: the count
-        itself (Adam's bias correction), or only whether this is its first step (SGD's buffer)."""
+        itself (Adam's bias correction), only whether this is its first step (SGD's buffer), or
+        nothing (Lion; the count itself under stochastic rounding, which is keyed by it)."""
         steps = np.asarray(steps, np.int64)
+        if self.kind == "lion":  # no bias correction: only the rounding keys depend on the step
+            return steps if self.state_rounding == "stochastic" else np.zeros_like(steps)
         return (steps == 1).astype(np.int64) if self.kind == "sgd" else steps
 
     def make_hp(self, hpd: dict, key: int, cmul: int = 0):
@@ -388,6 +413,14 @@ class UpdateCore:
             return sgd_hparams(hpd["lr"], hpd["momentum"], hpd["dampening"], hpd["weight_decay"],
                                nesterov=hpd["nesterov"], maximize=hpd["maximize"], first=bool(key),
                                grad_div=float(self.ws), carry_mul=carry_mul)
+        if self.kind == "lion":
+            if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
+                check_bf16_state_lion_group(hpd, self.state_rounding)
+            hp = lion_hparams(hpd["lr"], hpd["beta1"], hpd["beta2"], hpd["weight_decay"],
+                              maximize=hpd["maximize"], grad_div=float(self.ws), carry_mul=carry_mul)
+            if self.state_rounding == "stochastic":  # the launch's keys travel with its struct
+                hp.sr_keys = sr_keys(self.state_seed, int(key))
+            return hp
         if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
             check_bf16_state_group(hpd, self.state_rounding)
         if self.master_free:
@@ -440,7 +473,10 @@ class UpdateCore:
             e0.record(stream)
         if guard and coef is None:
             raise ValueError("zero_amd: the guarded update tests the clip coefficient")
-        if self.update_norms:
+        if self.kind == "lion":
+            sr = (self.m.data_ptr(), hp.sr_keys) if self.state_rounding == "stochastic" else None
+            aset.run(hp, stream, coef=coef, guard=guard, sr=sr)
+        elif self.update_norms:
             if stats is None:
                 raise ValueError("zero_amd: param_update_norms: a launch without its partials")
             aset.run_stats(hp, int(stats), stream, coef=coef, guard=guard)

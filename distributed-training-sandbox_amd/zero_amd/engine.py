@@ -37,8 +37,8 @@ import torch
 
 from . import _lib
 from .comm import StreamEvent, comm_stream, zs_dtype
-from ._update import MASTERS, UpdateCore, check_master_free, check_params
-from .kernels import AdamSet, CopySet, SgdSet
+from ._update import KINDS, MASTERS, UpdateCore, check_master_free, check_params
+from .kernels import AdamSet, CopySet, LionSet, SgdSet
 from .plan import Plan
 
 ALIGN_ELEMS = 64  # every stream piece starts 256 B (f32) / 128 B (bf16) aligned
@@ -302,8 +302,8 @@ class ShardEngine(UpdateCore):
                  kind: str = "adam", momentum: bool = True, state_dtype=None,
                  state_rounding=None, state_seed: int = 0, ema: bool = False,
                  update_norms: bool = False):
-        if kind not in ("adam", "sgd"):
-            raise ValueError(f"ShardEngine: kind must be 'adam' or 'sgd' (got {kind!r})")
+        if kind not in KINDS:
+            raise ValueError(f"ShardEngine: kind must be 'adam', 'sgd' or 'lion' (got {kind!r})")
         if not params:
             raise ValueError("ShardEngine: no parameters")
         dev, dtype = check_params(params)
@@ -435,10 +435,14 @@ class ShardEngine(UpdateCore):
         return self._adam_rows(idx, g, mst, mst, p_out, so, n)
 
     def new_set(self, rows):
-        """The update's kernel set over ``rows``: AdamSet, or SgdSet for an SGD engine."""
+        """The update's kernel set over ``rows``: AdamSet, SgdSet for an SGD engine, LionSet for a
+        Lion engine."""
         gz = getattr(self, "czdtype", self.zdtype)  # dtype of the reduced grad the update reads
         if self.kind == "sgd":
             return SgdSet(rows, gz, self.p_dtype)
+        if self.kind == "lion":
+            return LionSet(rows, gz, self.p_dtype, state_dtype=zs_dtype(self.state_dtype),
+                           state_rounding=self.state_rounding)
         if self.master_free:
             return AdamSet(rows, gz, self.p_dtype, state_dtype=zs_dtype(self.state_dtype),
                            wide_grads=gz == _lib.ZS_F32, state_rounding=self.state_rounding)

@@ -8,6 +8,8 @@
 finite; ``run_sr`` with ``sr_keys`` stores bf16 moments with stochastic rounding; a set with
 ``p_dtype=ZS_BF16_SR`` keeps no master and ``run_psr`` rounds its bf16 parameters stochastically.
 ``SgdSet``   — the same tables with torch.optim.SGD's update (momentum, Nesterov); ``sgd_hparams``.
+``LionSet``  — the same tables with zero_amd.optim.Lion's update (one moment, fp32 or bf16);
+``lion_hparams``.
 ``adam_step`` — the same update over one contiguous range (zs_adam_step_ex; no table to keep).
 
 Both upload their segment table once; ``run(stream)`` only enqueues a kernel on ``stream``.
@@ -21,7 +23,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import AdamHParams, AdamSeg, SgdHParams
+from ._lib import AdamHParams, AdamSeg, LionHParams, SgdHParams
 
 _PU64 = ctypes.POINTER(ctypes.c_uint64)
 _PI64 = ctypes.POINTER(ctypes.c_int64)
@@ -161,7 +163,8 @@ class AdamSet:
         if state_rounding not in ("nearest", "stochastic"):
             raise ValueError(f"zero_amd: state_rounding must be 'nearest' or 'stochastic', got "
                              f"{state_rounding!r}")
-        if state_rounding == "stochastic" and not (psr and state_dtype == _lib.ZS_BF16):
+        lion = self._CREATE == "zs_lionset_create"
+        if state_rounding == "stochastic" and not ((psr or lion) and state_dtype == _lib.ZS_BF16):
             raise _lib.ZeroAmdError(self._CREATE, _lib.ZS_ERR_INVALID,
                                     "state_rounding is a ZS_BF16_SR set's with ZS_BF16 state (other "
                                     "sets choose by run / run_sr)")
@@ -173,7 +176,10 @@ class AdamSet:
         arr = (AdamSeg * max(len(segs), 1))()
         ctypes.memmove(arr, segs.ctypes.data, segs.nbytes)
         h = ctypes.c_void_p()
-        if state_dtype == _lib.ZS_F32 and not (psr and self._CREATE == "zs_adamset_create"):
+        if lion:
+            _lib.call(self._CREATE, arr, len(segs), int(g_dtype), int(p_dtype), state_dtype,
+                      ctypes.byref(h))
+        elif state_dtype == _lib.ZS_F32 and not (psr and self._CREATE == "zs_adamset_create"):
             _lib.call(self._CREATE, arr, len(segs), int(g_dtype), int(p_dtype), ctypes.byref(h))
         elif self._CREATE != "zs_adamset_create":
             raise _lib.ZeroAmdError(self._CREATE, _lib.ZS_ERR_INVALID,
@@ -392,6 +398,49 @@ class SgdSet(AdamSet):
         raise _lib.ZeroAmdError("zs_adamset_run_guarded", _lib.ZS_ERR_INVALID,
                                 "the guarded update is Adam's (SGD tells its first step from the "
                                 "host's count, which a skipped step would advance)")
+
+
+def lion_hparams(lr, beta1=0.9, beta2=0.99, weight_decay=0.0, *, maximize=False, grad_div=1.0,
+                 carry_mul=0.0) -> LionHParams:
+    hp = LionHParams()
+    _lib.call("zs_lion_hparams_init", float(lr), float(beta1), float(beta2), float(weight_decay),
+              int(bool(maximize)), float(grad_div), float(carry_mul), ctypes.byref(hp))
+    return hp
+
+
+class LionSet(AdamSet):
+    """Fused Lion over segments in zs_adam_seg order (zs_lionset_create): column ``m`` is
+    ``exp_avg`` on every row, fp32 or (``state_dtype=ZS_BF16``) bf16, stored to nearest or with
+    ``state_rounding="stochastic"``; ``v`` and ``vmax`` are 0.  ``set_grads``, ``grad_sqnorm``,
+    ``grad_sqnorm_segs``, ``bytes`` and ``grad_bytes`` as ``AdamSet``."""
+
+    _CREATE = "zs_lionset_create"
+
+    def run(self, hp: LionHParams, stream, coef=None, guard=False, sr=None) -> None:
+        """One step (zs_lionset_run).  ``coef``: None, or the fp32 device scalar (a tensor or its
+        address) every averaged gradient is multiplied by; ``guard``: a NaN ``coef`` skips the
+        step, nothing is read or written; ``sr`` (a set with stochastic rounding):
+        ``(m_base, (key0, key1))`` as ``AdamSet.run_sr`` takes them."""
+        ptr = None if coef is None else coef if isinstance(coef, int) else coef.data_ptr()
+        if (sr is None) != (self.state_rounding != "stochastic"):
+            raise _lib.ZeroAmdError("zs_lionset_run", _lib.ZS_ERR_INVALID,
+                                    "sr=(m_base, keys) goes with state_rounding='stochastic', and "
+                                    "only with it")
+        m_base, keys = (0, (0, 0)) if sr is None else sr
+        _lib.call("zs_lionset_run", self._h, ctypes.byref(hp), ptr, int(bool(guard)), int(m_base),
+                  int(keys[0]), int(keys[1]), stream_handle(stream))
+
+    def run_clipped(self, hp, coef, stream) -> None:
+        self.run(hp, stream, coef=coef)
+
+    def run_guarded(self, hp, coef, stream) -> None:
+        self.run(hp, stream, coef=coef, guard=True)
+
+    def _not_lion(self, *a, **k):
+        raise _lib.ZeroAmdError("zs_lionset_run", _lib.ZS_ERR_INVALID,
+                                "a Lion set runs through LionSet.run")
+
+    run_sr = run_psr = run_ema = run_stats = _not_lion
 
 
 def sqnorm_reduce(partials, n: int, sumsq, stream) -> None:

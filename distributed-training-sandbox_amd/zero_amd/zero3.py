@@ -69,14 +69,14 @@ from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_BF16_SR, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
 from ._sharded import group_hparams, optimizer_kind
-from ._update import (GradClip, UpdateCore, UpdateNorms, check_bf16_state_group, check_ema,
-                      check_ema_decay, check_ema_group, check_master_free, check_update_norms,
+from ._update import (GradClip, UpdateCore, UpdateNorms, check_bf16_state_group,
+                      check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group, check_master_free, check_update_norms,
                       check_update_norms_group,
                       check_master_free_group, check_max_grad_norm, check_param_grad_norms, check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
                       owner_range)
 from .comm import STREAM_SYNC, RcclComm, Sync, comm_stream, sync_kind, zs_dtype
 from .engine import ALIGN_ELEMS
-from .kernels import AdamSet, SgdSet, convert, stream_handle
+from .kernels import AdamSet, LionSet, SgdSet, convert, stream_handle
 from .training_utils.utils import get
 
 try:  # the hooks' per-module install / release in C++ (csrc/zs_host_ext.cpp, built with the library)
@@ -1933,6 +1933,8 @@ class ShardedOptimizer:
             hpd = group_hparams(self._kind, group, optimizer)
             if self.state_dtype == torch.bfloat16 and self._kind == "adam":
                 check_bf16_state_group(hpd, self.state_rounding)
+            if self.state_dtype == torch.bfloat16 and self._kind == "lion":
+                check_bf16_state_lion_group(hpd, self.state_rounding)
             if master == "none":
                 check_master_free_group(hpd)
             if self._ema_decay is not None:
@@ -2327,6 +2329,8 @@ class ShardedOptimizer:
             self._split or self._master_free or (self._grad_comm and self.world_size > 1)) else ZS_F32
         kw = {} if self._kind == "sgd" else dict(state_dtype=zs_dtype(self.state_dtype))
         mk = SgdSet if self._kind == "sgd" else AdamSet
+        if self._kind == "lion":  # (never master-free: refused at construction)
+            mk, kw["state_rounding"] = LionSet, self.state_rounding
         if self._master_free:
             return mk(rows, gz, ZS_BF16_SR, wide_grads=acc, state_rounding=self.state_rounding, **kw)
         if self._split:
@@ -2336,9 +2340,9 @@ class ShardedOptimizer:
     def _step_update(self):
         red, ar = self._reducer, self._arena
         if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
+            check = check_bf16_state_lion_group if self._kind == "lion" else check_bf16_state_group
             for group in self._groups:
-                check_bf16_state_group(group_hparams(self._kind, group, self.optimizer),
-                                       self.state_rounding)
+                check(group_hparams(self._kind, group, self.optimizer), self.state_rounding)
         if self._master_free:
             for group in self._groups:
                 check_master_free_group(group_hparams(self._kind, group, self.optimizer))
@@ -2416,12 +2420,14 @@ class ShardedOptimizer:
             self._stats_finish(cur)
         if self._kind == "sgd":  # torch's SGD keeps no step: the buffer appears after the first
             self._expose_sgd(idx)
-        elif uniform:  # torch's state['step'] (a CPU tensor): one shared tensor, updated in place
+        elif uniform and bool((core.steps[idx] == core.steps[idx[0]]).all()):
+            # torch's state['step'] (a CPU tensor): one shared tensor, updated in place (the count
+            # itself: Lion's hp_key above is constant)
             t = self._step_shared
             if t is None:
-                t = self._step_shared = torch.tensor(float(steps[0]))
+                t = self._step_shared = torch.tensor(float(core.steps[idx[0]]))
             else:
-                t.fill_(float(steps[0]))
+                t.fill_(float(core.steps[idx[0]]))
             if sig is None or self._step_shared_sig != sig:
                 for i in idx.tolist():
                     self.optimizer.state[self.params[i]]["step"] = t

@@ -581,6 +581,65 @@ int zs_sgdset_create(const zs_adam_seg* segs, int64_t n, int g_dtype, int p_dtyp
 int zs_sgdset_run(const zs_adamset* as, const zs_sgd_hparams* hp, const float* coef,
                   uintptr_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Fused Lion (Chen et al. 2023, arXiv:2302.06675), additive in ABI v13.  The update of          */
+/* zero_amd.optim.Lion on the owned shard: one moment (exp_avg), no bias correction, through the */
+/* Adam's tables and kernels' shape.  14 B/element over the split master with bf16 momentum and  */
+/* bf16 gradients, 18 with fp32 momentum (SGD-with-momentum's traffic; Adam's: 26, or 18 with    */
+/* bf16 moments).                                                                                 */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  /* doubles on the host, rounded to f32 once */
+  float neg_lr;           /* -lr */
+  float beta1;            /* the update's interpolation: c = beta1 * m + (1 - beta1) * g */
+  float one_minus_beta1;
+  float beta2;            /* the momentum's decay: m = beta2 * m + (1 - beta2) * g */
+  float one_minus_beta2;
+  float decay_mul;        /* 1 - lr * weight_decay (decoupled); 1 when weight_decay == 0 */
+  float grad_div;         /* divide the reduced sum by this (world size) */
+  float carry_mul;        /* ZeRO-1: sum += carry_mul * carry (ws-1) */
+  int32_t maximize;
+} zs_lion_hparams;
+
+/* Fill hp from a Lion param group's scalars.  ZS_ERR_INVALID for what zero_amd.optim.Lion refuses
+ * (lr < 0, a beta outside [0, 1), weight_decay < 0), for grad_div <= 0 and for a NULL hp. */
+int zs_lion_hparams_init(double lr, double beta1, double beta2, double weight_decay, int maximize,
+                         double grad_div, double carry_mul, zs_lion_hparams* hp);
+/* A zs_adamset whose update is Lion's: segs, g_dtype, p_dtype, alignment and the vector / scalar
+ * split exactly as zs_adamset_create_ex, with m = exp_avg (updated in place) set on every
+ * non-empty segment and v == vmax == 0.  state_dtype is the element type of m: ZS_F32, or ZS_BF16
+ * (m 8-byte aligned for the vector part; rounded to nearest even when stored, or stochastically
+ * after zs_adamset_set_state_rounding(as, 1)); a 16-bit v stream does not exist.
+ * ZS_ERR_INVALID: a NULL out or table, n < 0, a bad g_dtype; p_dtype other than ZS_BF16 or
+ * ZS_BF16_SPLIT (ZS_BF16_SR: Lion has no master-free instances); state_dtype other than ZS_F32 or
+ * ZS_BF16; a non-empty segment without master or m, or with v or vmax; a split master without
+ * master_out and p_out; a carry with ZS_BF16 state, or with fp32 gradients over the split master,
+ * or on some segments only.  zs_adamset_set_grads, zs_adamset_sqnorm_partials,
+ * zs_adamset_grad_sqnorm, zs_adamset_sqnorm_seg_partials, zs_adamset_grad_sqnorm_segs,
+ * zs_adamset_destroy and zs_adamset_stats (gradient + parameter read and write + momentum read and
+ * write) work on it unchanged; every zs_adamset_run* and zs_sgdset_run return ZS_ERR_INVALID on
+ * it, as zs_lionset_run does on their sets. */
+int zs_lionset_create(const zs_adam_seg* segs, int64_t n, int g_dtype, int p_dtype,
+                      int state_dtype, zs_adamset** out);
+/* One Lion step over the set, per element (fp32, only the written fma fused):
+ *   g = (sum [+ carry_mul * carry]) / grad_div;  [carry = g];  [g *= *coef];  [g = -g]
+ *   p = p * decay_mul;  c = fma(1 - beta1, g, m * beta1);  u = (c > 0) - (c < 0)
+ *   p = fma(-lr, u, p);  m = fma(1 - beta2, g, m * beta2)
+ * u is torch.sign's value: +-0 gives +0, and so does a NaN.  A segment without a gradient reads
+ * g = 0 and runs like any other.  m as stored is widened before the rule (exact) and narrowed
+ * after it; the stochastic store of element e takes r16 = zs_sr_bits(e, key0, key1) & 0xFFFF, the
+ * draw zs_adamset_run_sr gives exp_avg, e = (the element's address in m - m_base) / 2, and the
+ * keys are the caller's zs_sr_keys(seed, t), t the parameter's step count after the step.  m_base,
+ * key0 and key1 are read only after zs_adamset_set_state_rounding(as, 1).
+ * coef: NULL = unclipped, else the device scalar of zs_clip_coef as in zs_adamset_run_clipped;
+ * guard != 0 as zs_adamset_run_guarded: a NaN coefficient ends every workgroup after the uniform
+ * load, nothing is read or written.  ZS_ERR_INVALID, nothing launched: a NULL set or hparams; a
+ * set not made by zs_lionset_create; guard without coef; coef on a set with the ZeRO-1 carry; a
+ * negative lr, a beta outside [0, 1] or grad_div <= 0 in a struct filled by hand; with stochastic
+ * rounding, a segment whose m lies below m_base or at an odd byte distance from it. */
+int zs_lionset_run(const zs_adamset* as, const zs_lion_hparams* hp, const float* coef, int guard,
+                   uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream);
+
 /* Single-range form, SURVEY.md §8(b)'s signature: one torch.optim.Adam/AdamW step over n
  * contiguous elements — the update of one flat shard (zero1.py:88 on a flattened group) with no
  * table to build.  p: fp32 master/param, updated in place; p_bf16: optional bf16 copy of the
