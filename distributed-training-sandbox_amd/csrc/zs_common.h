@@ -34,6 +34,12 @@ inline int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+// First word of every kernel-set handle: zs_adamset (Adam, SGD, Lion; zs_kernels.hip) and
+// zs_adafactorset (zs_adafactor.hip) are both reached through opaque pointers, and each family's
+// run entry points refuse the other's sets by this word.
+constexpr unsigned kAdamSetTag = 0x5a41444du;       // "ZADM"
+constexpr unsigned kAdafactorSetTag = 0x5a414446u;  // "ZADF"
+
 }  // namespace zs
 
 #define ZS_REQUIRE(cond, ...)                           \

@@ -2167,6 +2167,7 @@ static int copy_unroll() {
 }
 
 struct zs_adamset {
+  unsigned tag = zs::kAdamSetTag;  // (zs_common.h: an Adafactor set carries another)
   // vector table (aligned, n % 4 == 0) and scalar table (tails, unaligned segments)
   AdamSeg* d_vec = nullptr;
   int64_t* d_vec_prefix = nullptr;
@@ -3145,6 +3146,8 @@ int zs_sgd_hparams_init(double lr, double momentum, double dampening, double wei
 int zs_sgdset_run(const zs_adamset* as, const zs_sgd_hparams* h, const float* coef,
                   uintptr_t stream) {
   ZS_REQUIRE(as && h, "zs_sgdset_run: NULL argument");
+  ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create (use "
+             "zs_adafactorset_run)", "zs_sgdset_run");
   ZS_REQUIRE(!as->lion, "zs_sgdset_run: the set was made by zs_lionset_create (use zs_lionset_run)");
   ZS_REQUIRE(as->sgd, "zs_sgdset_run: the set was made by zs_adamset_create (use zs_adamset_run)");
   // a struct filled by hand gets zs_sgd_hparams_init's rules too (-0.0f is lr = 0)
@@ -3203,6 +3206,8 @@ int zs_lionset_run(const zs_adamset* as, const zs_lion_hparams* h, const float* 
                    uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream) {
   const char* fn = "zs_lionset_run";
   ZS_REQUIRE(as && h, "%s: NULL argument", fn);
+  ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create (use "
+             "zs_adafactorset_run)", fn);
   ZS_REQUIRE(as->lion, "%s: the set was not made by zs_lionset_create", fn);
   ZS_REQUIRE(!guard || coef, "%s: the guard tests the clip coefficient, which is NULL", fn);
   // a struct filled by hand gets zs_lion_hparams_init's rules too (-0.0f is lr = 0)
@@ -3247,6 +3252,8 @@ struct SrArgs {
 static int adam_run(const char* fn, const zs_adamset* as, const zs_adam_hparams* h, bool need_coef,
                     const float* coef, const SrArgs* sr, uintptr_t stream, bool guard = false) {
   ZS_REQUIRE(as && h && (coef || !need_coef), "%s: NULL argument", fn);
+  ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create (use "
+             "zs_adafactorset_run)", fn);
   ZS_REQUIRE(!as->lion, "%s: the set was made by zs_lionset_create (use zs_lionset_run)", fn);
   ZS_REQUIRE(!guard || !as->sgd, "%s: the guarded update is Adam's (the set was made by "
              "zs_sgdset_create)", fn);
@@ -3309,6 +3316,8 @@ int zs_adamset_run_psr(const zs_adamset* as, const zs_adam_hparams* h, const flo
                        uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream) {
   const char* fn = "zs_adamset_run_psr";
   ZS_REQUIRE(as && h, "%s: NULL argument", fn);
+  ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create (use "
+             "zs_adafactorset_run)", fn);
   ZS_REQUIRE(as->p_dtype == ZS_BF16_SR && !as->sgd && !as->lion,
              "%s: the set was not made with p_dtype ZS_BF16_SR (zs_adamset_create_ex)", fn);
   ZS_REQUIRE(!guard || coef, "%s: the guard tests the clip coefficient, which is NULL", fn);
@@ -3337,6 +3346,8 @@ int zs_adamset_run_ema(const zs_adamset* as, const zs_adam_hparams* h, const flo
                        float ema_weight, uintptr_t stream) {
   const char* fn = "zs_adamset_run_ema";
   ZS_REQUIRE(as && h, "%s: NULL argument", fn);
+  ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create (use "
+             "zs_adafactorset_run)", fn);
   ZS_REQUIRE(!as->sgd, "%s: the EMA rides on Adam's update (the set was made by zs_sgdset_create)",
              fn);
   ZS_REQUIRE(!as->lion, "%s: the EMA rides on Adam's update (the set was made by "
@@ -3368,6 +3379,8 @@ int zs_adamset_run_stats(const zs_adamset* as, const zs_adam_hparams* h, const f
                          int guard, double* partials, uintptr_t stream) {
   const char* fn = "zs_adamset_run_stats";
   ZS_REQUIRE(as && h, "%s: NULL argument", fn);
+  ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create (use "
+             "zs_adafactorset_run)", fn);
   ZS_REQUIRE(!as->sgd, "%s: the norms ride on Adam's update (the set was made by zs_sgdset_create)",
              fn);
   ZS_REQUIRE(!as->lion, "%s: the norms ride on Adam's update (the set was made by "

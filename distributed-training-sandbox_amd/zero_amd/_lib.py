@@ -46,6 +46,8 @@ EXPORTED = (
     "zs_adamset_update_norm_slots", "zs_adamset_run_stats", "zs_update_norms",
     "zs_sgd_hparams_init", "zs_sgdset_create", "zs_sgdset_run",
     "zs_lion_hparams_init", "zs_lionset_create", "zs_lionset_run",
+    "zs_adafactor_hparams_init", "zs_adafactorset_create", "zs_adafactorset_run",
+    "zs_adafactorset_run_pass", "zs_adafactorset_stats", "zs_adafactorset_destroy",
     "zs_comm_unique_id", "zs_comm_init", "zs_comm_destroy", "zs_reduce_scatter", "zs_all_gather",
     "zs_all_reduce", "zs_reduce", "zs_broadcast", "zs_reduce_group", "zs_broadcast_group", "zs_all_gather_group", "zs_reduce_scatter_group",
     "zs_all_gather_group_ordered", "zs_reduce_scatter_group_ordered", "zs_stream_wait_event",
@@ -94,6 +96,20 @@ class LionHParams(ctypes.Structure):
                 ("one_minus_beta2", ctypes.c_float), ("decay_mul", ctypes.c_float),
                 ("grad_div", ctypes.c_float), ("carry_mul", ctypes.c_float),
                 ("maximize", ctypes.c_int32)]
+
+
+class AdafactorSeg(ctypes.Structure):
+    _fields_ = [("g", ctypes.c_uint64), ("master", ctypes.c_uint64),
+                ("master_out", ctypes.c_uint64), ("p_out", ctypes.c_uint64),
+                ("row_var", ctypes.c_uint64), ("col_var", ctypes.c_uint64),
+                ("R", ctypes.c_int64), ("C", ctypes.c_int64), ("param", ctypes.c_int64)]
+
+
+class AdafactorHParams(ctypes.Structure):
+    _fields_ = [("lr", ctypes.c_double), ("beta2_decay", ctypes.c_double),
+                ("eps1", ctypes.c_double), ("eps2", ctypes.c_double), ("d", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("grad_div", ctypes.c_double),
+                ("maximize", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 _P = ctypes.c_void_p
@@ -193,6 +209,16 @@ _SIGS = {
                            ctypes.POINTER(_P)], ctypes.c_int),
     "zs_lionset_run": ([_P, ctypes.POINTER(LionHParams), _P, ctypes.c_int, ctypes.c_uint64,
                         ctypes.c_uint32, ctypes.c_uint32, _U], ctypes.c_int),
+    "zs_adafactor_hparams_init": ([ctypes.c_double] * 2 + [ctypes.c_int] + [ctypes.c_double] * 4 +
+                                  [ctypes.c_int, ctypes.c_double, ctypes.POINTER(AdafactorHParams)],
+                                  ctypes.c_int),
+    "zs_adafactorset_create": ([ctypes.POINTER(AdafactorSeg), _I64, ctypes.c_int, ctypes.c_int,
+                                ctypes.POINTER(_P)], ctypes.c_int),
+    "zs_adafactorset_run": ([_P, ctypes.POINTER(AdafactorHParams), _I64, _U], ctypes.c_int),
+    "zs_adafactorset_run_pass": ([_P, ctypes.POINTER(AdafactorHParams), _I64, ctypes.c_int, _U],
+                                 ctypes.c_int),
+    "zs_adafactorset_stats": ([_P, _PI64, _PI64, _PI64, _PI64], ctypes.c_int),
+    "zs_adafactorset_destroy": ([_P], ctypes.c_int),
     "zs_adam_step": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_float] * 5 +
                      [ctypes.c_int, _I64, ctypes.c_float, _P, ctypes.c_float, _U], ctypes.c_int),
     "zs_adam_step_ex": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_double] * 5 +

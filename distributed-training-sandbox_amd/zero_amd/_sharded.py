@@ -21,7 +21,7 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import (check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
+from ._update import (check_adafactor, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
                       check_max_grad_norm, check_param_grad_norms, check_update_norms,
                       check_update_norms_group,
                       check_skip_nonfinite, check_master_free, check_master_free_group,
@@ -67,16 +67,31 @@ def lion_group_hparams(group: dict) -> dict:
                 maximize=bool(group.get("maximize", False)), amsgrad=False)
 
 
+def adafactor_group_hparams(group: dict) -> dict:
+    """Hyper-parameters of one torch.optim.Adafactor param group (``lr``: a float, or the
+    one-element tensor torch allows); ``foreach`` only picks torch's implementation."""
+    lr = group["lr"]
+    lr = float(lr.item()) if torch.is_tensor(lr) else float(lr)
+    eps1, eps2 = group["eps"]
+    return dict(lr=lr, beta2_decay=float(group["beta2_decay"]),
+                eps=(None if eps1 is None else float(eps1), float(eps2)), d=float(group["d"]),
+                weight_decay=float(group.get("weight_decay", 0.0)),
+                maximize=bool(group.get("maximize", False)), amsgrad=False)
+
+
 def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
-    """One param group's hyper-parameters for the ``kind`` ("adam" / "sgd" / "lion") update."""
+    """One param group's hyper-parameters for the ``kind`` ("adam" / "sgd" / "lion" / "adafactor")
+    update."""
     if kind == "lion":
         return lion_group_hparams(group)
+    if kind == "adafactor":
+        return adafactor_group_hparams(group)
     return sgd_group_hparams(group) if kind == "sgd" else adam_group_hparams(group, optimizer)
 
 
 def optimizer_kind(optimizer: Optimizer) -> str:
-    """"adam" (torch.optim.Adam / AdamW), "sgd" (torch.optim.SGD) or "lion"
-    (zero_amd.optim.Lion); TypeError for anything else."""
+    """"adam" (torch.optim.Adam / AdamW), "sgd" (torch.optim.SGD), "lion" (zero_amd.optim.Lion) or
+    "adafactor" (torch.optim.Adafactor); TypeError for anything else."""
     from .optim import Lion
 
     if isinstance(optimizer, torch.optim.Adam):
@@ -85,7 +100,9 @@ def optimizer_kind(optimizer: Optimizer) -> str:
         return "sgd"
     if isinstance(optimizer, Lion):
         return "lion"
-    raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD or "
+    if isinstance(optimizer, torch.optim.Adafactor):
+        return "adafactor"
+    raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD / Adafactor or "
                     f"zero_amd.optim.Lion (got {type(optimizer).__name__})")
 
 
@@ -133,6 +150,13 @@ class ShardedOptimizerBase:
             self._clip_unsupported = f"layout={layout!r} (it runs on the bucket arena)"
         self._check_clip()
         self._kind = optimizer_kind(optimizer)
+        if self._kind == "adafactor":  # (refused here, on every rank, before anything collective)
+            check_adafactor(carry=self._carry and get("ws") > 1, layout=layout, arena=arena,
+                            overlap=overlap, grad_comm=grad_comm, max_grad_norm=max_grad_norm,
+                            skip_nonfinite=skip_nonfinite, param_grad_norms=param_grad_norms,
+                            state_dtype=state_dtype, state_rounding=state_rounding, master=master,
+                            ema_decay=ema_decay, param_update_norms=param_update_norms)
+            arena = "flat"  # arena='auto' would time the bucket arena as a candidate
         # skip_nonfinite (with max_grad_norm; Adam): a step whose gradient norm is not finite is
         # skipped on the device — nothing in device memory changes, the host proceeds as for any
         # step; refused here, on every rank and before anything collective
@@ -474,7 +498,8 @@ class ShardedOptimizerBase:
         self._expose_state()
 
     def _expose_state(self):
-        """optimizer.state[p] = {'step', 'exp_avg', 'exp_avg_sq'} as views of the flat shard."""
+        """optimizer.state[p] = {'step', 'exp_avg', 'exp_avg_sq'} as views of the flat shard
+        (Adafactor: 'row_var' and 'col_var', or 'variance', in torch's shapes)."""
         eng = self.engine
         if self._kind == "sgd":
             self._update_step_state()

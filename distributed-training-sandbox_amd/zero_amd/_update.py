@@ -49,9 +49,53 @@ def check_params(params):
 BF16_STATE_MIN_ONE_MINUS_BETA = 2.0 ** -8
 
 
-KINDS = ("adam", "sgd", "lion")
+KINDS = ("adam", "sgd", "lion", "adafactor")
 # what the messages call the optimizer of a kind that an option does not support
-KIND_NAMES = {"sgd": "torch.optim.SGD", "lion": "zero_amd.optim.Lion"}
+KIND_NAMES = {"sgd": "torch.optim.SGD", "lion": "zero_amd.optim.Lion",
+              "adafactor": "torch.optim.Adafactor"}
+
+
+def check_adafactor(*, zero3: bool = False, carry: bool = False, layout: str = "reference",
+                    arena: str = "flat", overlap: bool = False, grad_comm=None, max_grad_norm=None,
+                    skip_nonfinite: bool = False, param_grad_norms: bool = False, state_dtype=None,
+                    state_rounding=None, master: str = "split", ema_decay=None,
+                    param_update_norms: bool = False) -> None:
+    """What torch.optim.Adafactor cannot be combined with, as ValueError.  The update needs whole
+    parameters on their owner (row and column sums, two norms), so it runs under ZeRO-2 on the flat
+    arena with the reference's ownership, and under ZeRO-1 at world size 1; it clips its own update
+    through ``d`` and keeps fp32 factors over an fp32 or split master."""
+    name = KIND_NAMES["adafactor"]
+
+    def no(what: str, why: str):
+        raise ValueError(f"zero_amd: {name} is not supported with {what} ({why})")
+
+    if zero3:
+        no("ZeRO-3", "the column sums and the two norms of a sharded parameter need a cross-rank "
+           "reduction")
+    if carry:
+        no("ZeRO-1 at world size > 1", "the gradient carry")
+    if layout != "reference":
+        no(f"layout={layout!r}", "a parameter may straddle two owners")
+    if arena == "buckets":
+        no("arena='buckets'", "the update runs on the flat arena")
+    if overlap:
+        no("overlap=True", "the update starts once every owned gradient is reduced")
+    if grad_comm is not None:
+        no(f"grad_comm={grad_comm!r}", "not covered yet")
+    for opt, val in (("skip_nonfinite", skip_nonfinite), ("param_grad_norms", param_grad_norms),
+                     ("max_grad_norm", max_grad_norm is not None)):
+        if val:
+            no(opt, "Adafactor clips its own update through d")
+    if state_dtype is not None and state_dtype != torch.float32:
+        no(f"state_dtype={state_dtype}", "the factors are fp32")
+    if state_rounding is not None:
+        no("state_rounding", "the factors are fp32")
+    if master == "none":
+        no("master='none'", "the update reads an fp32 or split master")
+    if ema_decay is not None:
+        no("ema_decay", "the EMA is fused into the Adam update")
+    if param_update_norms:
+        no("param_update_norms", "the norms are summed inside the fused Adam update")
 
 
 def check_state_dtype(state_dtype):
@@ -229,6 +273,8 @@ def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = 
             lay["lo"] = (pad(total), torch.int16)
             total = pad(total) + words
         return total, lay
+    if kind == "adafactor":  # the factored state is an arena of its own (flat.AdafactorState)
+        momentum = False
     names = ["m", "v"][:2 if kind == "adam" else 1 if kind == "lion" else int(bool(momentum))]
     names += ["carry"] * bool(carry) + ["master"] * bool(fp32_master)
     lay = {name: (k * L, torch.float32) for k, name in enumerate(names)}
@@ -250,7 +296,8 @@ class UpdateCore:
         from .engine import probed_zeros  # (engine.py builds on this module)
 
         if kind not in KINDS:
-            raise ValueError(f"UpdateCore: kind must be 'adam', 'sgd' or 'lion' (got {kind!r})")
+            raise ValueError("UpdateCore: kind must be 'adam', 'sgd', 'lion' or 'adafactor' "
+                             f"(got {kind!r})")
         # the update: torch.optim.Adam's, torch.optim.SGD's (`momentum`: some group has a
         # momentum, so the shard holds a momentum buffer; none of them: no optimizer state at all)
         # or zero_amd.optim.Lion's (one moment, exp_avg, always)
@@ -306,6 +353,8 @@ class UpdateCore:
             views = {} if self.m is None else {"momentum_buffer": cut(self.m)}
         elif self.kind == "lion":
             views = {"exp_avg": cut(self.m)}
+        elif self.kind == "adafactor":  # (the engine adds the factors: flat.AdafactorState)
+            views = {}
         else:
             views = {"exp_avg": cut(self.m), "exp_avg_sq": cut(self.v)}
         if self.master is not None:

@@ -51,7 +51,8 @@ from ._hooks import WeakCall
 from ._update import GradClip, UpdateNorms
 from .comm import StreamEvent
 from .engine import ALIGN_ELEMS, ShardEngine, _ptr
-from .kernels import check_extents, check_extents_enabled, copy_direct
+from .kernels import (AdafactorSet, adafactor_hparams, check_extents, check_extents_enabled,
+                      copy_direct)
 
 _I32P = np.int32
 LAND_BATCH_BYTES = 64 << 20  # fresh gradients landed per hook batch (ws > 1, no overlap)
@@ -79,6 +80,8 @@ class FlatEngine(ShardEngine):
     Either way rank r's stream is one contiguous region of P (Layout F: P is the aligned
     concatenation itself, rank r's slice at r·S), so the rounds, the Adam rows and the grouped
     reduce / broadcast are the same code."""
+
+    af = None  # (AdafactorState of an Adafactor engine)
 
     def __init__(self, params, group_of, ws: int, rank: int, *, carry=False, comm=None,
                  bucket_bytes: int = 256 << 20, master: str = "split", placement_tries: int = 8,
@@ -142,7 +145,7 @@ class FlatEngine(ShardEngine):
         # the arena view, or the fresh tensor backward left after a set-to-None zero_grad(), in
         # place (zero2.py:120 reads p.grad as backward left it): no landing copy, and G exists
         # only once a caller asks for grad views (zero_grad(set_to_none=False), ZeRO-1's views)
-        self.inplace = ws == 1 and self.grad_comm is None
+        self.inplace = ws == 1 and self.grad_comm is None and kind != "adafactor"
         self.G, self.grad_placement = None, None
         self._total = total
         if not self.inplace:
@@ -198,6 +201,10 @@ class FlatEngine(ShardEngine):
         self.land_pending, self.land_pending_bytes = [], 0
         self.land_marked = np.zeros(n, bool)
         self.inplace_reads = 0  # gradients the last step's Adam read in place (ws == 1)
+        # torch.optim.Adafactor: the factored second moment of the owned parameters, an arena of
+        # its own (the update reads every gradient from its arena slot: its tables keep their
+        # pointers from step to step)
+        self.af = AdafactorState(self) if kind == "adafactor" else None
 
     # ------------------------------------------------------------------------------------------
     def _ensure_G(self):
@@ -243,6 +250,30 @@ class FlatEngine(ShardEngine):
         else:  # fp32: P is the master, updated in place
             rows = self._adam_rows(idx, g, pslot, pslot, 0, so, ln)
         return _Round(j, send, recv, count, bcast, rows, idx)
+
+    def state_views(self, i: int, *, ckpt: bool = False):
+        views = super().state_views(i, ckpt=ckpt)
+        if self.af is not None and views is not None:
+            views = {**self.af.views(i), **views}
+        return views
+
+    def _adafactor_update(self, has, hparams_of, stream):
+        """The whole step's Adafactor update: one AdafactorSet per (param group, step count) over
+        the owned parameters that have a gradient, cached while its parameters stay the same."""
+        own = np.asarray(self.owned_param_indices(), np.int64)
+        own = own[has[own]]
+        if not len(own):
+            return
+        keys = np.stack([np.asarray(self.group_of)[own], self.steps[own]], axis=1)
+        for gi, t in np.unique(keys, axis=0):
+            idx = own[(keys == (gi, t)).all(axis=1)]
+            aset = self.cached(("adafactor", int(gi), int(idx[0]), len(idx)), idx.tobytes(),
+                               lambda: self.af.new_set(idx))
+            h = hparams_of(int(gi))
+            hp = adafactor_hparams(h["lr"], h["beta2_decay"], h["eps"], h["d"], h["weight_decay"],
+                                   maximize=h["maximize"], grad_div=float(self.ws))
+            aset.run(hp, int(t), stream)
+            self.last_adam_bytes += aset.bytes
 
     def own_window(self) -> torch.Tensor:
         """This rank's stream in P: the parameters its shard's state (and EMA) belongs to."""
@@ -762,7 +793,7 @@ class FlatEngine(ShardEngine):
         # fast path: every owned param has a grad and, per param group, one (step, carry) key
         own = self.owned
         hps = {}
-        if has[own].all():
+        if has[own].all() and self.af is None:
             gof = np.asarray(self.group_of)
             for gi in np.unique(gof[own]):
                 sel = own & (gof == gi)
@@ -805,6 +836,8 @@ class FlatEngine(ShardEngine):
                     self._clip_run(deferred, 0, len(deferred), stream)
                 elif stats:
                     self._stats_run(deferred, 0, len(deferred), stream)
+                elif self.af is not None:
+                    self._adafactor_update(has, hparams_of, stream)
                 else:
                     for rd in self.rounds:
                         self._adam_round(rd, has, cmul, hps, hparams_of, stream, gptr)
@@ -838,8 +871,14 @@ class FlatEngine(ShardEngine):
                     stream.wait_event(self.ev_red[rd.j])
                     self._clip_norm(deferred[:b], a, stream)
                 self._clip_coef(deferred, stream)
+            if self.af is not None:  # whole parameters: every round's reduction, then one update
+                for rd in self.rounds:
+                    stream.wait_event(self.ev_red[rd.j])
+                self._adafactor_update(has, hparams_of, stream)
             for k, rd in enumerate(self.rounds):
-                if clip:
+                if self.af is not None:
+                    pass
+                elif clip:
                     self._clip_run(deferred, ends[k - 1] if k else 0, ends[k], stream)
                 elif stats:
                     stream.wait_event(self.ev_red[rd.j])
@@ -911,6 +950,85 @@ class FlatEngine(ShardEngine):
         if self.ws == 1:
             return 0.0
         return max(0.0, self.ev_c0.elapsed_time(self.ev_c1) / 1e3)
+
+
+class AdafactorState:
+    """The factored second moment of a flat engine's owned parameters (Layout R: whole
+    parameters): per parameter ``row_var`` (B * R floats) and ``col_var`` (B * C), or ``variance``
+    (n) for a parameter of fewer than two dimensions, each array at a 16-byte multiple of one fp32
+    arena; and the AdafactorSet tables over them."""
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.off, total = {}, 0
+        for i in eng.owned_param_indices():
+            sizes = self.sizes(eng.params[i].shape)
+            offs = []
+            for n in sizes:
+                offs.append(total)
+                total += (n + 3) // 4 * 4
+            self.off[i] = tuple(offs)
+        self.state = torch.zeros(max(total, 4), dtype=torch.float32, device=eng.device)
+
+    @staticmethod
+    def sizes(shape) -> tuple:
+        """Elements of (row_var, col_var) of a parameter of ``shape``, or of (variance,)."""
+        shape = tuple(shape)
+        if len(shape) < 2:
+            return (int(np.prod(shape, dtype=np.int64)),)
+        batch = int(np.prod(shape[:-2], dtype=np.int64))
+        return (batch * shape[-2], batch * shape[-1])
+
+    def views(self, i: int) -> dict:
+        """Parameter i's factors as live views in torch's shapes: (..., R, 1) and (..., 1, C), or
+        the parameter's own shape."""
+        shape = tuple(self.eng.params[i].shape)
+        off, sizes = self.off[i], self.sizes(shape)
+        cut = [self.state[o:o + n] for o, n in zip(off, sizes)]
+        if len(shape) < 2:
+            return {"variance": cut[0].view(shape)}
+        return {"row_var": cut[0].view(shape[:-1] + (1,)),
+                "col_var": cut[1].view(shape[:-2] + (1, shape[-1]))}
+
+    def new_set(self, idx):
+        """The AdafactorSet of parameters ``idx``: one entry per batch matrix; the gradient from
+        the reduced stream R, the master from P (fp32), the fp32 master array or P + residual."""
+        eng = self.eng
+        pc = eng.pieces
+        so_of = {int(i): int(so) for i, so, n in zip(pc.param, pc.stream_off, pc.length) if n > 0}
+        sb = self.state.data_ptr()
+        rows = []
+        for i in idx:
+            i = int(i)
+            shape, so = tuple(eng.params[i].shape), so_of[i]
+            oned = len(shape) < 2
+            R, C = (1, int(eng.numel[i])) if oned else shape[-2:]
+            B = 1 if oned else int(np.prod(shape[:-2], dtype=np.int64))
+            for b in range(B if R * C else 0):
+                e = so + b * R * C  # the matrix's element offset in this rank's stream
+                g = eng.R.data_ptr() + e * eng.ces
+                pslot = eng.P.data_ptr() + (int(eng.base[eng.rank]) + e) * eng.es
+                if not eng.mixed:
+                    mst, mo, po = pslot, pslot, 0
+                elif eng.split:
+                    mst, mo, po = pslot, eng.lo.data_ptr() + e * 2, pslot
+                else:
+                    mst = mo = eng.master.data_ptr() + e * 4
+                    po = pslot
+                rv = sb + 4 * (self.off[i][0] + b * R)
+                cv = 0 if oned else sb + 4 * (self.off[i][1] + b * C)
+                rows.append([g, mst, mo, po, rv, cv, R, C, i])
+        rows = np.array(rows, np.uint64).reshape(-1, 9)
+        if check_extents_enabled():  # every entry inside its tensors (tests turn this on)
+            R, C = rows[:, 6].astype(np.int64), rows[:, 7].astype(np.int64)
+            msz = 2 if eng.split else 4
+            check_extents(rows[:, 0], R * C * eng.ces, [eng.R], "Adafactor gradient")
+            check_extents(rows[:, 1], R * C * msz, [eng.P, eng.master], "Adafactor master")
+            check_extents(rows[:, 2], R * C * msz, [eng.P, eng.master, eng.lo], "Adafactor master out")
+            check_extents(rows[:, 3], R * C * 2, [eng.P], "Adafactor bf16 parameter")
+            check_extents(rows[:, 4], np.where(rows[:, 5] == 0, C, R) * 4, [self.state], "row_var")
+            check_extents(rows[:, 5], C * 4, [self.state], "col_var")
+        return AdafactorSet(rows, eng.czdtype, eng.p_dtype)
 
 
 def _dense(g: torch.Tensor, p: torch.Tensor) -> bool:

@@ -10,6 +10,8 @@ finite; ``run_sr`` with ``sr_keys`` stores bf16 moments with stochastic rounding
 ``SgdSet``   — the same tables with torch.optim.SGD's update (momentum, Nesterov); ``sgd_hparams``.
 ``LionSet``  — the same tables with zero_amd.optim.Lion's update (one moment, fp32 or bf16);
 ``lion_hparams``.
+``AdafactorSet`` — torch.optim.Adafactor's update over a table of matrices (csrc/zs_adafactor.hip):
+factored second moment, three passes, every scalar on the device; ``adafactor_hparams``.
 ``adam_step`` — the same update over one contiguous range (zs_adam_step_ex; no table to keep).
 
 Both upload their segment table once; ``run(stream)`` only enqueues a kernel on ``stream``.
@@ -23,7 +25,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import AdamHParams, AdamSeg, LionHParams, SgdHParams
+from ._lib import AdafactorHParams, AdafactorSeg, AdamHParams, AdamSeg, LionHParams, SgdHParams
 
 _PU64 = ctypes.POINTER(ctypes.c_uint64)
 _PI64 = ctypes.POINTER(ctypes.c_int64)
@@ -441,6 +443,60 @@ class LionSet(AdamSet):
                                 "a Lion set runs through LionSet.run")
 
     run_sr = run_psr = run_ema = run_stats = _not_lion
+
+
+def adafactor_hparams(lr=1e-2, beta2_decay=-0.8, eps=(None, 1e-3), d=1.0, weight_decay=0.0, *,
+                      maximize=False, grad_div=1.0) -> AdafactorHParams:
+    """A torch.optim.Adafactor group's scalars (zs_adafactor_hparams_init); ``eps[0]`` None is
+    fp32's epsilon, whatever the parameter dtype: the arithmetic is fp32."""
+    hp = AdafactorHParams()
+    eps1, eps2 = eps
+    _lib.call("zs_adafactor_hparams_init", float(lr), float(beta2_decay), int(eps1 is not None),
+              0.0 if eps1 is None else float(eps1), float(eps2), float(d), float(weight_decay),
+              int(bool(maximize)), float(grad_div), ctypes.byref(hp))
+    return hp
+
+
+class AdafactorSet:
+    """Fused Adafactor over a table with one entry per (parameter, batch matrix); ``segs`` is an
+    (n, 9) int64/uint64 array in zs_adafactor_seg order: g, master, master_out, p_out, row_var,
+    col_var, R, C, param (col_var 0: a 1-D entry whose ``row_var`` is the variance).  ``run`` is
+    one step: three passes and their reduce kernels, nothing on the host."""
+
+    FIELDS = ("g", "master", "master_out", "p_out", "row_var", "col_var", "R", "C", "param")
+
+    def __init__(self, segs: np.ndarray, g_dtype: int, p_dtype: int = _lib.ZS_BF16):
+        segs = np.ascontiguousarray(np.asarray(segs, dtype=np.uint64).reshape(-1, 9))
+        arr = (AdafactorSeg * max(len(segs), 1))()
+        ctypes.memmove(arr, segs.ctypes.data, segs.nbytes)
+        h = ctypes.c_void_p()
+        _lib.call("zs_adafactorset_create", arr if len(segs) else None, len(segs), int(g_dtype),
+                  int(p_dtype), ctypes.byref(h))
+        self._h = h
+        self.nseg = len(segs)
+        e, b, s = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        pb = (ctypes.c_int64 * 3)()
+        _lib.call("zs_adafactorset_stats", h, ctypes.byref(e), ctypes.byref(b), pb, ctypes.byref(s))
+        self.elems, self.bytes, self.scratch_bytes = e.value, b.value, s.value
+        self.pass_bytes = tuple(pb)
+
+    def run(self, hp: AdafactorHParams, step: int, stream) -> None:
+        """One step; ``step`` is the entries' step count after it (zs_adafactorset_run)."""
+        _lib.call("zs_adafactorset_run", self._h, ctypes.byref(hp), int(step), stream_handle(stream))
+
+    def run_pass(self, hp: AdafactorHParams, step: int, which: int, stream) -> None:
+        """Pass ``which`` (0: statistics, 1: update norm, 2: apply) alone, for measurement."""
+        _lib.call("zs_adafactorset_run_pass", self._h, ctypes.byref(hp), int(step), int(which),
+                  stream_handle(stream))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib is not None:
+            try:
+                _lib.lib.zs_adafactorset_destroy(h)
+            except Exception:  # interpreter teardown
+                pass
+            self._h = None
 
 
 def sqnorm_reduce(partials, n: int, sumsq, stream) -> None:

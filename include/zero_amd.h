@@ -640,6 +640,78 @@ int zs_lionset_create(const zs_adam_seg* segs, int64_t n, int g_dtype, int p_dty
 int zs_lionset_run(const zs_adamset* as, const zs_lion_hparams* hp, const float* coef, int guard,
                    uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Fused Adafactor (Shazeer & Stern 2018, arXiv:1804.04235; torch.optim.Adafactor's rule),      */
+/* additive in ABI v13.  The second moment of an R x C matrix is a row vector and a column      */
+/* vector (R + C floats), of a 1-D parameter one float per element.  A step is three passes     */
+/* over the set (statistics, update norm, apply) with small reduce kernels between them; every  */
+/* scalar stays on the device, nothing is atomic and the bits repeat from run to run.  With     */
+/* bf16 gradients over the split master the passes move 6, 2 and 10 B/element.                  */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint64_t g;          /* reduced gradient sum, R * C elements of g_dtype (required) */
+  uint64_t master;     /* as zs_adam_seg: the fp32 master, or (ZS_BF16_SPLIT) the bf16 param read */
+  uint64_t master_out; /* the fp32 master again (updated in place), or (ZS_BF16_SPLIT) the int16
+                          residual, read and rewritten */
+  uint64_t p_out;      /* optional bf16 copy of the updated param; (ZS_BF16_SPLIT) the bf16 param
+                          written, required */
+  uint64_t row_var;    /* fp32, R elements, updated in place; a 1-D entry: variance, C elements */
+  uint64_t col_var;    /* fp32, C elements, updated in place; 0 marks a 1-D entry (R must be 1) */
+  int64_t R, C;        /* rows and columns: row i starts at element i * C */
+  int64_t param;       /* the caller's index of the entry's parameter: the entries of one parameter
+                          (the matrices of a batch) are adjacent, and sum p^2 / sum u^2 run over all
+                          of them */
+} zs_adafactor_seg;
+
+typedef struct {
+  /* the group's scalars as doubles; a run rounds what it derives from them to f32 once */
+  double lr;
+  double beta2_decay;
+  double eps1;         /* resolved: eps=(None, .) is fp32's epsilon, 2^-23 */
+  double eps2;
+  double d;
+  double weight_decay;
+  double grad_div;     /* divide the reduced sum by this (world size) */
+  int32_t maximize;
+  int32_t reserved;
+} zs_adafactor_hparams;
+
+/* Fill hp from a torch.optim.Adafactor param group.  has_eps1 == 0: eps1 is fp32's epsilon (the
+ * arithmetic is fp32 whatever the parameter dtype).  ZS_ERR_INVALID unless lr > 0, beta2_decay <= 0,
+ * eps1 >= 0 when given, eps2 > 0, d >= 1, weight_decay >= 0, grad_div > 0 and hp is not NULL. */
+int zs_adafactor_hparams_init(double lr, double beta2_decay, int has_eps1, double eps1, double eps2,
+                              double d, double weight_decay, int maximize, double grad_div,
+                              zs_adafactor_hparams* hp);
+typedef struct zs_adafactorset zs_adafactorset;
+/* g_dtype ZS_F32 or ZS_BF16; p_dtype ZS_BF16 (fp32 master in place, optional bf16 p_out) or
+ * ZS_BF16_SPLIT.  A matrix entry with R > 1, C a multiple of the 16-byte gradient vector (8 bf16,
+ * 4 fp32) and aligned pointers takes 16-byte accesses; any other entry the element-wise path with
+ * the same arithmetic and reduction order.  The set owns its scratch (per-tile partial sums, row
+ * factors, per-parameter scalars).  Every check comes before any allocation or upload. */
+int zs_adafactorset_create(const zs_adafactor_seg* segs, int64_t n, int g_dtype, int p_dtype,
+                           zs_adafactorset** out);
+/* One Adafactor step over the set, step = the entries' step count after it (>= 1), per parameter
+ * p with averaged gradient g (fp32; only the written fma fused; sqrt and / correctly rounded):
+ *   w = step^beta2_decay;  rho = min(lr, 1/sqrt(step));  alpha = max(eps2, ||p|| / sqrt(numel)) * rho
+ *   row_var = lerp(row_var, mean_j g^2, w);  col_var = lerp(col_var, mean_i g^2, w)
+ *   v = (row_var[i] / max(mean_i row_var, eps1)) * col_var[j]      (1-D: v = variance = lerp(., g^2, w))
+ *   u = g * (1 / sqrt(max(v, eps1^2)));  denom = max(1, ||u|| / (sqrt(numel) * d))
+ *   p = fma(-alpha / denom, u, p * (1 - lr * weight_decay))
+ * Sums run in fp32 inside a lane (at most 16 terms) and in double above; the order depends on the
+ * parameter's shape alone.  ZS_ERR_INVALID, nothing launched: a NULL argument, a set of another
+ * family, step < 1, hyper-parameters zs_adafactor_hparams_init would refuse. */
+int zs_adafactorset_run(const zs_adafactorset* as, const zs_adafactor_hparams* hp, int64_t step,
+                        uintptr_t stream);
+/* One pass of zs_adafactorset_run with the small kernels behind it (0: statistics, factors, alpha;
+ * 1: update norm, step size; 2: apply), for measurement; 0, 1, 2 in order are one run. */
+int zs_adafactorset_run_pass(const zs_adafactorset* as, const zs_adafactor_hparams* hp,
+                             int64_t step, int pass, uintptr_t stream);
+/* Elements covered, algorithmic HBM bytes of one run, and (optional, may be NULL) the bytes of
+ * each of the three passes and of the set's scratch allocation. */
+int zs_adafactorset_stats(const zs_adafactorset* as, int64_t* elems, int64_t* bytes,
+                          int64_t* pass_bytes, int64_t* scratch_bytes);
+int zs_adafactorset_destroy(zs_adafactorset* as);
+
 /* Single-range form, SURVEY.md §8(b)'s signature: one torch.optim.Adam/AdamW step over n
  * contiguous elements — the update of one flat shard (zero1.py:88 on a flattened group) with no
  * table to build.  p: fp32 master/param, updated in place; p_bf16: optional bf16 copy of the
