@@ -39,6 +39,7 @@ inline int fail(int code, const char* fmt, ...) {
 // run entry points refuse the other's sets by this word.
 constexpr unsigned kAdamSetTag = 0x5a41444du;       // "ZADM"
 constexpr unsigned kAdafactorSetTag = 0x5a414446u;  // "ZADF"
+constexpr unsigned kMuonSetTag = 0x5a4d554fu;       // "ZMUO" (zs_muonset, zs_muon.hip)
 
 }  // namespace zs
 

@@ -48,6 +48,8 @@ EXPORTED = (
     "zs_lion_hparams_init", "zs_lionset_create", "zs_lionset_run",
     "zs_adafactor_hparams_init", "zs_adafactorset_create", "zs_adafactorset_run",
     "zs_adafactorset_run_pass", "zs_adafactorset_stats", "zs_adafactorset_destroy",
+    "zs_muon_hparams_init", "zs_muonset_create", "zs_muonset_run", "zs_muonset_run_pass",
+    "zs_muonset_stats", "zs_muonset_batch", "zs_muonset_destroy", "zs_muon_gemm_nt",
     "zs_comm_unique_id", "zs_comm_init", "zs_comm_destroy", "zs_reduce_scatter", "zs_all_gather",
     "zs_all_reduce", "zs_reduce", "zs_broadcast", "zs_reduce_group", "zs_broadcast_group", "zs_all_gather_group", "zs_reduce_scatter_group",
     "zs_all_gather_group_ordered", "zs_reduce_scatter_group_ordered", "zs_stream_wait_event",
@@ -110,6 +112,22 @@ class AdafactorHParams(ctypes.Structure):
                 ("eps1", ctypes.c_double), ("eps2", ctypes.c_double), ("d", ctypes.c_double),
                 ("weight_decay", ctypes.c_double), ("grad_div", ctypes.c_double),
                 ("maximize", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class MuonSeg(ctypes.Structure):
+    _fields_ = [("g", ctypes.c_uint64), ("master", ctypes.c_uint64),
+                ("master_out", ctypes.c_uint64), ("p_out", ctypes.c_uint64),
+                ("buf", ctypes.c_uint64), ("R", ctypes.c_int64), ("C", ctypes.c_int64),
+                ("param", ctypes.c_int64)]
+
+
+class MuonHParams(ctypes.Structure):
+    _fields_ = [("lr", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("momentum", ctypes.c_double), ("ns_a", ctypes.c_double),
+                ("ns_b", ctypes.c_double), ("ns_c", ctypes.c_double), ("eps", ctypes.c_double),
+                ("grad_div", ctypes.c_double), ("nesterov", ctypes.c_int32),
+                ("ns_steps", ctypes.c_int32), ("adjust_lr", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 _P = ctypes.c_void_p
@@ -219,6 +237,19 @@ _SIGS = {
                                  ctypes.c_int),
     "zs_adafactorset_stats": ([_P, _PI64, _PI64, _PI64, _PI64], ctypes.c_int),
     "zs_adafactorset_destroy": ([_P], ctypes.c_int),
+    "zs_muon_hparams_init": ([ctypes.c_double] * 3 + [ctypes.c_int] + [ctypes.c_double] * 4 +
+                             [ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                              ctypes.POINTER(MuonHParams)], ctypes.c_int),
+    "zs_muonset_create": ([ctypes.POINTER(MuonSeg), _I64, ctypes.c_int, ctypes.c_int, _I64,
+                           ctypes.POINTER(_P)], ctypes.c_int),
+    "zs_muonset_run": ([_P, ctypes.POINTER(MuonHParams), _U], ctypes.c_int),
+    "zs_muonset_run_pass": ([_P, ctypes.POINTER(MuonHParams), ctypes.c_int, ctypes.c_int, _I64, _U],
+                            ctypes.c_int),
+    "zs_muonset_stats": ([_P, _PI64, ctypes.c_int], ctypes.c_int),
+    "zs_muonset_batch": ([_P, _I64, _PI64], ctypes.c_int),
+    "zs_muonset_destroy": ([_P], ctypes.c_int),
+    "zs_muon_gemm_nt": ([ctypes.c_uint64, _I64] * 5 + [_I64] * 3 + [ctypes.c_double] * 2 +
+                        [ctypes.c_int, _U], ctypes.c_int),
     "zs_adam_step": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_float] * 5 +
                      [ctypes.c_int, _I64, ctypes.c_float, _P, ctypes.c_float, _U], ctypes.c_int),
     "zs_adam_step_ex": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_double] * 5 +

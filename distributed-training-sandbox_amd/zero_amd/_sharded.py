@@ -21,7 +21,7 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import (check_adafactor, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
+from ._update import (check_adafactor, check_muon, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
                       check_max_grad_norm, check_param_grad_norms, check_update_norms,
                       check_update_norms_group,
                       check_skip_nonfinite, check_master_free, check_master_free_group,
@@ -79,9 +79,23 @@ def adafactor_group_hparams(group: dict) -> dict:
                 maximize=bool(group.get("maximize", False)), amsgrad=False)
 
 
+def muon_group_hparams(group: dict) -> dict:
+    """Hyper-parameters of one torch.optim.Muon param group (``lr``: a float, or the one-element
+    tensor torch allows)."""
+    lr = group["lr"]
+    lr = float(lr.item()) if torch.is_tensor(lr) else float(lr)
+    return dict(lr=lr, weight_decay=float(group["weight_decay"]), momentum=float(group["momentum"]),
+                nesterov=bool(group["nesterov"]),
+                ns_coefficients=tuple(float(x) for x in group["ns_coefficients"]),
+                eps=float(group["eps"]), ns_steps=int(group["ns_steps"]),
+                adjust_lr_fn=group["adjust_lr_fn"], maximize=False, amsgrad=False)
+
+
 def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
-    """One param group's hyper-parameters for the ``kind`` ("adam" / "sgd" / "lion" / "adafactor")
-    update."""
+    """One param group's hyper-parameters for the ``kind`` ("adam" / "sgd" / "lion" / "adafactor" /
+    "muon") update."""
+    if kind == "muon":
+        return muon_group_hparams(group)
     if kind == "lion":
         return lion_group_hparams(group)
     if kind == "adafactor":
@@ -90,8 +104,8 @@ def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
 
 
 def optimizer_kind(optimizer: Optimizer) -> str:
-    """"adam" (torch.optim.Adam / AdamW), "sgd" (torch.optim.SGD), "lion" (zero_amd.optim.Lion) or
-    "adafactor" (torch.optim.Adafactor); TypeError for anything else."""
+    """"adam" (torch.optim.Adam / AdamW), "sgd" (torch.optim.SGD), "lion" (zero_amd.optim.Lion),
+    "adafactor" (torch.optim.Adafactor) or "muon" (torch.optim.Muon); TypeError for anything else."""
     from .optim import Lion
 
     if isinstance(optimizer, torch.optim.Adam):
@@ -102,7 +116,9 @@ def optimizer_kind(optimizer: Optimizer) -> str:
         return "lion"
     if isinstance(optimizer, torch.optim.Adafactor):
         return "adafactor"
-    raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD / Adafactor or "
+    if isinstance(optimizer, torch.optim.Muon):
+        return "muon"
+    raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD / Adafactor / Muon or "
                     f"zero_amd.optim.Lion (got {type(optimizer).__name__})")
 
 
@@ -157,6 +173,13 @@ class ShardedOptimizerBase:
                             state_dtype=state_dtype, state_rounding=state_rounding, master=master,
                             ema_decay=ema_decay, param_update_norms=param_update_norms)
             arena = "flat"  # arena='auto' would time the bucket arena as a candidate
+        if self._kind == "muon":  # (likewise)
+            check_muon(carry=self._carry and get("ws") > 1, layout=layout, arena=arena,
+                       overlap=overlap, grad_comm=grad_comm, max_grad_norm=max_grad_norm,
+                       skip_nonfinite=skip_nonfinite, param_grad_norms=param_grad_norms,
+                       state_dtype=state_dtype, state_rounding=state_rounding, master=master,
+                       ema_decay=ema_decay, param_update_norms=param_update_norms)
+            arena = "flat"
         # skip_nonfinite (with max_grad_norm; Adam): a step whose gradient norm is not finite is
         # skipped on the device — nothing in device memory changes, the host proceeds as for any
         # step; refused here, on every rank and before anything collective
@@ -517,6 +540,8 @@ class ShardedOptimizerBase:
         if self._kind == "sgd":
             eng.expose_sgd(self.optimizer, self.params, self._groups, eng.owned_param_indices(),
                            eng.state_views)
+            return
+        if self._kind == "muon":  # torch's Muon keeps no step
             return
         for i in eng.owned_param_indices():
             s = int(eng.steps[i])

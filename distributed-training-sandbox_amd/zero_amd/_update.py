@@ -49,10 +49,10 @@ def check_params(params):
 BF16_STATE_MIN_ONE_MINUS_BETA = 2.0 ** -8
 
 
-KINDS = ("adam", "sgd", "lion", "adafactor")
+KINDS = ("adam", "sgd", "lion", "adafactor", "muon")
 # what the messages call the optimizer of a kind that an option does not support
 KIND_NAMES = {"sgd": "torch.optim.SGD", "lion": "zero_amd.optim.Lion",
-              "adafactor": "torch.optim.Adafactor"}
+              "adafactor": "torch.optim.Adafactor", "muon": "torch.optim.Muon"}
 
 
 def check_adafactor(*, zero3: bool = False, carry: bool = False, layout: str = "reference",
@@ -90,6 +90,51 @@ def check_adafactor(*, zero3: bool = False, carry: bool = False, layout: str = "
         no(f"state_dtype={state_dtype}", "the factors are fp32")
     if state_rounding is not None:
         no("state_rounding", "the factors are fp32")
+    if master == "none":
+        no("master='none'", "the update reads an fp32 or split master")
+    if ema_decay is not None:
+        no("ema_decay", "the EMA is fused into the Adam update")
+    if param_update_norms:
+        no("param_update_norms", "the norms are summed inside the fused Adam update")
+
+
+def check_muon(*, zero3: bool = False, carry: bool = False, layout: str = "reference",
+               arena: str = "flat", overlap: bool = False, grad_comm=None, max_grad_norm=None,
+               skip_nonfinite: bool = False, param_grad_norms: bool = False, state_dtype=None,
+               state_rounding=None, master: str = "split", ema_decay=None,
+               param_update_norms: bool = False, grad_accumulation: bool = False) -> None:
+    """What torch.optim.Muon cannot be combined with, as ValueError.  The Newton-Schulz iteration
+    needs a whole matrix on its owner, so the update runs under ZeRO-2 on the flat arena with the
+    reference's ownership, and under ZeRO-1 at world size 1, after all of the step's reductions,
+    with an fp32 momentum buffer over an fp32 or split master."""
+    name = KIND_NAMES["muon"]
+
+    def no(what: str, why: str):
+        raise ValueError(f"zero_amd: {name} is not supported with {what} ({why})")
+
+    if grad_accumulation:
+        no("grad_accumulation", "it is ZeRO-3's")
+    if zero3:
+        no("ZeRO-3", "a sharded matrix's momentum would have to be all-gathered for the "
+           "Newton-Schulz products")
+    if carry:
+        no("ZeRO-1 at world size > 1", "the gradient carry")
+    if layout != "reference":
+        no(f"layout={layout!r}", "a matrix may be cut across two owners")
+    if arena == "buckets":
+        no("arena='buckets'", "the update runs on the flat arena")
+    if overlap:
+        no("overlap=True", "the update starts once every owned gradient is reduced")
+    if grad_comm is not None:
+        no(f"grad_comm={grad_comm!r}", "not covered yet")
+    for opt, val in (("skip_nonfinite", skip_nonfinite), ("param_grad_norms", param_grad_norms),
+                     ("max_grad_norm", max_grad_norm is not None)):
+        if val:
+            no(opt, "Muon normalises its own update; the norm pass is the element-wise updates'")
+    if state_dtype is not None and state_dtype != torch.float32:
+        no(f"state_dtype={state_dtype}", "the momentum buffer is fp32")
+    if state_rounding is not None:
+        no("state_rounding", "the momentum buffer is fp32")
     if master == "none":
         no("master='none'", "the update reads an fp32 or split master")
     if ema_decay is not None:
@@ -275,7 +320,9 @@ def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = 
         return total, lay
     if kind == "adafactor":  # the factored state is an arena of its own (flat.AdafactorState)
         momentum = False
-    names = ["m", "v"][:2 if kind == "adam" else 1 if kind == "lion" else int(bool(momentum))]
+    # (Muon: ``m`` alone, always: the momentum buffer)
+    names = ["m", "v"][:2 if kind == "adam" else 1 if kind in ("lion", "muon")
+                       else int(bool(momentum))]
     names += ["carry"] * bool(carry) + ["master"] * bool(fp32_master)
     lay = {name: (k * L, torch.float32) for k, name in enumerate(names)}
     total = len(names) * L
@@ -296,8 +343,8 @@ class UpdateCore:
         from .engine import probed_zeros  # (engine.py builds on this module)
 
         if kind not in KINDS:
-            raise ValueError("UpdateCore: kind must be 'adam', 'sgd', 'lion' or 'adafactor' "
-                             f"(got {kind!r})")
+            raise ValueError("UpdateCore: kind must be 'adam', 'sgd', 'lion', 'adafactor' or "
+                             f"'muon' (got {kind!r})")
         # the update: torch.optim.Adam's, torch.optim.SGD's (`momentum`: some group has a
         # momentum, so the shard holds a momentum buffer; none of them: no optimizer state at all)
         # or zero_amd.optim.Lion's (one moment, exp_avg, always)
@@ -355,6 +402,8 @@ class UpdateCore:
             views = {"exp_avg": cut(self.m)}
         elif self.kind == "adafactor":  # (the engine adds the factors: flat.AdafactorState)
             views = {}
+        elif self.kind == "muon":  # torch's Muon state: the buffer alone
+            views = {"momentum_buffer": cut(self.m)}
         else:
             views = {"exp_avg": cut(self.m), "exp_avg_sq": cut(self.v)}
         if self.master is not None:
@@ -412,7 +461,7 @@ class UpdateCore:
         if self.kind == "sgd":  # torch's SGD entry: the buffer once it exists, no step
             if self.steps[i] == 0 or "momentum_buffer" not in torch_state:
                 entry.pop("momentum_buffer", None)
-        else:
+        elif self.kind != "muon":  # (torch's Muon entry: the buffer, no step)
             entry["step"] = torch.tensor(float(self.steps[i]), dtype=torch.float32)
         return entry
 

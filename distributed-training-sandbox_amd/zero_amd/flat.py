@@ -51,8 +51,8 @@ from ._hooks import WeakCall
 from ._update import GradClip, UpdateNorms
 from .comm import StreamEvent
 from .engine import ALIGN_ELEMS, ShardEngine, _ptr
-from .kernels import (AdafactorSet, adafactor_hparams, check_extents, check_extents_enabled,
-                      copy_direct)
+from .kernels import (AdafactorSet, MuonSet, adafactor_hparams, check_extents,
+                      check_extents_enabled, copy_direct, muon_hparams)
 
 _I32P = np.int32
 LAND_BATCH_BYTES = 64 << 20  # fresh gradients landed per hook batch (ws > 1, no overlap)
@@ -82,6 +82,7 @@ class FlatEngine(ShardEngine):
     reduce / broadcast are the same code."""
 
     af = None  # (AdafactorState of an Adafactor engine)
+    muon_scratch_bytes = 0  # the MuonSets' scratch budget (0: the library's default, 1 GiB)
 
     def __init__(self, params, group_of, ws: int, rank: int, *, carry=False, comm=None,
                  bucket_bytes: int = 256 << 20, master: str = "split", placement_tries: int = 8,
@@ -145,7 +146,7 @@ class FlatEngine(ShardEngine):
         # the arena view, or the fresh tensor backward left after a set-to-None zero_grad(), in
         # place (zero2.py:120 reads p.grad as backward left it): no landing copy, and G exists
         # only once a caller asks for grad views (zero_grad(set_to_none=False), ZeRO-1's views)
-        self.inplace = ws == 1 and self.grad_comm is None and kind != "adafactor"
+        self.inplace = ws == 1 and self.grad_comm is None and kind not in ("adafactor", "muon")
         self.G, self.grad_placement = None, None
         self._total = total
         if not self.inplace:
@@ -274,6 +275,32 @@ class FlatEngine(ShardEngine):
                                    maximize=h["maximize"], grad_div=float(self.ws))
             aset.run(hp, int(t), stream)
             self.last_adam_bytes += aset.bytes
+
+    def _muon_update(self, has, hparams_of, stream):
+        """The whole step's Muon update: one MuonSet per param group over the owned matrices that
+        have a gradient (shape groups and batches inside it), cached while they stay the same."""
+        own = np.asarray(self.owned_param_indices(), np.int64)
+        own = own[has[own]]
+        if not len(own):
+            return
+        gof = np.asarray(self.group_of)[own]
+        for gi in np.unique(gof):
+            idx = own[gof == gi]
+            mset = self.cached(("muon", int(gi), int(idx[0]), len(idx)), idx.tobytes(),
+                               lambda: muon_set(self, idx))
+            h = hparams_of(int(gi))
+            hp = muon_hparams(h["lr"], h["weight_decay"], h["momentum"], h["nesterov"],
+                              h["ns_coefficients"], h["eps"], h["ns_steps"], h["adjust_lr_fn"],
+                              grad_div=float(self.ws))
+            mset.run(hp, stream)
+            self.last_adam_bytes += mset.bytes
+
+    def _whole_update(self, has, hparams_of, stream):
+        """The updates that need whole parameters on their owner, after all of the reductions."""
+        if self.kind == "muon":
+            self._muon_update(has, hparams_of, stream)
+        else:
+            self._adafactor_update(has, hparams_of, stream)
 
     def own_window(self) -> torch.Tensor:
         """This rank's stream in P: the parameters its shard's state (and EMA) belongs to."""
@@ -793,7 +820,8 @@ class FlatEngine(ShardEngine):
         # fast path: every owned param has a grad and, per param group, one (step, carry) key
         own = self.owned
         hps = {}
-        if has[own].all() and self.af is None:
+        whole = self.af is not None or self.kind == "muon"
+        if has[own].all() and not whole:
             gof = np.asarray(self.group_of)
             for gi in np.unique(gof[own]):
                 sel = own & (gof == gi)
@@ -836,8 +864,8 @@ class FlatEngine(ShardEngine):
                     self._clip_run(deferred, 0, len(deferred), stream)
                 elif stats:
                     self._stats_run(deferred, 0, len(deferred), stream)
-                elif self.af is not None:
-                    self._adafactor_update(has, hparams_of, stream)
+                elif whole:
+                    self._whole_update(has, hparams_of, stream)
                 else:
                     for rd in self.rounds:
                         self._adam_round(rd, has, cmul, hps, hparams_of, stream, gptr)
@@ -871,12 +899,12 @@ class FlatEngine(ShardEngine):
                     stream.wait_event(self.ev_red[rd.j])
                     self._clip_norm(deferred[:b], a, stream)
                 self._clip_coef(deferred, stream)
-            if self.af is not None:  # whole parameters: every round's reduction, then one update
+            if whole:  # whole parameters: every round's reduction, then one update
                 for rd in self.rounds:
                     stream.wait_event(self.ev_red[rd.j])
-                self._adafactor_update(has, hparams_of, stream)
+                self._whole_update(has, hparams_of, stream)
             for k, rd in enumerate(self.rounds):
-                if self.af is not None:
+                if whole:
                     pass
                 elif clip:
                     self._clip_run(deferred, ends[k - 1] if k else 0, ends[k], stream)
@@ -1029,6 +1057,40 @@ class AdafactorState:
             check_extents(rows[:, 4], np.where(rows[:, 5] == 0, C, R) * 4, [self.state], "row_var")
             check_extents(rows[:, 5], C * 4, [self.state], "col_var")
         return AdafactorSet(rows, eng.czdtype, eng.p_dtype)
+
+
+def muon_set(eng, idx):
+    """The MuonSet of a flat engine's owned matrices ``idx`` (Layout R: whole parameters): the
+    gradient from the reduced stream R, the master as for Adafactor, the momentum buffer from the
+    flat state's ``m``."""
+    pc = eng.pieces
+    so_of = {int(i): int(so) for i, so, n in zip(pc.param, pc.stream_off, pc.length) if n > 0}
+    rows = []
+    for i in idx:
+        i = int(i)
+        (R, C), so = tuple(eng.params[i].shape), so_of[i]
+        if R * C == 0:
+            continue
+        g = eng.R.data_ptr() + so * eng.ces
+        pslot = eng.P.data_ptr() + (int(eng.base[eng.rank]) + so) * eng.es
+        if not eng.mixed:
+            mst, mo, po = pslot, pslot, 0
+        elif eng.split:
+            mst, mo, po = pslot, eng.lo.data_ptr() + so * 2, pslot
+        else:
+            mst = mo = eng.master.data_ptr() + so * 4
+            po = pslot
+        rows.append([g, mst, mo, po, eng.m.data_ptr() + so * 4, R, C, i])
+    rows = np.array(rows, np.uint64).reshape(-1, 8)
+    if check_extents_enabled():  # every entry inside its tensors (tests turn this on)
+        n = rows[:, 5].astype(np.int64) * rows[:, 6].astype(np.int64)
+        msz = 2 if eng.split else 4
+        check_extents(rows[:, 0], n * eng.ces, [eng.R], "Muon gradient")
+        check_extents(rows[:, 1], n * msz, [eng.P, eng.master], "Muon master")
+        check_extents(rows[:, 2], n * msz, [eng.P, eng.master, eng.lo], "Muon master out")
+        check_extents(rows[:, 3], n * 2, [eng.P], "Muon bf16 parameter")
+        check_extents(rows[:, 4], n * 4, [eng.m], "Muon momentum buffer")
+    return MuonSet(rows, eng.czdtype, eng.p_dtype, scratch_budget=eng.muon_scratch_bytes)
 
 
 def _dense(g: torch.Tensor, p: torch.Tensor) -> bool:

@@ -12,6 +12,8 @@ finite; ``run_sr`` with ``sr_keys`` stores bf16 moments with stochastic rounding
 ``lion_hparams``.
 ``AdafactorSet`` — torch.optim.Adafactor's update over a table of matrices (csrc/zs_adafactor.hip):
 factored second moment, three passes, every scalar on the device; ``adafactor_hparams``.
+``MuonSet`` — torch.optim.Muon's update over a table of matrices (csrc/zs_muon.hip): momentum, the
+Newton-Schulz iteration as bf16 MFMA products, the apply pass; ``muon_hparams``, ``muon_gemm_nt``.
 ``adam_step`` — the same update over one contiguous range (zs_adam_step_ex; no table to keep).
 
 Both upload their segment table once; ``run(stream)`` only enqueues a kernel on ``stream``.
@@ -25,7 +27,8 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import AdafactorHParams, AdafactorSeg, AdamHParams, AdamSeg, LionHParams, SgdHParams
+from ._lib import (AdafactorHParams, AdafactorSeg, AdamHParams, AdamSeg, LionHParams, MuonHParams,
+                   MuonSeg, SgdHParams)
 
 _PU64 = ctypes.POINTER(ctypes.c_uint64)
 _PI64 = ctypes.POINTER(ctypes.c_int64)
@@ -497,6 +500,114 @@ class AdafactorSet:
             except Exception:  # interpreter teardown
                 pass
             self._h = None
+
+
+MUON_ADJUST_LR = {None: 0, "original": 0, "match_rms_adamw": 1}
+
+
+def muon_hparams(lr=1e-3, weight_decay=0.1, momentum=0.95, nesterov=True,
+                 ns_coefficients=(3.4445, -4.775, 2.0315), eps=1e-7, ns_steps=5,
+                 adjust_lr_fn=None, *, grad_div=1.0) -> MuonHParams:
+    """A torch.optim.Muon group's scalars (zs_muon_hparams_init)."""
+    if adjust_lr_fn not in MUON_ADJUST_LR:
+        raise ValueError(f"Adjust learning rate function {adjust_lr_fn} is not supported")
+    if len(ns_coefficients) != 3:
+        raise ValueError("Coefficients must be a tuple of exactly 3 values")
+    a, b, c = (float(x) for x in ns_coefficients)
+    hp = MuonHParams()
+    _lib.call("zs_muon_hparams_init", float(lr), float(weight_decay), float(momentum),
+              int(bool(nesterov)), a, b, c, float(eps), int(ns_steps),
+              MUON_ADJUST_LR[adjust_lr_fn], float(grad_div), ctypes.byref(hp))
+    return hp
+
+
+class MuonSet:
+    """Fused Muon over a table with one entry per owned matrix; ``segs`` is an (n, 8) int64/uint64
+    array in zs_muon_seg order: g, master, master_out, p_out, buf, R, C, param.  ``run`` is one
+    step: per batch of same-shape matrices the passes M1, M2, ns_steps x three MFMA products and
+    P, nothing on the host.  ``scratch_budget`` (bytes, 0: the library's default) bounds the
+    scratch and so the batch size."""
+
+    FIELDS = ("g", "master", "master_out", "p_out", "buf", "R", "C", "param")
+    STATS = ("elems", "bytes", "m1_bytes", "m2_bytes", "p_bytes", "scratch_bytes", "flops_iter",
+             "flops_iter_run", "batches")
+
+    def __init__(self, segs: np.ndarray, g_dtype: int, p_dtype: int = _lib.ZS_BF16,
+                 scratch_budget: int = 0):
+        segs = np.ascontiguousarray(np.asarray(segs, dtype=np.uint64).reshape(-1, 8))
+        arr = (MuonSeg * max(len(segs), 1))()
+        ctypes.memmove(arr, segs.ctypes.data, segs.nbytes)
+        h = ctypes.c_void_p()
+        _lib.call("zs_muonset_create", arr if len(segs) else None, len(segs), int(g_dtype),
+                  int(p_dtype), int(scratch_budget), ctypes.byref(h))
+        self._h = h
+        self.nseg = len(segs)
+        out = (ctypes.c_int64 * len(self.STATS))()
+        _lib.call("zs_muonset_stats", h, out, len(self.STATS))
+        for name, v in zip(self.STATS, out):
+            setattr(self, name, int(v))
+
+    def run(self, hp: MuonHParams, stream) -> None:
+        _lib.call("zs_muonset_run", self._h, ctypes.byref(hp), stream_handle(stream))
+
+    def run_pass(self, hp: MuonHParams, which: int, stream, *, product: int = -1,
+                 batch: int = -1) -> None:
+        """Pass ``which`` (0: M1 and the norm, 1: M2, 2: the products -- all iterations, or
+        ``product`` 0, 1, 2 of one --, 3: P) over ``batch`` (-1: all), for tests and measurement."""
+        _lib.call("zs_muonset_run_pass", self._h, ctypes.byref(hp), int(which), int(product),
+                  int(batch), stream_handle(stream))
+
+    def batch(self, b: int) -> dict:
+        """Where batch ``b``'s scratch arrays lie (zs_muonset_batch)."""
+        out = (ctypes.c_int64 * 12)()
+        _lib.call("zs_muonset_batch", self._h, int(b), out)
+        names = ("first", "count", "R", "C", "ldr", "ldc", "X", "XT", "A", "Bm", "norm",
+                 "scratch_bytes")
+        return dict(zip(names, (int(v) for v in out)))
+
+    def read(self, b: int, name: str, stream):
+        """A copy of batch ``b``'s scratch array ``name`` ("X", "XT", "A", "Bm": bf16, (matrices,
+        rows, columns); "norm": fp32, one per matrix) as it stands in stream order; diagnostic."""
+        import torch
+
+        info = self.batch(b)
+        r, c = min(info["R"], info["C"]), max(info["R"], info["C"])
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if name == "norm":
+            out = torch.empty(info["count"], dtype=torch.float32, device=dev)
+            cols = None
+        else:
+            rows, cols, ld = {"X": (r, c, info["ldc"]), "XT": (c, r, info["ldr"]),
+                              "A": (r, r, info["ldr"]), "Bm": (r, r, info["ldr"])}[name]
+            out = torch.empty((info["count"], rows, ld), dtype=torch.bfloat16, device=dev)
+        copy_direct([info[name]], [out.data_ptr()], [out.numel() * out.element_size()], stream)
+        return out if cols is None else out[:, :, :cols]
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib is not None:
+            try:
+                _lib.lib.zs_muonset_destroy(h)
+            except Exception:  # interpreter teardown
+                pass
+            self._h = None
+
+
+def muon_gemm_nt(A, B, D, *, E=None, D2=None, alpha=1.0, beta=0.0, sym=False, stream=None) -> None:
+    """``D = bf16(alpha * A @ B.T + beta * E)`` on 2-D bf16 tensors whose rows are contiguous
+    (any row stride); ``D2`` receives ``D.T``; ``sym``: D is known symmetric (zs_muon_gemm_nt)."""
+    def ld(t):
+        if t is None:
+            return 0, 0
+        if t.dim() != 2 or t.stride(1) != 1 or t.element_size() != 2:
+            raise ValueError("muon_gemm_nt: operands are 2-D bf16 tensors with contiguous rows")
+        return t.data_ptr(), t.stride(0)
+    (M, K), N = A.shape, B.shape[0]
+    args = []
+    for t in (A, B, E, D, D2):
+        args += ld(t)
+    _lib.call("zs_muon_gemm_nt", *args, M, N, K, float(alpha), float(beta), int(bool(sym)),
+              stream_handle(stream))
 
 
 def sqnorm_reduce(partials, n: int, sumsq, stream) -> None:

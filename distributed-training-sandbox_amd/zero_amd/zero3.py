@@ -69,7 +69,7 @@ from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_BF16_SR, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
 from ._sharded import group_hparams, optimizer_kind
-from ._update import (GradClip, UpdateCore, UpdateNorms, check_adafactor, check_bf16_state_group,
+from ._update import (GradClip, UpdateCore, UpdateNorms, check_adafactor, check_muon, check_bf16_state_group,
                       check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group, check_master_free, check_update_norms,
                       check_update_norms_group,
                       check_master_free_group, check_max_grad_norm, check_param_grad_norms, check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
@@ -1852,6 +1852,8 @@ class ShardedOptimizer:
         self.update = bool(update)
         if optimizer_kind(optimizer) == "adafactor":  # both modes: refused before anything else
             check_adafactor(zero3=True)
+        if optimizer_kind(optimizer) == "muon":
+            check_muon(zero3=True, grad_accumulation=bool(grad_accumulation))
         self.max_grad_norm = max_grad_norm
         self._check_clip()
         self.skip_nonfinite = check_skip_nonfinite(skip_nonfinite, max_grad_norm,

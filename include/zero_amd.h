@@ -712,6 +712,83 @@ int zs_adafactorset_stats(const zs_adafactorset* as, int64_t* elems, int64_t* by
                           int64_t* pass_bytes, int64_t* scratch_bytes);
 int zs_adafactorset_destroy(zs_adafactorset* as);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Fused Muon (torch.optim.Muon's rule), additive in ABI v13.  Per owned R x C matrix: momentum, */
+/* Newton-Schulz orthogonalisation of the bf16 update on the matrix cores (bf16 MFMA, fp32       */
+/* accumulators, torch's three bf16 rounding points per iteration), decoupled weight decay.      */
+/* With r = min(R, C), c = max(R, C) an iteration is 4 r^2 c + 2 r^3 flops, of which the two      */
+/* symmetric products compute the upper triangle of tiles only.                                   */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint64_t g;          /* reduced gradient sum, R * C elements of g_dtype (required) */
+  uint64_t master;     /* as zs_adafactor_seg: the fp32 master, or (ZS_BF16_SPLIT) the bf16 param */
+  uint64_t master_out; /* the fp32 master again (in place), or (ZS_BF16_SPLIT) the int16 residual */
+  uint64_t p_out;      /* optional bf16 copy; (ZS_BF16_SPLIT) the bf16 param written, required */
+  uint64_t buf;        /* fp32 momentum buffer, R * C elements, updated in place */
+  int64_t R, C;        /* rows and columns: row i starts at element i * C */
+  int64_t param;       /* the caller's index of the entry's parameter (>= 0) */
+} zs_muon_seg;
+
+typedef struct {
+  /* the group's scalars as doubles; a run rounds what it derives from them to f32 once */
+  double lr, weight_decay, momentum;
+  double ns_a, ns_b, ns_c; /* ns_coefficients */
+  double eps;
+  double grad_div;         /* divide the reduced sum by this (world size) */
+  int32_t nesterov;
+  int32_t ns_steps;        /* 0 .. 99 */
+  int32_t adjust_lr;       /* 0: None / "original" (sqrt(max(1, R / C))); 1: "match_rms_adamw" */
+  int32_t reserved;
+} zs_muon_hparams;
+
+/* torch.optim.Muon's rules: ZS_ERR_INVALID unless lr >= 0, momentum >= 0, weight_decay >= 0,
+ * 0 <= ns_steps < 100, adjust_lr in {0, 1}, eps >= 0, grad_div > 0 and hp is not NULL. */
+int zs_muon_hparams_init(double lr, double weight_decay, double momentum, int nesterov, double ns_a,
+                         double ns_b, double ns_c, double eps, int ns_steps, int adjust_lr,
+                         double grad_div, zs_muon_hparams* hp);
+typedef struct zs_muonset zs_muonset;
+/* g_dtype ZS_F32 or ZS_BF16; p_dtype ZS_BF16 (fp32 master in place, optional bf16 p_out) or
+ * ZS_BF16_SPLIT.  Entries are grouped by shape and run in batches of same-shape matrices (one
+ * launch per pass and product, grid z = matrix).  The set owns one scratch allocation that holds a
+ * batch: per matrix X (r x c), two copies of X^T (the third product writes the new transpose
+ * beside the one other workgroups still read), A and Bm (r x r) in bf16, rows padded to 16 bytes.
+ * scratch_budget bounds those bytes (0: 1 GiB) and so the batch size; a matrix that alone exceeds
+ * it is refused.  Every check comes before any allocation or upload. */
+int zs_muonset_create(const zs_muon_seg* segs, int64_t n, int g_dtype, int p_dtype,
+                      int64_t scratch_budget, zs_muonset** out);
+/* One Muon step over the set, per matrix p (R x C) with averaged gradient g:
+ *   buf = lerp(buf, g, 1 - momentum);  u = nesterov ? lerp(g, buf, momentum) : buf   (ATen's lerp)
+ *   X = bf16(u), transposed if R > C;  X = bf16(float(X) / float(bf16(max(||X||_F, eps))))
+ *   ns_steps times: A = bf16(X X^T); Bm = bf16(b A + c A A); X = bf16(a X + Bm X)
+ *   p = fma(-adjust_lr(lr), float(O), p * (1 - lr * weight_decay)),  O = X in p's orientation
+ * The norm's squares are summed in fp32 over 4 terms and in double above, in an order fixed by the
+ * shape; the root is rounded to fp32 and then to bf16.  ZS_ERR_INVALID, nothing launched: a NULL
+ * argument, a set of another family, hyper-parameters zs_muon_hparams_init would refuse. */
+int zs_muonset_run(zs_muonset* ms, const zs_muon_hparams* hp, uintptr_t stream);
+/* One pass of zs_muonset_run over batch `batch` (-1: every batch): 0 = M1 and the norm, 1 = M2,
+ * 2 = the products (product -1: all ns_steps iterations; 0, 1, 2: that one product of one
+ * iteration), 3 = P.  For tests and measurement; with more than one batch the scratch holds the
+ * batch run last. */
+int zs_muonset_run_pass(zs_muonset* ms, const zs_muon_hparams* hp, int pass, int product,
+                        int64_t batch, uintptr_t stream);
+/* out[0 .. n) of: elements, stream-pass HBM bytes of one run, the bytes of M1, M2 and P, scratch
+ * bytes, flops of one Newton-Schulz iteration (nominal), flops its tiles compute, batches. */
+int zs_muonset_stats(const zs_muonset* ms, int64_t* out, int n);
+/* Diagnostic, like zs_muonset_run_pass: out[0 .. 12) of batch `batch`: first entry (in the
+ * shape-grouped order), matrices, R, C, the row strides of the r- and c-column arrays, the device
+ * addresses of X, the current X^T, A, Bm and the norms (fp32, one per matrix), scratch bytes.
+ * Matrix k of the batch starts k * rows * stride elements into each array. */
+int zs_muonset_batch(const zs_muonset* ms, int64_t batch, int64_t* out);
+int zs_muonset_destroy(zs_muonset* ms);
+/* The bare product of the iteration on caller buffers (diagnostic, like zs_tune):
+ *   D[M x N] = bf16(alpha * A[M x K] * B[N x K]^T + beta * E[M x N]),  bf16 in, fp32 accumulate,
+ * K contiguous in A and B; D2 (optional, N x M) receives D^T, bit for bit.  sym != 0: M == N and D
+ * is known symmetric: only tiles with tile_n >= tile_m are computed and each is mirrored into D
+ * (D2 must be 0).  E may be D.  Any sizes and strides; 16-byte aligned rows take 16-byte accesses. */
+int zs_muon_gemm_nt(uint64_t A, int64_t lda, uint64_t B, int64_t ldb, uint64_t E, int64_t lde,
+                    uint64_t D, int64_t ldd, uint64_t D2, int64_t ldd2, int64_t M, int64_t N,
+                    int64_t K, double alpha, double beta, int sym, uintptr_t stream);
+
 /* Single-range form, SURVEY.md §8(b)'s signature: one torch.optim.Adam/AdamW step over n
  * contiguous elements — the update of one flat shard (zero1.py:88 on a flattened group) with no
  * table to build.  p: fp32 master/param, updated in place; p_bf16: optional bf16 copy of the
