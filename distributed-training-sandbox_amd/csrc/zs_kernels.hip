@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "zs_common.h"
+#include "zs_lamb.h"
 #include "zs_sr.h"
 
 namespace {
@@ -46,7 +47,7 @@ constexpr int64_t copy_chunk_bytes(int u) { return int64_t(kThreads) * 16 * u; }
 constexpr int adam_groups(bool split) { return split ? 4 : 2; }
 constexpr int64_t adam_chunk(bool split) { return int64_t(kThreads) * 4 * adam_groups(split); }
 
-int grid_cap() {
+[[maybe_unused]] int grid_cap() {  // (zs_lamb.hip's inclusion has no caller)
   static int cap = 0;
   if (cap == 0) {
     int dev = 0, cus = 256;
@@ -329,6 +330,7 @@ struct AdamRule {
   static constexpr bool kPsr = false;  // AdamPsrRule: no master, the bf16 parameter in place
   static constexpr bool kEma = false;  // AdamEmaRule: the vmax stream is an EMA of the stored master
   static constexpr bool kStats = false;  // AdamStatsRule: per-chunk sums of (p1 - p0)^2 and p1^2
+  static constexpr bool kNoStore = false;  // LambRule: elem leaves u in p, which is not stored
   using Stats = NoStats;
 
   // One element of torch.optim.Adam's single-tensor update (adam.py:394-547), one fp32 operation
@@ -537,6 +539,7 @@ struct SgdRule {
   static constexpr bool kPsr = false;
   static constexpr bool kEma = false;
   static constexpr bool kStats = false;
+  static constexpr bool kNoStore = false;
   using Stats = NoStats;
 
   // One element of torch.optim.SGD's single-tensor update (sgd.py _single_tensor_sgd), in the
@@ -579,6 +582,7 @@ struct LionRuleT {
   static constexpr bool kPsr = false;
   static constexpr bool kEma = false;
   static constexpr bool kStats = false;
+  static constexpr bool kNoStore = false;
   using Stats = NoStats;
 
   // One element of zero_amd.optim.Lion's step, in the rounding order of torch's CPU kernels:
@@ -794,7 +798,10 @@ __device__ __forceinline__ void update_full_chunk(const AdamSeg& s, int64_t e0,
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(o4), "+v"(o2));  // as above, for the block the stores are in
 #endif
-    if constexpr (PSR) {
+    if constexpr (Rule::kNoStore) {  // (LambRule: pp holds u; the master stays as it is)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) Rule::stat(p0[j], pp[j], acc);
+    } else if constexpr (PSR) {
       const uint2 r = psr_pack_bf16x4(pp, psr_seg_index<ST>(s.m, hp) + uint64_t(e0),
                                       (uint32_t(u) * kThreads + threadIdx.x) * 4u, hp);
       nt_st8(pb.at(u, o2), r);
@@ -933,7 +940,10 @@ __device__ __forceinline__ void update_pred_groups(const AdamSeg& s, int64_t e0,
         if constexpr (Rule::kX) xp[j] = xv;
         if constexpr (CARRY) cp[j] = cv;
       }
-      if constexpr (PSR) {
+      if constexpr (Rule::kNoStore) {  // (LambRule: pp holds u; the master stays as it is)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Rule::stat(p0[j], pp[j], acc);
+      } else if constexpr (PSR) {
         const uint2 r = psr_pack_bf16x4(pp, psr_seg_index<ST>(s.m, hp) + uint64_t(e0),
                                         (uint32_t(u) * kThreads + threadIdx.x) * 4u, hp);
         nt_st8(s.p_out + i, r);
@@ -1051,9 +1061,17 @@ __global__ __launch_bounds__(kThreads) void adam_segments_kernel(
     constexpr int G = adam_groups(SPLIT);
     const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT);
     typename Rule::Stats acc;  // kStats: this lane's sums over the chunk, +0 at its start
+    if constexpr (Rule::kNoStore) {
+      if (!s.g) {  // (uniform) LambRule: not part of the step, its slots get +0.0
+        stats_store(acc, hp, hp.vec_off[seg] + 4 * (c - chunk_prefix[seg]) + (threadIdx.x >> 6));
+        continue;
+      }
+    }
     if constexpr (LOADS_FIRST) {
       if (e0 + adam_chunk(SPLIT) <= s.n) {  // uniform per workgroup
-        if (s.g) update_full_chunk<Rule, GT, CARRY, SPLIT, true, CLIP, ST>(s, e0, hp, coef, acc);
+        if constexpr (Rule::kNoStore)
+          update_full_chunk<Rule, GT, CARRY, SPLIT, true, CLIP, ST>(s, e0, hp, coef, acc);
+        else if (s.g) update_full_chunk<Rule, GT, CARRY, SPLIT, true, CLIP, ST>(s, e0, hp, coef, acc);
         else update_full_chunk<Rule, GT, CARRY, SPLIT, false, CLIP, ST>(s, e0, hp, coef, acc);
       } else {
 #pragma unroll 1
@@ -1096,6 +1114,12 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
     const int64_t i0 = (c - chunk_prefix[seg]) * kThreads;  // uniform
     const int64_t i = i0 + threadIdx.x;
     typename Rule::Stats acc;  // kStats: a lane past n adds nothing and still joins the wave's sum
+    if constexpr (Rule::kNoStore) {
+      if (!s.g) {  // (uniform) LambRule: not part of the step, its slots get +0.0
+        stats_store(acc, hp, hp.sca_off[seg] + 4 * (c - chunk_prefix[seg]) + (threadIdx.x >> 6));
+        continue;
+      }
+    }
     if (i < s.n) {
       float gs = s.g ? load_g1<GT>(s.g, i) : 0.0f;
       const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
@@ -1119,7 +1143,9 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
       float cr = CARRY ? glob(s.carry)[i] : 0.0f;
       const float p0 = p;  // the master as loaded (kStats)
       Rule::template elem<CARRY, CLIP>(gs, p, m, v, vm, cr, hp, coef);
-      if constexpr (PSR) {
+      if constexpr (Rule::kNoStore) {  // (LambRule: p holds u; the master stays as it is)
+        Rule::stat(p0, p, acc);
+      } else if constexpr (PSR) {
         const uint32_t r16 = psr_r16_at(psr_seg_index<ST>(s.m, hp) + uint64_t(i0), threadIdx.x, hp);
         glob(s.p_out)[i] = (unsigned short)(sr_word(p, r16) >> 16);
       } else if constexpr (SPLIT) {
@@ -1161,6 +1187,13 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
       stats_store(acc, hp, hp.sca_off[seg] + 4 * (c - chunk_prefix[seg]) + (threadIdx.x >> 6));
   }
 }
+
+// csrc/zs_lamb.hip includes this file up to here (ZS_UPDATE_SKELETON_ONLY): the LAMB instances of
+// the two kernels above belong to a translation unit of their own, which the Makefile compiles
+// without packed fp32 instructions, as it does the Adafactor and Muon kernels.
+#ifdef ZS_UPDATE_SKELETON_ONLY
+}  // namespace
+#else
 
 // ----------------------------------------------------------------------------------------------
 // gradient sum of squares over an Adam set (global-norm clipping, clip_grad_norm_'s norm)
@@ -2213,6 +2246,12 @@ struct zs_adamset {
   int m_one_mod4 = 1;
   // zs_adamset_set_state_rounding: a ZS_BF16_SR set's bf16 moments round stochastically
   int state_sr = 0;
+  // zs_lambset_bind_params: the input segment of every table entry (vector entries, then scalar
+  // ones), the parameter of every entry as bound last, on the host and on the device, and the
+  // largest of them (-1: none bound)
+  std::vector<int32_t> entry_in, entry_param;
+  int32_t* d_entry_param = nullptr;
+  int64_t param_max = -1;
 };
 
 // ZS_BF16_SR (master-free) sets have the split master's geometry: 16-bit parameter stream, 4 groups
@@ -3083,6 +3122,8 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   as->m_lowest = m_lowest;
   as->m_one_parity = m_one_parity;
   as->m_one_mod4 = m_one_mod4;
+  as->entry_in = vec_in;
+  as->entry_in.insert(as->entry_in.end(), sca_in.begin(), sca_in.end());
   int rc = ZS_OK;
   if (as->nvec) {
     rc = upload(vec, &as->d_vec);
@@ -3375,6 +3416,25 @@ int zs_adamset_update_norm_slots(const zs_adamset* as, int64_t* n, int64_t* seg_
   return ZS_OK;
 }
 
+// The stats fields of a launch over `as`: the planes and the per-entry slot offsets, uploaded by the
+// first such run.
+static int stats_planes(const zs_adamset* as, double* partials, StatsHP* hp) {
+  const int64_t nslots = as->un_seg_off.back();
+  if (nslots && !as->d_un_off) {
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!as->d_un_off) {
+      const int rc = upload(as->un_off, &as->d_un_off);
+      if (rc != ZS_OK) return rc;
+    }
+  }
+  hp->planes = partials;
+  hp->nslots = nslots;
+  hp->vec_off = as->d_un_off;
+  hp->sca_off = as->d_un_off ? as->d_un_off + as->nvec : nullptr;
+  return ZS_OK;
+}
+
 int zs_adamset_run_stats(const zs_adamset* as, const zs_adam_hparams* h, const float* coef,
                          int guard, double* partials, uintptr_t stream) {
   const char* fn = "zs_adamset_run_stats";
@@ -3394,21 +3454,126 @@ int zs_adamset_run_stats(const zs_adamset* as, const zs_adam_hparams* h, const f
   ZS_REQUIRE(!guard || coef, "%s: the guard tests the clip coefficient, which is NULL", fn);
   const int64_t nslots = as->un_seg_off.back();
   ZS_REQUIRE(partials != nullptr || nslots == 0, "%s: partials is NULL", fn);
-  if (nslots && !as->d_un_off) {  // first use: the per-entry slot offsets
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!as->d_un_off) {
-      const int rc = upload(as->un_off, &as->d_un_off);
-      if (rc != ZS_OK) return rc;
-    }
-  }
   StatsHP hp;
   static_cast<HP&>(hp) = make_hp(h);
-  hp.planes = partials;
-  hp.nslots = nslots;
-  hp.vec_off = as->d_un_off;
-  hp.sca_off = as->d_un_off ? as->d_un_off + as->nvec : nullptr;
+  const int rc = stats_planes(as, partials, &hp);
+  if (rc != ZS_OK) return rc;
   return run_set<AdamStatsFamily>(as, false, hp, coef, stream, guard != 0);
+}
+
+/* ---- fused LAMB: L1 (moments and partials), the finishing kernel, L2 (apply) ---- */
+
+int zs_lamb_hparams_init(double beta1, double beta2, double eps, double weight_decay,
+                         int bias_correction, int maximize, int64_t step, double grad_div,
+                         zs_lamb_hparams* hp) {
+  const char* fn = "zs_lamb_hparams_init";
+  ZS_REQUIRE(hp != nullptr, "%s: hp is NULL", fn);
+  ZS_REQUIRE(step >= 1, "%s: step must be >= 1", fn);
+  ZS_REQUIRE(grad_div > 0.0, "%s: grad_div must be > 0", fn);
+  // zero_amd.optim.LAMB.__init__'s rules
+  ZS_REQUIRE(beta1 >= 0.0 && beta1 < 1.0, "%s: invalid beta1 %g", fn, beta1);
+  ZS_REQUIRE(beta2 >= 0.0 && beta2 < 1.0, "%s: invalid beta2 %g", fn, beta2);
+  ZS_REQUIRE(eps >= 0.0, "%s: invalid eps %g", fn, eps);
+  ZS_REQUIRE(weight_decay >= 0.0, "%s: invalid weight_decay %g", fn, weight_decay);
+  const double t = double(step);
+  hp->one_minus_beta1 = float(1.0 - beta1);
+  hp->beta2 = float(beta2);
+  hp->one_minus_beta2 = float(1.0 - beta2);
+  hp->bc1 = bias_correction ? float(1.0 - std::pow(beta1, t)) : 1.0f;
+  hp->bc2_sqrt = bias_correction ? float(std::pow(1.0 - std::pow(beta2, t), 0.5)) : 1.0f;
+  hp->eps = float(eps);
+  hp->weight_decay = float(weight_decay);
+  hp->grad_div = float(grad_div);
+  hp->maximize = maximize ? 1 : 0;
+  return ZS_OK;
+}
+
+// the set's tables and the update's grids for zs_lamb.hip (its L1 is the loads-first instance)
+static zs::LambTables lamb_tables(const zs_adamset* as) {
+  const bool split = split_geometry(as);
+  const int64_t vcap = adam_grid_cap(split ? kAdamLoadsFirstWgPerCu : kAdamWgPerCu);
+  return {as->d_vec, as->d_vec_prefix, as->nvec, as->vec_chunks,
+          as->d_sca, as->d_sca_prefix, as->nsca, as->sca_chunks,
+          int(std::min(as->vec_chunks, vcap)),
+          int(std::min(as->sca_chunks, adam_grid_cap(kAdamWgPerCu))), as->g_dtype, split};
+}
+
+// what both passes ask of their set and struct (`fn`: the entry point, in messages)
+static int lamb_check(const char* fn, const zs_adamset* as, const zs_lamb_hparams* h) {
+  ZS_REQUIRE(as && h, "%s: NULL argument", fn);
+  ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create", fn);
+  ZS_REQUIRE(!as->sgd && !as->lion, "%s: LAMB runs over a set made by zs_adamset_create (this one "
+             "was made by %s)", fn, as->sgd ? "zs_sgdset_create" : "zs_lionset_create");
+  ZS_REQUIRE(as->state_dtype == ZS_F32, "%s: a set with ZS_BF16 state has no LAMB instances", fn);
+  ZS_REQUIRE(as->p_dtype != ZS_BF16_SR, "%s: a ZS_BF16_SR set has no master to measure", fn);
+  ZS_REQUIRE(!as->has_carry, "%s: a set with the ZeRO-1 carry has no LAMB instances", fn);
+  ZS_REQUIRE(!as->has_vmax, "%s: a set with the vmax column (amsgrad, EMA) has no LAMB instances",
+             fn);
+  // a struct filled by hand gets zs_lamb_hparams_init's rules too
+  ZS_REQUIRE(h->bc1 > 0.0f && h->bc2_sqrt > 0.0f, "%s: bias corrections must be > 0", fn);
+  ZS_REQUIRE(h->eps >= 0.0f && h->weight_decay >= 0.0f, "%s: negative eps or weight_decay", fn);
+  ZS_REQUIRE(h->grad_div > 0.0f, "%s: grad_div must be > 0", fn);
+  return ZS_OK;
+}
+
+int zs_lambset_run_moments(const zs_adamset* as, const zs_lamb_hparams* h, const float* coef,
+                           double* partials, uintptr_t stream) {
+  const char* fn = "zs_lambset_run_moments";
+  int rc = lamb_check(fn, as, h);
+  if (rc != ZS_OK) return rc;
+  ZS_REQUIRE(partials != nullptr || as->un_seg_off.back() == 0, "%s: partials is NULL", fn);
+  StatsHP pl;
+  rc = stats_planes(as, partials, &pl);
+  if (rc != ZS_OK) return rc;
+  return zs::lamb_moments(lamb_tables(as), *h, coef, {pl.planes, pl.nslots, pl.vec_off, pl.sca_off},
+                          stream);
+}
+
+int zs_lamb_finish(const float* sums3, int64_t n_params, const float* lr, float* norms2,
+                   float* ratios, float* neg_s, uintptr_t stream) {
+  ZS_REQUIRE(n_params >= 0 && (n_params == 0 || (sums3 && lr && norms2 && ratios && neg_s)),
+             "zs_lamb_finish: %lld parameters at NULL", (long long)n_params);
+  if (n_params == 0) return ZS_OK;
+  return zs::lamb_finish(sums3, n_params, lr, norms2, ratios, neg_s, stream);
+}
+
+int zs_lambset_bind_params(zs_adamset* as, int64_t n, const int32_t* seg_param) {
+  const char* fn = "zs_lambset_bind_params";
+  ZS_REQUIRE(as != nullptr, "%s: NULL set", fn);
+  ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create", fn);
+  ZS_REQUIRE(n == int64_t(as->in_n.size()), "%s: %lld parameters for a set of %lld segments", fn,
+             (long long)n, (long long)as->in_n.size());
+  ZS_REQUIRE(n == 0 || seg_param != nullptr, "%s: NULL table", fn);
+  std::vector<int32_t> ep(as->entry_in.size());
+  int64_t mx = -1;
+  for (size_t e = 0; e < ep.size(); ++e) {
+    ep[e] = seg_param[as->entry_in[e]];
+    ZS_REQUIRE(ep[e] >= 0, "%s: seg_param[%d] = %d is negative", fn, int(as->entry_in[e]), int(ep[e]));
+    mx = std::max<int64_t>(mx, ep[e]);
+  }
+  if (as->d_entry_param && ep == as->entry_param) return ZS_OK;  // bound to these already
+  int32_t* d = nullptr;
+  const int rc = upload(ep, &d);
+  if (rc != ZS_OK) return rc;
+  // (a rebind frees the old table, which synchronises the device: the engines bind once per set)
+  if (as->d_entry_param) (void)hipFree(as->d_entry_param);
+  as->d_entry_param = d;
+  as->entry_param = std::move(ep);
+  as->param_max = mx;
+  return ZS_OK;
+}
+
+int zs_lambset_run_apply(const zs_adamset* as, const zs_lamb_hparams* h, const float* neg_s,
+                         int64_t n_params, uintptr_t stream) {
+  const char* fn = "zs_lambset_run_apply";
+  const int rc = lamb_check(fn, as, h);
+  if (rc != ZS_OK) return rc;
+  if (as->nvec + as->nsca == 0) return ZS_OK;
+  ZS_REQUIRE(as->d_entry_param != nullptr, "%s: no parameters bound (zs_lambset_bind_params)", fn);
+  ZS_REQUIRE(neg_s != nullptr, "%s: neg_s is NULL", fn);
+  ZS_REQUIRE(as->param_max < n_params, "%s: a segment is bound to parameter %lld of %lld", fn,
+             (long long)as->param_max, (long long)n_params);
+  return zs::lamb_apply(lamb_tables(as), *h, as->d_entry_param, neg_s, stream);
 }
 
 int zs_update_norms(const float* sums3, int64_t n_params, const float* coef, float* update_norms,
@@ -3714,6 +3879,7 @@ int zs_adamset_destroy(zs_adamset* as) {
   if (as->d_vec_slots) (void)hipFree(as->d_vec_slots);
   if (as->d_sca_slots) (void)hipFree(as->d_sca_slots);
   if (as->d_un_off) (void)hipFree(as->d_un_off);
+  if (as->d_entry_param) (void)hipFree(as->d_entry_param);
   delete as;
   return ZS_OK;
 }
@@ -3984,3 +4150,5 @@ int zs_device_free(void* p) {
 }
 
 }  // extern "C"
+
+#endif  // ZS_UPDATE_SKELETON_ONLY

@@ -46,6 +46,8 @@ EXPORTED = (
     "zs_adamset_update_norm_slots", "zs_adamset_run_stats", "zs_update_norms",
     "zs_sgd_hparams_init", "zs_sgdset_create", "zs_sgdset_run",
     "zs_lion_hparams_init", "zs_lionset_create", "zs_lionset_run",
+    "zs_lamb_hparams_init", "zs_lambset_run_moments", "zs_lamb_finish", "zs_lambset_bind_params",
+    "zs_lambset_run_apply",
     "zs_adafactor_hparams_init", "zs_adafactorset_create", "zs_adafactorset_run",
     "zs_adafactorset_run_pass", "zs_adafactorset_stats", "zs_adafactorset_destroy",
     "zs_muon_hparams_init", "zs_muonset_create", "zs_muonset_run", "zs_muonset_run_pass",
@@ -97,6 +99,14 @@ class LionHParams(ctypes.Structure):
                 ("one_minus_beta1", ctypes.c_float), ("beta2", ctypes.c_float),
                 ("one_minus_beta2", ctypes.c_float), ("decay_mul", ctypes.c_float),
                 ("grad_div", ctypes.c_float), ("carry_mul", ctypes.c_float),
+                ("maximize", ctypes.c_int32)]
+
+
+class LambHParams(ctypes.Structure):
+    _fields_ = [("one_minus_beta1", ctypes.c_float), ("beta2", ctypes.c_float),
+                ("one_minus_beta2", ctypes.c_float), ("bc1", ctypes.c_float),
+                ("bc2_sqrt", ctypes.c_float), ("eps", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("grad_div", ctypes.c_float),
                 ("maximize", ctypes.c_int32)]
 
 
@@ -227,6 +237,12 @@ _SIGS = {
                            ctypes.POINTER(_P)], ctypes.c_int),
     "zs_lionset_run": ([_P, ctypes.POINTER(LionHParams), _P, ctypes.c_int, ctypes.c_uint64,
                         ctypes.c_uint32, ctypes.c_uint32, _U], ctypes.c_int),
+    "zs_lamb_hparams_init": ([ctypes.c_double] * 4 + [ctypes.c_int] * 2 +
+                             [_I64, ctypes.c_double, ctypes.POINTER(LambHParams)], ctypes.c_int),
+    "zs_lambset_run_moments": ([_P, ctypes.POINTER(LambHParams), _P, _P, _U], ctypes.c_int),
+    "zs_lamb_finish": ([_P, _I64, _P, _P, _P, _P, _U], ctypes.c_int),
+    "zs_lambset_bind_params": ([_P, _I64, _P], ctypes.c_int),
+    "zs_lambset_run_apply": ([_P, ctypes.POINTER(LambHParams), _P, _I64, _U], ctypes.c_int),
     "zs_adafactor_hparams_init": ([ctypes.c_double] * 2 + [ctypes.c_int] + [ctypes.c_double] * 4 +
                                   [ctypes.c_int, ctypes.c_double, ctypes.POINTER(AdafactorHParams)],
                                   ctypes.c_int),

@@ -21,7 +21,7 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import (check_adafactor, check_muon, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
+from ._update import (check_adafactor, check_lamb, check_muon, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
                       check_max_grad_norm, check_param_grad_norms, check_update_norms,
                       check_update_norms_group,
                       check_skip_nonfinite, check_master_free, check_master_free_group,
@@ -67,6 +67,17 @@ def lion_group_hparams(group: dict) -> dict:
                 maximize=bool(group.get("maximize", False)), amsgrad=False)
 
 
+def lamb_group_hparams(group: dict) -> dict:
+    """Hyper-parameters of one zero_amd.optim.LAMB param group."""
+    lr = group["lr"]
+    lr = float(lr.item()) if torch.is_tensor(lr) else float(lr)
+    beta1, beta2 = group["betas"]
+    return dict(lr=lr, beta1=float(beta1), beta2=float(beta2), eps=float(group["eps"]),
+                weight_decay=float(group.get("weight_decay", 0.0)),
+                bias_correction=bool(group.get("bias_correction", True)),
+                maximize=bool(group.get("maximize", False)), amsgrad=False)
+
+
 def adafactor_group_hparams(group: dict) -> dict:
     """Hyper-parameters of one torch.optim.Adafactor param group (``lr``: a float, or the
     one-element tensor torch allows); ``foreach`` only picks torch's implementation."""
@@ -98,6 +109,8 @@ def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
         return muon_group_hparams(group)
     if kind == "lion":
         return lion_group_hparams(group)
+    if kind == "lamb":
+        return lamb_group_hparams(group)
     if kind == "adafactor":
         return adafactor_group_hparams(group)
     return sgd_group_hparams(group) if kind == "sgd" else adam_group_hparams(group, optimizer)
@@ -105,8 +118,9 @@ def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
 
 def optimizer_kind(optimizer: Optimizer) -> str:
     """"adam" (torch.optim.Adam / AdamW), "sgd" (torch.optim.SGD), "lion" (zero_amd.optim.Lion),
-    "adafactor" (torch.optim.Adafactor) or "muon" (torch.optim.Muon); TypeError for anything else."""
-    from .optim import Lion
+    "adafactor" (torch.optim.Adafactor), "muon" (torch.optim.Muon) or "lamb" (zero_amd.optim.LAMB);
+    TypeError for anything else."""
+    from .optim import LAMB, Lion
 
     if isinstance(optimizer, torch.optim.Adam):
         return "adam"
@@ -114,12 +128,14 @@ def optimizer_kind(optimizer: Optimizer) -> str:
         return "sgd"
     if isinstance(optimizer, Lion):
         return "lion"
+    if isinstance(optimizer, LAMB):
+        return "lamb"
     if isinstance(optimizer, torch.optim.Adafactor):
         return "adafactor"
     if isinstance(optimizer, torch.optim.Muon):
         return "muon"
     raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD / Adafactor / Muon or "
-                    f"zero_amd.optim.Lion (got {type(optimizer).__name__})")
+                    f"zero_amd.optim.Lion / LAMB (got {type(optimizer).__name__})")
 
 
 class ShardedOptimizerBase:
@@ -180,6 +196,11 @@ class ShardedOptimizerBase:
                        state_dtype=state_dtype, state_rounding=state_rounding, master=master,
                        ema_decay=ema_decay, param_update_norms=param_update_norms)
             arena = "flat"
+        if self._kind == "lamb":  # (likewise)
+            check_lamb(carry=self._carry and get("ws") > 1, arena=arena, overlap=overlap,
+                       skip_nonfinite=skip_nonfinite, state_dtype=state_dtype,
+                       state_rounding=state_rounding, master=master, ema_decay=ema_decay,
+                       param_update_norms=param_update_norms)
         # skip_nonfinite (with max_grad_norm; Adam): a step whose gradient norm is not finite is
         # skipped on the device — nothing in device memory changes, the host proceeds as for any
         # step; refused here, on every rank and before anything collective
@@ -252,8 +273,8 @@ class ShardedOptimizerBase:
                 raise ValueError("zero_amd: state_dtype=torch.bfloat16 is not supported with the "
                                  f"bucket arena (arena={arena!r}, layout={layout!r}); use the "
                                  "flat arena")
-        if self._kind in ("sgd", "lion"):
-            # the SGD and Lion updates run on the flat arena (and its rounds) only
+        if self._kind in ("sgd", "lion", "lamb"):
+            # the SGD, Lion and LAMB updates run on the flat arena (and its rounds) only
             name = KIND_NAMES[self._kind]
             if arena == "buckets":
                 raise ValueError(f"zero_amd: {name} is not supported with arena='buckets' "
@@ -446,12 +467,28 @@ class ShardedOptimizerBase:
         return None if clip is None else clip.param_norms
 
     @property
+    def last_trust_ratios(self):
+        """1-D fp32 device tensor of ``len(params)`` (zero_amd.optim.LAMB): entry i is the trust
+        ratio the last step applied to parameter i, ‖w‖ / ‖u‖ on the fp32 master, or 1 where a norm
+        is 0 and for a parameter without a gradient; NaN before the first step.  The same bits on
+        every rank, valid in stream order after step(), overwritten (the same tensor) by the next
+        step; None for another optimizer."""
+        un = None if self.engine is None else getattr(self.engine, "stats", None)
+        return getattr(un, "ratios", None)
+
+    @property
     def last_param_update_norms(self):
         """1-D fp32 device tensor of ``len(params)`` (``param_update_norms``): entry i is the L2
         norm of (fp32 master after - fp32 master before) of parameter i in the last step; +0.0 for
         a parameter that step did not update and for a step ``skip_nonfinite`` skipped; NaN before
         the first step.  The same bits on every rank, valid in stream order after step(),
-        overwritten (the same tensor) by the next step; None without the option."""
+        overwritten (the same tensor) by the next step; None without the option.
+
+        Under zero_amd.optim.LAMB (always reported): entry i is ‖u‖, the norm of the direction
+        u = m_hat / (sqrt(v_hat) + eps) + weight_decay * w before the trust ratio and the learning
+        rate scale it -- not the norm of the parameter's change --, and ``last_param_weight_norms``
+        is ‖w‖ of the fp32 master before the step; a parameter without a gradient has +0.0 in
+        both."""
         un = None if self.engine is None else getattr(self.engine, "stats", None)
         return None if un is None else un.update
 

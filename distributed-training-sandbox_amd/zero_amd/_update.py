@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .checkpoint import step_of
-from .kernels import adam_hparams, lion_hparams, sgd_hparams, sr_keys
+from .kernels import adam_hparams, lamb_hparams, lion_hparams, sgd_hparams, sr_keys
 
 # master="none": bf16 parameters without any master — the fused update reads the bf16 parameter,
 # runs the fp32 rule and stores it back rounded stochastically ("Master-free bf16
@@ -49,10 +49,46 @@ def check_params(params):
 BF16_STATE_MIN_ONE_MINUS_BETA = 2.0 ** -8
 
 
-KINDS = ("adam", "sgd", "lion", "adafactor", "muon")
+KINDS = ("adam", "sgd", "lion", "adafactor", "muon", "lamb")
 # what the messages call the optimizer of a kind that an option does not support
 KIND_NAMES = {"sgd": "torch.optim.SGD", "lion": "zero_amd.optim.Lion",
-              "adafactor": "torch.optim.Adafactor", "muon": "torch.optim.Muon"}
+              "adafactor": "torch.optim.Adafactor", "muon": "torch.optim.Muon",
+              "lamb": "zero_amd.optim.LAMB"}
+
+
+def check_lamb(*, carry: bool = False, arena: str = "flat", overlap: bool = False,
+               zero3_reference: bool = False, skip_nonfinite: bool = False, state_dtype=None,
+               state_rounding=None, master: str = "split", ema_decay=None,
+               param_update_norms: bool = False) -> None:
+    """What zero_amd.optim.LAMB cannot be combined with, as ValueError.  The update is two fused
+    passes around a per-parameter reduction: it runs where every update of a step can be collected
+    before the first is launched (the flat arena without overlap, ZeRO-3's update mode), on fp32
+    moments over an fp32 or split master ("Fused LAMB"; §8 lists these as
+    follow-ups)."""
+    def no(what: str, why: str):
+        raise ValueError(f"zero_amd: LAMB ({KIND_NAMES['lamb']}) is not supported with {what} "
+                         f"({why})")
+
+    if carry:
+        no("ZeRO-1 at world size > 1", "the gradient carry has no LAMB instances")
+    if arena == "buckets":
+        no("arena='buckets'", "the two passes run on the flat arena")
+    if overlap:
+        no("overlap=True", "the trust ratio needs every owned gradient reduced before pass L2")
+    if zero3_reference:
+        no("ZeRO-3 reference mode", "the fused passes are update mode's")
+    if skip_nonfinite:
+        no("skip_nonfinite", "the guarded instances are Adam's")
+    if state_dtype is not None and state_dtype != torch.float32:
+        no(f"state_dtype={state_dtype}", "pass L2 forms u again from fp32 moments")
+    if state_rounding is not None:
+        no("state_rounding", "the moments are fp32")
+    if master == "none":
+        no("master='none'", "the norms are taken on an fp32 or split master")
+    if ema_decay is not None:
+        no("ema_decay", "the EMA is fused into the Adam update")
+    if param_update_norms:
+        no("param_update_norms", "LAMB reports its own norms: last_param_update_norms is ‖u‖")
 
 
 def check_adafactor(*, zero3: bool = False, carry: bool = False, layout: str = "reference",
@@ -321,7 +357,7 @@ def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = 
     if kind == "adafactor":  # the factored state is an arena of its own (flat.AdafactorState)
         momentum = False
     # (Muon: ``m`` alone, always: the momentum buffer)
-    names = ["m", "v"][:2 if kind == "adam" else 1 if kind in ("lion", "muon")
+    names = ["m", "v"][:2 if kind in ("adam", "lamb") else 1 if kind in ("lion", "muon")
                        else int(bool(momentum))]
     names += ["carry"] * bool(carry) + ["master"] * bool(fp32_master)
     lay = {name: (k * L, torch.float32) for k, name in enumerate(names)}
@@ -343,11 +379,12 @@ class UpdateCore:
         from .engine import probed_zeros  # (engine.py builds on this module)
 
         if kind not in KINDS:
-            raise ValueError("UpdateCore: kind must be 'adam', 'sgd', 'lion', 'adafactor' or "
-                             f"'muon' (got {kind!r})")
+            raise ValueError("UpdateCore: kind must be 'adam', 'sgd', 'lion', 'adafactor', 'muon' "
+                             f"or 'lamb' (got {kind!r})")
         # the update: torch.optim.Adam's, torch.optim.SGD's (`momentum`: some group has a
         # momentum, so the shard holds a momentum buffer; none of them: no optimizer state at all)
-        # or zero_amd.optim.Lion's (one moment, exp_avg, always)
+        # or zero_amd.optim.Lion's (one moment, exp_avg, always); zero_amd.optim.LAMB's has Adam's
+        # state and two launches per set, with a LambNorms stage between them
         self.kind, self.L, self.device, self.ws = kind, int(L), device, ws
         self.group_of = list(group_of)
         # the moments' dtype: torch.float32, or torch.bfloat16 (Adam without amsgrad or carry; one
@@ -519,6 +556,11 @@ class UpdateCore:
             if self.state_rounding == "stochastic":  # the launch's keys travel with its struct
                 hp.sr_keys = sr_keys(self.state_seed, int(key))
             return hp
+        if self.kind == "lamb":
+            hp = lamb_hparams(hpd["beta1"], hpd["beta2"], hpd["eps"], hpd["weight_decay"], int(key),
+                              bias_correction=hpd["bias_correction"], maximize=hpd["maximize"],
+                              grad_div=float(self.ws))
+            return hp
         if self.state_dtype == torch.bfloat16:  # (groups are mutable between steps)
             check_bf16_state_group(hpd, self.state_rounding)
         if self.master_free:
@@ -574,6 +616,10 @@ class UpdateCore:
         if self.kind == "lion":
             sr = (self.m.data_ptr(), hp.sr_keys) if self.state_rounding == "stochastic" else None
             aset.run(hp, stream, coef=coef, guard=guard, sr=sr)
+        elif self.kind == "lamb":  # pass L1; launch_apply is L2
+            if stats is None or guard:
+                raise ValueError("zero_amd: LAMB: a launch without its partials, or a guarded one")
+            aset.run_lamb_moments(hp, int(stats), stream, coef=coef)
         elif self.update_norms:
             if stats is None:
                 raise ValueError("zero_amd: param_update_norms: a launch without its partials")
@@ -595,6 +641,19 @@ class UpdateCore:
             e1.record(stream)
             ev.append((e0, e1, aset.bytes))
         self.last_adam_bytes += aset.bytes
+
+    def launch_apply(self, aset, hp, neg_s, stream) -> None:
+        """LAMB's pass L2 over ``aset`` (``neg_s``: ``LambNorms.neg_s``, finished in stream order
+        before this launch); timed like ``launch``."""
+        ev = self.timing_events
+        if ev is not None:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+        aset.run_lamb_apply(hp, neg_s, stream)
+        if ev is not None:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record(stream)
+            ev.append((e0, e1, aset.bytes))
 
     def run_parts(self, tag, rows, param_idx, hparams_of, stream, *, carry_mul=None, gptr=None,
                   defer=None, new_set=None):
@@ -910,3 +969,86 @@ class UpdateNorms:
         from .kernels import update_norms
 
         update_norms(self.sums3, self.n_params, coef_ptr, self.update, self.weight, stream)
+
+
+class LambNorms(UpdateNorms):
+    """The stage between the two passes of a "lamb" core ("Fused LAMB"), shared by the
+    ZeRO-1/2 flat arena and ZeRO-3's update mode like its base: ``prepare`` also binds every set's
+    rows to their parameters, pass L1 of set k runs with ``stats=planes(k)``, then in stream order
+    ``reduce`` (``sums3`` = [sum u^2 | sum p^2 | touched], which the caller all-reduces at world
+    size > 1), ``finish`` and ``apply`` (pass L2).  ``weight`` is ‖w‖ of the fp32 master before the
+    step, ``update`` is ‖u‖ -- the norm of the direction, not of the parameter's change --,
+    ``ratios`` the trust ratios and ``neg_s`` = -(lr * ratio): the same bits on every rank, NaN
+    before the first step.  A parameter without a gradient: norms +0.0, ratio 1."""
+
+    def __init__(self, core: UpdateCore):
+        super().__init__(core)
+        dev, n = core.device, self.n_params
+        self.norms2 = torch.full((2 * n,), float("nan"), dtype=torch.float32, device=dev)
+        self.weight, self.update = self.norms2[:n], self.norms2[n:]
+        self.ratios = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
+        self.neg_s = torch.zeros(n, dtype=torch.float32, device=dev)
+        # the learning rate per parameter: filled per group by a kernel with the value in its
+        # arguments, in stream order, when the group's lr changed -- no copy from the host
+        self.lr = torch.zeros(n, dtype=torch.float32, device=dev)
+        gof = np.asarray(core.group_of, np.int64)
+        self._group_idx = {int(g): torch.from_numpy(np.nonzero(gof == g)[0]).to(dev)
+                           for g in np.unique(gof)}
+        # (the host's copy of what ``lr`` holds: valid because ``finish`` alone writes ``lr``, and the
+        # groups are those of construction -- ``add_param_group`` afterwards is not supported)
+        self._group_lr = {}
+
+    def prepare(self, deferred, seg_params) -> None:
+        super().prepare(deferred, seg_params)
+        for (aset, _, _), idx in zip(deferred, seg_params):
+            aset.bind_params(idx)
+
+    def finish(self, hparams_of, stream) -> None:
+        """After the caller's all-reduce of ``sums3``: the norms, the ratios and ``neg_s``."""
+        from .kernels import lamb_finish
+
+        with torch.cuda.stream(stream):
+            for g, idx in self._group_idx.items():
+                lr = float(hparams_of(g)["lr"])
+                if self._group_lr.get(g) != lr:
+                    self.lr.index_fill_(0, idx, lr)
+                    self._group_lr[g] = lr
+        lamb_finish(self.sums3, self.n_params, self.lr, self.norms2, self.ratios, self.neg_s,
+                    stream)
+
+    def apply(self, deferred, first, last, stream) -> None:
+        """Pass L2 of ``deferred[first:last]``."""
+        for k in range(first, min(last, len(deferred))):
+            aset, hp, _ = deferred[k]
+            self.core.launch_apply(aset, hp, self.neg_s, stream)
+
+
+class LambSetStage:
+    """``LambNorms`` for one ``AdamSet`` outside a core and at world size 1 (tools/lamb_ab.py, the
+    kernel test): binds ``seg_params``, owns the set's ``partials`` (two planes, filled with
+    ``fill``), the CSR, ``sums3``, ``lr`` (one value for all ``n_params``), ``norms2``, ``ratios`` and
+    ``neg_s``; ``finish`` is the two reduces and the finishing kernel."""
+
+    def __init__(self, aset, seg_params, n_params: int, lr: float, device, fill: float = 0.0):
+        seg_params = np.asarray(seg_params, np.int64)
+        aset.bind_params(seg_params)
+        off = aset.update_norm_offsets
+        csr, touched = UpdateNorms.tables([0], [off], [seg_params], n_params)
+        self.n, self.nr = n_params, (len(csr) - (n_params + 1)) // 3
+        self.csr = torch.from_numpy(csr).to(device)
+        self.partials = torch.full((max(2 * int(off[-1]), 1),), fill, dtype=torch.float64,
+                                   device=device)
+        self.sums3 = torch.zeros(3 * n_params, device=device)
+        self.sums3[2 * n_params:] = torch.from_numpy(touched).to(device)
+        self.lr = torch.full((n_params,), lr, device=device)
+        self.norms2, self.ratios, self.neg_s = (torch.zeros(j * n_params, device=device)
+                                                for j in (2, 1, 1))
+
+    def finish(self, stream) -> None:
+        from .kernels import lamb_finish, sqnorm_reduce_params
+
+        n, nr, t = self.n, self.nr, self.csr
+        for plane in (0, 1):
+            sqnorm_reduce_params(self.partials, t[:n + 1], t[n + 1 + plane * nr:n + 1 + (plane + 1) * nr],
+                                 t[n + 1 + 2 * nr:], n, self.sums3[plane * n:], stream)
+        lamb_finish(self.sums3, n, self.lr, self.norms2, self.ratios, self.neg_s, stream)

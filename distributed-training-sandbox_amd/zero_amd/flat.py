@@ -48,7 +48,7 @@ import torch
 
 from . import _lib
 from ._hooks import WeakCall
-from ._update import GradClip, UpdateNorms
+from ._update import GradClip, LambNorms, UpdateNorms
 from .comm import StreamEvent
 from .engine import ALIGN_ELEMS, ShardEngine, _ptr
 from .kernels import (AdafactorSet, MuonSet, adafactor_hparams, check_extents,
@@ -104,6 +104,9 @@ class FlatEngine(ShardEngine):
         if self.update_norms:  # the stage and its NaN-filled results exist from construction on
             self.stats = UpdateNorms(self)
             self.ev_stats = (StreamEvent(), StreamEvent())  # around the sums' all-reduce
+        if kind == "lamb":  # likewise the stage between LAMB's two passes
+            self.stats = LambNorms(self)
+            self.ev_stats = (StreamEvent(), StreamEvent())
         self.arena_kind = "flat"
         self.layout = layout
         plan, es, dev, dt = self.plan, self.es, self.device, self.dtype
@@ -476,7 +479,7 @@ class FlatEngine(ShardEngine):
                 aset.set_grads(g, stream)
             self.launch(aset, hp, stream, stats=self.stats.planes(k))
 
-    def _stats_finish(self, stream):
+    def _stats_finish(self, stream, hparams_of=None):
         """After the step's last update: [sum d^2 | sum p1^2 | touched] per parameter, one
         all-reduce of the 3 n floats on the communication stream (ordered by events on both
         sides; every parameter has one owner and the others add 0: the sum is exact), the norms.
@@ -490,6 +493,9 @@ class FlatEngine(ShardEngine):
             self.comm.all_reduce(st.sums3, cs)
             self.ev_stats[1].record(cs)
             stream.wait_event(self.ev_stats[1])
+        if self.kind == "lamb":
+            st.finish(hparams_of, stream)
+            return
         guarded = self.max_grad_norm is not None and self.skip_nonfinite
         st.finish(self.clip.out.data_ptr() + 4 if guarded else None, stream)
 
@@ -856,6 +862,7 @@ class FlatEngine(ShardEngine):
                 self._clip_prepare(deferred)
             if stats:
                 self.stats.prepare(deferred, [aset.seg_params for aset, _, _ in deferred])
+        lamb = self.kind == "lamb"  # two passes: L1 as the stats run, the norms, then L2
         if self.ws == 1:  # zero1.py:107-108 / zero2.py:120 at ws=1: Adam on the local grads
             with _lib.phase_range("optimizer_step"):
                 if clip:
@@ -870,7 +877,9 @@ class FlatEngine(ShardEngine):
                     for rd in self.rounds:
                         self._adam_round(rd, has, cmul, hps, hparams_of, stream, gptr)
                 if stats:
-                    self._stats_finish(stream)
+                    self._stats_finish(stream, hparams_of)
+                if lamb:
+                    self.stats.apply(deferred, 0, len(deferred), stream)
             if self.inplace:
                 if self.overlap:
                     self.launched_in_backward = self.ov_launched
@@ -914,7 +923,13 @@ class FlatEngine(ShardEngine):
                 else:
                     stream.wait_event(self.ev_red[rd.j])
                     self._adam_round(rd, has, cmul, hps, hparams_of, stream)
-                self.ev_adam[rd.j].record(stream)
+                if not lamb:
+                    self.ev_adam[rd.j].record(stream)
+            if lamb:  # every round's L1 is queued: the norms, then L2 round by round
+                self._stats_finish(stream, hparams_of)
+                for k, rd in enumerate(self.rounds):
+                    self.stats.apply(deferred, ends[k - 1] if k else 0, ends[k], stream)
+                    self.ev_adam[rd.j].record(stream)
         with _lib.phase_range("broadcast_parameters"):  # zero1.py:91-102
             for rd in self.rounds:
                 cs.wait_event(self.ev_adam[rd.j])
@@ -922,8 +937,8 @@ class FlatEngine(ShardEngine):
                 self._bcast_round(rd, cs)
                 self.ev_bc[rd.j].record(cs)
                 self._timed_end(e0, cs, "ag", int(rd.count.sum()))
-        if stats:  # (behind the broadcasts on the communication stream: they do not wait for it)
-            self._stats_finish(stream)
+        if stats and not lamb:  # (behind the broadcasts on the communication stream: they do not
+            self._stats_finish(stream)  # wait for it)
         stream.wait_event(self.ev_bc[self.K - 1])  # the parameters are P: next forward reads it
         self._reinstall(has, view)
 

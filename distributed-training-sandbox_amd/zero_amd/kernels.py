@@ -10,6 +10,8 @@ finite; ``run_sr`` with ``sr_keys`` stores bf16 moments with stochastic rounding
 ``SgdSet``   — the same tables with torch.optim.SGD's update (momentum, Nesterov); ``sgd_hparams``.
 ``LionSet``  — the same tables with zero_amd.optim.Lion's update (one moment, fp32 or bf16);
 ``lion_hparams``.
+``AdamSet.run_lamb_moments`` / ``lamb_finish`` / ``AdamSet.run_lamb_apply`` — zero_amd.optim.LAMB's
+update over an Adam set, two passes (csrc/zs_lamb.hip); ``lamb_hparams``.
 ``AdafactorSet`` — torch.optim.Adafactor's update over a table of matrices (csrc/zs_adafactor.hip):
 factored second moment, three passes, every scalar on the device; ``adafactor_hparams``.
 ``MuonSet`` — torch.optim.Muon's update over a table of matrices (csrc/zs_muon.hip): momentum, the
@@ -27,11 +29,17 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (AdafactorHParams, AdafactorSeg, AdamHParams, AdamSeg, LionHParams, MuonHParams,
-                   MuonSeg, SgdHParams)
+from ._lib import (AdafactorHParams, AdafactorSeg, AdamHParams, AdamSeg, LambHParams, LionHParams,
+                   MuonHParams, MuonSeg, SgdHParams)
 
 _PU64 = ctypes.POINTER(ctypes.c_uint64)
 _PI64 = ctypes.POINTER(ctypes.c_int64)
+
+
+def adam_groups(split: bool) -> int:
+    """float4 groups per thread of the update kernels (csrc/zs_kernels.hip adam_groups): a chunk is
+    256 * 4 * adam_groups elements, and a lane sums 4 * adam_groups fp32 terms of it."""
+    return 4 if split else 2
 
 
 def stream_handle(stream) -> int:
@@ -339,6 +347,35 @@ class AdamSet:
         _lib.call("zs_adamset_run_stats", self._h, ctypes.byref(hp), ptr, int(bool(guard)),
                   partials or None, stream_handle(stream))
 
+    # fused LAMB (zero_amd.optim.LAMB) over an Adam set: L1, then lamb_finish, then L2
+    def run_lamb_moments(self, hp: LambHParams, partials, stream, coef=None) -> None:
+        """Pass L1 (zs_lambset_run_moments): m and v move as Adam's, the parameter stays; per slot
+        the sums of u^2 and of master^2 into the two planes of ``partials`` (``run_stats``'s
+        shape).  A row without a gradient is left out: its slots get +0.0."""
+        if not isinstance(partials, int):
+            assert partials.dtype.itemsize == 8
+            assert partials.numel() >= 2 * self.update_norm_offsets[-1]
+            partials = partials.data_ptr()
+        ptr = None if coef is None else coef if isinstance(coef, int) else coef.data_ptr()
+        _lib.call("zs_lambset_run_moments", self._h, ctypes.byref(hp), ptr, partials or None,
+                  stream_handle(stream))
+
+    def bind_params(self, seg_params) -> None:
+        """Row i belongs to parameter ``seg_params[i]`` (zs_lambset_bind_params; the same indices
+        again: nothing happens)."""
+        idx = np.ascontiguousarray(np.asarray(seg_params, dtype=np.int32))
+        assert idx.shape == (self.nseg,)
+        if getattr(self, "_bound", None) is not None and np.array_equal(idx, self._bound):
+            return
+        _lib.call("zs_lambset_bind_params", self._h, self.nseg, idx.ctypes.data)
+        self._bound = idx
+
+    def run_lamb_apply(self, hp: LambHParams, neg_s, stream) -> None:
+        """Pass L2 (zs_lambset_run_apply): p = fma(neg_s[parameter of the row], u, p) with u formed
+        again from the moments L1 stored; ``neg_s``: the fp32 device tensor ``lamb_finish`` wrote."""
+        _lib.call("zs_lambset_run_apply", self._h, ctypes.byref(hp), neg_s.data_ptr(),
+                  int(neg_s.numel()), stream_handle(stream))
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib is not None:
@@ -445,7 +482,28 @@ class LionSet(AdamSet):
         raise _lib.ZeroAmdError("zs_lionset_run", _lib.ZS_ERR_INVALID,
                                 "a Lion set runs through LionSet.run")
 
-    run_sr = run_psr = run_ema = run_stats = _not_lion
+    run_sr = run_psr = run_ema = run_stats = run_lamb_moments = run_lamb_apply = _not_lion
+
+
+def lamb_hparams(beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=0.0, step=1, *,
+                 bias_correction=True, maximize=False, grad_div=1.0) -> LambHParams:
+    """A zero_amd.optim.LAMB group's scalars at step count ``step`` (zs_lamb_hparams_init); the
+    learning rate goes to ``lamb_finish``."""
+    hp = LambHParams()
+    _lib.call("zs_lamb_hparams_init", float(beta1), float(beta2), float(eps), float(weight_decay),
+              int(bool(bias_correction)), int(bool(maximize)), int(step), float(grad_div),
+              ctypes.byref(hp))
+    return hp
+
+
+def lamb_finish(sums3, n: int, lr, norms2, ratios, neg_s, stream) -> None:
+    """Between LAMB's passes (zs_lamb_finish) over ``sums3`` = [sum u^2 | sum p^2 | touched] and the
+    per-parameter learning rates ``lr`` (fp32 device tensors): ``norms2`` = [‖w‖ | ‖u‖], the trust
+    ratios and ``neg_s`` = -(lr * ratio)."""
+    assert sums3.numel() >= 3 * n and norms2.numel() >= 2 * n
+    assert min(lr.numel(), ratios.numel(), neg_s.numel()) >= n
+    _lib.call("zs_lamb_finish", sums3.data_ptr(), int(n), lr.data_ptr(), norms2.data_ptr(),
+              ratios.data_ptr(), neg_s.data_ptr(), stream_handle(stream))
 
 
 def adafactor_hparams(lr=1e-2, beta2_decay=-0.8, eps=(None, 1e-3), d=1.0, weight_decay=0.0, *,

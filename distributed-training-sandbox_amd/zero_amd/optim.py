@@ -1,5 +1,8 @@
 """Optimizers torch does not ship, in the form ``ShardedOptimizer`` wraps.
 
+``LAMB`` (You et al. 2020, arXiv:1904.00962): Adam's direction rescaled per parameter by the trust
+ratio; see the class.
+
 ``Lion`` (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms", arXiv:2302.06675): one
 moment, the sign of an interpolation as the update, decoupled weight decay, no bias correction.
 Its own ``step()`` is plain torch and runs on any device; handed to ``zero_amd.zero1`` / ``zero2`` /
@@ -63,4 +66,88 @@ class Lion(Optimizer):
                 u = m.mul(beta1).add_(g, alpha=1 - beta1).sign_()
                 p.add_(u, alpha=-lr)
                 m.mul_(beta2).add_(g, alpha=1 - beta2)
+        return loss
+
+
+class LAMB(Optimizer):
+    """``LAMB(params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, *,
+    bias_correction=True, maximize=False)``: You et al. 2020, "Large Batch Optimization for Deep
+    Learning: Training BERT in 76 minutes" (arXiv:1904.00962) -- Adam's direction, rescaled per
+    parameter by the trust ratio ``‖w‖ / ‖u‖``.
+
+    Per parameter, with ``m = state["exp_avg"]``, ``v = state["exp_avg_sq"]`` and ``t`` the step
+    count after the increment::
+
+        m.lerp_(g, 1 - beta1)
+        v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+        u = (m / (1 - beta1**t)).div_(sqrt(v).div_(sqrt(1 - beta2**t)).add_(eps))  # IEEE sqrt
+        u.add_(p, alpha=weight_decay)                  # decoupled, inside the trust ratio
+        r = 1 if ‖p‖ == 0 or ‖u‖ == 0 else ‖p‖ / ‖u‖    # fp32; a NaN norm gives a NaN ratio
+        p.add_(u, alpha=-(fp32(lr) * r))
+
+    Without ``bias_correction`` both corrections are 1.  The trust ratio applies to every
+    parameter of a group.  ``state[p]`` holds ``step`` (an fp32 CPU scalar, as torch.optim.Adam
+    keeps it), ``exp_avg`` and ``exp_avg_sq``.  Handed to ``zero_amd.zero1`` / ``zero2`` /
+    ``zero3.ShardedOptimizer`` the update runs in the fused HIP kernels instead (DESIGN.md §4,
+    "Fused LAMB"), whose moments equal this ``step()``'s on fp32 CPU tensors bit for bit, and whose
+    parameters do given the same ``-s``.
+    """
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6,
+                 weight_decay: float = 0.0, *, bias_correction: bool = True,
+                 maximize: bool = False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      bias_correction=bool(bias_correction), maximize=maximize))
+        # parameter -> the 0-d fp32 trust ratio its last step applied (a report, not state)
+        self.last_trust_ratios = {}
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            beta1, beta2 = group["betas"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("LAMB does not support sparse gradients")
+                g = -p.grad if group["maximize"] else p.grad
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                m, v = state["exp_avg"], state["exp_avg_sq"]
+                state["step"] += 1
+                t = float(state["step"])
+                m.lerp_(g, 1 - beta1)
+                v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+                bc1 = bc2_sqrt = 1.0
+                if group["bias_correction"]:
+                    bc1, bc2_sqrt = 1 - beta1 ** t, (1 - beta2 ** t) ** 0.5
+                # the root through float64: torch's vectorised fp32 CPU sqrt is not correctly
+                # rounded, the kernel's is; the double root rounded to fp32 is (53 >= 2 * 24 + 2)
+                root = v.to(torch.float64).sqrt_().to(v.dtype)
+                u = (m / bc1).div_(root.div_(bc2_sqrt).add_(group["eps"]))
+                if group["weight_decay"] != 0:
+                    u.add_(p, alpha=group["weight_decay"])
+                wn = torch.linalg.vector_norm(p).to(torch.float32)
+                un = torch.linalg.vector_norm(u).to(torch.float32)
+                r = torch.where((wn == 0) | (un == 0), torch.ones_like(wn), wn / un)
+                self.last_trust_ratios[p] = r
+                s = torch.tensor(group["lr"], dtype=torch.float32, device=r.device) * r
+                p.add_(u, alpha=-float(s))  # (the fp32 value, exact in a Python float)
         return loss

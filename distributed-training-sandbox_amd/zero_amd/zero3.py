@@ -69,7 +69,7 @@ from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_BF16_SR, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
 from ._sharded import group_hparams, optimizer_kind
-from ._update import (GradClip, UpdateCore, UpdateNorms, check_adafactor, check_muon, check_bf16_state_group,
+from ._update import (GradClip, LambNorms, UpdateCore, UpdateNorms, check_adafactor, check_lamb, check_muon, check_bf16_state_group,
                       check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group, check_master_free, check_update_norms,
                       check_update_norms_group,
                       check_master_free_group, check_max_grad_norm, check_param_grad_norms, check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
@@ -1854,6 +1854,10 @@ class ShardedOptimizer:
             check_adafactor(zero3=True)
         if optimizer_kind(optimizer) == "muon":
             check_muon(zero3=True, grad_accumulation=bool(grad_accumulation))
+        if optimizer_kind(optimizer) == "lamb":
+            check_lamb(zero3_reference=not update, skip_nonfinite=skip_nonfinite,
+                       state_dtype=state_dtype, state_rounding=state_rounding, master=master,
+                       ema_decay=ema_decay, param_update_norms=param_update_norms)
         self.max_grad_norm = max_grad_norm
         self._check_clip()
         self.skip_nonfinite = check_skip_nonfinite(skip_nonfinite, max_grad_norm,
@@ -2028,6 +2032,8 @@ class ShardedOptimizer:
                                 update_norms=self.param_update_norms)
         if self.param_update_norms:  # the stage and its NaN-filled results exist from here on
             self._stats = UpdateNorms(self._core)
+        if self._kind == "lamb":  # likewise the stage between LAMB's two passes
+            self._stats = LambNorms(self._core)
         if self._core.ema is not None:  # the EMA starts at the master: the chunks, widened
             self._core.ema.copy_(ar.P)
         self._core.timing_events = self._timing_events
@@ -2117,6 +2123,14 @@ class ShardedOptimizer:
         """0-d fp32 device tensor: min(1, max_grad_norm / (last_grad_norm + 1e-6)), as above (NaN:
         ``skip_nonfinite`` skipped the step)."""
         return None if self._clip is None else self._clip.out[1]
+
+    @property
+    def last_trust_ratios(self):
+        """1-D fp32 device tensor of ``len(params)`` (zero_amd.optim.LAMB): the trust ratio the last
+        step applied to each whole parameter, as ``zero2.ShardedOptimizer.last_trust_ratios``; with
+        it ``last_param_update_norms`` is ‖u‖ and ``last_param_weight_norms`` ‖w‖ before the step.
+        None for another optimizer."""
+        return getattr(self._stats, "ratios", None)
 
     @property
     def last_param_update_norms(self):
@@ -2421,7 +2435,7 @@ class ShardedOptimizer:
             for k, (aset, hp, _) in enumerate(deferred):
                 core.launch(aset, hp, cur, stats=stats.planes(k))
         if stats is not None:  # (every rank, also one that updates nothing: the all-reduce)
-            self._stats_finish(cur)
+            self._stats_finish(cur, hps, deferred)
         if self._kind == "sgd":  # torch's SGD keeps no step: the buffer appears after the first
             self._expose_sgd(idx)
         elif uniform and bool((core.steps[idx] == core.steps[idx[0]]).all()):
@@ -2490,7 +2504,7 @@ class ShardedOptimizer:
         clip.run(deferred, 0, len(deferred), cur, stats=self._stats)
         self._last_norm_bytes = clip.last_norm_bytes
 
-    def _stats_finish(self, cur):
+    def _stats_finish(self, cur, hps, deferred):
         """After the step's one fused update (``param_update_norms``; _update.UpdateNorms): each
         parameter's [sum d^2 | sum p1^2 | touched] over this rank's chunks, one all-reduce of the
         3 n floats where ``_clip_update`` sends its own (every rank holds a chunk of a parameter,
@@ -2512,6 +2526,10 @@ class ShardedOptimizer:
                 self.comm.all_reduce(st.sums3, side)
                 done.record(side.cuda_stream)
                 done.wait(cur.cuda_stream)
+        if self._kind == "lamb":  # the ratios, then pass L2 over what L1 ran over
+            st.finish(hps.__getitem__, cur)
+            st.apply(deferred, 0, len(deferred), cur)
+            return
         guarded = self.max_grad_norm is not None and self.skip_nonfinite
         st.finish(self._clip.out.data_ptr() + 4 if guarded else None, cur)
 

@@ -641,6 +641,71 @@ int zs_lionset_run(const zs_adamset* as, const zs_lion_hparams* hp, const float*
                    uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Fused LAMB (You et al. 2020, arXiv:1904.00962), additive in ABI v13.  The update of          */
+/* zero_amd.optim.LAMB on the owned shard, over a set made by zs_adamset_create (fp32 moments,  */
+/* fp32 or split master, no carry, no vmax), in two stream passes with the per-parameter norms  */
+/* between them: no atomics, no host wait, the same bits from run to run.  Over the split       */
+/* master with bf16 gradients the passes move 22 and 16 B/element (Adam's one pass: 26).        */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  /* doubles on the host, rounded to f32 once */
+  float one_minus_beta1;
+  float beta2;
+  float one_minus_beta2;
+  float bc1;          /* 1 - beta1^t; 1 without bias correction */
+  float bc2_sqrt;     /* sqrt(1 - beta2^t); 1 without bias correction */
+  float eps;
+  float weight_decay; /* decoupled, inside the trust ratio: u = fma(wd, p, u); 0 = off */
+  float grad_div;     /* divide the reduced sum by this (world size) */
+  int32_t maximize;
+} zs_lamb_hparams;
+
+/* Fill hp from a LAMB param group's scalars at step count `step` (after the increment, >= 1); the
+ * learning rate is not part of it (zs_lamb_finish takes it per parameter).  ZS_ERR_INVALID for what
+ * zero_amd.optim.LAMB refuses (a beta outside [0, 1), eps < 0, weight_decay < 0), for step < 1,
+ * grad_div <= 0 and a NULL hp. */
+int zs_lamb_hparams_init(double beta1, double beta2, double eps, double weight_decay,
+                         int bias_correction, int maximize, int64_t step, double grad_div,
+                         zs_lamb_hparams* hp);
+/* Pass L1.  Per element of every segment that has a gradient (fp32, only the written fma fused):
+ *   g = sum / grad_div;  [g *= *coef];  [g = -g]
+ *   m = lerp(m, g, 1 - beta1);  v = fma((1 - beta2) * g, g, v * beta2)      (as zs_adamset_run)
+ *   u = (m / bc1) / (sqrt(v) / bc2_sqrt + eps);  [u = fma(wd, p, u)]
+ * m and v are stored, the parameter is not; accu = fma(u, u, accu) and accw = fma(p, p, accw) (p the
+ * fp32 master as loaded) go through zs_adamset_run_stats's partials: the same slots
+ * (zs_adamset_update_norm_slots), plane 0 = sum u^2, plane 1 = sum p^2, every slot written.  A
+ * segment with g == 0 is not part of the step: nothing of it is read or written, its slots get
+ * +0.0.  coef: NULL, or the device scalar of zs_clip_coef.  ZS_ERR_INVALID, nothing launched: a NULL
+ * set or hparams; a set made by zs_sgdset_create, zs_lionset_create or zs_adafactorset_create;
+ * ZS_BF16 state; a ZS_BF16_SR set; the carry or the vmax column; NULL partials for a set that has
+ * slots; bc1 or bc2_sqrt <= 0, eps or weight_decay < 0, grad_div <= 0 in a struct filled by hand. */
+int zs_lambset_run_moments(const zs_adamset* as, const zs_lamb_hparams* hp, const float* coef,
+                           double* partials, uintptr_t stream);
+/* Between the passes, per parameter i of sums3 = [sum u^2 | sum p^2 | touched], n_params floats
+ * each (zs_sqnorm_reduce_params over the two planes; summed over the ranks where a parameter is cut):
+ *   un = (float)sqrt((double)sums3[i]),  wn = (float)sqrt((double)sums3[n_params + i])
+ *   r  = (wn == 0 || un == 0) ? 1 : wn / un;   neg_s[i] = -(lr[i] * r)
+ * norms2 = [wn | un], ratios[i] = r.  A NaN norm gives a NaN ratio.  touched[i] == 0: wn = un = +0.0
+ * and r = 1.  All pointers are device memory.  ZS_ERR_INVALID: n_params < 0, or a NULL pointer with
+ * n_params > 0. */
+int zs_lamb_finish(const float* sums3, int64_t n_params, const float* lr, float* norms2,
+                   float* ratios, float* neg_s, uintptr_t stream);
+/* seg_param[0 .. n) (host memory): the parameter index of each input segment of the set, n the
+ * number it was created with.  Uploaded as one index per table entry; binding the same indices
+ * again does nothing, other indices replace the table (which waits for the device).
+ * ZS_ERR_INVALID: a NULL set, n other than the set's segments, a NULL table, a negative index. */
+int zs_lambset_bind_params(zs_adamset* as, int64_t n, const int32_t* seg_param);
+/* Pass L2, after zs_lamb_finish in stream order.  Per element of every segment that has a gradient:
+ *   u as in L1 from m and v as L1 stored them (the same operations: the same bits)
+ *   p = fma(neg_s[parameter of the segment], u, p)
+ * stored as zs_adamset_run stores the master (ZS_BF16_SPLIT: the bf16 parameter and the residual;
+ * ZS_BF16: master_out and / or p_out).  hp is L1's.  neg_s: n_params device floats.
+ * ZS_ERR_INVALID, nothing launched: what zs_lambset_run_moments refuses of the set and the struct;
+ * a non-empty set without bound parameters; a NULL neg_s; a bound index >= n_params. */
+int zs_lambset_run_apply(const zs_adamset* as, const zs_lamb_hparams* hp, const float* neg_s,
+                         int64_t n_params, uintptr_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Fused Adafactor (Shazeer & Stern 2018, arXiv:1804.04235; torch.optim.Adafactor's rule),      */
 /* additive in ABI v13.  The second moment of an R x C matrix is a row vector and a column      */
 /* vector (R + C floats), of a 1-D parameter one float per element.  A step is three passes     */
