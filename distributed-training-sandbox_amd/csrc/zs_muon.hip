@@ -247,6 +247,196 @@ __global__ __launch_bounds__(kThreads) void muon_apply_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
+// NorMuon (zero_amd.optim.NorMuon): after the last product O stands in the scratch in the
+// parameter's orientation, rows 16-byte multiples.  N1 takes each row's sum of squares, N2 the row
+// second moment, the matrix's scale and a step per row, N3 applies it.  N1 and N3 are row-tiled: a
+// workgroup owns a strip of kStripRows rows, wave w of it rows w, w + 4, ...; a lane moves the
+// 16-byte pieces at columns lane * 8 + 512 k, kRowLoads of them in flight.  A row's step is
+// wave-uniform, so no element pays a division or an index split.
+constexpr int kStripRows = 8;              // rows of a workgroup's strip (two per wave)
+constexpr int kRowLoads = 4;               // 16-byte pieces a lane holds in flight
+constexpr int kRowSeg = 512 * kRowLoads;   // columns of a row one pass of a wave covers
+
+struct NorHP {
+  Lerp to_v;          // v = lerp(v, mean(O^2), 1 - beta2)
+  float norm_eps;
+  double neg_scale;   // -(0.2 lr sqrt(R C)), per batch
+};
+
+// the widened halves of a word of two bf16
+__device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
+
+// the sum of the squares of the first `valid` of a piece's eight bf16: one fp32 chain (the squares
+// themselves are exact); what lies past `valid` is a row's padding and may hold anything
+__device__ __forceinline__ float sumsq8(const uint4 v, int valid) {
+#pragma clang fp contract(off)
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  float s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float x = (j & 1) ? bf16_hi(w[j >> 1]) : bf16_lo(w[j >> 1]);
+    s = fmaf(j < valid ? x : 0.0f, j < valid ? x : 0.0f, s);
+  }
+  return s;
+}
+
+// Pass N1: rowsq[matrix][i] = sum_j O_ij^2, the pieces of a lane in fp32 (sumsq8), everything above
+// in double: the lane along the row, then one shuffle tree per row.  Read-only over O; no LDS
+__global__ __launch_bounds__(kThreads) void normuon_rowsq_kernel(const bf16_t* __restrict__ o,
+                                                                 int R, int C, int64_t ld_o,
+                                                                 int64_t s_o,
+                                                                 double* __restrict__ rowsq) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const bf16_t* om = o + int64_t(blockIdx.z) * s_o;
+#pragma unroll 1
+  for (int k = 0; k < kStripRows / kWaves; ++k) {
+    const int row = blockIdx.x * kStripRows + wave + kWaves * k;
+    if (row >= R) break;
+    const bf16_t* orow = om + int64_t(row) * ld_o;
+    double acc = 0.0;
+    for (int c0 = lane * 8; c0 < C; c0 += kRowSeg) {
+      uint4 v[kRowLoads];
+#pragma unroll
+      for (int u = 0; u < kRowLoads; ++u) {  // (a piece that starts inside the row ends inside ld_o)
+        const int c = c0 + 512 * u;
+        v[u] = c < C ? *reinterpret_cast<const uint4*>(orow + c) : make_uint4(0u, 0u, 0u, 0u);
+      }
+#pragma unroll
+      for (int u = 0; u < kRowLoads; ++u) acc += double(sumsq8(v[u], C - (c0 + 512 * u)));
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) rowsq[int64_t(blockIdx.z) * R + row] = acc;
+  }
+}
+
+// Pass N2, one workgroup per matrix: v_i = lerp(v_i, fp32(rowsq_i / C), 1 - beta2), stored;
+// q_i = sqrt(v_i) + norm_eps; F^2 = sum_i rowsq_i / q_i^2 in double (the squared norm of the
+// row-normalised O, from the row sums alone); rowstep_i = fp32(neg_scale / (sqrt(F^2) q_i)), +0.0 for
+// every row when F^2 == 0 (a NaN is not 0: it propagates)
+__global__ __launch_bounds__(kThreads) void normuon_finish_kernel(
+    const double* __restrict__ rowsq, float* const* __restrict__ rowv, int R, int C, const NorHP nh,
+    float* __restrict__ rowstep) {
+#pragma clang fp contract(off)
+  __shared__ double wave_part[kWaves];
+  const double* rs = rowsq + int64_t(blockIdx.x) * R;
+  float* v = rowv[blockIdx.x];
+  float* out = rowstep + int64_t(blockIdx.x) * R;
+  double f2 = 0.0;
+  for (int i = threadIdx.x; i < R; i += kThreads) {
+    const double s = rs[i];
+    const float vi = lerp_to(v[i], float(s / double(C)), nh.to_v);
+    v[i] = vi;
+    const double q = double(sqrtf(vi) + nh.norm_eps);
+    f2 += s / (q * q);
+  }
+  f2 = block_sum(f2, wave_part);
+  const double f = sqrt(f2);
+  for (int i = threadIdx.x; i < R; i += kThreads) {  // (v[i]: this thread's own store)
+    const double q = double(sqrtf(v[i]) + nh.norm_eps);
+    out[i] = f2 == 0.0 ? 0.0f : float(nh.neg_scale / (f * q));
+  }
+}
+
+// eight updated masters to element i.. through store_p1's encodings, as 16-byte stores
+template <bool SPLIT>
+__device__ __forceinline__ void store_p8(const MuEntry& e, int64_t i, const float (&p)[8]) {
+  uint32_t hi[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) hi[j] = f32_to_bf16(p[j]);
+  const uint4 h = make_uint4(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16),
+                             hi[6] | (hi[7] << 16));
+  if constexpr (SPLIT) {
+    uint32_t lo[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) lo[j] = master_residual(p[j], hi[j]);
+    *reinterpret_cast<uint4*>(e.p_out + i) = h;
+    *reinterpret_cast<uint4*>(reinterpret_cast<unsigned short*>(e.master_out) + i) =
+        make_uint4(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16),
+                   lo[6] | (lo[7] << 16));
+  } else {
+    float4* dst = reinterpret_cast<float4*>(reinterpret_cast<float*>(e.master_out) + i);
+    dst[0] = make_float4(p[0], p[1], p[2], p[3]);
+    dst[1] = make_float4(p[4], p[5], p[6], p[7]);
+    if (e.p_out) *reinterpret_cast<uint4*>(e.p_out + i) = h;
+  }
+}
+
+// Pass N3: p_ij = fma(rowstep_i, float(O_ij), p_ij * (1 - lr * weight_decay)).  grid x = the strip of
+// rows, y = the segment of kRowSeg columns, z = the matrix.  A matrix whose rows are 16-byte
+// multiples in every array (C a multiple of 8, the entry's pointers 16-byte aligned) moves 16 bytes
+// of O with 2 x 16 of fp32 master (or 16 of bf16 parameter + 16 of residual); any other takes
+// element accesses to the master, with the same arithmetic
+template <bool SPLIT>
+__global__ __launch_bounds__(kThreads) void normuon_apply_kernel(
+    const MuEntry* __restrict__ entries, int R, int C, const bf16_t* __restrict__ o, int64_t ld_o,
+    int64_t s_o, const float* __restrict__ rowstep, float decay_mul) {
+#pragma clang fp contract(off)
+  const MuEntry e = entries[blockIdx.z];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const bf16_t* om = o + int64_t(blockIdx.z) * s_o;
+  const uint64_t ptrs = reinterpret_cast<uint64_t>(e.master) |
+                        reinterpret_cast<uint64_t>(e.master_out) |
+                        reinterpret_cast<uint64_t>(e.p_out);
+  const bool vec = (C & 7) == 0 && (ptrs & 15) == 0;
+  const int c0 = blockIdx.y * kRowSeg + lane * 8;
+#pragma unroll 1
+  for (int k = 0; k < kStripRows / kWaves; ++k) {
+    const int row = blockIdx.x * kStripRows + wave + kWaves * k;
+    if (row >= R) break;
+    const float step = rowstep[int64_t(blockIdx.z) * R + row];
+    const bf16_t* orow = om + int64_t(row) * ld_o;
+    const int64_t base = int64_t(row) * C;
+    uint4 ov[kRowLoads], ma[kRowLoads], mb[kRowLoads];
+#pragma unroll
+    for (int u = 0; u < kRowLoads; ++u) {
+      const int c = c0 + 512 * u;
+      if (c >= C) continue;
+      ov[u] = *reinterpret_cast<const uint4*>(orow + c);  // (ends inside ld_o)
+      if (!vec) continue;
+      if constexpr (SPLIT) {
+        ma[u] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(e.master) + base + c);
+        mb[u] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(e.master_out) + base + c);
+      } else {
+        const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(e.master) + base + c);
+        ma[u] = src[0], mb[u] = src[1];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kRowLoads; ++u) {
+      const int c = c0 + 512 * u;
+      if (c >= C) continue;
+      const uint32_t w[4] = {ov[u].x, ov[u].y, ov[u].z, ov[u].w};
+      if (vec) {
+        const uint32_t mw[8] = {ma[u].x, ma[u].y, ma[u].z, ma[u].w,
+                                mb[u].x, mb[u].y, mb[u].z, mb[u].w};
+        float p[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int sh = 16 * (j & 1);
+          float m;
+          if constexpr (SPLIT)
+            m = join_master((mw[j >> 1] >> sh) & 0xFFFFu, (mw[4 + (j >> 1)] >> sh) & 0xFFFFu);
+          else m = __uint_as_float(mw[j]);
+          const float x = (j & 1) ? bf16_hi(w[j >> 1]) : bf16_lo(w[j >> 1]);
+          p[j] = fmaf(step, x, m * decay_mul);
+        }
+        store_p8<SPLIT>(e, base + c, p);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (c + j >= C) break;
+          const float x = (j & 1) ? bf16_hi(w[j >> 1]) : bf16_lo(w[j >> 1]);
+          store_p1<SPLIT>(e, base + c + j, fmaf(step, x, load_p1<SPLIT>(e, base + c + j) * decay_mul));
+        }
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // The NT product
 struct GemmArgs {
   const bf16_t* A;   // M x K
@@ -472,6 +662,13 @@ struct zs_muonset {
   unsigned char* d_scratch = nullptr;
   std::vector<Batch> batches;
   std::vector<int> cur;  // per batch: which XT holds the current transpose (run_pass's products)
+  // NorMuon's row state (zs_muonset_attach_rows): the entries' row vectors in the shape-grouped
+  // order, and the row scratch: row_slots doubles (rowsq), then row_slots floats (rowstep)
+  std::vector<int64_t> order;  // the caller's index of each shape-grouped entry
+  float** d_rowv = nullptr;
+  unsigned char* d_rows = nullptr;
+  int64_t row_slots = 0, row_bytes = 0;
+  bool has_rows = false;
   int64_t partial_slots = 0, nrm_slots = 0, bf16_elems = 0;
   int64_t nent = 0, elems = 0, bytes = 0, pass_bytes[3] = {0, 0, 0}, scratch_bytes = 0;
   int64_t flops_iter = 0, flops_iter_run = 0;
@@ -499,11 +696,14 @@ static int64_t matrix_scratch_elems(int64_t R, int64_t C) {
   return r * round8(c) + 2 * c * round8(r) + 2 * r * round8(r);
 }
 
+static Lerp make_lerp(double weight);
+
 // the passes of one batch; mask: 1 = M1 and the norm, 2 = M2, 4 = the iteration, 8 = P;
 // product >= 0 with mask 4: that one product of one iteration
+// NorMuon (nh != NULL): 16 = N1, 32 = N2, 64 = N3
 template <typename GT, bool SPLIT>
 static int run_batch(zs_muonset* s, size_t bi, const zs_muon_hparams* h, const MuHP& hp, int mask,
-                     int product, hipStream_t st) {
+                     int product, hipStream_t st, const zs_normuon_hparams* nh = nullptr) {
   const Batch& b = s->batches[bi];
   const Layout l = layout_of(s, b);
   const MuEntry* ent = s->d_entries + b.e0;
@@ -568,6 +768,30 @@ static int run_batch(zs_muonset* s, size_t bi, const zs_muon_hparams* h, const M
     muon_apply_kernel<SPLIT><<<sgrid, block, 0, st>>>(ent, n, b.C, o, ldo, int64_t(b.R) * ldo,
                                                       neg_alr, decay_mul);
   }
+  if (mask & 112) {
+    const bf16_t* o = tall ? l.XT[s->cur[bi]] : l.X;
+    const int64_t ldo = tall ? l.ldr : l.ldc;
+    double* rowsq = reinterpret_cast<double*>(s->d_rows);
+    float* rowstep = reinterpret_cast<float*>(rowsq + s->row_slots);
+    const unsigned strips = unsigned((b.R + kStripRows - 1) / kStripRows);
+    if (mask & 16)
+      normuon_rowsq_kernel<<<dim3(strips, 1, nb), block, 0, st>>>(o, b.R, b.C, ldo,
+                                                                  int64_t(b.R) * ldo, rowsq);
+    if (mask & 32) {
+      NorHP q;
+      q.to_v = make_lerp(1.0 - nh->beta2);
+      q.norm_eps = float(nh->norm_eps);
+      q.neg_scale = -(0.2 * h->lr * std::sqrt(double(b.R) * double(b.C)));
+      normuon_finish_kernel<<<dim3(nb), block, 0, st>>>(rowsq, s->d_rowv + b.e0, b.R, b.C, q,
+                                                        rowstep);
+    }
+    if (mask & 64) {
+      const float decay_mul = float(1.0 - h->lr * h->weight_decay);
+      const dim3 g3(strips, unsigned((b.C + kRowSeg - 1) / kRowSeg), nb);
+      normuon_apply_kernel<SPLIT><<<g3, block, 0, st>>>(ent, b.R, b.C, o, ldo, int64_t(b.R) * ldo,
+                                                        rowstep, decay_mul);
+    }
+  }
   ZS_HIP(hipGetLastError());
   return ZS_OK;
 }
@@ -593,11 +817,20 @@ static Lerp make_lerp(double weight) {
   return l;
 }
 
+static int check_normuon(const char* fn, const zs_normuon_hparams* nh) {
+  if (int rc = check_hparams(fn, &nh->muon)) return rc;
+  ZS_REQUIRE(nh->beta2 >= 0.0 && nh->beta2 < 1.0, "%s: beta2 must be in [0, 1)", fn);
+  ZS_REQUIRE(nh->norm_eps >= 0.0, "%s: norm_eps should be >= 0", fn);
+  return ZS_OK;
+}
+
 static int run_checked(const char* fn, zs_muonset* s, const zs_muon_hparams* h, int mask,
-                       int product, int64_t batch, uintptr_t stream) {
+                       int product, int64_t batch, uintptr_t stream,
+                       const zs_normuon_hparams* nh = nullptr) {
   ZS_REQUIRE(s && h, "%s: NULL argument", fn);
   ZS_REQUIRE(s->tag == zs::kMuonSetTag, "%s: the set was not made by zs_muonset_create", fn);
-  if (int rc = check_hparams(fn, h)) return rc;
+  if (int rc = nh ? check_normuon(fn, nh) : check_hparams(fn, h)) return rc;
+  ZS_REQUIRE(!nh || s->has_rows, "%s: the set has no row state (zs_muonset_attach_rows)", fn);
   ZS_REQUIRE(batch >= -1 && batch < int64_t(s->batches.size()), "%s: batch %lld of %lld", fn,
              (long long)batch, (long long)s->batches.size());
   if (s->nent == 0) return ZS_OK;
@@ -616,11 +849,11 @@ static int run_checked(const char* fn, zs_muonset* s, const zs_muon_hparams* h, 
     if (batch >= 0 && int64_t(bi) != batch) continue;
     int rc;
     if (g32)
-      rc = split ? run_batch<float, true>(s, bi, h, hp, mask, product, st)
-                 : run_batch<float, false>(s, bi, h, hp, mask, product, st);
+      rc = split ? run_batch<float, true>(s, bi, h, hp, mask, product, st, nh)
+                 : run_batch<float, false>(s, bi, h, hp, mask, product, st, nh);
     else
-      rc = split ? run_batch<unsigned short, true>(s, bi, h, hp, mask, product, st)
-                 : run_batch<unsigned short, false>(s, bi, h, hp, mask, product, st);
+      rc = split ? run_batch<unsigned short, true>(s, bi, h, hp, mask, product, st, nh)
+                 : run_batch<unsigned short, false>(s, bi, h, hp, mask, product, st, nh);
     if (rc != ZS_OK) return rc;
   }
   return ZS_OK;
@@ -699,6 +932,7 @@ int zs_muonset_create(const zs_muon_seg* in, int64_t n, int g_dtype, int p_dtype
       e.p_out = reinterpret_cast<unsigned short*>(in[k].p_out);
       e.buf = reinterpret_cast<float*>(in[k].buf);
       ent.push_back(e);
+      order.push_back(k);
     }
     const int64_t count = int64_t(ent.size()) - first;
     const int64_t per = matrix_scratch_elems(R, C);
@@ -711,6 +945,7 @@ int zs_muonset_create(const zs_muon_seg* in, int64_t n, int g_dtype, int p_dtype
       ms->partial_slots = std::max(ms->partial_slots, cnt * ((ne + kChunk - 1) / kChunk));
       ms->nrm_slots = std::max(ms->nrm_slots, (cnt + 3) / 4 * 4);
       ms->bf16_elems = std::max(ms->bf16_elems, cnt * per);
+      ms->row_slots = std::max(ms->row_slots, cnt * R);
     }
     ms->elems += count * ne;
     ms->pass_bytes[0] += count * ne * int64_t(gsz + 8);
@@ -722,6 +957,7 @@ int zs_muonset_create(const zs_muon_seg* in, int64_t n, int g_dtype, int p_dtype
     ms->flops_iter_run += count * 2 * T * T * (tri * (tc * T) + tri * (t * T) + t * tc * (t * T));
   }
   ms->cur.assign(ms->batches.size(), 0);
+  ms->order = order;
   ms->bytes = ms->pass_bytes[0] + ms->pass_bytes[1] + ms->pass_bytes[2];
   ms->scratch_bytes = ms->partial_slots * 8 + ms->nrm_slots * 4 + ms->bf16_elems * 2;
   int rc = ZS_OK;
@@ -794,7 +1030,93 @@ int zs_muonset_destroy(zs_muonset* ms) {
              "zs_muonset_create");
   if (ms->d_entries) (void)hipFree(ms->d_entries);
   if (ms->d_scratch) (void)hipFree(ms->d_scratch);
+  if (ms->d_rowv) (void)hipFree(ms->d_rowv);
+  if (ms->d_rows) (void)hipFree(ms->d_rows);
   delete ms;
+  return ZS_OK;
+}
+
+int zs_normuon_hparams_init(double lr, double weight_decay, double momentum, int nesterov,
+                            double ns_a, double ns_b, double ns_c, double eps, int ns_steps,
+                            double beta2, double norm_eps, double grad_div, zs_normuon_hparams* hp) {
+  const char* fn = "zs_normuon_hparams_init";
+  ZS_REQUIRE(hp != nullptr, "%s: hp is NULL", fn);
+  zs_normuon_hparams h{};
+  h.muon.lr = lr, h.muon.weight_decay = weight_decay, h.muon.momentum = momentum;
+  h.muon.ns_a = ns_a, h.muon.ns_b = ns_b, h.muon.ns_c = ns_c, h.muon.eps = eps;
+  h.muon.grad_div = grad_div, h.muon.nesterov = nesterov ? 1 : 0, h.muon.ns_steps = ns_steps;
+  h.beta2 = beta2, h.norm_eps = norm_eps;
+  if (int rc = check_normuon(fn, &h)) return rc;
+  *hp = h;
+  return ZS_OK;
+}
+
+int zs_muonset_attach_rows(zs_muonset* ms, const uint64_t* row_v, int64_t n) {
+  const char* fn = "zs_muonset_attach_rows";
+  ZS_REQUIRE(ms != nullptr, "%s: NULL argument", fn);
+  ZS_REQUIRE(ms->tag == zs::kMuonSetTag, "%s: the set was not made by zs_muonset_create", fn);
+  ZS_REQUIRE(!ms->has_rows, "%s: the set already has row state", fn);
+  ZS_REQUIRE(n == ms->nent && (n == 0 || row_v), "%s: %lld addresses for a table of %lld entries",
+             fn, (long long)n, (long long)ms->nent);
+  for (int64_t i = 0; i < n; ++i)
+    ZS_REQUIRE(row_v[i] && aligned(row_v[i], 4), "%s: entry %lld: a NULL or misaligned address", fn,
+               (long long)i);
+  if (n == 0) {
+    ms->has_rows = true;
+    return ZS_OK;
+  }
+  std::vector<float*> rowv(static_cast<size_t>(n));
+  for (int64_t k = 0; k < n; ++k)
+    rowv[size_t(k)] = reinterpret_cast<float*>(row_v[ms->order[size_t(k)]]);
+  hipStream_t st = upload_stream();
+  if (!st) return zs::fail(ZS_ERR_HIP, "%s: no upload stream", fn);
+  const int64_t row_bytes = ms->row_slots * 12;
+  hipError_t he = hipMalloc(reinterpret_cast<void**>(&ms->d_rows), size_t(row_bytes));
+  if (he == hipSuccess)
+    he = hipMalloc(reinterpret_cast<void**>(&ms->d_rowv), rowv.size() * sizeof(float*));
+  if (he == hipSuccess)
+    he = hipMemcpyAsync(ms->d_rowv, rowv.data(), rowv.size() * sizeof(float*),
+                        hipMemcpyHostToDevice, st);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) {
+    if (ms->d_rows) (void)hipFree(ms->d_rows);
+    if (ms->d_rowv) (void)hipFree(ms->d_rowv);
+    ms->d_rows = nullptr, ms->d_rowv = nullptr;
+    return zs::fail(ZS_ERR_HIP, "%s: allocation or upload failed (%lld row scratch bytes): %s", fn,
+                    (long long)row_bytes, hipGetErrorString(he));
+  }
+  ms->row_bytes = row_bytes, ms->scratch_bytes += row_bytes;
+  ms->has_rows = true;
+  return ZS_OK;
+}
+
+int zs_muonset_run_normuon(zs_muonset* ms, const zs_normuon_hparams* h, uintptr_t stream) {
+  return run_checked("zs_muonset_run_normuon", ms, h ? &h->muon : nullptr, 7 | 112, -1, -1, stream,
+                     h);
+}
+
+int zs_muonset_run_normuon_pass(zs_muonset* ms, const zs_normuon_hparams* h, int pass, int product,
+                                int64_t batch, uintptr_t stream) {
+  const char* fn = "zs_muonset_run_normuon_pass";
+  ZS_REQUIRE(pass >= 0 && pass <= 5,
+             "%s: pass must be 0 (M1), 1 (M2), 2 (products), 3 (N1), 4 (N2) or 5 (N3)", fn);
+  ZS_REQUIRE(product >= -1 && product <= 2, "%s: product must be -1 (all) or 0, 1, 2", fn);
+  return run_checked(fn, ms, h ? &h->muon : nullptr, pass < 3 ? 1 << pass : 16 << (pass - 3),
+                     pass == 2 ? product : -1, batch, stream, h);
+}
+
+int zs_muonset_rows(const zs_muonset* ms, int64_t batch, int64_t* out) {
+  const char* fn = "zs_muonset_rows";
+  ZS_REQUIRE(ms && out, "%s: NULL argument", fn);
+  ZS_REQUIRE(ms->tag == zs::kMuonSetTag, "%s: the set was not made by zs_muonset_create", fn);
+  ZS_REQUIRE(ms->has_rows, "%s: the set has no row state (zs_muonset_attach_rows)", fn);
+  ZS_REQUIRE(batch >= 0 && batch < int64_t(ms->batches.size()), "%s: batch %lld of %lld", fn,
+             (long long)batch, (long long)ms->batches.size());
+  const double* rowsq = reinterpret_cast<const double*>(ms->d_rows);
+  out[0] = int64_t(reinterpret_cast<uintptr_t>(rowsq));
+  out[1] = int64_t(reinterpret_cast<uintptr_t>(rowsq + ms->row_slots));
+  out[2] = ms->batches[size_t(batch)].R;
+  out[3] = ms->row_bytes;
   return ZS_OK;
 }
 

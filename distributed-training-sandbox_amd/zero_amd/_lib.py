@@ -52,6 +52,8 @@ EXPORTED = (
     "zs_adafactorset_run_pass", "zs_adafactorset_stats", "zs_adafactorset_destroy",
     "zs_muon_hparams_init", "zs_muonset_create", "zs_muonset_run", "zs_muonset_run_pass",
     "zs_muonset_stats", "zs_muonset_batch", "zs_muonset_destroy", "zs_muon_gemm_nt",
+    "zs_normuon_hparams_init", "zs_muonset_attach_rows", "zs_muonset_run_normuon",
+    "zs_muonset_run_normuon_pass", "zs_muonset_rows",
     "zs_comm_unique_id", "zs_comm_init", "zs_comm_destroy", "zs_reduce_scatter", "zs_all_gather",
     "zs_all_reduce", "zs_reduce", "zs_broadcast", "zs_reduce_group", "zs_broadcast_group", "zs_all_gather_group", "zs_reduce_scatter_group",
     "zs_all_gather_group_ordered", "zs_reduce_scatter_group_ordered", "zs_stream_wait_event",
@@ -138,6 +140,10 @@ class MuonHParams(ctypes.Structure):
                 ("grad_div", ctypes.c_double), ("nesterov", ctypes.c_int32),
                 ("ns_steps", ctypes.c_int32), ("adjust_lr", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
+
+
+class NorMuonHParams(ctypes.Structure):
+    _fields_ = [("muon", MuonHParams), ("beta2", ctypes.c_double), ("norm_eps", ctypes.c_double)]
 
 
 _P = ctypes.c_void_p
@@ -266,6 +272,14 @@ _SIGS = {
     "zs_muonset_destroy": ([_P], ctypes.c_int),
     "zs_muon_gemm_nt": ([ctypes.c_uint64, _I64] * 5 + [_I64] * 3 + [ctypes.c_double] * 2 +
                         [ctypes.c_int, _U], ctypes.c_int),
+    "zs_normuon_hparams_init": ([ctypes.c_double] * 3 + [ctypes.c_int] + [ctypes.c_double] * 4 +
+                                [ctypes.c_int] + [ctypes.c_double] * 3 +
+                                [ctypes.POINTER(NorMuonHParams)], ctypes.c_int),
+    "zs_muonset_attach_rows": ([_P, _PU64, _I64], ctypes.c_int),
+    "zs_muonset_run_normuon": ([_P, ctypes.POINTER(NorMuonHParams), _U], ctypes.c_int),
+    "zs_muonset_run_normuon_pass": ([_P, ctypes.POINTER(NorMuonHParams), ctypes.c_int, ctypes.c_int,
+                                     _I64, _U], ctypes.c_int),
+    "zs_muonset_rows": ([_P, _I64, _PI64], ctypes.c_int),
     "zs_adam_step": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_float] * 5 +
                      [ctypes.c_int, _I64, ctypes.c_float, _P, ctypes.c_float, _U], ctypes.c_int),
     "zs_adam_step_ex": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_double] * 5 +

@@ -21,7 +21,7 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import (check_adafactor, check_lamb, check_muon, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
+from ._update import (MUON_KINDS, check_adafactor, check_lamb, check_muon, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
                       check_max_grad_norm, check_param_grad_norms, check_update_norms,
                       check_update_norms_group,
                       check_skip_nonfinite, check_master_free, check_master_free_group,
@@ -102,11 +102,20 @@ def muon_group_hparams(group: dict) -> dict:
                 adjust_lr_fn=group["adjust_lr_fn"], maximize=False, amsgrad=False)
 
 
+def normuon_group_hparams(group: dict) -> dict:
+    """Hyper-parameters of one zero_amd.optim.NorMuon param group."""
+    h = muon_group_hparams({**group, "adjust_lr_fn": None})
+    del h["adjust_lr_fn"]
+    return dict(h, beta2=float(group["beta2"]), norm_eps=float(group["norm_eps"]))
+
+
 def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
     """One param group's hyper-parameters for the ``kind`` ("adam" / "sgd" / "lion" / "adafactor" /
-    "muon") update."""
+    "muon" / "lamb" / "normuon") update."""
     if kind == "muon":
         return muon_group_hparams(group)
+    if kind == "normuon":
+        return normuon_group_hparams(group)
     if kind == "lion":
         return lion_group_hparams(group)
     if kind == "lamb":
@@ -118,9 +127,9 @@ def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
 
 def optimizer_kind(optimizer: Optimizer) -> str:
     """"adam" (torch.optim.Adam / AdamW), "sgd" (torch.optim.SGD), "lion" (zero_amd.optim.Lion),
-    "adafactor" (torch.optim.Adafactor), "muon" (torch.optim.Muon) or "lamb" (zero_amd.optim.LAMB);
-    TypeError for anything else."""
-    from .optim import LAMB, Lion
+    "adafactor" (torch.optim.Adafactor), "muon" (torch.optim.Muon), "lamb" (zero_amd.optim.LAMB) or
+    "normuon" (zero_amd.optim.NorMuon); TypeError for anything else."""
+    from .optim import LAMB, Lion, NorMuon
 
     if isinstance(optimizer, torch.optim.Adam):
         return "adam"
@@ -134,8 +143,10 @@ def optimizer_kind(optimizer: Optimizer) -> str:
         return "adafactor"
     if isinstance(optimizer, torch.optim.Muon):
         return "muon"
+    if isinstance(optimizer, NorMuon):
+        return "normuon"
     raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD / Adafactor / Muon or "
-                    f"zero_amd.optim.Lion / LAMB (got {type(optimizer).__name__})")
+                    f"zero_amd.optim.Lion / LAMB / NorMuon (got {type(optimizer).__name__})")
 
 
 class ShardedOptimizerBase:
@@ -189,8 +200,8 @@ class ShardedOptimizerBase:
                             state_dtype=state_dtype, state_rounding=state_rounding, master=master,
                             ema_decay=ema_decay, param_update_norms=param_update_norms)
             arena = "flat"  # arena='auto' would time the bucket arena as a candidate
-        if self._kind == "muon":  # (likewise)
-            check_muon(carry=self._carry and get("ws") > 1, layout=layout, arena=arena,
+        if self._kind in MUON_KINDS:  # (likewise)
+            check_muon(kind=self._kind, carry=self._carry and get("ws") > 1, layout=layout, arena=arena,
                        overlap=overlap, grad_comm=grad_comm, max_grad_norm=max_grad_norm,
                        skip_nonfinite=skip_nonfinite, param_grad_norms=param_grad_norms,
                        state_dtype=state_dtype, state_rounding=state_rounding, master=master,
@@ -578,7 +589,7 @@ class ShardedOptimizerBase:
             eng.expose_sgd(self.optimizer, self.params, self._groups, eng.owned_param_indices(),
                            eng.state_views)
             return
-        if self._kind == "muon":  # torch's Muon keeps no step
+        if self._kind in MUON_KINDS:  # torch's Muon keeps no step
             return
         for i in eng.owned_param_indices():
             s = int(eng.steps[i])

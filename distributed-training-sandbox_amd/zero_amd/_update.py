@@ -49,11 +49,13 @@ def check_params(params):
 BF16_STATE_MIN_ONE_MINUS_BETA = 2.0 ** -8
 
 
-KINDS = ("adam", "sgd", "lion", "adafactor", "muon", "lamb")
+KINDS = ("adam", "sgd", "lion", "adafactor", "muon", "lamb", "normuon")
+# torch.optim.Muon and zero_amd.optim.NorMuon: one engine path, one set of refusals
+MUON_KINDS = ("muon", "normuon")
 # what the messages call the optimizer of a kind that an option does not support
 KIND_NAMES = {"sgd": "torch.optim.SGD", "lion": "zero_amd.optim.Lion",
               "adafactor": "torch.optim.Adafactor", "muon": "torch.optim.Muon",
-              "lamb": "zero_amd.optim.LAMB"}
+              "lamb": "zero_amd.optim.LAMB", "normuon": "zero_amd.optim.NorMuon"}
 
 
 def check_lamb(*, carry: bool = False, arena: str = "flat", overlap: bool = False,
@@ -138,12 +140,14 @@ def check_muon(*, zero3: bool = False, carry: bool = False, layout: str = "refer
                arena: str = "flat", overlap: bool = False, grad_comm=None, max_grad_norm=None,
                skip_nonfinite: bool = False, param_grad_norms: bool = False, state_dtype=None,
                state_rounding=None, master: str = "split", ema_decay=None,
-               param_update_norms: bool = False, grad_accumulation: bool = False) -> None:
-    """What torch.optim.Muon cannot be combined with, as ValueError.  The Newton-Schulz iteration
+               param_update_norms: bool = False, grad_accumulation: bool = False,
+               kind: str = "muon") -> None:
+    """What torch.optim.Muon (``kind`` "normuon": zero_amd.optim.NorMuon, whose row statistic needs
+    the same whole matrix) cannot be combined with, as ValueError.  The Newton-Schulz iteration
     needs a whole matrix on its owner, so the update runs under ZeRO-2 on the flat arena with the
     reference's ownership, and under ZeRO-1 at world size 1, after all of the step's reductions,
     with an fp32 momentum buffer over an fp32 or split master."""
-    name = KIND_NAMES["muon"]
+    name = KIND_NAMES[kind]
 
     def no(what: str, why: str):
         raise ValueError(f"zero_amd: {name} is not supported with {what} ({why})")
@@ -357,7 +361,7 @@ def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = 
     if kind == "adafactor":  # the factored state is an arena of its own (flat.AdafactorState)
         momentum = False
     # (Muon: ``m`` alone, always: the momentum buffer)
-    names = ["m", "v"][:2 if kind in ("adam", "lamb") else 1 if kind in ("lion", "muon")
+    names = ["m", "v"][:2 if kind in ("adam", "lamb") else 1 if kind in ("lion",) + MUON_KINDS
                        else int(bool(momentum))]
     names += ["carry"] * bool(carry) + ["master"] * bool(fp32_master)
     lay = {name: (k * L, torch.float32) for k, name in enumerate(names)}
@@ -379,8 +383,8 @@ class UpdateCore:
         from .engine import probed_zeros  # (engine.py builds on this module)
 
         if kind not in KINDS:
-            raise ValueError("UpdateCore: kind must be 'adam', 'sgd', 'lion', 'adafactor', 'muon' "
-                             f"or 'lamb' (got {kind!r})")
+            raise ValueError("UpdateCore: kind must be 'adam', 'sgd', 'lion', 'adafactor', 'muon', "
+                             f"'lamb' or 'normuon' (got {kind!r})")
         # the update: torch.optim.Adam's, torch.optim.SGD's (`momentum`: some group has a
         # momentum, so the shard holds a momentum buffer; none of them: no optimizer state at all)
         # or zero_amd.optim.Lion's (one moment, exp_avg, always); zero_amd.optim.LAMB's has Adam's
@@ -439,7 +443,8 @@ class UpdateCore:
             views = {"exp_avg": cut(self.m)}
         elif self.kind == "adafactor":  # (the engine adds the factors: flat.AdafactorState)
             views = {}
-        elif self.kind == "muon":  # torch's Muon state: the buffer alone
+        elif self.kind in MUON_KINDS:  # torch's Muon state: the buffer alone (NorMuon: the engine
+            # adds the row second moment, flat.NorMuonState)
             views = {"momentum_buffer": cut(self.m)}
         else:
             views = {"exp_avg": cut(self.m), "exp_avg_sq": cut(self.v)}
@@ -498,7 +503,7 @@ class UpdateCore:
         if self.kind == "sgd":  # torch's SGD entry: the buffer once it exists, no step
             if self.steps[i] == 0 or "momentum_buffer" not in torch_state:
                 entry.pop("momentum_buffer", None)
-        elif self.kind != "muon":  # (torch's Muon entry: the buffer, no step)
+        elif self.kind not in MUON_KINDS:  # (torch's Muon entry: the buffer, no step)
             entry["step"] = torch.tensor(float(self.steps[i]), dtype=torch.float32)
         return entry
 

@@ -48,11 +48,11 @@ import torch
 
 from . import _lib
 from ._hooks import WeakCall
-from ._update import GradClip, LambNorms, UpdateNorms
+from ._update import MUON_KINDS, GradClip, LambNorms, UpdateNorms
 from .comm import StreamEvent
 from .engine import ALIGN_ELEMS, ShardEngine, _ptr
 from .kernels import (AdafactorSet, MuonSet, adafactor_hparams, check_extents,
-                      check_extents_enabled, copy_direct, muon_hparams)
+                      check_extents_enabled, copy_direct, muon_hparams, normuon_hparams)
 
 _I32P = np.int32
 LAND_BATCH_BYTES = 64 << 20  # fresh gradients landed per hook batch (ws > 1, no overlap)
@@ -82,6 +82,7 @@ class FlatEngine(ShardEngine):
     reduce / broadcast are the same code."""
 
     af = None  # (AdafactorState of an Adafactor engine)
+    nm = None  # (NorMuonState of a NorMuon engine)
     muon_scratch_bytes = 0  # the MuonSets' scratch budget (0: the library's default, 1 GiB)
 
     def __init__(self, params, group_of, ws: int, rank: int, *, carry=False, comm=None,
@@ -149,7 +150,7 @@ class FlatEngine(ShardEngine):
         # the arena view, or the fresh tensor backward left after a set-to-None zero_grad(), in
         # place (zero2.py:120 reads p.grad as backward left it): no landing copy, and G exists
         # only once a caller asks for grad views (zero_grad(set_to_none=False), ZeRO-1's views)
-        self.inplace = ws == 1 and self.grad_comm is None and kind not in ("adafactor", "muon")
+        self.inplace = ws == 1 and self.grad_comm is None and kind not in ("adafactor",) + MUON_KINDS
         self.G, self.grad_placement = None, None
         self._total = total
         if not self.inplace:
@@ -209,6 +210,8 @@ class FlatEngine(ShardEngine):
         # its own (the update reads every gradient from its arena slot: its tables keep their
         # pointers from step to step)
         self.af = AdafactorState(self) if kind == "adafactor" else None
+        # zero_amd.optim.NorMuon: the row second moments of the owned matrices, likewise
+        self.nm = NorMuonState(self) if kind == "normuon" else None
 
     # ------------------------------------------------------------------------------------------
     def _ensure_G(self):
@@ -259,6 +262,8 @@ class FlatEngine(ShardEngine):
         views = super().state_views(i, ckpt=ckpt)
         if self.af is not None and views is not None:
             views = {**self.af.views(i), **views}
+        if self.nm is not None and views is not None:
+            views = {**views, **self.nm.views(i)}
         return views
 
     def _adafactor_update(self, has, hparams_of, stream):
@@ -280,8 +285,9 @@ class FlatEngine(ShardEngine):
             self.last_adam_bytes += aset.bytes
 
     def _muon_update(self, has, hparams_of, stream):
-        """The whole step's Muon update: one MuonSet per param group over the owned matrices that
-        have a gradient (shape groups and batches inside it), cached while they stay the same."""
+        """The whole step's Muon (or NorMuon) update: one MuonSet per param group over the owned
+        matrices that have a gradient (shape groups and batches inside it), cached while they stay
+        the same; a NorMuon engine's sets carry the row state."""
         own = np.asarray(self.owned_param_indices(), np.int64)
         own = own[has[own]]
         if not len(own):
@@ -292,15 +298,21 @@ class FlatEngine(ShardEngine):
             mset = self.cached(("muon", int(gi), int(idx[0]), len(idx)), idx.tobytes(),
                                lambda: muon_set(self, idx))
             h = hparams_of(int(gi))
-            hp = muon_hparams(h["lr"], h["weight_decay"], h["momentum"], h["nesterov"],
-                              h["ns_coefficients"], h["eps"], h["ns_steps"], h["adjust_lr_fn"],
-                              grad_div=float(self.ws))
-            mset.run(hp, stream)
+            if self.nm is not None:
+                hp = normuon_hparams(h["lr"], h["weight_decay"], h["momentum"], h["nesterov"],
+                                     h["ns_coefficients"], h["eps"], h["ns_steps"], h["beta2"],
+                                     h["norm_eps"], grad_div=float(self.ws))
+                mset.run_normuon(hp, stream)
+            else:
+                hp = muon_hparams(h["lr"], h["weight_decay"], h["momentum"], h["nesterov"],
+                                  h["ns_coefficients"], h["eps"], h["ns_steps"], h["adjust_lr_fn"],
+                                  grad_div=float(self.ws))
+                mset.run(hp, stream)
             self.last_adam_bytes += mset.bytes
 
     def _whole_update(self, has, hparams_of, stream):
         """The updates that need whole parameters on their owner, after all of the reductions."""
-        if self.kind == "muon":
+        if self.kind in MUON_KINDS:
             self._muon_update(has, hparams_of, stream)
         else:
             self._adafactor_update(has, hparams_of, stream)
@@ -826,7 +838,7 @@ class FlatEngine(ShardEngine):
         # fast path: every owned param has a grad and, per param group, one (step, carry) key
         own = self.owned
         hps = {}
-        whole = self.af is not None or self.kind == "muon"
+        whole = self.af is not None or self.kind in MUON_KINDS
         if has[own].all() and not whole:
             gof = np.asarray(self.group_of)
             for gi in np.unique(gof[own]):
@@ -1105,7 +1117,35 @@ def muon_set(eng, idx):
         check_extents(rows[:, 2], n * msz, [eng.P, eng.master, eng.lo], "Muon master out")
         check_extents(rows[:, 3], n * 2, [eng.P], "Muon bf16 parameter")
         check_extents(rows[:, 4], n * 4, [eng.m], "Muon momentum buffer")
-    return MuonSet(rows, eng.czdtype, eng.p_dtype, scratch_budget=eng.muon_scratch_bytes)
+    mset = MuonSet(rows, eng.czdtype, eng.p_dtype, scratch_budget=eng.muon_scratch_bytes)
+    if eng.nm is not None:  # NorMuon: the entries' row second moments
+        rv = eng.nm.addresses(rows[:, 7].astype(np.int64))
+        if check_extents_enabled():
+            check_extents(rv, rows[:, 5].astype(np.int64) * 4, [eng.nm.state], "row_exp_avg_sq")
+        mset.attach_rows(rv)
+    return mset
+
+
+class NorMuonState:
+    """The row second moments of a flat engine's owned matrices (Layout R: whole parameters): per
+    matrix R floats at a 16-byte multiple of one fp32 arena, as ``AdafactorState`` keeps its
+    factors."""
+
+    def __init__(self, eng):
+        self.off, total = {}, 0
+        for i in eng.owned_param_indices():
+            self.off[i] = (total, int(eng.params[i].shape[0]))
+            total += (self.off[i][1] + 3) // 4 * 4
+        self.state = torch.zeros(max(total, 4), dtype=torch.float32, device=eng.device)
+
+    def views(self, i: int) -> dict:
+        """Parameter i's ``row_exp_avg_sq`` as a live view, R elements."""
+        o, n = self.off[i]
+        return {"row_exp_avg_sq": self.state[o:o + n]}
+
+    def addresses(self, idx) -> np.ndarray:
+        """The device addresses of the row vectors of parameters ``idx``."""
+        return np.array([self.state.data_ptr() + 4 * self.off[int(i)][0] for i in idx], np.uint64)
 
 
 def _dense(g: torch.Tensor, p: torch.Tensor) -> bool:

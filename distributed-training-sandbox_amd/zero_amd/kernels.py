@@ -16,6 +16,8 @@ update over an Adam set, two passes (csrc/zs_lamb.hip); ``lamb_hparams``.
 factored second moment, three passes, every scalar on the device; ``adafactor_hparams``.
 ``MuonSet`` — torch.optim.Muon's update over a table of matrices (csrc/zs_muon.hip): momentum, the
 Newton-Schulz iteration as bf16 MFMA products, the apply pass; ``muon_hparams``, ``muon_gemm_nt``.
+With ``attach_rows`` the same set runs zero_amd.optim.NorMuon's update (``run_normuon``: the row
+sums of squares, the row second moment and steps, a row-tiled apply); ``normuon_hparams``.
 ``adam_step`` — the same update over one contiguous range (zs_adam_step_ex; no table to keep).
 
 Both upload their segment table once; ``run(stream)`` only enqueues a kernel on ``stream``.
@@ -30,7 +32,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (AdafactorHParams, AdafactorSeg, AdamHParams, AdamSeg, LambHParams, LionHParams,
-                   MuonHParams, MuonSeg, SgdHParams)
+                   MuonHParams, MuonSeg, NorMuonHParams, SgdHParams)
 
 _PU64 = ctypes.POINTER(ctypes.c_uint64)
 _PI64 = ctypes.POINTER(ctypes.c_int64)
@@ -579,6 +581,20 @@ def muon_hparams(lr=1e-3, weight_decay=0.1, momentum=0.95, nesterov=True,
     return hp
 
 
+def normuon_hparams(lr=1e-3, weight_decay=0.1, momentum=0.95, nesterov=True,
+                    ns_coefficients=(3.4445, -4.775, 2.0315), eps=1e-7, ns_steps=5, beta2=0.95,
+                    norm_eps=1e-8, *, grad_div=1.0) -> NorMuonHParams:
+    """A zero_amd.optim.NorMuon group's scalars (zs_normuon_hparams_init)."""
+    if len(ns_coefficients) != 3:
+        raise ValueError("Coefficients must be a tuple of exactly 3 values")
+    a, b, c = (float(x) for x in ns_coefficients)
+    hp = NorMuonHParams()
+    _lib.call("zs_normuon_hparams_init", float(lr), float(weight_decay), float(momentum),
+              int(bool(nesterov)), a, b, c, float(eps), int(ns_steps), float(beta2),
+              float(norm_eps), float(grad_div), ctypes.byref(hp))
+    return hp
+
+
 class MuonSet:
     """Fused Muon over a table with one entry per owned matrix; ``segs`` is an (n, 8) int64/uint64
     array in zs_muon_seg order: g, master, master_out, p_out, buf, R, C, param.  ``run`` is one
@@ -600,8 +616,11 @@ class MuonSet:
                   int(p_dtype), int(scratch_budget), ctypes.byref(h))
         self._h = h
         self.nseg = len(segs)
+        self._read_stats()
+
+    def _read_stats(self) -> None:
         out = (ctypes.c_int64 * len(self.STATS))()
-        _lib.call("zs_muonset_stats", h, out, len(self.STATS))
+        _lib.call("zs_muonset_stats", self._h, out, len(self.STATS))
         for name, v in zip(self.STATS, out):
             setattr(self, name, int(v))
 
@@ -623,15 +642,45 @@ class MuonSet:
                  "scratch_bytes")
         return dict(zip(names, (int(v) for v in out)))
 
+    def attach_rows(self, row_v) -> None:
+        """NorMuon's row state: ``row_v[k]`` is the device address of entry k's R fp32 second
+        moments (zs_muonset_attach_rows); the set then takes ``run_normuon``."""
+        arr = (ctypes.c_uint64 * max(len(row_v), 1))(*(int(a) for a in row_v))
+        _lib.call("zs_muonset_attach_rows", self._h, arr if len(row_v) else None, len(row_v))
+        self._read_stats()  # (the scratch bytes now count the row scratch)
+
+    def run_normuon(self, hp: NorMuonHParams, stream) -> None:
+        """One NorMuon step: M1, M2 and the products as ``run``, then N1, N2, N3."""
+        _lib.call("zs_muonset_run_normuon", self._h, ctypes.byref(hp), stream_handle(stream))
+
+    def run_normuon_pass(self, hp: NorMuonHParams, which: int, stream, *, product: int = -1,
+                         batch: int = -1) -> None:
+        """Pass ``which`` of ``run_normuon`` (0, 1, 2 as ``run_pass``; 3: N1, the row sums of
+        squares; 4: N2, the row moments and steps; 5: N3, the apply), for tests and measurement."""
+        _lib.call("zs_muonset_run_normuon_pass", self._h, ctypes.byref(hp), int(which),
+                  int(product), int(batch), stream_handle(stream))
+
+    def rows(self, b: int) -> dict:
+        """Where batch ``b``'s row scratch lies (zs_muonset_rows)."""
+        out = (ctypes.c_int64 * 4)()
+        _lib.call("zs_muonset_rows", self._h, int(b), out)
+        return dict(zip(("rowsq", "rowstep", "R", "row_bytes"), (int(v) for v in out)))
+
     def read(self, b: int, name: str, stream):
         """A copy of batch ``b``'s scratch array ``name`` ("X", "XT", "A", "Bm": bf16, (matrices,
-        rows, columns); "norm": fp32, one per matrix) as it stands in stream order; diagnostic."""
+        rows, columns); "norm": fp32, one per matrix; NorMuon's "rowsq": float64 and "rowstep": fp32,
+        (matrices, R)) as it stands in stream order; diagnostic."""
         import torch
 
         info = self.batch(b)
         r, c = min(info["R"], info["C"]), max(info["R"], info["C"])
         dev = torch.device("cuda", torch.cuda.current_device())
-        if name == "norm":
+        if name in ("rowsq", "rowstep"):
+            info = {**info, **self.rows(b)}
+            out = torch.empty((info["count"], info["R"]), device=dev,
+                              dtype=torch.float64 if name == "rowsq" else torch.float32)
+            cols = None
+        elif name == "norm":
             out = torch.empty(info["count"], dtype=torch.float32, device=dev)
             cols = None
         else:

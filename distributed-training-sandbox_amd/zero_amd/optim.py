@@ -8,6 +8,9 @@ moment, the sign of an interpolation as the update, decoupled weight decay, no b
 Its own ``step()`` is plain torch and runs on any device; handed to ``zero_amd.zero1`` / ``zero2`` /
 ``zero3.ShardedOptimizer`` the update runs in the fused HIP kernels instead ("Fused
 Lion"), which compute what this ``step()`` computes on fp32 CPU tensors, bit for bit.
+
+``NorMuon`` (Li et al. 2025): Muon's orthogonalised update normalised per output neuron by a
+running row second moment; see the class, which is this project's definition of the rule.
 """
 from __future__ import annotations
 
@@ -66,6 +69,92 @@ class Lion(Optimizer):
                 u = m.mul(beta1).add_(g, alpha=1 - beta1).sign_()
                 p.add_(u, alpha=-lr)
                 m.mul_(beta2).add_(g, alpha=1 - beta2)
+        return loss
+
+
+class NorMuon(Optimizer):
+    """``NorMuon(params, lr=1e-3, weight_decay=0.1, momentum=0.95, nesterov=True,
+    ns_coefficients=<torch.optim.Muon's>, eps=1e-7, ns_steps=5, beta2=0.95, norm_eps=1e-8)``: Li et
+    al. 2025, "NorMuon: Making Muon more efficient and scalable" -- Muon's orthogonalised update,
+    every output neuron's row of it divided by a running second moment of that row, the whole
+    rescaled so that the update's RMS is ``0.2 * lr``.  2-D parameters only, like torch's Muon.
+
+    Per R x C parameter, with ``buf = state["momentum_buffer"]`` and ``v = state["row_exp_avg_sq"]``
+    (fp32, R elements, starts at 0)::
+
+        buf.lerp_(g, 1 - momentum);  u = g.lerp(buf, momentum) if nesterov else buf
+        O  = torch.optim._muon._zeropower_via_newtonschulz(u, ns_coefficients, ns_steps, eps)
+        Of = O.float()
+        v.lerp_(Of.square().mean(dim=1), 1 - beta2)
+        q  = v.sqrt() + norm_eps
+        On = Of / q[:, None];   F = ||On||_F
+        s  = 0 if F == 0 else 0.2 * lr * sqrt(R * C) / F
+        p.mul_(1 - lr * weight_decay);  p.add_(On, alpha=-s)
+
+    There is no bias correction (the rescale by ``F`` removes any global factor), no
+    ``adjust_lr_fn`` (the rescale is the adjustment) and no ``step`` in the state, as torch's Muon
+    keeps none.  Handed to ``zero_amd.zero2.ShardedOptimizer`` (or ``zero1`` at world size 1) the
+    update runs in the fused HIP kernels instead ("Fused NorMuon").
+    """
+
+    def __init__(self, params, lr: float = 1e-3, weight_decay: float = 0.1, momentum: float = 0.95,
+                 nesterov: bool = True, ns_coefficients=None, eps: float = 1e-7, ns_steps: int = 5,
+                 beta2: float = 0.95, norm_eps: float = 1e-8):
+        from torch.optim import _muon
+
+        if ns_coefficients is None:
+            ns_coefficients = (_muon.DEFAULT_A, _muon.DEFAULT_B, _muon.DEFAULT_C)
+        if not 0.0 <= lr:
+            raise ValueError(f"Learning rate should be >= 0 but is: {lr}")
+        if not 0.0 <= momentum:
+            raise ValueError(f"momentum should be >= 0 but is: {momentum}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"weight decay should be >= 0 but is: {weight_decay}")
+        if not 0.0 <= beta2 < 1.0:
+            raise ValueError(f"beta2 should be in [0, 1) but is: {beta2}")
+        if not 0.0 <= norm_eps:
+            raise ValueError(f"norm_eps should be >= 0 but is: {norm_eps}")
+        super().__init__(params, dict(lr=lr, weight_decay=weight_decay, momentum=momentum,
+                                      nesterov=nesterov, ns_coefficients=tuple(ns_coefficients),
+                                      eps=eps, ns_steps=ns_steps, beta2=beta2, norm_eps=norm_eps))
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.ndim != 2:
+                    raise ValueError("NorMuon only supports 2D parameters whereas we found a "
+                                     f"parameter with size: {p.size()}")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from torch.optim._muon import _zeropower_via_newtonschulz
+
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            lr, momentum = float(group["lr"]), group["momentum"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("NorMuon does not support sparse gradients")
+                g = p.grad
+                state = self.state[p]
+                if "momentum_buffer" not in state:
+                    state["momentum_buffer"] = torch.zeros_like(g, memory_format=torch.preserve_format)
+                    state["row_exp_avg_sq"] = torch.zeros(p.shape[0], dtype=torch.float32,
+                                                          device=p.device)
+                buf, v = state["momentum_buffer"], state["row_exp_avg_sq"]
+                buf.lerp_(g, 1 - momentum)
+                u = g.lerp(buf, momentum) if group["nesterov"] else buf
+                Of = _zeropower_via_newtonschulz(u, group["ns_coefficients"], group["ns_steps"],
+                                                 group["eps"]).float()
+                v.lerp_(Of.square().mean(dim=1), 1 - group["beta2"])
+                On = Of / (v.sqrt() + group["norm_eps"])[:, None]
+                F = float(torch.linalg.vector_norm(On))
+                s = 0.0 if F == 0 else 0.2 * lr * (p.shape[0] * p.shape[1]) ** 0.5 / F
+                p.mul_(1 - lr * group["weight_decay"])
+                p.add_(On.to(p.dtype), alpha=-s)
         return loss
 
 

@@ -1852,8 +1852,9 @@ class ShardedOptimizer:
         self.update = bool(update)
         if optimizer_kind(optimizer) == "adafactor":  # both modes: refused before anything else
             check_adafactor(zero3=True)
-        if optimizer_kind(optimizer) == "muon":
-            check_muon(zero3=True, grad_accumulation=bool(grad_accumulation))
+        if optimizer_kind(optimizer) in ("muon", "normuon"):
+            check_muon(zero3=True, grad_accumulation=bool(grad_accumulation),
+                       kind=optimizer_kind(optimizer))
         if optimizer_kind(optimizer) == "lamb":
             check_lamb(zero3_reference=not update, skip_nonfinite=skip_nonfinite,
                        state_dtype=state_dtype, state_rounding=state_rounding, master=master,

@@ -854,6 +854,46 @@ int zs_muon_gemm_nt(uint64_t A, int64_t lda, uint64_t B, int64_t ldb, uint64_t E
                     uint64_t D, int64_t ldd, uint64_t D2, int64_t ldd2, int64_t M, int64_t N,
                     int64_t K, double alpha, double beta, int sym, uintptr_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Fused NorMuon (zero_amd.optim.NorMuon), additive in ABI v13: Muon's orthogonalised update,   */
+/* every row of it divided by a running second moment of that row (one fp32 per row), the whole */
+/* rescaled so that the update's RMS is 0.2 lr.  It runs on a zs_muonset that has row state.    */
+typedef struct {
+  zs_muon_hparams muon;  /* adjust_lr is unused: the rescale is the adjustment */
+  double beta2;          /* the row second moment's decay, in [0, 1) */
+  double norm_eps;       /* added to the root of the row second moment, >= 0 */
+} zs_normuon_hparams;
+
+/* zs_muon_hparams_init's rules (adjust_lr 0), and ZS_ERR_INVALID unless 0 <= beta2 < 1 and
+ * norm_eps >= 0. */
+int zs_normuon_hparams_init(double lr, double weight_decay, double momentum, int nesterov,
+                            double ns_a, double ns_b, double ns_c, double eps, int ns_steps,
+                            double beta2, double norm_eps, double grad_div, zs_normuon_hparams* hp);
+/* Gives the set its row state: row_v[k] is the device address of entry k's R fp32 (the order of
+ * zs_muonset_create's table), read and written by every NorMuon run.  The set allocates the row
+ * scratch here, apart from the Muon scratch: R doubles (the row sums of squares) and R floats (the
+ * steps) per matrix of the largest batch; zs_muonset_stats' scratch bytes grow by it.  A set that
+ * never gets row state allocates and reports what it always did.  ZS_ERR_INVALID, nothing
+ * allocated: n is not the table's length, a NULL or misaligned address, row state given twice. */
+int zs_muonset_attach_rows(zs_muonset* ms, const uint64_t* row_v, int64_t n);
+/* One NorMuon step over the set: zs_muonset_run's M1, norm, M2 and products, then per matrix
+ *   N1  rowsq_i = sum_j O_ij^2: eight squares of a 16-byte piece in fp32, doubles above, in an order
+ *       fixed by C
+ *   N2  v_i = lerp(v_i, fp32(rowsq_i / C), 1 - beta2);  q_i = sqrt(v_i) + norm_eps  (fp32)
+ *       F^2 = sum_i rowsq_i / q_i^2  (double);  rowstep_i = fp32(-(0.2 lr sqrt(R C)) / (sqrt(F^2) q_i)),
+ *       +0.0 for every row if F^2 == 0
+ *   N3  p_ij = fma(rowstep_i, float(O_ij), p_ij * (1 - lr * weight_decay))
+ * ZS_ERR_INVALID, nothing launched: what zs_muonset_run refuses, hyper-parameters
+ * zs_normuon_hparams_init would refuse, a set without row state. */
+int zs_muonset_run_normuon(zs_muonset* ms, const zs_normuon_hparams* hp, uintptr_t stream);
+/* One pass of zs_muonset_run_normuon, as zs_muonset_run_pass: 0 = M1 and the norm, 1 = M2, 2 = the
+ * products (`product` as there), 3 = N1, 4 = N2, 5 = N3. */
+int zs_muonset_run_normuon_pass(zs_muonset* ms, const zs_normuon_hparams* hp, int pass, int product,
+                                int64_t batch, uintptr_t stream);
+/* Diagnostic, beside zs_muonset_batch: out[0 .. 4) of batch `batch`: the device addresses of rowsq
+ * (doubles) and rowstep (floats), matrix k of the batch R elements in; R; the row scratch's bytes. */
+int zs_muonset_rows(const zs_muonset* ms, int64_t batch, int64_t* out);
+
 /* Single-range form, SURVEY.md §8(b)'s signature: one torch.optim.Adam/AdamW step over n
  * contiguous elements — the update of one flat shard (zero1.py:88 on a flattened group) with no
  * table to build.  p: fp32 master/param, updated in place; p_bf16: optional bf16 copy of the
