@@ -54,6 +54,8 @@ EXPORTED = (
     "zs_muonset_stats", "zs_muonset_batch", "zs_muonset_destroy", "zs_muon_gemm_nt",
     "zs_normuon_hparams_init", "zs_muonset_attach_rows", "zs_muonset_run_normuon",
     "zs_muonset_run_normuon_pass", "zs_muonset_rows",
+    "zs_adamini_hparams_init", "zs_adaminiset_create", "zs_adaminiset_run",
+    "zs_adaminiset_run_pass", "zs_adaminiset_stats", "zs_adaminiset_destroy",
     "zs_comm_unique_id", "zs_comm_init", "zs_comm_destroy", "zs_reduce_scatter", "zs_all_gather",
     "zs_all_reduce", "zs_reduce", "zs_broadcast", "zs_reduce_group", "zs_broadcast_group", "zs_all_gather_group", "zs_reduce_scatter_group",
     "zs_all_gather_group_ordered", "zs_reduce_scatter_group_ordered", "zs_stream_wait_event",
@@ -144,6 +146,20 @@ class MuonHParams(ctypes.Structure):
 
 class NorMuonHParams(ctypes.Structure):
     _fields_ = [("muon", MuonHParams), ("beta2", ctypes.c_double), ("norm_eps", ctypes.c_double)]
+
+
+class AdamMiniSeg(ctypes.Structure):
+    _fields_ = [("g", ctypes.c_uint64), ("master", ctypes.c_uint64),
+                ("master_out", ctypes.c_uint64), ("p_out", ctypes.c_uint64),
+                ("m", ctypes.c_uint64), ("v", ctypes.c_uint64), ("R", ctypes.c_int64),
+                ("C", ctypes.c_int64), ("block_rows", ctypes.c_int64), ("param", ctypes.c_int64)]
+
+
+class AdamMiniHParams(ctypes.Structure):
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("grad_div", ctypes.c_double), ("maximize", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 _P = ctypes.c_void_p
@@ -280,6 +296,16 @@ _SIGS = {
     "zs_muonset_run_normuon_pass": ([_P, ctypes.POINTER(NorMuonHParams), ctypes.c_int, ctypes.c_int,
                                      _I64, _U], ctypes.c_int),
     "zs_muonset_rows": ([_P, _I64, _PI64], ctypes.c_int),
+    "zs_adamini_hparams_init": ([ctypes.c_double] * 5 + [ctypes.c_int, ctypes.c_double,
+                                                         ctypes.POINTER(AdamMiniHParams)],
+                                ctypes.c_int),
+    "zs_adaminiset_create": ([ctypes.POINTER(AdamMiniSeg), _I64, ctypes.c_int, ctypes.c_int, _I64,
+                              ctypes.POINTER(_P)], ctypes.c_int),
+    "zs_adaminiset_run": ([_P, ctypes.POINTER(AdamMiniHParams), _I64, _U], ctypes.c_int),
+    "zs_adaminiset_run_pass": ([_P, ctypes.POINTER(AdamMiniHParams), _I64, ctypes.c_int, _U],
+                               ctypes.c_int),
+    "zs_adaminiset_stats": ([_P, _PI64, _I64], ctypes.c_int),
+    "zs_adaminiset_destroy": ([_P], ctypes.c_int),
     "zs_adam_step": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_float] * 5 +
                      [ctypes.c_int, _I64, ctypes.c_float, _P, ctypes.c_float, _U], ctypes.c_int),
     "zs_adam_step_ex": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_double] * 5 +

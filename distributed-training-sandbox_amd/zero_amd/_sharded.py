@@ -21,7 +21,7 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import (MUON_KINDS, check_adafactor, check_lamb, check_muon, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
+from ._update import (MUON_KINDS, check_adafactor, check_adamini, check_lamb, check_muon, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
                       check_max_grad_norm, check_param_grad_norms, check_update_norms,
                       check_update_norms_group,
                       check_skip_nonfinite, check_master_free, check_master_free_group,
@@ -109,9 +109,22 @@ def normuon_group_hparams(group: dict) -> dict:
     return dict(h, beta2=float(group["beta2"]), norm_eps=float(group["norm_eps"]))
 
 
+def adamini_group_hparams(group: dict) -> dict:
+    """Hyper-parameters of one zero_amd.optim.AdamMini param group."""
+    lr = group["lr"]
+    lr = float(lr.item()) if torch.is_tensor(lr) else float(lr)
+    beta1, beta2 = group["betas"]
+    return dict(lr=lr, beta1=float(beta1), beta2=float(beta2), eps=float(group["eps"]),
+                weight_decay=float(group.get("weight_decay", 0.0)),
+                block_rows=int(group.get("block_rows", 1)),
+                maximize=bool(group.get("maximize", False)), amsgrad=False)
+
+
 def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
     """One param group's hyper-parameters for the ``kind`` ("adam" / "sgd" / "lion" / "adafactor" /
-    "muon" / "lamb" / "normuon") update."""
+    "muon" / "lamb" / "normuon" / "adamini") update."""
+    if kind == "adamini":
+        return adamini_group_hparams(group)
     if kind == "muon":
         return muon_group_hparams(group)
     if kind == "normuon":
@@ -127,9 +140,10 @@ def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
 
 def optimizer_kind(optimizer: Optimizer) -> str:
     """"adam" (torch.optim.Adam / AdamW), "sgd" (torch.optim.SGD), "lion" (zero_amd.optim.Lion),
-    "adafactor" (torch.optim.Adafactor), "muon" (torch.optim.Muon), "lamb" (zero_amd.optim.LAMB) or
-    "normuon" (zero_amd.optim.NorMuon); TypeError for anything else."""
-    from .optim import LAMB, Lion, NorMuon
+    "adafactor" (torch.optim.Adafactor), "muon" (torch.optim.Muon), "lamb" (zero_amd.optim.LAMB),
+    "normuon" (zero_amd.optim.NorMuon) or "adamini" (zero_amd.optim.AdamMini); TypeError for
+    anything else."""
+    from .optim import LAMB, AdamMini, Lion, NorMuon
 
     if isinstance(optimizer, torch.optim.Adam):
         return "adam"
@@ -145,8 +159,10 @@ def optimizer_kind(optimizer: Optimizer) -> str:
         return "muon"
     if isinstance(optimizer, NorMuon):
         return "normuon"
+    if isinstance(optimizer, AdamMini):
+        return "adamini"
     raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD / Adafactor / Muon or "
-                    f"zero_amd.optim.Lion / LAMB / NorMuon (got {type(optimizer).__name__})")
+                    f"zero_amd.optim.Lion / LAMB / NorMuon / AdamMini (got {type(optimizer).__name__})")
 
 
 class ShardedOptimizerBase:
@@ -206,6 +222,13 @@ class ShardedOptimizerBase:
                        skip_nonfinite=skip_nonfinite, param_grad_norms=param_grad_norms,
                        state_dtype=state_dtype, state_rounding=state_rounding, master=master,
                        ema_decay=ema_decay, param_update_norms=param_update_norms)
+            arena = "flat"
+        if self._kind == "adamini":  # (likewise)
+            check_adamini(carry=self._carry and get("ws") > 1, layout=layout, arena=arena,
+                          overlap=overlap, grad_comm=grad_comm, max_grad_norm=max_grad_norm,
+                          skip_nonfinite=skip_nonfinite, param_grad_norms=param_grad_norms,
+                          state_dtype=state_dtype, state_rounding=state_rounding, master=master,
+                          ema_decay=ema_decay, param_update_norms=param_update_norms)
             arena = "flat"
         if self._kind == "lamb":  # (likewise)
             check_lamb(carry=self._carry and get("ws") > 1, arena=arena, overlap=overlap,
@@ -558,7 +581,10 @@ class ShardedOptimizerBase:
                                      ema=self._ema_decay is not None,
                                      update_norms=self.param_update_norms,
                                      momentum=self._kind == "sgd" and any(
-                                         g.get("momentum", 0) != 0 for g in self._groups))
+                                         g.get("momentum", 0) != 0 for g in self._groups),
+                                     block_rows=[self._groups[gi].get("block_rows", 1)
+                                                 for gi in self._group_of]
+                                     if self._kind == "adamini" else None)
         else:
             self.engine = ShardEngine(self.params, self._group_of, self.world_size, self.rank,
                                       layout=self._layout, carry=carry, comm=comm,
@@ -570,7 +596,8 @@ class ShardedOptimizerBase:
 
     def _expose_state(self):
         """optimizer.state[p] = {'step', 'exp_avg', 'exp_avg_sq'} as views of the flat shard
-        (Adafactor: 'row_var' and 'col_var', or 'variance', in torch's shapes)."""
+        (Adafactor: 'row_var' and 'col_var', or 'variance', in torch's shapes; Adam-mini: 'exp_avg'
+        and 'block_exp_avg_sq')."""
         eng = self.engine
         if self._kind == "sgd":
             self._update_step_state()

@@ -303,8 +303,8 @@ class ShardEngine(UpdateCore):
                  state_rounding=None, state_seed: int = 0, ema: bool = False,
                  update_norms: bool = False):
         if kind not in KINDS:
-            raise ValueError("ShardEngine: kind must be 'adam', 'sgd', 'lion', 'adafactor', 'muon', 'normuon' "
-                             f"or 'lamb' (got {kind!r})")
+            raise ValueError("ShardEngine: kind must be 'adam', 'sgd', 'lion', 'adafactor', 'muon', 'normuon', "
+                             f"'adamini' or 'lamb' (got {kind!r})")
         if not params:
             raise ValueError("ShardEngine: no parameters")
         dev, dtype = check_params(params)

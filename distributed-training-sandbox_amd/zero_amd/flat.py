@@ -51,8 +51,9 @@ from ._hooks import WeakCall
 from ._update import MUON_KINDS, GradClip, LambNorms, UpdateNorms
 from .comm import StreamEvent
 from .engine import ALIGN_ELEMS, ShardEngine, _ptr
-from .kernels import (AdafactorSet, MuonSet, adafactor_hparams, check_extents,
-                      check_extents_enabled, copy_direct, muon_hparams, normuon_hparams)
+from .kernels import (ADAMINI_RESIDENT_CAP, AdafactorSet, AdamMiniSet, MuonSet, adafactor_hparams,
+                      adamini_hparams, check_extents, check_extents_enabled, copy_direct,
+                      muon_hparams, normuon_hparams)
 
 _I32P = np.int32
 LAND_BATCH_BYTES = 64 << 20  # fresh gradients landed per hook batch (ws > 1, no overlap)
@@ -83,13 +84,16 @@ class FlatEngine(ShardEngine):
 
     af = None  # (AdafactorState of an Adafactor engine)
     nm = None  # (NorMuonState of a NorMuon engine)
+    am = None  # (AdamMiniState of an Adam-mini engine)
+    adamini_resident_cap = ADAMINI_RESIDENT_CAP  # the AdamMiniSets' resident_cap (0: two passes)
     muon_scratch_bytes = 0  # the MuonSets' scratch budget (0: the library's default, 1 GiB)
 
     def __init__(self, params, group_of, ws: int, rank: int, *, carry=False, comm=None,
                  bucket_bytes: int = 256 << 20, master: str = "split", placement_tries: int = 8,
                  grad_comm: str | None = None, layout: str = "reference", kind: str = "adam",
                  momentum: bool = True, state_dtype=None, state_rounding=None,
-                 state_seed: int = 0, ema: bool = False, update_norms: bool = False):
+                 state_seed: int = 0, ema: bool = False, update_norms: bool = False,
+                 block_rows=None):
         if layout not in ("reference", "flat"):
             raise ValueError(f"the flat arena takes layout 'reference' or 'flat' (got {layout!r})")
         if layout == "flat" and carry:
@@ -150,7 +154,7 @@ class FlatEngine(ShardEngine):
         # the arena view, or the fresh tensor backward left after a set-to-None zero_grad(), in
         # place (zero2.py:120 reads p.grad as backward left it): no landing copy, and G exists
         # only once a caller asks for grad views (zero_grad(set_to_none=False), ZeRO-1's views)
-        self.inplace = ws == 1 and self.grad_comm is None and kind not in ("adafactor",) + MUON_KINDS
+        self.inplace = ws == 1 and self.grad_comm is None and kind not in ("adafactor", "adamini") + MUON_KINDS
         self.G, self.grad_placement = None, None
         self._total = total
         if not self.inplace:
@@ -212,6 +216,9 @@ class FlatEngine(ShardEngine):
         self.af = AdafactorState(self) if kind == "adafactor" else None
         # zero_amd.optim.NorMuon: the row second moments of the owned matrices, likewise
         self.nm = NorMuonState(self) if kind == "normuon" else None
+        # zero_amd.optim.AdamMini: the block second moments of the owned parameters, likewise
+        # (``block_rows``: every parameter's, from its group)
+        self.am = AdamMiniState(self, block_rows) if kind == "adamini" else None
 
     # ------------------------------------------------------------------------------------------
     def _ensure_G(self):
@@ -264,6 +271,8 @@ class FlatEngine(ShardEngine):
             views = {**self.af.views(i), **views}
         if self.nm is not None and views is not None:
             views = {**views, **self.nm.views(i)}
+        if self.am is not None and views is not None:
+            views = {**views, **self.am.views(i)}
         return views
 
     def _adafactor_update(self, has, hparams_of, stream):
@@ -310,10 +319,30 @@ class FlatEngine(ShardEngine):
                 mset.run(hp, stream)
             self.last_adam_bytes += mset.bytes
 
+    def _adamini_update(self, has, hparams_of, stream):
+        """The whole step's Adam-mini update: one AdamMiniSet per (param group, step count) over
+        the owned parameters that have a gradient, cached while its parameters stay the same."""
+        own = np.asarray(self.owned_param_indices(), np.int64)
+        own = own[has[own]]
+        if not len(own):
+            return
+        keys = np.stack([np.asarray(self.group_of)[own], self.steps[own]], axis=1)
+        for gi, t in np.unique(keys, axis=0):
+            idx = own[(keys == (gi, t)).all(axis=1)]
+            aset = self.cached(("adamini", int(gi), int(idx[0]), len(idx)), idx.tobytes(),
+                               lambda: self.am.new_set(idx))
+            h = hparams_of(int(gi))
+            hp = adamini_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"],
+                                 maximize=h["maximize"], grad_div=float(self.ws))
+            aset.run(hp, int(t), stream)
+            self.last_adam_bytes += aset.bytes
+
     def _whole_update(self, has, hparams_of, stream):
         """The updates that need whole parameters on their owner, after all of the reductions."""
         if self.kind in MUON_KINDS:
             self._muon_update(has, hparams_of, stream)
+        elif self.am is not None:
+            self._adamini_update(has, hparams_of, stream)
         else:
             self._adafactor_update(has, hparams_of, stream)
 
@@ -838,7 +867,7 @@ class FlatEngine(ShardEngine):
         # fast path: every owned param has a grad and, per param group, one (step, carry) key
         own = self.owned
         hps = {}
-        whole = self.af is not None or self.kind in MUON_KINDS
+        whole = self.af is not None or self.am is not None or self.kind in MUON_KINDS
         if has[own].all() and not whole:
             gof = np.asarray(self.group_of)
             for gi in np.unique(gof[own]):
@@ -1146,6 +1175,73 @@ class NorMuonState:
     def addresses(self, idx) -> np.ndarray:
         """The device addresses of the row vectors of parameters ``idx``."""
         return np.array([self.state.data_ptr() + 4 * self.off[int(i)][0] for i in idx], np.uint64)
+
+
+class AdamMiniState:
+    """The block second moments of a flat engine's owned parameters (Layout R: whole parameters):
+    per parameter B floats (``block_exp_avg_sq``) at a 16-byte multiple of one fp32 arena, as
+    ``NorMuonState`` keeps its rows; and the AdamMiniSet tables over them."""
+
+    def __init__(self, eng, block_rows):
+        self.eng = eng
+        self.block_rows = [int(b) for b in block_rows]
+        self.off, total = {}, 0
+        for i in eng.owned_param_indices():
+            self.off[i] = (total, self.blocks(eng.params[i].shape, self.block_rows[i]))
+            total += (self.off[i][1] + 3) // 4 * 4
+        self.state = torch.zeros(max(total, 4), dtype=torch.float32, device=eng.device)
+
+    @staticmethod
+    def blocks(shape, block_rows: int) -> int:
+        """Blocks of a parameter of ``shape`` (zero_amd.optim.AdamMini's partition)."""
+        from .optim import adamini_blocks
+
+        return adamini_blocks(tuple(shape), block_rows)
+
+    def views(self, i: int) -> dict:
+        """Parameter i's ``block_exp_avg_sq`` as a live view, B elements."""
+        o, n = self.off[i]
+        return {"block_exp_avg_sq": self.state[o:o + n]}
+
+    def new_set(self, idx):
+        """The AdamMiniSet of parameters ``idx``: the gradient from the reduced stream R, the
+        master as for Adafactor, exp_avg from the flat state's ``m``."""
+        eng = self.eng
+        pc = eng.pieces
+        so_of = {int(i): int(so) for i, so, n in zip(pc.param, pc.stream_off, pc.length) if n > 0}
+        rows = []
+        for i in idx:
+            i = int(i)
+            shape, n = tuple(eng.params[i].shape), int(eng.numel[i])
+            if n == 0:
+                continue
+            so = so_of[i]
+            oned = len(shape) < 2
+            R = 1 if oned else int(shape[0])
+            g = eng.R.data_ptr() + so * eng.ces
+            pslot = eng.P.data_ptr() + (int(eng.base[eng.rank]) + so) * eng.es
+            if not eng.mixed:
+                mst, mo, po = pslot, pslot, 0
+            elif eng.split:
+                mst, mo, po = pslot, eng.lo.data_ptr() + so * 2, pslot
+            else:
+                mst = mo = eng.master.data_ptr() + so * 4
+                po = pslot
+            rows.append([g, mst, mo, po, eng.m.data_ptr() + so * 4,
+                         self.state.data_ptr() + 4 * self.off[i][0], R, n // R,
+                         0 if oned else self.block_rows[i], i])
+        rows = np.array(rows, np.uint64).reshape(-1, 10)
+        if check_extents_enabled():  # every entry inside its tensors (tests turn this on)
+            n = rows[:, 6].astype(np.int64) * rows[:, 7].astype(np.int64)
+            nb = np.array([self.off[int(i)][1] for i in rows[:, 9]], np.int64)
+            msz = 2 if eng.split else 4
+            check_extents(rows[:, 0], n * eng.ces, [eng.R], "Adam-mini gradient")
+            check_extents(rows[:, 1], n * msz, [eng.P, eng.master], "Adam-mini master")
+            check_extents(rows[:, 2], n * msz, [eng.P, eng.master, eng.lo], "Adam-mini master out")
+            check_extents(rows[:, 3], n * 2, [eng.P], "Adam-mini bf16 parameter")
+            check_extents(rows[:, 4], n * 4, [eng.m], "Adam-mini exp_avg")
+            check_extents(rows[:, 5], nb * 4, [self.state], "block_exp_avg_sq")
+        return AdamMiniSet(rows, eng.czdtype, eng.p_dtype, resident_cap=eng.adamini_resident_cap)
 
 
 def _dense(g: torch.Tensor, p: torch.Tensor) -> bool:

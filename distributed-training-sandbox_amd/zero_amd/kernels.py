@@ -18,6 +18,9 @@ factored second moment, three passes, every scalar on the device; ``adafactor_hp
 Newton-Schulz iteration as bf16 MFMA products, the apply pass; ``muon_hparams``, ``muon_gemm_nt``.
 With ``attach_rows`` the same set runs zero_amd.optim.NorMuon's update (``run_normuon``: the row
 sums of squares, the row second moment and steps, a row-tiled apply); ``normuon_hparams``.
+``AdamMiniSet`` — zero_amd.optim.AdamMini's update over a table of parameters cut into blocks
+(csrc/zs_adamini.hip): a workgroup holds a block's gradient in registers between the reduction and
+the apply, larger blocks take two passes; ``adamini_hparams``.
 ``adam_step`` — the same update over one contiguous range (zs_adam_step_ex; no table to keep).
 
 Both upload their segment table once; ``run(stream)`` only enqueues a kernel on ``stream``.
@@ -31,8 +34,9 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (AdafactorHParams, AdafactorSeg, AdamHParams, AdamSeg, LambHParams, LionHParams,
-                   MuonHParams, MuonSeg, NorMuonHParams, SgdHParams)
+from ._lib import (AdafactorHParams, AdafactorSeg, AdamHParams, AdamMiniHParams, AdamMiniSeg,
+                   AdamSeg, LambHParams, LionHParams, MuonHParams, MuonSeg, NorMuonHParams,
+                   SgdHParams)
 
 _PU64 = ctypes.POINTER(ctypes.c_uint64)
 _PI64 = ctypes.POINTER(ctypes.c_int64)
@@ -695,6 +699,77 @@ class MuonSet:
         if h is not None and h.value and _lib is not None:
             try:
                 _lib.lib.zs_muonset_destroy(h)
+            except Exception:  # interpreter teardown
+                pass
+            self._h = None
+
+
+ADAMINI_RESIDENT_CAP = 16384  # elements; the shipped default of resident_cap
+
+
+def adamini_hparams(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, *,
+                    maximize=False, grad_div=1.0) -> AdamMiniHParams:
+    """A zero_amd.optim.AdamMini group's scalars (zs_adamini_hparams_init)."""
+    hp = AdamMiniHParams()
+    _lib.call("zs_adamini_hparams_init", float(lr), float(beta1), float(beta2), float(eps),
+              float(weight_decay), int(bool(maximize)), float(grad_div), ctypes.byref(hp))
+    return hp
+
+
+class AdamMiniSet:
+    """Fused Adam-mini over a table with one entry per parameter; ``segs`` is an (n, 10)
+    int64/uint64 array in zs_adamini_seg order: g, master, master_out, p_out, m, v, R, C,
+    block_rows, param.  A block of at most ``resident_cap`` elements is owned by one workgroup that
+    reads its gradient once; larger blocks take two passes (0: every block).  ``run`` is one step,
+    nothing on the host."""
+
+    FIELDS = ("g", "master", "master_out", "p_out", "m", "v", "R", "C", "block_rows", "param")
+    STATS = ("elems", "bytes", "resident_elems", "resident_bytes", "twopass_elems", "twopass_bytes",
+             "scratch_bytes", "blocks", "a_addr")
+
+    def __init__(self, segs: np.ndarray, g_dtype: int, p_dtype: int = _lib.ZS_BF16,
+                 resident_cap: int = ADAMINI_RESIDENT_CAP):
+        segs = np.ascontiguousarray(np.asarray(segs, dtype=np.uint64).reshape(-1, 10))
+        arr = (AdamMiniSeg * max(len(segs), 1))()
+        ctypes.memmove(arr, segs.ctypes.data, segs.nbytes)
+        h = ctypes.c_void_p()
+        _lib.call("zs_adaminiset_create", arr if len(segs) else None, len(segs), int(g_dtype),
+                  int(p_dtype), int(resident_cap), ctypes.byref(h))
+        self._h = h
+        self.nseg = len(segs)
+        out = (ctypes.c_int64 * len(self.STATS))()
+        _lib.call("zs_adaminiset_stats", h, out, len(self.STATS))
+        for name, v in zip(self.STATS, out):
+            setattr(self, name, int(v))
+
+    def run(self, hp: AdamMiniHParams, step: int, stream) -> None:
+        """One step; ``step`` is the entries' step count after it (zs_adaminiset_run)."""
+        _lib.call("zs_adaminiset_run", self._h, ctypes.byref(hp), int(step), stream_handle(stream))
+
+    def run_pass(self, hp: AdamMiniHParams, step: int, which: int, stream) -> None:
+        """Part ``which`` (0: the resident kernel, 1: pass 1 and the finish kernel, 2: pass 2)
+        alone, for measurement."""
+        _lib.call("zs_adaminiset_run_pass", self._h, ctypes.byref(hp), int(step), int(which),
+                  stream_handle(stream))
+
+    def read(self, name: str, stream):
+        """A copy of the scratch array ``name`` ("a": the step a_b of every block, fp32, the
+        entries' blocks in table order) as it stands in stream order; diagnostic."""
+        import torch
+
+        if name != "a":
+            raise ValueError(f"AdamMiniSet.read: no array {name!r}")
+        out = torch.empty(self.blocks, dtype=torch.float32,
+                          device=torch.device("cuda", torch.cuda.current_device()))
+        if self.blocks:
+            copy_direct([self.a_addr], [out.data_ptr()], [4 * self.blocks], stream)
+        return out
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib is not None:
+            try:
+                _lib.lib.zs_adaminiset_destroy(h)
             except Exception:  # interpreter teardown
                 pass
             self._h = None

@@ -11,6 +11,9 @@ Lion"), which compute what this ``step()`` computes on fp32 CPU tensors, bit for
 
 ``NorMuon`` (Li et al. 2025): Muon's orthogonalised update normalised per output neuron by a
 running row second moment; see the class, which is this project's definition of the rule.
+
+``AdamMini`` (Zhang et al. 2024): Adam's first moment per element, one second moment per block of
+rows; see the class, likewise.
 """
 from __future__ import annotations
 
@@ -239,4 +242,97 @@ class LAMB(Optimizer):
                 self.last_trust_ratios[p] = r
                 s = torch.tensor(group["lr"], dtype=torch.float32, device=r.device) * r
                 p.add_(u, alpha=-float(s))  # (the fp32 value, exact in a Python float)
+        return loss
+
+
+def adamini_blocks(shape, block_rows: int) -> int:
+    """How many blocks ``AdamMini`` cuts a parameter of ``shape`` into (ValueError when
+    ``block_rows`` does not divide its rows)."""
+    if len(shape) < 2 or block_rows == 0:
+        return 1
+    rows = int(shape[0])
+    if block_rows < 0 or rows % block_rows != 0:
+        raise ValueError(f"AdamMini: block_rows={block_rows} does not divide the {rows} rows of a "
+                         f"parameter with size: {tuple(shape)}")
+    return rows // block_rows
+
+
+class AdamMini(Optimizer):
+    """``AdamMini(params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, *,
+    block_rows=1, maximize=False)``: Zhang et al. 2024, "Adam-mini: Use Fewer Learning Rates To Gain
+    More" (arXiv:2406.16793) -- Adam's first moment per element, one second moment per block of the
+    parameter: 4 B of state per parameter plus one float per block.
+
+    A parameter with ``ndim >= 2`` is viewed as ``R = shape[0]`` rows of ``C = numel / R`` elements
+    and cut into blocks of ``block_rows`` consecutive rows (``B = R / block_rows``; it must divide
+    ``R``); ``block_rows=0`` makes the whole parameter one block, and a parameter with ``ndim <= 1``
+    is always one block.  ``block_rows`` is a per-group option.  Of the paper's partition,
+    ``block_rows=1`` is the per-output-neuron rule of the MLP, value and projection matrices and
+    the per-token rule of the embedding and output layers, ``block_rows=head_dim`` on the query and
+    key matrices is the per-head rule, and ``block_rows=0`` is the whole tensor.
+
+    Per parameter, with ``m = state["exp_avg"]``, ``v = state["block_exp_avg_sq"]`` (fp32, B
+    elements, starts at 0) and ``t`` the step count after the increment::
+
+        m.lerp_(g, 1 - beta1)
+        s_b = mean over block b of g^2                      (fp32 result)
+        v.mul_(beta2).add_(s, alpha=1 - beta2)
+        a_b = fp32( -(lr / (1 - beta1^t)) / (sqrt(double(v_b)) / sqrt(1 - beta2^t) + eps) )
+        p.mul_(1 - lr * weight_decay);   p_ij += a_b * m_ij          (block b of element ij)
+
+    ``state[p]`` also holds ``step`` (an fp32 CPU scalar, as torch.optim.Adam keeps it).  Handed to
+    ``zero_amd.zero2.ShardedOptimizer`` (or ``zero1`` at world size 1) the update runs in the fused
+    HIP kernels instead ("Fused Adam-mini").
+    """
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, *, block_rows: int = 1, maximize: bool = False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      block_rows=int(block_rows), maximize=maximize))
+        for group in self.param_groups:
+            for p in group["params"]:
+                adamini_blocks(p.shape, group["block_rows"])
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            beta1, beta2 = group["betas"]
+            lr = float(group["lr"])
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("AdamMini does not support sparse gradients")
+                g = -p.grad if group["maximize"] else p.grad
+                nblk = adamini_blocks(p.shape, group["block_rows"])
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["block_exp_avg_sq"] = torch.zeros(nblk, dtype=torch.float32,
+                                                            device=p.device)
+                m, v = state["exp_avg"], state["block_exp_avg_sq"]
+                state["step"] += 1
+                t = float(state["step"])
+                m.lerp_(g, 1 - beta1)
+                s = g.reshape(nblk, -1).float().square().mean(dim=1)
+                v.mul_(beta2).add_(s, alpha=1 - beta2)
+                a = (-(lr / (1 - beta1 ** t)) /
+                     (v.double().sqrt() / (1 - beta2 ** t) ** 0.5 + group["eps"])).float()
+                p.mul_(1 - lr * group["weight_decay"])
+                p.view(nblk, -1).add_((a[:, None] * m.reshape(nblk, -1).float()).to(p.dtype))
         return loss

@@ -894,6 +894,76 @@ int zs_muonset_run_normuon_pass(zs_muonset* ms, const zs_normuon_hparams* hp, in
  * (doubles) and rowstep (floats), matrix k of the batch R elements in; R; the row scratch's bytes. */
 int zs_muonset_rows(const zs_muonset* ms, int64_t batch, int64_t* out);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Fused Adam-mini (Zhang et al. 2024, arXiv:2406.16793; zero_amd.optim.AdamMini's rule),        */
+/* additive in ABI v13: Adam's first moment per element, one second moment per block of the      */
+/* parameter (block_rows consecutive rows, or the whole of it).  A block of at most resident_cap */
+/* elements is owned by one workgroup that holds its gradient in registers between the           */
+/* reduction and the apply (g read once; 18 B/element with bf16 gradients over the split         */
+/* master); a larger block takes two passes with a finish kernel between them (20 B/element).    */
+/* Nothing is atomic, every scalar stays on the device and the bits repeat from run to run.      */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint64_t g;          /* reduced gradient sum, R * C elements of g_dtype (required) */
+  uint64_t master;     /* as zs_adafactor_seg: the fp32 master, or (ZS_BF16_SPLIT) the bf16 param read */
+  uint64_t master_out; /* the fp32 master again (updated in place), or (ZS_BF16_SPLIT) the int16
+                          residual, read and rewritten */
+  uint64_t p_out;      /* optional bf16 copy of the updated param; (ZS_BF16_SPLIT) the bf16 param
+                          written, required */
+  uint64_t m;          /* fp32 exp_avg, R * C elements, updated in place */
+  uint64_t v;          /* fp32 block_exp_avg_sq, one per block, updated in place */
+  int64_t R, C;        /* rows and columns: row i starts at element i * C (1-D: R = 1) */
+  int64_t block_rows;  /* rows of a block; it divides R; 0: the whole entry is one block */
+  int64_t param;       /* the caller's index of the entry's parameter */
+} zs_adamini_seg;
+
+typedef struct {
+  /* the group's scalars as doubles; a run rounds what it derives from them to f32 once */
+  double lr;
+  double beta1;
+  double beta2;
+  double eps;
+  double weight_decay;
+  double grad_div;     /* divide the reduced sum by this (world size) */
+  int32_t maximize;
+  int32_t reserved;
+} zs_adamini_hparams;
+
+/* Fill hp from a zero_amd.optim.AdamMini param group.  ZS_ERR_INVALID unless lr >= 0, both betas in
+ * [0, 1), eps >= 0, weight_decay >= 0, grad_div > 0 and hp is not NULL. */
+int zs_adamini_hparams_init(double lr, double beta1, double beta2, double eps, double weight_decay,
+                            int maximize, double grad_div, zs_adamini_hparams* hp);
+typedef struct zs_adaminiset zs_adaminiset;
+/* g_dtype ZS_F32 or ZS_BF16; p_dtype ZS_BF16 (fp32 master in place, optional bf16 p_out) or
+ * ZS_BF16_SPLIT.  resident_cap, in [0, 16384] elements: a block of at most that many takes the
+ * resident path, a larger one the two passes (0: every block).  An entry whose block length is a
+ * multiple of the 16-byte gradient vector (8 bf16, 4 fp32) and whose pointers are 16-byte aligned
+ * takes 16-byte accesses; any other entry element accesses in the same kernels with the same
+ * arithmetic and reduction order.  The set owns its scratch (the tiles' partial sums, a_b of every
+ * block).  Every check comes before any allocation or upload. */
+int zs_adaminiset_create(const zs_adamini_seg* segs, int64_t n, int g_dtype, int p_dtype,
+                         int64_t resident_cap, zs_adaminiset** out);
+/* One Adam-mini step over the set, step = the entries' step count t after it (>= 1), per block b
+ * with averaged gradient g (fp32; only the written fma fused; sqrt and / correctly rounded):
+ *   m = lerp(m, g, 1 - beta1)                                   (ATen's two-range lerp)
+ *   v_b = fma(1 - beta2, fp32(sum g^2 / L), v_b * beta2)
+ *   a_b = fp32(-(lr / (1 - beta1^t)) / (sqrt(double(v_b)) / sqrt(1 - beta2^t) + eps))   (double)
+ *   p = fma(a_b, m, p * (1 - lr * weight_decay))
+ * Sums run in fp32 inside a 16-byte piece and in double above; the order depends on the block's
+ * length and path alone.  ZS_ERR_INVALID, nothing launched: a NULL argument, a set of another
+ * family, step < 1, hyper-parameters zs_adamini_hparams_init would refuse. */
+int zs_adaminiset_run(const zs_adaminiset* as, const zs_adamini_hparams* hp, int64_t step,
+                      uintptr_t stream);
+/* One part of zs_adaminiset_run (0: the resident kernel; 1: pass 1 and the finish kernel; 2: pass
+ * 2), for measurement; 0, 1, 2 in order are one run. */
+int zs_adaminiset_run_pass(const zs_adaminiset* as, const zs_adamini_hparams* hp, int64_t step,
+                           int pass, uintptr_t stream);
+/* out[0 .. min(n, 9)): elements covered; algorithmic HBM bytes of one run; elements and bytes of
+ * the resident path; elements and bytes of the two-pass path; bytes of the set's scratch; blocks;
+ * the device address of the blocks' a_b (fp32, table order, the last run's; diagnostic). */
+int zs_adaminiset_stats(const zs_adaminiset* as, int64_t* out, int64_t n);
+int zs_adaminiset_destroy(zs_adaminiset* as);
+
 /* Single-range form, SURVEY.md §8(b)'s signature: one torch.optim.Adam/AdamW step over n
  * contiguous elements — the update of one flat shard (zero1.py:88 on a flattened group) with no
  * table to build.  p: fp32 master/param, updated in place; p_bf16: optional bf16 copy of the
