@@ -41,6 +41,7 @@ constexpr unsigned kAdamSetTag = 0x5a41444du;       // "ZADM"
 constexpr unsigned kAdafactorSetTag = 0x5a414446u;  // "ZADF"
 constexpr unsigned kMuonSetTag = 0x5a4d554fu;       // "ZMUO" (zs_muonset, zs_muon.hip)
 constexpr unsigned kAdaminiSetTag = 0x5a414d49u;    // "ZAMI" (zs_adaminiset, zs_adamini.hip)
+constexpr unsigned kApolloSetTag = 0x5a41504fu;     // "ZAPO" (zs_apolloset, zs_apollo.hip)
 
 }  // namespace zs
 

@@ -56,6 +56,8 @@ EXPORTED = (
     "zs_muonset_run_normuon_pass", "zs_muonset_rows",
     "zs_adamini_hparams_init", "zs_adaminiset_create", "zs_adaminiset_run",
     "zs_adaminiset_run_pass", "zs_adaminiset_stats", "zs_adaminiset_destroy",
+    "zs_apollo_hparams_init", "zs_apolloset_create", "zs_apolloset_run", "zs_apolloset_run_pass",
+    "zs_apolloset_stats", "zs_apolloset_destroy",
     "zs_comm_unique_id", "zs_comm_init", "zs_comm_destroy", "zs_reduce_scatter", "zs_all_gather",
     "zs_all_reduce", "zs_reduce", "zs_broadcast", "zs_reduce_group", "zs_broadcast_group", "zs_all_gather_group", "zs_reduce_scatter_group",
     "zs_all_gather_group_ordered", "zs_reduce_scatter_group_ordered", "zs_stream_wait_event",
@@ -161,6 +163,24 @@ class AdamMiniHParams(ctypes.Structure):
                 ("grad_div", ctypes.c_double), ("maximize", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
 
+
+class ApolloSeg(ctypes.Structure):
+    _fields_ = [("g", ctypes.c_uint64), ("master", ctypes.c_uint64),
+                ("master_out", ctypes.c_uint64), ("p_out", ctypes.c_uint64),
+                ("m", ctypes.c_uint64), ("v", ctypes.c_uint64), ("fprev", ctypes.c_uint64),
+                ("R", ctypes.c_int64), ("C", ctypes.c_int64), ("seed", ctypes.c_uint64),
+                ("param", ctypes.c_int64)]
+
+
+class ApolloHParams(ctypes.Structure):
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("scale", ctypes.c_double), ("norm_growth", ctypes.c_double),
+                ("grad_div", ctypes.c_double), ("update_proj_gap", ctypes.c_int64),
+                ("scale_type", ctypes.c_int32), ("maximize", ctypes.c_int32)]
+
+
+APOLLO_SCALE_TYPES = {"channel": 0, "tensor": 1}
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -306,6 +326,16 @@ _SIGS = {
                                ctypes.c_int),
     "zs_adaminiset_stats": ([_P, _PI64, _I64], ctypes.c_int),
     "zs_adaminiset_destroy": ([_P], ctypes.c_int),
+    "zs_apollo_hparams_init": ([ctypes.c_double] * 6 + [ctypes.c_int, _I64, ctypes.c_double,
+                                                        ctypes.c_int, ctypes.c_double,
+                                                        ctypes.POINTER(ApolloHParams)], ctypes.c_int),
+    "zs_apolloset_create": ([ctypes.POINTER(ApolloSeg), _I64, ctypes.c_int, ctypes.c_int, _I64,
+                             ctypes.POINTER(_P)], ctypes.c_int),
+    "zs_apolloset_run": ([_P, ctypes.POINTER(ApolloHParams), _I64, _U], ctypes.c_int),
+    "zs_apolloset_run_pass": ([_P, ctypes.POINTER(ApolloHParams), _I64, ctypes.c_int, _U],
+                              ctypes.c_int),
+    "zs_apolloset_stats": ([_P, _PI64, _I64], ctypes.c_int),
+    "zs_apolloset_destroy": ([_P], ctypes.c_int),
     "zs_adam_step": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_float] * 5 +
                      [ctypes.c_int, _I64, ctypes.c_float, _P, ctypes.c_float, _U], ctypes.c_int),
     "zs_adam_step_ex": ([_P, _P, _P, ctypes.c_int, _P, _P, _I64] + [ctypes.c_double] * 5 +

@@ -21,7 +21,7 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import (MUON_KINDS, check_adafactor, check_adamini, check_lamb, check_muon, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
+from ._update import (MUON_KINDS, check_adafactor, check_adamini, check_apollo, check_lamb, check_muon, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
                       check_max_grad_norm, check_param_grad_norms, check_update_norms,
                       check_update_norms_group,
                       check_skip_nonfinite, check_master_free, check_master_free_group,
@@ -120,9 +120,20 @@ def adamini_group_hparams(group: dict) -> dict:
                 maximize=bool(group.get("maximize", False)), amsgrad=False)
 
 
+def apollo_group_hparams(group: dict) -> dict:
+    """Hyper-parameters of one zero_amd.optim.Apollo param group."""
+    h = adamini_group_hparams(group)
+    del h["block_rows"]
+    return dict(h, rank=int(group["rank"]), scale=float(group["scale"]),
+                scale_type=str(group["scale_type"]), update_proj_gap=int(group["update_proj_gap"]),
+                norm_growth=float(group["norm_growth"]), seed=int(group["seed"]))
+
+
 def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
     """One param group's hyper-parameters for the ``kind`` ("adam" / "sgd" / "lion" / "adafactor" /
-    "muon" / "lamb" / "normuon" / "adamini") update."""
+    "muon" / "lamb" / "normuon" / "adamini" / "apollo") update."""
+    if kind == "apollo":
+        return apollo_group_hparams(group)
     if kind == "adamini":
         return adamini_group_hparams(group)
     if kind == "muon":
@@ -141,9 +152,9 @@ def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
 def optimizer_kind(optimizer: Optimizer) -> str:
     """"adam" (torch.optim.Adam / AdamW), "sgd" (torch.optim.SGD), "lion" (zero_amd.optim.Lion),
     "adafactor" (torch.optim.Adafactor), "muon" (torch.optim.Muon), "lamb" (zero_amd.optim.LAMB),
-    "normuon" (zero_amd.optim.NorMuon) or "adamini" (zero_amd.optim.AdamMini); TypeError for
-    anything else."""
-    from .optim import LAMB, AdamMini, Lion, NorMuon
+    "normuon" (zero_amd.optim.NorMuon), "adamini" (zero_amd.optim.AdamMini) or "apollo"
+    (zero_amd.optim.Apollo); TypeError for anything else."""
+    from .optim import LAMB, AdamMini, Apollo, Lion, NorMuon
 
     if isinstance(optimizer, torch.optim.Adam):
         return "adam"
@@ -161,8 +172,10 @@ def optimizer_kind(optimizer: Optimizer) -> str:
         return "normuon"
     if isinstance(optimizer, AdamMini):
         return "adamini"
+    if isinstance(optimizer, Apollo):
+        return "apollo"
     raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD / Adafactor / Muon or "
-                    f"zero_amd.optim.Lion / LAMB / NorMuon / AdamMini (got {type(optimizer).__name__})")
+                    f"zero_amd.optim.Lion / LAMB / NorMuon / AdamMini / Apollo (got {type(optimizer).__name__})")
 
 
 class ShardedOptimizerBase:
@@ -229,6 +242,13 @@ class ShardedOptimizerBase:
                           skip_nonfinite=skip_nonfinite, param_grad_norms=param_grad_norms,
                           state_dtype=state_dtype, state_rounding=state_rounding, master=master,
                           ema_decay=ema_decay, param_update_norms=param_update_norms)
+            arena = "flat"
+        if self._kind == "apollo":  # (likewise)
+            check_apollo(carry=self._carry and get("ws") > 1, layout=layout, arena=arena,
+                         overlap=overlap, grad_comm=grad_comm, max_grad_norm=max_grad_norm,
+                         skip_nonfinite=skip_nonfinite, param_grad_norms=param_grad_norms,
+                         state_dtype=state_dtype, state_rounding=state_rounding, master=master,
+                         ema_decay=ema_decay, param_update_norms=param_update_norms)
             arena = "flat"
         if self._kind == "lamb":  # (likewise)
             check_lamb(carry=self._carry and get("ws") > 1, arena=arena, overlap=overlap,
@@ -584,7 +604,10 @@ class ShardedOptimizerBase:
                                          g.get("momentum", 0) != 0 for g in self._groups),
                                      block_rows=[self._groups[gi].get("block_rows", 1)
                                                  for gi in self._group_of]
-                                     if self._kind == "adamini" else None)
+                                     if self._kind == "adamini" else None,
+                                     apollo=[(self._groups[gi]["rank"], self._groups[gi]["seed"])
+                                             for gi in self._group_of]
+                                     if self._kind == "apollo" else None)
         else:
             self.engine = ShardEngine(self.params, self._group_of, self.world_size, self.rank,
                                       layout=self._layout, carry=carry, comm=comm,
@@ -597,7 +620,7 @@ class ShardedOptimizerBase:
     def _expose_state(self):
         """optimizer.state[p] = {'step', 'exp_avg', 'exp_avg_sq'} as views of the flat shard
         (Adafactor: 'row_var' and 'col_var', or 'variance', in torch's shapes; Adam-mini: 'exp_avg'
-        and 'block_exp_avg_sq')."""
+        and 'block_exp_avg_sq'; Apollo: the sketch moments, 'scaled_grad_norm' and 'seed')."""
         eng = self.engine
         if self._kind == "sgd":
             self._update_step_state()

@@ -49,14 +49,14 @@ def check_params(params):
 BF16_STATE_MIN_ONE_MINUS_BETA = 2.0 ** -8
 
 
-KINDS = ("adam", "sgd", "lion", "adafactor", "muon", "lamb", "normuon", "adamini")
+KINDS = ("adam", "sgd", "lion", "adafactor", "muon", "lamb", "normuon", "adamini", "apollo")
 # torch.optim.Muon and zero_amd.optim.NorMuon: one engine path, one set of refusals
 MUON_KINDS = ("muon", "normuon")
 # what the messages call the optimizer of a kind that an option does not support
 KIND_NAMES = {"sgd": "torch.optim.SGD", "lion": "zero_amd.optim.Lion",
               "adafactor": "torch.optim.Adafactor", "muon": "torch.optim.Muon",
               "lamb": "zero_amd.optim.LAMB", "normuon": "zero_amd.optim.NorMuon",
-              "adamini": "zero_amd.optim.AdamMini"}
+              "adamini": "zero_amd.optim.AdamMini", "apollo": "zero_amd.optim.Apollo"}
 
 
 def check_lamb(*, carry: bool = False, arena: str = "flat", overlap: bool = False,
@@ -172,6 +172,48 @@ def check_adamini(*, zero3: bool = False, carry: bool = False, layout: str = "re
         no(f"state_dtype={state_dtype}", "exp_avg is fp32")
     if state_rounding is not None:
         no("state_rounding", "exp_avg is fp32")
+    if master == "none":
+        no("master='none'", "the update reads an fp32 or split master")
+    if ema_decay is not None:
+        no("ema_decay", "the EMA is fused into the Adam update")
+    if param_update_norms:
+        no("param_update_norms", "the norms are summed inside the fused Adam update")
+
+
+def check_apollo(*, zero3: bool = False, carry: bool = False, layout: str = "reference",
+                 arena: str = "flat", overlap: bool = False, grad_comm=None, max_grad_norm=None,
+                 skip_nonfinite: bool = False, param_grad_norms: bool = False, state_dtype=None,
+                 state_rounding=None, master: str = "split", ema_decay=None,
+                 param_update_norms: bool = False) -> None:
+    """What zero_amd.optim.Apollo cannot be combined with, as ValueError.  A channel's sketch and
+    the matrix's norm need the whole matrix on one owner, so the update runs under Adam-mini's
+    conditions: ZeRO-2 on the flat arena with the reference's ownership, ZeRO-1 at world size 1,
+    fp32 sketch moments over an fp32 or split master."""
+    name = KIND_NAMES["apollo"]
+
+    def no(what: str, why: str):
+        raise ValueError(f"zero_amd: {name} is not supported with {what} ({why})")
+
+    if zero3:
+        no("ZeRO-3", "the sketch of a sharded matrix needs a cross-rank reduction")
+    if carry:
+        no("ZeRO-1 at world size > 1", "the gradient carry")
+    if layout != "reference":
+        no(f"layout={layout!r}", "a parameter may straddle two owners")
+    if arena == "buckets":
+        no("arena='buckets'", "the update runs on the flat arena")
+    if overlap:
+        no("overlap=True", "the update starts once every owned gradient is reduced")
+    if grad_comm is not None:
+        no(f"grad_comm={grad_comm!r}", "not covered yet")
+    for opt, val in (("skip_nonfinite", skip_nonfinite), ("param_grad_norms", param_grad_norms),
+                     ("max_grad_norm", max_grad_norm is not None)):
+        if val:
+            no(opt, "the channel steps take no clip coefficient yet")
+    if state_dtype is not None and state_dtype != torch.float32:
+        no(f"state_dtype={state_dtype}", "the sketch moments are fp32")
+    if state_rounding is not None:
+        no("state_rounding", "the sketch moments are fp32")
     if master == "none":
         no("master='none'", "the update reads an fp32 or split master")
     if ema_decay is not None:
@@ -402,8 +444,8 @@ def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = 
             lay["lo"] = (pad(total), torch.int16)
             total = pad(total) + words
         return total, lay
-    if kind == "adafactor":  # the factored state is an arena of its own (flat.AdafactorState)
-        momentum = False
+    if kind in ("adafactor", "apollo"):  # their state is an arena of its own (flat.AdafactorState,
+        momentum = False                  # flat.ApolloState): nothing per element
     # (Muon: ``m`` alone, always: the momentum buffer)
     # (Adam-mini: ``m`` alone, exp_avg; the block second moment is flat.AdamMiniState's arena)
     names = ["m", "v"][:2 if kind in ("adam", "lamb")
@@ -429,7 +471,7 @@ class UpdateCore:
 
         if kind not in KINDS:
             raise ValueError("UpdateCore: kind must be 'adam', 'sgd', 'lion', 'adafactor', 'muon', "
-                             f"'lamb', 'normuon' or 'adamini' (got {kind!r})")
+                             f"'lamb', 'normuon', 'adamini' or 'apollo' (got {kind!r})")
         # the update: torch.optim.Adam's, torch.optim.SGD's (`momentum`: some group has a
         # momentum, so the shard holds a momentum buffer; none of them: no optimizer state at all)
         # or zero_amd.optim.Lion's (one moment, exp_avg, always); zero_amd.optim.LAMB's has Adam's
@@ -486,8 +528,8 @@ class UpdateCore:
             views = {} if self.m is None else {"momentum_buffer": cut(self.m)}
         elif self.kind in ("lion", "adamini"):  # (Adam-mini: the engine adds block_exp_avg_sq)
             views = {"exp_avg": cut(self.m)}
-        elif self.kind == "adafactor":  # (the engine adds the factors: flat.AdafactorState)
-            views = {}
+        elif self.kind in ("adafactor", "apollo"):  # (the engine adds the factors / the sketch
+            views = {}                              # moments: flat.AdafactorState, flat.ApolloState)
         elif self.kind in MUON_KINDS:  # torch's Muon state: the buffer alone (NorMuon: the engine
             # adds the row second moment, flat.NorMuonState)
             views = {"momentum_buffer": cut(self.m)}
@@ -562,7 +604,7 @@ class UpdateCore:
                 view.copy_(src.reshape(view.shape))
             elif name == "master_param":
                 view.copy_(param.detach().reshape(view.shape))
-            elif name != "ema_param":
+            elif name not in ("ema_param", "seed"):  # (Apollo's seed: the optimizer's own)
                 view.zero_()
         if "ema_param" in views and entry.get("ema_param") is None:
             view = views["ema_param"]

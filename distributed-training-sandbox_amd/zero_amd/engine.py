@@ -304,7 +304,7 @@ class ShardEngine(UpdateCore):
                  update_norms: bool = False):
         if kind not in KINDS:
             raise ValueError("ShardEngine: kind must be 'adam', 'sgd', 'lion', 'adafactor', 'muon', 'normuon', "
-                             f"'adamini' or 'lamb' (got {kind!r})")
+                             f"'adamini', 'apollo' or 'lamb' (got {kind!r})")
         if not params:
             raise ValueError("ShardEngine: no parameters")
         dev, dtype = check_params(params)

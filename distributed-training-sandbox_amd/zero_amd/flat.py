@@ -51,8 +51,8 @@ from ._hooks import WeakCall
 from ._update import MUON_KINDS, GradClip, LambNorms, UpdateNorms
 from .comm import StreamEvent
 from .engine import ALIGN_ELEMS, ShardEngine, _ptr
-from .kernels import (ADAMINI_RESIDENT_CAP, AdafactorSet, AdamMiniSet, MuonSet, adafactor_hparams,
-                      adamini_hparams, check_extents, check_extents_enabled, copy_direct,
+from .kernels import (ADAMINI_RESIDENT_CAP, AdafactorSet, AdamMiniSet, ApolloSet, MuonSet,
+                      adafactor_hparams, adamini_hparams, apollo_hparams, check_extents, check_extents_enabled, copy_direct,
                       muon_hparams, normuon_hparams)
 
 _I32P = np.int32
@@ -85,6 +85,7 @@ class FlatEngine(ShardEngine):
     af = None  # (AdafactorState of an Adafactor engine)
     nm = None  # (NorMuonState of a NorMuon engine)
     am = None  # (AdamMiniState of an Adam-mini engine)
+    ap = None  # (ApolloState of an Apollo engine)
     adamini_resident_cap = ADAMINI_RESIDENT_CAP  # the AdamMiniSets' resident_cap (0: two passes)
     muon_scratch_bytes = 0  # the MuonSets' scratch budget (0: the library's default, 1 GiB)
 
@@ -93,7 +94,7 @@ class FlatEngine(ShardEngine):
                  grad_comm: str | None = None, layout: str = "reference", kind: str = "adam",
                  momentum: bool = True, state_dtype=None, state_rounding=None,
                  state_seed: int = 0, ema: bool = False, update_norms: bool = False,
-                 block_rows=None):
+                 block_rows=None, apollo=None):
         if layout not in ("reference", "flat"):
             raise ValueError(f"the flat arena takes layout 'reference' or 'flat' (got {layout!r})")
         if layout == "flat" and carry:
@@ -154,7 +155,7 @@ class FlatEngine(ShardEngine):
         # the arena view, or the fresh tensor backward left after a set-to-None zero_grad(), in
         # place (zero2.py:120 reads p.grad as backward left it): no landing copy, and G exists
         # only once a caller asks for grad views (zero_grad(set_to_none=False), ZeRO-1's views)
-        self.inplace = ws == 1 and self.grad_comm is None and kind not in ("adafactor", "adamini") + MUON_KINDS
+        self.inplace = ws == 1 and self.grad_comm is None and kind not in ("adafactor", "adamini", "apollo") + MUON_KINDS
         self.G, self.grad_placement = None, None
         self._total = total
         if not self.inplace:
@@ -219,6 +220,9 @@ class FlatEngine(ShardEngine):
         # zero_amd.optim.AdamMini: the block second moments of the owned parameters, likewise
         # (``block_rows``: every parameter's, from its group)
         self.am = AdamMiniState(self, block_rows) if kind == "adamini" else None
+        # zero_amd.optim.Apollo: the sketch moments and F_prev of the owned matrices, likewise
+        # (``apollo``: every parameter's (rank, seed), from its group)
+        self.ap = ApolloState(self, apollo) if kind == "apollo" else None
 
     # ------------------------------------------------------------------------------------------
     def _ensure_G(self):
@@ -273,6 +277,8 @@ class FlatEngine(ShardEngine):
             views = {**views, **self.nm.views(i)}
         if self.am is not None and views is not None:
             views = {**views, **self.am.views(i)}
+        if self.ap is not None and views is not None:
+            views = {**self.ap.views(i), **views}
         return views
 
     def _adafactor_update(self, has, hparams_of, stream):
@@ -337,12 +343,35 @@ class FlatEngine(ShardEngine):
             aset.run(hp, int(t), stream)
             self.last_adam_bytes += aset.bytes
 
+    def _apollo_update(self, has, hparams_of, stream):
+        """The whole step's APOLLO update: one ApolloSet per (param group, step count) over the
+        owned matrices that have a gradient, cached while its parameters and seeds stay the same."""
+        own = np.asarray(self.owned_param_indices(), np.int64)
+        own = own[has[own]]
+        if not len(own):
+            return
+        keys = np.stack([np.asarray(self.group_of)[own], self.steps[own]], axis=1)
+        for gi, t in np.unique(keys, axis=0):
+            idx = own[(keys == (gi, t)).all(axis=1)]
+            h = hparams_of(int(gi))
+            aset = self.cached(("apollo", int(gi), int(idx[0]), len(idx)),
+                               idx.tobytes() + self.ap.seeds(idx).tobytes(),
+                               lambda: self.ap.new_set(idx))
+            hp = apollo_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"],
+                                scale=h["scale"], scale_type=h["scale_type"],
+                                update_proj_gap=h["update_proj_gap"], norm_growth=h["norm_growth"],
+                                maximize=h["maximize"], grad_div=float(self.ws))
+            aset.run(hp, int(t), stream)
+            self.last_adam_bytes += aset.bytes
+
     def _whole_update(self, has, hparams_of, stream):
         """The updates that need whole parameters on their owner, after all of the reductions."""
         if self.kind in MUON_KINDS:
             self._muon_update(has, hparams_of, stream)
         elif self.am is not None:
             self._adamini_update(has, hparams_of, stream)
+        elif self.ap is not None:
+            self._apollo_update(has, hparams_of, stream)
         else:
             self._adafactor_update(has, hparams_of, stream)
 
@@ -867,7 +896,8 @@ class FlatEngine(ShardEngine):
         # fast path: every owned param has a grad and, per param group, one (step, carry) key
         own = self.owned
         hps = {}
-        whole = self.af is not None or self.am is not None or self.kind in MUON_KINDS
+        whole = (self.af is not None or self.am is not None or self.ap is not None
+                 or self.kind in MUON_KINDS)
         if has[own].all() and not whole:
             gof = np.asarray(self.group_of)
             for gi in np.unique(gof[own]):
@@ -1242,6 +1272,83 @@ class AdamMiniState:
             check_extents(rows[:, 4], n * 4, [eng.m], "Adam-mini exp_avg")
             check_extents(rows[:, 5], nb * 4, [self.state], "block_exp_avg_sq")
         return AdamMiniSet(rows, eng.czdtype, eng.p_dtype, resident_cap=eng.adamini_resident_cap)
+
+
+class ApolloState:
+    """The APOLLO state of a flat engine's owned matrices (Layout R: whole parameters): per matrix
+    ``exp_avg`` and ``exp_avg_sq`` (N x rank each, channel-major, N = max(R, C)) and
+    ``scaled_grad_norm`` (one float) at 16-byte multiples of one fp32 arena, ``seed`` (the group's
+    seed + the parameter's ordinal) as an int64 CPU scalar; and the ApolloSet tables over them."""
+
+    def __init__(self, eng, rank_seed):
+        self.eng = eng
+        self.rank = {i: int(rank_seed[i][0]) for i in eng.owned_param_indices()}
+        self.seed = {i: torch.tensor(int(rank_seed[i][1]) + i, dtype=torch.int64)
+                     for i in eng.owned_param_indices()}
+        self.off, total = {}, 0
+        for i in eng.owned_param_indices():
+            shape = tuple(eng.params[i].shape)
+            if len(shape) != 2:
+                raise ValueError(f"zero_amd: Apollo takes 2-D parameters (got size {shape})")
+            n = max(shape) * self.rank[i]
+            self.off[i] = (total, max(shape), n)
+            total += 2 * ((n + 3) // 4 * 4) + 4
+        self.state = torch.zeros(max(total, 4), dtype=torch.float32, device=eng.device)
+
+    def _cuts(self, i: int):
+        o, N, n = self.off[i]
+        pad = (n + 3) // 4 * 4
+        return o, o + pad, o + 2 * pad, N, n
+
+    def views(self, i: int) -> dict:
+        """Parameter i's sketch moments, ``scaled_grad_norm`` and ``seed`` as live views."""
+        m, v, f, N, n = self._cuts(i)
+        st = self.state
+        return {"exp_avg": st[m:m + n].view(N, -1), "exp_avg_sq": st[v:v + n].view(N, -1),
+                "scaled_grad_norm": st[f:f + 1].view(()), "seed": self.seed[i]}
+
+    def seeds(self, idx):
+        return np.array([int(self.seed[int(i)]) for i in idx], np.int64)
+
+    def new_set(self, idx):
+        """The ApolloSet of matrices ``idx`` (one group: one rank): the gradient from the reduced
+        stream R, the master as for Adafactor."""
+        eng = self.eng
+        pc = eng.pieces
+        so_of = {int(i): int(so) for i, so, n in zip(pc.param, pc.stream_off, pc.length) if n > 0}
+        base, rows = self.state.data_ptr(), []
+        for i in idx:
+            i = int(i)
+            if int(eng.numel[i]) == 0:
+                continue
+            R, C = (int(d) for d in eng.params[i].shape)
+            so = so_of[i]
+            g = eng.R.data_ptr() + so * eng.ces
+            pslot = eng.P.data_ptr() + (int(eng.base[eng.rank]) + so) * eng.es
+            if not eng.mixed:
+                mst, mo, po = pslot, pslot, 0
+            elif eng.split:
+                mst, mo, po = pslot, eng.lo.data_ptr() + so * 2, pslot
+            else:
+                mst = mo = eng.master.data_ptr() + so * 4
+                po = pslot
+            m, v, f, _, _ = self._cuts(i)
+            rows.append([g, mst, mo, po, base + 4 * m, base + 4 * v, base + 4 * f, R, C,
+                         int(self.seed[i]) % (1 << 64), i])
+        rows = np.array(rows, np.uint64).reshape(-1, 11)
+        rank = self.rank[int(idx[0])]
+        if check_extents_enabled():  # every entry inside its tensors (tests turn this on)
+            n = rows[:, 7].astype(np.int64) * rows[:, 8].astype(np.int64)
+            ns = np.maximum(rows[:, 7], rows[:, 8]).astype(np.int64) * rank
+            msz = 2 if eng.split else 4
+            check_extents(rows[:, 0], n * eng.ces, [eng.R], "Apollo gradient")
+            check_extents(rows[:, 1], n * msz, [eng.P, eng.master], "Apollo master")
+            check_extents(rows[:, 2], n * msz, [eng.P, eng.master, eng.lo], "Apollo master out")
+            check_extents(rows[:, 3], n * 2, [eng.P], "Apollo bf16 parameter")
+            check_extents(rows[:, 4], ns * 4, [self.state], "Apollo exp_avg")
+            check_extents(rows[:, 5], ns * 4, [self.state], "Apollo exp_avg_sq")
+            check_extents(rows[:, 6], np.full(len(rows), 4), [self.state], "Apollo scaled_grad_norm")
+        return ApolloSet(rows, eng.czdtype, eng.p_dtype, rank=rank)
 
 
 def _dense(g: torch.Tensor, p: torch.Tensor) -> bool:

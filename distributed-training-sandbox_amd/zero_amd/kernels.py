@@ -21,6 +21,9 @@ sums of squares, the row second moment and steps, a row-tiled apply); ``normuon_
 ``AdamMiniSet`` — zero_amd.optim.AdamMini's update over a table of parameters cut into blocks
 (csrc/zs_adamini.hip): a workgroup holds a block's gradient in registers between the reduction and
 the apply, larger blocks take two passes; ``adamini_hparams``.
+``ApolloSet`` — zero_amd.optim.Apollo's update over a table of matrices (csrc/zs_apollo.hip): the
+sign sketch on MFMA with the signs formed in registers, the sketch-space Adam, the finish, the
+apply; ``apollo_hparams``.
 ``adam_step`` — the same update over one contiguous range (zs_adam_step_ex; no table to keep).
 
 Both upload their segment table once; ``run(stream)`` only enqueues a kernel on ``stream``.
@@ -35,7 +38,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (AdafactorHParams, AdafactorSeg, AdamHParams, AdamMiniHParams, AdamMiniSeg,
-                   AdamSeg, LambHParams, LionHParams, MuonHParams, MuonSeg, NorMuonHParams,
+                   AdamSeg, ApolloHParams, ApolloSeg, LambHParams, LionHParams, MuonHParams, MuonSeg, NorMuonHParams,
                    SgdHParams)
 
 _PU64 = ctypes.POINTER(ctypes.c_uint64)
@@ -770,6 +773,81 @@ class AdamMiniSet:
         if h is not None and h.value and _lib is not None:
             try:
                 _lib.lib.zs_adaminiset_destroy(h)
+            except Exception:  # interpreter teardown
+                pass
+            self._h = None
+
+
+def apollo_hparams(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, *, scale=1.0,
+                   scale_type="channel", update_proj_gap=200, norm_growth=1.01, maximize=False,
+                   grad_div=1.0) -> ApolloHParams:
+    """A zero_amd.optim.Apollo group's scalars (zs_apollo_hparams_init)."""
+    if scale_type not in _lib.APOLLO_SCALE_TYPES:
+        raise ValueError(f"apollo_hparams: scale_type must be 'channel' or 'tensor' (got {scale_type!r})")
+    hp = ApolloHParams()
+    _lib.call("zs_apollo_hparams_init", float(lr), float(beta1), float(beta2), float(eps),
+              float(weight_decay), float(scale), _lib.APOLLO_SCALE_TYPES[scale_type],
+              int(update_proj_gap), float(norm_growth), int(bool(maximize)), float(grad_div),
+              ctypes.byref(hp))
+    return hp
+
+
+class ApolloSet:
+    """Fused APOLLO over a table with one entry per matrix; ``segs`` is an (n, 11) int64/uint64
+    array in zs_apollo_seg order: g, master, master_out, p_out, m, v, fprev, R, C, seed, param.
+    ``run`` is one step (the sketch, the sketch-space Adam, the finish, the apply), nothing on the
+    host."""
+
+    FIELDS = ("g", "master", "master_out", "p_out", "m", "v", "fprev", "R", "C", "seed", "param")
+    STATS = ("elems", "bytes", "scratch_bytes", "a_addr", "channels", "state_elems", "sketch_addr",
+             "sketch_workgroups", "sketch_elems")
+
+    def __init__(self, segs: np.ndarray, g_dtype: int, p_dtype: int = _lib.ZS_BF16, rank: int = 256):
+        segs = np.ascontiguousarray(np.asarray(segs, dtype=np.uint64).reshape(-1, 11))
+        arr = (ApolloSeg * max(len(segs), 1))()
+        ctypes.memmove(arr, segs.ctypes.data, segs.nbytes)
+        h = ctypes.c_void_p()
+        _lib.call("zs_apolloset_create", arr if len(segs) else None, len(segs), int(g_dtype),
+                  int(p_dtype), int(rank), ctypes.byref(h))
+        self._h = h
+        self.nseg, self.rank = len(segs), int(rank)
+        out = (ctypes.c_int64 * len(self.STATS))()
+        _lib.call("zs_apolloset_stats", h, out, len(self.STATS))
+        for name, v in zip(self.STATS, out):
+            setattr(self, name, int(v))
+
+    def run(self, hp: ApolloHParams, step: int, stream) -> None:
+        """One step; ``step`` is the entries' step count after it (zs_apolloset_run)."""
+        _lib.call("zs_apolloset_run", self._h, ctypes.byref(hp), int(step), stream_handle(stream))
+
+    def run_pass(self, hp: ApolloHParams, step: int, which: int, stream) -> None:
+        """Kernel ``which`` (0: the sketch, 1: the sketch-space Adam, 2: the finish, 3: the apply)
+        alone, for measurement."""
+        _lib.call("zs_apolloset_run_pass", self._h, ctypes.byref(hp), int(step), int(which),
+                  stream_handle(stream))
+
+    def read(self, name: str, stream, n: int | None = None):
+        """A copy of a scratch array as it stands in stream order, fp32; diagnostic.  "a": the step
+        a_c of every channel, the entries in table order; "sketch": the first ``n`` (default: all
+        ``sketch_elems``) partial sketch sums, per entry [cut][channel][rank] at a multiple of 4
+        floats, before the scale."""
+        import torch
+
+        if name not in ("a", "sketch"):
+            raise ValueError(f"ApolloSet.read: no array {name!r}")
+        n = self.channels if name == "a" else self.sketch_elems if n is None else int(n)
+        out = torch.empty(n, dtype=torch.float32,
+                          device=torch.device("cuda", torch.cuda.current_device()))
+        if n:
+            copy_direct([self.a_addr if name == "a" else self.sketch_addr], [out.data_ptr()],
+                        [4 * n], stream)
+        return out
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib is not None:
+            try:
+                _lib.lib.zs_apolloset_destroy(h)
             except Exception:  # interpreter teardown
                 pass
             self._h = None

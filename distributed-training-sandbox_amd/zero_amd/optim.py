@@ -14,9 +14,13 @@ running row second moment; see the class, which is this project's definition of 
 
 ``AdamMini`` (Zhang et al. 2024): Adam's first moment per element, one second moment per block of
 rows; see the class, likewise.
+
+``Apollo`` (Zhu et al. 2024): Adam's moments on a random sign sketch of the gradient, one step scale
+per channel applied to the raw gradient; see the class, likewise.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 from torch.optim import Optimizer
 
@@ -335,4 +339,142 @@ class AdamMini(Optimizer):
                      (v.double().sqrt() / (1 - beta2 ** t) ** 0.5 + group["eps"])).float()
                 p.mul_(1 - lr * group["weight_decay"])
                 p.view(nblk, -1).add_((a[:, None] * m.reshape(nblk, -1).float()).to(p.dtype))
+        return loss
+
+
+def _lowbias32(x):
+    """csrc/zs_sr.h's hash on a numpy uint32 array."""
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7feb352d)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846ca68b)
+    return x ^ (x >> np.uint32(16))
+
+
+def apollo_sigma(K: int, rank: int, seed: int, epoch: int):
+    """``Apollo``'s K x rank sign matrix of one (seed, epoch), fp32 +-1: zs_sr::keys and
+    zs_sr::bits restated in numpy.  One hash word serves 32 consecutive k of one column."""
+    seed, epoch = int(seed) % (1 << 64), int(epoch)
+    u = lambda v: np.array([v & 0xFFFFFFFF], np.uint32)  # noqa: E731
+    k0 = _lowbias32(u(epoch) ^ u(seed))
+    k1 = _lowbias32((k0 ^ u(seed >> 32) ^ u(epoch >> 32)) + np.uint32(0x9E3779B9))
+    kw = np.arange((K + 31) // 32, dtype=np.uint32)[:, None]
+    j = np.arange(rank, dtype=np.uint32)[None, :]
+    h = _lowbias32(kw ^ k0 ^ (j * np.uint32(0x9E3779B9))) ^ k1
+    bits = (h[:, None, :] >> np.arange(32, dtype=np.uint32)[None, :, None]) & np.uint32(1)
+    return 1.0 - 2.0 * bits.reshape(-1, rank)[:K].astype(np.float32)
+
+
+class Apollo(Optimizer):
+    """``Apollo(params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, *, rank=256,
+    scale=1.0, scale_type="channel", update_proj_gap=200, norm_growth=1.01, seed=0,
+    maximize=False)``: Zhu et al. 2024, "APOLLO: SGD-like Memory, AdamW-level Performance"
+    (arXiv:2412.05270) -- Adam's moments run on a rank-``rank`` random sketch of the gradient and
+    only set one step scale per channel (``scale_type="tensor"`` with ``rank=1``: per tensor,
+    APOLLO-Mini), which multiplies the raw gradient.  State is ``2 rank`` floats per channel.
+
+    2-D parameters only.  An R x C parameter has ``N = max(R, C)`` channels of ``K = min(R, C)``
+    elements: its rows when ``R >= C``, its columns otherwise; ``G`` is the N x K gradient.  With
+    ``q`` the parameter's ordinal in the optimizer and ``t`` the step count after the increment::
+
+        sigma = apollo_sigma(K, rank, seed + q, (t - 1) // update_proj_gap)       (+-1, K x rank)
+        S = (bf16(G) @ sigma) * fp32(1 / sqrt(rank))                             (fp32, N x rank)
+        M.lerp_(S, 1 - beta1);   V = (1 - beta2) * S * S + beta2 * V
+        Nh = (M / (1 - beta1^t)) / (sqrt(V) / sqrt(1 - beta2^t) + eps)
+        s_c = |Nh_c| / (|S_c| + 1e-8)        (double; "tensor": both norms over the whole matrix)
+        F = sqrt(sum_c s_c^2 |G_c|^2)
+        lam = max(F / (F_prev + 1e-8), norm_growth) / norm_growth  if norm_growth > 0 and F_prev > 0 else 1
+        F_prev = F / lam
+        p = p * (1 - lr * weight_decay) - lr * sqrt(scale) * s_c / lam * g
+
+    Two deliberate deviations from the paper: the projection is +-1 signs drawn from the counter
+    hash of csrc/zs_sr.h (a Johnson-Lindenstrauss projection like the Gaussian, exact in bf16, and
+    a function of indices, so no kernel ever stores it), and the sketch reads the gradient rounded
+    to bf16 (``|G_c|`` and the step use the full value).  ``state[p]`` holds ``step`` (an fp32 CPU
+    scalar), ``exp_avg`` and ``exp_avg_sq`` (fp32, N x rank), ``scaled_grad_norm`` (fp32, F_prev)
+    and ``seed`` (int64, ``seed + q``).  Handed to ``zero_amd.zero2.ShardedOptimizer`` (or
+    ``zero1`` at world size 1) the update runs in the fused HIP kernels instead (DESIGN.md §4,
+    "Fused APOLLO").
+    """
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, *, rank: int = 256, scale: float = 1.0,
+                 scale_type: str = "channel", update_proj_gap: int = 200,
+                 norm_growth: float = 1.01, seed: int = 0, maximize: bool = False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if int(rank) != rank or not 1 <= rank <= 256:
+            raise ValueError(f"Invalid rank: {rank} (an integer in [1, 256])")
+        if not 0.0 < scale:
+            raise ValueError(f"Invalid scale: {scale}")
+        if scale_type not in ("channel", "tensor"):
+            raise ValueError(f"Invalid scale_type: {scale_type!r} ('channel' or 'tensor')")
+        if int(update_proj_gap) != update_proj_gap or update_proj_gap < 1:
+            raise ValueError(f"Invalid update_proj_gap: {update_proj_gap}")
+        if not (norm_growth == 0 or norm_growth > 1):
+            raise ValueError(f"Invalid norm_growth: {norm_growth} (0, or above 1)")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      rank=int(rank), scale=scale, scale_type=scale_type,
+                                      update_proj_gap=int(update_proj_gap),
+                                      norm_growth=norm_growth, seed=int(seed), maximize=maximize))
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.ndim != 2:
+                    raise ValueError(f"Apollo takes 2-D parameters (got size: {tuple(p.shape)})")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        q = -1
+        for group in self.param_groups:
+            beta1, beta2 = group["betas"]
+            lr, rank, ng = float(group["lr"]), group["rank"], float(group["norm_growth"])
+            for p in group["params"]:
+                q += 1
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("Apollo does not support sparse gradients")
+                g = (-p.grad if group["maximize"] else p.grad).float()
+                tall = p.shape[0] >= p.shape[1]
+                G = g if tall else g.t()
+                N, K = G.shape
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["exp_avg"] = torch.zeros(N, rank, dtype=torch.float32, device=p.device)
+                    state["exp_avg_sq"] = torch.zeros(N, rank, dtype=torch.float32, device=p.device)
+                    state["scaled_grad_norm"] = torch.zeros((), dtype=torch.float32, device=p.device)
+                    state["seed"] = torch.tensor(group["seed"] + q, dtype=torch.int64)
+                M, V = state["exp_avg"], state["exp_avg_sq"]
+                state["step"] += 1
+                t = float(state["step"])
+                sigma = apollo_sigma(K, rank, int(state["seed"]), (int(t) - 1) // group["update_proj_gap"])
+                S = (G.to(torch.bfloat16).float() @ torch.from_numpy(sigma).to(p.device)) * rank ** -0.5
+                M.lerp_(S, 1 - beta1)
+                V.mul_(beta2).addcmul_(S, S, value=1 - beta2)
+                Nh = (M / (1 - beta1 ** t)) / (V.sqrt() / (1 - beta2 ** t) ** 0.5 + group["eps"])
+                nn, ss = Nh.double().square().sum(1), S.double().square().sum(1)
+                if group["scale_type"] == "tensor":
+                    nn, ss = nn.sum().expand(N), ss.sum().expand(N)
+                s = nn.sqrt() / (ss.sqrt() + 1e-8)
+                F = float((s * s * G.double().square().sum(1)).sum().sqrt())
+                Fp = float(state["scaled_grad_norm"])
+                lam = max(F / (Fp + 1e-8), ng) / ng if ng > 0 and Fp > 0 else 1.0
+                state["scaled_grad_norm"].fill_(F / lam)
+                a = (-lr * group["scale"] ** 0.5 * s / lam).float()
+                upd = a[:, None] * G
+                p.mul_(1 - lr * group["weight_decay"])
+                p.add_((upd if tall else upd.t()).to(p.dtype))
         return loss

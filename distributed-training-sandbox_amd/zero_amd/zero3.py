@@ -69,7 +69,7 @@ from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_BF16_SR, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
 from ._sharded import group_hparams, optimizer_kind
-from ._update import (GradClip, LambNorms, UpdateCore, UpdateNorms, check_adafactor, check_adamini, check_lamb, check_muon, check_bf16_state_group,
+from ._update import (GradClip, LambNorms, UpdateCore, UpdateNorms, check_adafactor, check_adamini, check_apollo, check_lamb, check_muon, check_bf16_state_group,
                       check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group, check_master_free, check_update_norms,
                       check_update_norms_group,
                       check_master_free_group, check_max_grad_norm, check_param_grad_norms, check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
@@ -1857,6 +1857,8 @@ class ShardedOptimizer:
                        kind=optimizer_kind(optimizer))
         if optimizer_kind(optimizer) == "adamini":
             check_adamini(zero3=True)
+        if optimizer_kind(optimizer) == "apollo":
+            check_apollo(zero3=True)
         if optimizer_kind(optimizer) == "lamb":
             check_lamb(zero3_reference=not update, skip_nonfinite=skip_nonfinite,
                        state_dtype=state_dtype, state_rounding=state_rounding, master=master,

@@ -964,6 +964,89 @@ int zs_adaminiset_run_pass(const zs_adaminiset* as, const zs_adamini_hparams* hp
 int zs_adaminiset_stats(const zs_adaminiset* as, int64_t* out, int64_t n);
 int zs_adaminiset_destroy(zs_adaminiset* as);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Fused APOLLO (Zhu et al. 2024, arXiv:2412.05270; zero_amd.optim.Apollo's rule), additive in   */
+/* ABI v13: Adam's moments on a rank-r sign sketch of the gradient, one step scale per channel   */
+/* (or per tensor) applied to the raw gradient; no per-element optimizer state.  An R x C entry  */
+/* has N = max(R, C) channels of K = min(R, C) elements (rows when R >= C, columns otherwise).   */
+/* The sketch runs on v_mfma_f32_32x32x16_bf16 with the +-1 operand formed in registers from     */
+/* zs_sr_bits; nothing is atomic, every scalar stays on the device, the bits repeat from run to  */
+/* run.                                                                                          */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint64_t g;          /* reduced gradient sum, R * C elements of g_dtype (required) */
+  uint64_t master;     /* as zs_adamini_seg */
+  uint64_t master_out; /* as zs_adamini_seg */
+  uint64_t p_out;      /* as zs_adamini_seg */
+  uint64_t m;          /* fp32 exp_avg, N * rank elements, channel-major, updated in place */
+  uint64_t v;          /* fp32 exp_avg_sq, likewise */
+  uint64_t fprev;      /* fp32 scaled_grad_norm, one element, read and rewritten */
+  int64_t R, C;        /* rows and columns: row i starts at element i * C */
+  uint64_t seed;       /* the optimizer's seed + the parameter's ordinal in it */
+  int64_t param;       /* the caller's index of the entry's parameter */
+} zs_apollo_seg;
+
+enum { ZS_APOLLO_CHANNEL = 0, ZS_APOLLO_TENSOR = 1 };
+
+typedef struct {
+  /* the group's scalars as doubles; a run rounds what it derives from them to f32 once */
+  double lr;
+  double beta1;
+  double beta2;
+  double eps;
+  double weight_decay;
+  double scale;            /* the step is multiplied by sqrt(scale) */
+  double norm_growth;      /* the norm-growth limiter's gamma (> 1), or 0: no limiter */
+  double grad_div;         /* divide the reduced sum by this (world size) */
+  int64_t update_proj_gap; /* the signs are re-drawn every this many steps */
+  int32_t scale_type;      /* ZS_APOLLO_CHANNEL or ZS_APOLLO_TENSOR */
+  int32_t maximize;
+} zs_apollo_hparams;
+
+/* Fill hp from a zero_amd.optim.Apollo param group.  ZS_ERR_INVALID unless lr >= 0, both betas in
+ * [0, 1), eps >= 0, weight_decay >= 0, scale > 0, scale_type is one of the two, update_proj_gap >= 1,
+ * norm_growth is 0 or > 1, grad_div > 0 and hp is not NULL. */
+int zs_apollo_hparams_init(double lr, double beta1, double beta2, double eps, double weight_decay,
+                           double scale, int scale_type, int64_t update_proj_gap,
+                           double norm_growth, int maximize, double grad_div,
+                           zs_apollo_hparams* hp);
+typedef struct zs_apolloset zs_apolloset;
+/* g_dtype ZS_F32 or ZS_BF16; p_dtype ZS_BF16 (fp32 master in place, optional bf16 p_out) or
+ * ZS_BF16_SPLIT; rank in [1, 256].  Entries of any shapes share a launch.  The set owns its scratch
+ * (the sketch's partial sums, the channels' sums and a_c).  Every check comes before any
+ * allocation or upload. */
+int zs_apolloset_create(const zs_apollo_seg* segs, int64_t n, int g_dtype, int p_dtype,
+                        int64_t rank, zs_apolloset** out);
+/* One APOLLO step over the set, step = the entries' step count t after it (>= 1).  Per entry, with
+ * g = gradsum / grad_div (fp32, negated under maximize) and G[c, k] channel c's k-th element:
+ *   (k0, k1) = zs_sr_keys(seed, (t - 1) / update_proj_gap)
+ *   sigma(k, j) = +1 if bit (k & 31) of zs_sr_bits((j << 32) | (k >> 5), k0, k1) is 0, else -1
+ *   S[c, j] = fp32(fp32(sum_k sigma(k, j) bf16(Gsum[c, k])) * fp32(1 / (grad_div sqrt(rank))))
+ *   M = lerp(M, S, 1 - beta1);  V = fma(1 - beta2, S * S, V * beta2)                      (fp32)
+ *   Nh = (M / (1 - beta1^t)) / (sqrt(V) / sqrt(1 - beta2^t) + eps)                        (fp32)
+ *   s_c = sqrt(sum_j Nh^2) / (sqrt(sum_j S^2) + 1e-8)          (double; "tensor": both sums over c too)
+ *   F = sqrt(sum_c s_c^2 sum_k g[c, k]^2)
+ *   lam = max(F / (F_prev + 1e-8), norm_growth) / norm_growth if norm_growth > 0 and F_prev > 0, else 1
+ *   F_prev = fp32(F / lam);  a_c = fp32(-lr sqrt(scale) s_c / lam)
+ *   p = fma(a_c, g, p * fp32(1 - lr * weight_decay))
+ * The sketch accumulates in the matrix cores' fp32; other sums run in fp32 inside a 16-byte piece
+ * and in double above, in an order that depends on the shape alone.  ZS_ERR_INVALID, nothing
+ * launched: a NULL argument, a set of another family, step < 1, hyper-parameters
+ * zs_apollo_hparams_init would refuse. */
+int zs_apolloset_run(const zs_apolloset* as, const zs_apollo_hparams* hp, int64_t step,
+                     uintptr_t stream);
+/* One kernel of zs_apolloset_run (0: the sketch and the sums of g^2; 1: the sketch-space Adam; 2:
+ * the finish; 3: the apply), for measurement; 0 .. 3 in order are one run. */
+int zs_apolloset_run_pass(const zs_apolloset* as, const zs_apollo_hparams* hp, int64_t step,
+                          int pass, uintptr_t stream);
+/* out[0 .. min(n, 9)): elements covered; algorithmic HBM bytes of one run; bytes of the set's
+ * scratch; the device address of a_c (fp32, the entries' channels in table order, the last run's);
+ * channels; elements of M and V together; the device address of the first entry's partial sketch
+ * sums (fp32 [cut][channel][rank] per entry, each entry at a multiple of 4 floats, before the
+ * scale; diagnostic); the sketch's workgroups; the floats of all entries' partial sums. */
+int zs_apolloset_stats(const zs_apolloset* as, int64_t* out, int64_t n);
+int zs_apolloset_destroy(zs_apolloset* as);
+
 /* Single-range form, SURVEY.md §8(b)'s signature: one torch.optim.Adam/AdamW step over n
  * contiguous elements — the update of one flat shard (zero1.py:88 on a flattened group) with no
  * table to build.  p: fp32 master/param, updated in place; p_bf16: optional bf16 copy of the
