@@ -1,9 +1,9 @@
 // CDNA4 (gfx950) kernels of the ZeRO step and the C entry points that launch them: segment copy
 // (pack / unpack), the fused optimizer update (one vector and one scalar kernel, instantiated over
 // the element rules: Adam, Adam with bf16 moments rounded to nearest or stochastically, Adam over
-// master-free bf16 parameters rounded stochastically, SGD), the
-// gradient sum of squares and clip coefficient, scale, accumulate, convert, the fp8 row quantizer
-// and gather, and the flag kernels.
+// master-free bf16 parameters rounded stochastically, SGD, Lion, Schedule-Free AdamW), the
+// Schedule-Free eval / train swap, the gradient sum of squares and clip coefficient, scale,
+// accumulate, convert, the fp8 row quantizer and gather, and the flag kernels.
 //
 // The copy and update kernels are HBM-bound streaming kernels (no MFMA, no LDS): 64-wide waves,
 // 256-thread workgroups, 16-byte-per-lane coalesced accesses, a grid of 128 workgroups per CU (16x
@@ -208,7 +208,8 @@ __global__ __launch_bounds__(kThreads) void copy_direct_kernel(const DirectSet s
 }
 
 // ----------------------------------------------------------------------------------------------
-// fused optimizer update: one chunk-streaming skeleton, three element rules (Adam, SGD, Lion)
+// fused optimizer update: one chunk-streaming skeleton, four element rules (Adam, SGD, Lion,
+// Schedule-Free AdamW)
 // ----------------------------------------------------------------------------------------------
 struct AdamSeg {
   const void* g;
@@ -605,6 +606,47 @@ template <bool>
 using LionRule = LionRuleT<LionHP>;
 template <bool>
 using LionSrRule = LionRuleT<LionSrHP>;
+
+// Schedule-Free AdamW (Defazio et al. 2024, "The Road Less Scheduled") over the same tables: the
+// master holds y (the point the gradient is taken at), field `m` of a segment is z (the base
+// iterate), `v` is exp_avg_sq; `vmax` is unused.  Adam's streams, so Adam's bytes.  The host forms
+// every scalar of the step (zs_sfadam_hparams_init): c = w_t / sum w, a = lr_t (beta1 (1 - c) - 1),
+// bc2 = 1 - beta2^t.  lerp_w / lerp_hi: ATen's lerp of weight c, as HP's of weight 1 - beta1.
+struct SfAdamHP {
+  float beta2, omb2, bc2, eps, wd, lerp_w, a, neg_lr, grad_div, inv_div, carry_mul;
+  int div_pow2, maximize, lerp_hi;
+};
+
+struct SfAdamRule {
+  using Hyper = SfAdamHP;
+  static constexpr bool kM = true, kV = true, kX = false, kGradOffset2 = true;
+  static constexpr bool kPsr = false;
+  static constexpr bool kEma = false;
+  static constexpr bool kStats = false;
+  static constexpr bool kNoStore = false;
+  using Stats = NoStats;
+
+  // One element of zero_amd.optim.ScheduleFreeAdamW's step, in the rounding order of torch's CPU
+  // kernels: v.mul_(b2).addcmul_(g, g, value=1-b2) = fma((1-b2)*g, g, v*b2); d = sqrt(v / bc2) + eps
+  // (IEEE division and root); n = g / d, n.add_(y, alpha=wd) = fma(wd, y, n); y.lerp_(z, c) =
+  // fma(c, z-y, y) or fma(c-1, z-y, z) (ATen Lerp.h, by |c| < 0.5); y.add_(n, alpha=a) =
+  // fma(a, n, y); z.add_(n, alpha=-lr_t) = fma(-lr_t, n, z).  Only explicit fmaf() fuse.
+  template <bool CARRY, bool CLIP>
+  static __device__ __forceinline__ void elem(float gsum, float& y, float& z, float& v, float&,
+                                              float& carry, const SfAdamHP& hp, float coef) {
+#pragma clang fp contract(off)
+    const float g = prep_grad<CARRY, CLIP>(gsum, carry, hp, coef);
+    v = fmaf(hp.omb2 * g, g, v * hp.beta2);
+    const float d = sqrtf(v / hp.bc2) + hp.eps;
+    float n = g / d;
+    if (hp.wd != 0.0f) n = fmaf(hp.wd, y, n);
+    y = fmaf(hp.lerp_w, z - y, hp.lerp_hi ? z : y);
+    y = fmaf(hp.a, n, y);
+    z = fmaf(hp.neg_lr, n, z);
+  }
+};
+template <bool>
+using SfAdamRuleOf = SfAdamRule;
 
 template <typename GT>
 __device__ __forceinline__ float load_g1(const void* g, int64_t i) {
@@ -1194,6 +1236,114 @@ __global__ __launch_bounds__(kThreads) void adam_scalar_kernel(
 #ifdef ZS_UPDATE_SKELETON_ONLY
 }  // namespace
 #else
+
+// ----------------------------------------------------------------------------------------------
+// Schedule-Free AdamW: the eval() / train() swap of the model parameters (zs_sfadamset_swap)
+// ----------------------------------------------------------------------------------------------
+// eval: x = lerp(y, z, 1 - 1/beta1), the averaged iterate; train: y = lerp(x, z, 1 - beta1).  One
+// pass over the set's own tables in the update's chunks: all of a chunk's loads (the master in its
+// encoding, z) before the first use, 16 bytes per lane per access (8 for the 16-bit arrays), then
+// the lerp and the stores group by group.  The weight, which operand the fma adds to (ATen's lerp,
+// as SfAdamRule's) and the direction are kernel arguments.  What a segment stores is uniform:
+//   an fp32 master beside a bf16 copy (p_out set, not SPLIT): only the copy is written -- eval
+//     stores bf16(x) and the master keeps y, train rounds the master again and never reads z;
+//   an fp32 parameter that is its own master: x (train: y) over the master, in place;
+//   SPLIT: the bf16 parameter is the master's high half, so it is in place too: x is split into
+//     p_out and the residual as the update splits y.
+struct SwapArgs {
+  float w;  // the weight, or weight - 1 when hi
+  int hi, to_eval;
+};
+
+__device__ __forceinline__ float swap_lerp(float p, float z, const SwapArgs& a) {
+#pragma clang fp contract(off)
+  return fmaf(a.w, z - p, a.hi ? z : p);
+}
+
+template <bool SPLIT>
+__global__ __launch_bounds__(kThreads) void sfadam_swap_kernel(
+    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
+    int64_t total_chunks, const SwapArgs a) {
+  constexpr int G = adam_groups(SPLIT);
+  int64_t seg = 0, top = nseg;
+  while (top - seg > 1) {  // the first chunk's segment by bisection, the rest by a forward scan
+    const int64_t mid = (seg + top) >> 1;
+    if (chunk_prefix[mid] <= int64_t(blockIdx.x)) seg = mid;
+    else top = mid;
+  }
+  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
+    while (chunk_prefix[seg + 1] <= c) ++seg;
+    const AdamSeg s = segs[seg];
+    const int64_t e0 = (c - chunk_prefix[seg]) * adam_chunk(SPLIT) + int64_t(threadIdx.x) * 4;
+    const bool copy = !SPLIT && s.p_out != nullptr;  // uniform
+    const bool lerp = !copy || a.to_eval;            // train on a copy: the master rounded again
+    uint4 pq[G], zq[G];
+    uint2 hd[G], ld[G];
+#pragma unroll
+    for (int u = 0; u < G; ++u) {  // every load of the chunk
+      const int64_t i = e0 + int64_t(u) * kThreads * 4;
+      if (i >= s.n) continue;  // (n % 4 == 0: a group lies inside the segment or outside)
+      if constexpr (SPLIT) {
+        hd[u] = nt_ld8(reinterpret_cast<const unsigned short*>(s.master) + i);
+        ld[u] = nt_ld8(reinterpret_cast<const unsigned short*>(s.master_out) + i);
+      } else {
+        pq[u] = nt_ld16(s.master + i);
+      }
+      if (lerp) zq[u] = nt_ld16(s.m + i);
+    }
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const int64_t i = e0 + int64_t(u) * kThreads * 4;
+      if (i >= s.n) continue;
+      float p[4], z[4];
+      if constexpr (SPLIT) join_master4(hd[u], ld[u], p);
+      else unpack4(pq[u], p);
+      if (lerp) {
+        unpack4(zq[u], z);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] = swap_lerp(p[j], z[j], a);
+      }
+      if constexpr (SPLIT) {
+        uint32_t h[4], l[4];
+        split_master4(p, h, l);
+        nt_st8(s.p_out + i, pack_u16x4(h));
+        nt_st8(reinterpret_cast<unsigned short*>(s.master_out) + i, pack_u16x4(l));
+      } else if (copy) {
+        nt_st8(s.p_out + i, pack_bf16x4(p));
+      } else if (s.master_out) {
+        nt_st16(s.master_out + i, pack4(p));
+      }
+    }
+  }
+}
+
+// the scalar table (tails, unaligned segments): one element per lane, 256-element chunks
+template <bool SPLIT>
+__global__ __launch_bounds__(kThreads) void sfadam_swap_scalar_kernel(
+    const AdamSeg* __restrict__ segs, const int64_t* __restrict__ chunk_prefix, int64_t nseg,
+    int64_t total_chunks, const SwapArgs a) {
+  int64_t seg = 0;
+  for (int64_t c = blockIdx.x; c < total_chunks; c += gridDim.x) {
+    while (chunk_prefix[seg + 1] <= c) ++seg;
+    const AdamSeg s = segs[seg];
+    const int64_t i = (c - chunk_prefix[seg]) * kThreads + threadIdx.x;
+    if (i >= s.n) continue;
+    const bool copy = !SPLIT && s.p_out != nullptr;
+    const gptr<unsigned short> lo = glob(reinterpret_cast<unsigned short*>(s.master_out));
+    float p = SPLIT ? join_master(glob(reinterpret_cast<const unsigned short*>(s.master))[i], lo[i])
+                    : glob(s.master)[i];
+    if (!copy || a.to_eval) p = swap_lerp(p, glob(s.m)[i], a);
+    if constexpr (SPLIT) {
+      const unsigned short h = f32_to_bf16(p);
+      glob(s.p_out)[i] = h;
+      lo[i] = (unsigned short)master_residual(p, h);
+    } else if (copy) {
+      glob(s.p_out)[i] = f32_to_bf16(p);
+    } else if (s.master_out) {
+      glob(s.master_out)[i] = p;
+    }
+  }
+}
 
 // ----------------------------------------------------------------------------------------------
 // gradient sum of squares over an Adam set (global-norm clipping, clip_grad_norm_'s norm)
@@ -2225,6 +2375,8 @@ struct zs_adamset {
   int sgd = 0, has_mom = 0;
   // zs_lionset_create: a Lion set (field m is exp_avg, fp32 or bf16 by state_dtype; no v)
   int lion = 0;
+  // zs_sfadamset_create: a Schedule-Free AdamW set (the master is y, field m is z, v exp_avg_sq)
+  int sfadam = 0;
   // zs_adamset_create_ex: the element type of m and v, ZS_F32 or ZS_BF16
   int state_dtype = ZS_F32;
   // zs_adamset_set_grads: which input segment each table entry came from (the scalar entries with
@@ -2382,6 +2534,10 @@ using SgdFamily = UpdateFamily<SgdRule, float, true>;
 using LionFamily = UpdateFamily<LionRule, float, true, true>;
 using LionBf16Family = UpdateFamily<LionRule, unsigned short, false, true>;
 using LionSrFamily = UpdateFamily<LionSrRule, SrBf16, false, true>;
+// zs_sfadamset_run: fp32 z and v (with the carry instances; the rule has no flag).  No guarded
+// instances: the host's weight sum would advance over a skipped step, so the entry point refuses
+// the guard until a caller can use it.
+using SfAdamFamily = UpdateFamily<SfAdamRuleOf, float, true>;
 template <bool>
 using AdamPsrRuleOf = AdamPsrRule;
 // zs_adamset_run_psr: the master-free instances, by how m and v are stored
@@ -2952,15 +3108,16 @@ int zs_adam_hparams_init(double lr, double beta1, double beta2, double eps, doub
 // state_dtype: the element type of m and v (ZS_BF16: zs_adamset_create_ex's bf16 moments, Lion's
 // bf16 momentum).
 static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n, int g_dtype,
-                      int p_dtype, int state_dtype, zs_adamset** out, bool lion = false) {
+                      int p_dtype, int state_dtype, zs_adamset** out, bool lion = false,
+                      bool sfadam = false) {
   ZS_REQUIRE(out != nullptr, "%s: out is NULL", fn);
   *out = nullptr;
   ZS_REQUIRE(n >= 0 && (n == 0 || in), "%s: bad table", fn);
   ZS_REQUIRE(g_dtype == ZS_F32 || g_dtype == ZS_BF16, "%s: bad g_dtype %d", fn, g_dtype);
   const bool psr = p_dtype == ZS_BF16_SR;  // master-free: zs_adamset_run_psr
-  ZS_REQUIRE(p_dtype == ZS_BF16 || p_dtype == ZS_BF16_SPLIT || (psr && !sgd && !lion),
+  ZS_REQUIRE(p_dtype == ZS_BF16 || p_dtype == ZS_BF16_SPLIT || (psr && !sgd && !lion && !sfadam),
              "%s: p_dtype must be ZS_BF16 or ZS_BF16_SPLIT%s (got %d)", fn,
-             sgd || lion ? "" : " or ZS_BF16_SR", p_dtype);
+             sgd || lion || sfadam ? "" : " or ZS_BF16_SR", p_dtype);
   ZS_REQUIRE(state_dtype == ZS_F32 || (state_dtype == ZS_BF16 && !sgd),
              "%s: state_dtype must be ZS_F32 or ZS_BF16 (got %d)", fn, state_dtype);
   const bool split = p_dtype == ZS_BF16_SPLIT;
@@ -3000,6 +3157,8 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
                  (long long)i);
     } else {
       ZS_REQUIRE(s.master && s.m && s.v, "%s: seg %lld missing master/m/v", fn, (long long)i);
+      ZS_REQUIRE(!sfadam || !s.vmax, "%s: seg %lld: vmax must be 0 in a Schedule-Free AdamW set",
+                 fn, (long long)i);
     }
     ZS_REQUIRE(!split || (s.master_out && s.p_out),
                "%s: seg %lld: a split master needs master_out (residual) and p_out", fn,
@@ -3114,6 +3273,7 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   as->sgd = sgd ? 1 : 0;
   as->has_mom = mom_state > 0 ? 1 : 0;
   as->lion = lion ? 1 : 0;
+  as->sfadam = sfadam ? 1 : 0;
   as->state_dtype = state_dtype;
   as->in_g = std::move(in_g);
   as->in_n = std::move(in_n);
@@ -3190,6 +3350,8 @@ int zs_sgdset_run(const zs_adamset* as, const zs_sgd_hparams* h, const float* co
   ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create (use "
              "zs_adafactorset_run)", "zs_sgdset_run");
   ZS_REQUIRE(!as->lion, "zs_sgdset_run: the set was made by zs_lionset_create (use zs_lionset_run)");
+  ZS_REQUIRE(!as->sfadam,
+             "zs_sgdset_run: the set was made by zs_sfadamset_create (use zs_sfadamset_run)");
   ZS_REQUIRE(as->sgd, "zs_sgdset_run: the set was made by zs_adamset_create (use zs_adamset_run)");
   // a struct filled by hand gets zs_sgd_hparams_init's rules too (-0.0f is lr = 0)
   ZS_REQUIRE(h->neg_lr <= 0.0f, "zs_sgdset_run: negative learning rate");
@@ -3284,6 +3446,113 @@ int zs_lionset_run(const zs_adamset* as, const zs_lion_hparams* h, const float* 
   return run_set<LionSrFamily>(as, false, hp, coef, stream, g);
 }
 
+int zs_sfadamset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype,
+                        zs_adamset** out) {
+  return set_create("zs_sfadamset_create", false, in, n, g_dtype, p_dtype, ZS_F32, out, false, true);
+}
+
+int zs_sfadam_hparams_init(double lr, double beta1, double beta2, double eps, double weight_decay,
+                           int64_t step, double c, int maximize, double grad_div, double carry_mul,
+                           zs_sfadam_hparams* hp) {
+  const char* fn = "zs_sfadam_hparams_init";
+  ZS_REQUIRE(hp != nullptr, "%s: hp is NULL", fn);
+  ZS_REQUIRE(grad_div > 0.0, "%s: grad_div must be > 0", fn);
+  ZS_REQUIRE(step >= 1, "%s: step must be >= 1 (got %lld)", fn, (long long)step);
+  // zero_amd.optim.ScheduleFreeAdamW.__init__'s rules (beta1 == 0: 1 - 1/beta1 is undefined)
+  ZS_REQUIRE(lr >= 0.0, "%s: invalid learning rate %g", fn, lr);
+  ZS_REQUIRE(beta1 > 0.0 && beta1 < 1.0, "%s: invalid beta1 %g", fn, beta1);
+  ZS_REQUIRE(beta2 >= 0.0 && beta2 < 1.0, "%s: invalid beta2 %g", fn, beta2);
+  ZS_REQUIRE(eps >= 0.0, "%s: invalid epsilon %g", fn, eps);
+  ZS_REQUIRE(weight_decay >= 0.0, "%s: invalid weight_decay %g", fn, weight_decay);
+  ZS_REQUIRE(c >= 0.0 && c <= 1.0, "%s: the averaging weight c must lie in [0, 1] (got %g)", fn, c);
+  hp->beta2 = float(beta2);
+  hp->one_minus_beta2 = float(1.0 - beta2);
+  hp->bc2 = float(1.0 - std::pow(beta2, double(step)));
+  hp->eps = float(eps);
+  hp->weight_decay = float(weight_decay);
+  hp->c = float(c);
+  hp->a = float(lr * (beta1 * (1.0 - c) - 1.0));
+  hp->lr_t = float(lr);
+  hp->grad_div = float(grad_div);
+  hp->carry_mul = float(carry_mul);
+  hp->maximize = maximize ? 1 : 0;
+  return ZS_OK;
+}
+
+// what zs_sfadamset_run and zs_sfadamset_swap ask of the set alike
+static int sfadam_set_check(const char* fn, const zs_adamset* as) {
+  ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create (use "
+             "zs_adafactorset_run)", fn);
+  ZS_REQUIRE(as->sfadam, "%s: the set was not made by zs_sfadamset_create", fn);
+  return ZS_OK;
+}
+
+int zs_sfadamset_run(const zs_adamset* as, const zs_sfadam_hparams* h, const float* coef, int guard,
+                     uintptr_t stream) {
+  const char* fn = "zs_sfadamset_run";
+  ZS_REQUIRE(as && h, "%s: NULL argument", fn);
+  if (const int rc = sfadam_set_check(fn, as)) return rc;
+  ZS_REQUIRE(!guard, "%s: the guard is not supported (the host's weight sum would advance over a "
+             "skipped step): no guarded instances exist", fn);
+  // a struct filled by hand gets zs_sfadam_hparams_init's rules too
+  ZS_REQUIRE(h->lr_t >= 0.0f, "%s: negative learning rate", fn);
+  ZS_REQUIRE(h->beta2 >= 0.0f && h->beta2 <= 1.0f, "%s: invalid beta2 %g", fn, double(h->beta2));
+  ZS_REQUIRE(h->bc2 > 0.0f && h->bc2 <= 1.0f, "%s: invalid bias correction %g", fn, double(h->bc2));
+  ZS_REQUIRE(h->eps >= 0.0f && h->weight_decay >= 0.0f, "%s: invalid eps or weight_decay", fn);
+  ZS_REQUIRE(h->c >= 0.0f && h->c <= 1.0f, "%s: the averaging weight c must lie in [0, 1]", fn);
+  ZS_REQUIRE(h->grad_div > 0.0f, "%s: grad_div must be > 0", fn);
+  ZS_REQUIRE(!coef || !as->has_carry, "%s: a set with the ZeRO-1 carry cannot be clipped", fn);
+  SfAdamHP hp;
+  hp.beta2 = h->beta2;
+  hp.omb2 = h->one_minus_beta2;
+  hp.bc2 = h->bc2;
+  hp.eps = h->eps;
+  hp.wd = h->weight_decay;
+  hp.lerp_hi = std::fabs(h->c) < 0.5f ? 0 : 1;
+  hp.lerp_w = hp.lerp_hi ? h->c - 1.0f : h->c;
+  hp.a = h->a;
+  hp.neg_lr = -h->lr_t;
+  hp.carry_mul = h->carry_mul;
+  set_grad_div(&hp, h->grad_div);
+  hp.maximize = h->maximize ? 1 : 0;
+  return run_set<SfAdamFamily>(as, false, hp, coef, stream);
+}
+
+int zs_sfadamset_swap(const zs_adamset* as, double weight, int to_eval, uintptr_t stream) {
+  const char* fn = "zs_sfadamset_swap";
+  ZS_REQUIRE(as != nullptr, "%s: NULL set", fn);
+  if (const int rc = sfadam_set_check(fn, as)) return rc;
+  ZS_REQUIRE(std::isfinite(weight), "%s: the weight must be finite (got %g)", fn, weight);
+  SwapArgs a;
+  const float w = float(weight);
+  a.hi = std::fabs(w) < 0.5f ? 0 : 1;
+  a.w = a.hi ? w - 1.0f : w;
+  a.to_eval = to_eval ? 1 : 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool split = as->p_dtype == ZS_BF16_SPLIT;
+  if (as->vec_chunks) {
+    const dim3 grid(int(std::min(as->vec_chunks, adam_grid_cap(kAdamWgPerCu))));
+    if (split)
+      hipLaunchKernelGGL(sfadam_swap_kernel<true>, grid, dim3(kThreads), 0, st, as->d_vec,
+                         as->d_vec_prefix, as->nvec, as->vec_chunks, a);
+    else
+      hipLaunchKernelGGL(sfadam_swap_kernel<false>, grid, dim3(kThreads), 0, st, as->d_vec,
+                         as->d_vec_prefix, as->nvec, as->vec_chunks, a);
+    ZS_HIP(hipGetLastError());
+  }
+  if (as->sca_chunks) {
+    const dim3 grid(int(std::min(as->sca_chunks, adam_grid_cap(kAdamWgPerCu))));
+    if (split)
+      hipLaunchKernelGGL(sfadam_swap_scalar_kernel<true>, grid, dim3(kThreads), 0, st, as->d_sca,
+                         as->d_sca_prefix, as->nsca, as->sca_chunks, a);
+    else
+      hipLaunchKernelGGL(sfadam_swap_scalar_kernel<false>, grid, dim3(kThreads), 0, st, as->d_sca,
+                         as->d_sca_prefix, as->nsca, as->sca_chunks, a);
+    ZS_HIP(hipGetLastError());
+  }
+  return ZS_OK;
+}
+
 // The three Adam entry points (`fn`: the one called, in messages).  need_coef: zs_adamset_run_clipped
 // requires its coefficient; sr: zs_adamset_run_sr's m_base and keys, over a set with bf16 moments.
 struct SrArgs {
@@ -3296,6 +3565,7 @@ static int adam_run(const char* fn, const zs_adamset* as, const zs_adam_hparams*
   ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create (use "
              "zs_adafactorset_run)", fn);
   ZS_REQUIRE(!as->lion, "%s: the set was made by zs_lionset_create (use zs_lionset_run)", fn);
+  ZS_REQUIRE(!as->sfadam, "%s: the set was made by zs_sfadamset_create (use zs_sfadamset_run)", fn);
   ZS_REQUIRE(!guard || !as->sgd, "%s: the guarded update is Adam's (the set was made by "
              "zs_sgdset_create)", fn);
   ZS_REQUIRE(!sr || (!as->sgd && as->state_dtype == ZS_BF16),
@@ -3359,7 +3629,7 @@ int zs_adamset_run_psr(const zs_adamset* as, const zs_adam_hparams* h, const flo
   ZS_REQUIRE(as && h, "%s: NULL argument", fn);
   ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create (use "
              "zs_adafactorset_run)", fn);
-  ZS_REQUIRE(as->p_dtype == ZS_BF16_SR && !as->sgd && !as->lion,
+  ZS_REQUIRE(as->p_dtype == ZS_BF16_SR && !as->sgd && !as->lion && !as->sfadam,
              "%s: the set was not made with p_dtype ZS_BF16_SR (zs_adamset_create_ex)", fn);
   ZS_REQUIRE(!guard || coef, "%s: the guard tests the clip coefficient, which is NULL", fn);
   ZS_REQUIRE(h->amsgrad == 0, "%s: a ZS_BF16_SR set has no amsgrad", fn);
@@ -3393,6 +3663,8 @@ int zs_adamset_run_ema(const zs_adamset* as, const zs_adam_hparams* h, const flo
              fn);
   ZS_REQUIRE(!as->lion, "%s: the EMA rides on Adam's update (the set was made by "
              "zs_lionset_create)", fn);
+  ZS_REQUIRE(!as->sfadam, "%s: the EMA rides on Adam's update (the set was made by "
+             "zs_sfadamset_create)", fn);
   ZS_REQUIRE(as->state_dtype == ZS_F32, "%s: a set with ZS_BF16 state has no EMA column", fn);
   ZS_REQUIRE(as->p_dtype != ZS_BF16_SR, "%s: a ZS_BF16_SR set has no master to average", fn);
   ZS_REQUIRE(!as->has_carry, "%s: a set with the ZeRO-1 carry has no EMA instances", fn);
@@ -3445,6 +3717,8 @@ int zs_adamset_run_stats(const zs_adamset* as, const zs_adam_hparams* h, const f
              fn);
   ZS_REQUIRE(!as->lion, "%s: the norms ride on Adam's update (the set was made by "
              "zs_lionset_create)", fn);
+  ZS_REQUIRE(!as->sfadam, "%s: the norms ride on Adam's update (the set was made by "
+             "zs_sfadamset_create)", fn);
   ZS_REQUIRE(as->state_dtype == ZS_F32, "%s: a set with ZS_BF16 state has no stats instances", fn);
   ZS_REQUIRE(as->p_dtype != ZS_BF16_SR, "%s: a ZS_BF16_SR set has no master to measure", fn);
   ZS_REQUIRE(!as->has_carry, "%s: a set with the ZeRO-1 carry has no stats instances", fn);
@@ -3502,8 +3776,9 @@ static zs::LambTables lamb_tables(const zs_adamset* as) {
 static int lamb_check(const char* fn, const zs_adamset* as, const zs_lamb_hparams* h) {
   ZS_REQUIRE(as && h, "%s: NULL argument", fn);
   ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create", fn);
-  ZS_REQUIRE(!as->sgd && !as->lion, "%s: LAMB runs over a set made by zs_adamset_create (this one "
-             "was made by %s)", fn, as->sgd ? "zs_sgdset_create" : "zs_lionset_create");
+  ZS_REQUIRE(!as->sgd && !as->lion && !as->sfadam,
+             "%s: LAMB runs over a set made by zs_adamset_create (this one was made by %s)", fn,
+             as->sgd ? "zs_sgdset_create" : as->lion ? "zs_lionset_create" : "zs_sfadamset_create");
   ZS_REQUIRE(as->state_dtype == ZS_F32, "%s: a set with ZS_BF16 state has no LAMB instances", fn);
   ZS_REQUIRE(as->p_dtype != ZS_BF16_SR, "%s: a ZS_BF16_SR set has no master to measure", fn);
   ZS_REQUIRE(!as->has_carry, "%s: a set with the ZeRO-1 carry has no LAMB instances", fn);

@@ -46,6 +46,7 @@ EXPORTED = (
     "zs_adamset_update_norm_slots", "zs_adamset_run_stats", "zs_update_norms",
     "zs_sgd_hparams_init", "zs_sgdset_create", "zs_sgdset_run",
     "zs_lion_hparams_init", "zs_lionset_create", "zs_lionset_run",
+    "zs_sfadam_hparams_init", "zs_sfadamset_create", "zs_sfadamset_run", "zs_sfadamset_swap",
     "zs_lamb_hparams_init", "zs_lambset_run_moments", "zs_lamb_finish", "zs_lambset_bind_params",
     "zs_lambset_run_apply",
     "zs_adafactor_hparams_init", "zs_adafactorset_create", "zs_adafactorset_run",
@@ -106,6 +107,14 @@ class LionHParams(ctypes.Structure):
                 ("one_minus_beta2", ctypes.c_float), ("decay_mul", ctypes.c_float),
                 ("grad_div", ctypes.c_float), ("carry_mul", ctypes.c_float),
                 ("maximize", ctypes.c_int32)]
+
+
+class SfAdamHParams(ctypes.Structure):
+    _fields_ = [("beta2", ctypes.c_float), ("one_minus_beta2", ctypes.c_float),
+                ("bc2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("c", ctypes.c_float), ("a", ctypes.c_float),
+                ("lr_t", ctypes.c_float), ("grad_div", ctypes.c_float),
+                ("carry_mul", ctypes.c_float), ("maximize", ctypes.c_int32)]
 
 
 class LambHParams(ctypes.Structure):
@@ -279,6 +288,13 @@ _SIGS = {
                            ctypes.POINTER(_P)], ctypes.c_int),
     "zs_lionset_run": ([_P, ctypes.POINTER(LionHParams), _P, ctypes.c_int, ctypes.c_uint64,
                         ctypes.c_uint32, ctypes.c_uint32, _U], ctypes.c_int),
+    "zs_sfadam_hparams_init": ([ctypes.c_double] * 5 + [_I64, ctypes.c_double, ctypes.c_int,
+                                ctypes.c_double, ctypes.c_double,
+                                ctypes.POINTER(SfAdamHParams)], ctypes.c_int),
+    "zs_sfadamset_create": ([ctypes.POINTER(AdamSeg), _I64, ctypes.c_int, ctypes.c_int,
+                             ctypes.POINTER(_P)], ctypes.c_int),
+    "zs_sfadamset_run": ([_P, ctypes.POINTER(SfAdamHParams), _P, ctypes.c_int, _U], ctypes.c_int),
+    "zs_sfadamset_swap": ([_P, ctypes.c_double, ctypes.c_int, _U], ctypes.c_int),
     "zs_lamb_hparams_init": ([ctypes.c_double] * 4 + [ctypes.c_int] * 2 +
                              [_I64, ctypes.c_double, ctypes.POINTER(LambHParams)], ctypes.c_int),
     "zs_lambset_run_moments": ([_P, ctypes.POINTER(LambHParams), _P, _P, _U], ctypes.c_int),

@@ -21,7 +21,7 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import (MUON_KINDS, check_adafactor, check_adamini, check_apollo, check_lamb, check_muon, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
+from ._update import (MUON_KINDS, check_adafactor, check_adamini, check_apollo, check_lamb, check_muon, check_sfadam, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
                       check_max_grad_norm, check_param_grad_norms, check_update_norms,
                       check_update_norms_group,
                       check_skip_nonfinite, check_master_free, check_master_free_group,
@@ -129,9 +129,55 @@ def apollo_group_hparams(group: dict) -> dict:
                 norm_growth=float(group["norm_growth"]), seed=int(group["seed"]))
 
 
+def sfadam_group_hparams(group: dict) -> dict:
+    """Hyper-parameters of one zero_amd.optim.ScheduleFreeAdamW param group, with the scalars its
+    last ``schedule_free_advance`` left (``step`` = k, ``lr_t``, ``c``)."""
+    lr = group["lr"]
+    lr = float(lr.item()) if torch.is_tensor(lr) else float(lr)
+    beta1, beta2 = group["betas"]
+    return dict(lr=lr, beta1=float(beta1), beta2=float(beta2), eps=float(group["eps"]),
+                weight_decay=float(group.get("weight_decay", 0.0)),
+                maximize=bool(group.get("maximize", False)), amsgrad=False,
+                step=int(group["k"]), lr_t=float(group["lr_t"]), c=float(group["c"]))
+
+
+SFADAM_HOST_SCALARS = ("k", "weight_sum", "lr_max", "lr_t", "c")
+
+
+@contextlib.contextmanager
+def sfadam_step(groups):
+    """Around the launches of one Schedule-Free AdamW step: RuntimeError in eval mode, as the
+    class's ``step()``; then every group's host scalars advance, on every rank alike (no
+    communication: they are a function of the count and the group's ``lr``).  The advance is
+    committed only when the block ends without an exception: a step that raises before its
+    launches are enqueued leaves ``k``, ``weight_sum`` and ``lr_max`` as they were, so a retried
+    step forms the same ``c`` and ``bc2``."""
+    from .optim import schedule_free_advance
+
+    if not all(g["train_mode"] for g in groups):
+        raise RuntimeError("zero_amd: ScheduleFreeAdamW: step() in eval mode (call train() first)")
+    saved = [{name: g[name] for name in SFADAM_HOST_SCALARS} for g in groups]
+    for g in groups:
+        schedule_free_advance(g)
+    try:
+        yield
+    except BaseException:
+        for g, old in zip(groups, saved):
+            g.update(old)
+        raise
+
+
+def sfadam_swap_weight(group: dict, to_eval: bool) -> float:
+    """The lerp weight of ``eval()`` (y -> x) or ``train()`` (x -> y) for one group."""
+    beta1 = float(group["betas"][0])
+    return 1 - 1 / beta1 if to_eval else 1 - beta1
+
+
 def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
     """One param group's hyper-parameters for the ``kind`` ("adam" / "sgd" / "lion" / "adafactor" /
-    "muon" / "lamb" / "normuon" / "adamini" / "apollo") update."""
+    "muon" / "lamb" / "normuon" / "adamini" / "apollo" / "sfadam") update."""
+    if kind == "sfadam":
+        return sfadam_group_hparams(group)
     if kind == "apollo":
         return apollo_group_hparams(group)
     if kind == "adamini":
@@ -152,9 +198,10 @@ def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
 def optimizer_kind(optimizer: Optimizer) -> str:
     """"adam" (torch.optim.Adam / AdamW), "sgd" (torch.optim.SGD), "lion" (zero_amd.optim.Lion),
     "adafactor" (torch.optim.Adafactor), "muon" (torch.optim.Muon), "lamb" (zero_amd.optim.LAMB),
-    "normuon" (zero_amd.optim.NorMuon), "adamini" (zero_amd.optim.AdamMini) or "apollo"
-    (zero_amd.optim.Apollo); TypeError for anything else."""
-    from .optim import LAMB, AdamMini, Apollo, Lion, NorMuon
+    "normuon" (zero_amd.optim.NorMuon), "adamini" (zero_amd.optim.AdamMini), "apollo"
+    (zero_amd.optim.Apollo) or "sfadam" (zero_amd.optim.ScheduleFreeAdamW); TypeError for anything
+    else."""
+    from .optim import LAMB, AdamMini, Apollo, Lion, NorMuon, ScheduleFreeAdamW
 
     if isinstance(optimizer, torch.optim.Adam):
         return "adam"
@@ -174,8 +221,11 @@ def optimizer_kind(optimizer: Optimizer) -> str:
         return "adamini"
     if isinstance(optimizer, Apollo):
         return "apollo"
+    if isinstance(optimizer, ScheduleFreeAdamW):
+        return "sfadam"
     raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD / Adafactor / Muon or "
-                    f"zero_amd.optim.Lion / LAMB / NorMuon / AdamMini / Apollo (got {type(optimizer).__name__})")
+                    "zero_amd.optim.Lion / LAMB / NorMuon / AdamMini / Apollo / ScheduleFreeAdamW "
+                    f"(got {type(optimizer).__name__})")
 
 
 class ShardedOptimizerBase:
@@ -195,6 +245,13 @@ class ShardedOptimizerBase:
                  ema_decay: float | None = None, param_update_norms: bool = False):
         if arena not in ("flat", "buckets", "auto"):
             raise ValueError(f"arena must be 'flat', 'buckets' or 'auto' (got {arena!r})")
+        if optimizer_kind(optimizer) == "sfadam":  # refused first, naming the class; it runs
+            # wherever Lion does: the flat arena and its rounds
+            check_sfadam(arena=arena, layout=layout, carry=self._carry,
+                         skip_nonfinite=skip_nonfinite, state_dtype=state_dtype,
+                         state_rounding=state_rounding, master=master, ema_decay=ema_decay,
+                         param_update_norms=param_update_norms)
+            arena = "flat"  # arena='auto' would time the bucket arena as a candidate
         # the moments' dtype: None / torch.float32, or torch.bfloat16 (opt-in: exp_avg and
         # exp_avg_sq stored in bf16, the arithmetic in fp32 as before).  What it
         # cannot be combined with is refused below, on every rank and before anything collective
@@ -440,6 +497,42 @@ class ShardedOptimizerBase:
         if self._ema_swapped:
             raise RuntimeError(f"zero_amd: {what} inside ema_parameters(): the parameters hold the "
                                "EMA, not the weights training continues from")
+
+    def _check_train_mode(self, what: str):
+        if self._kind == "sfadam" and not all(g["train_mode"] for g in self._groups):
+            raise RuntimeError(f"zero_amd: {what} in eval mode: the parameters hold x, not the y "
+                               "training continues from (call train() first)")
+
+    def _sf_swap(self, to_eval: bool):
+        """Schedule-Free AdamW's ``eval()`` / ``train()``: every owner runs the swap kernel over
+        what it owns (the groups not yet in that mode), then the parameters are broadcast as after
+        a step.  Collective at world size > 1; nothing for another optimizer."""
+        todo = [gi for gi, g in enumerate(self._groups) if g["train_mode"] == to_eval] \
+            if self._kind == "sfadam" else []
+        if not todo:
+            return
+        if self.engine is None:
+            self._build_engine()
+        eng = self.engine
+        with torch.no_grad():
+            eng.swap_params(to_eval, {gi: sfadam_swap_weight(self._groups[gi], to_eval)
+                                      for gi in todo}, torch.cuda.current_stream(eng.device))
+        for gi in todo:
+            self._groups[gi]["train_mode"] = not to_eval
+        if self._sync:
+            torch.cuda.synchronize(eng.device)
+
+    @on_param_device
+    def eval(self):
+        """zero_amd.optim.ScheduleFreeAdamW: the parameters to ``x``, the average the model is
+        evaluated at (idempotent; ``step()``, ``state_dict()`` and ``load_state_dict()`` raise
+        until ``train()``).  A no-op for every other optimizer."""
+        self._sf_swap(True)
+
+    @on_param_device
+    def train(self):
+        """The parameters back to ``y`` (idempotent; a no-op for every other optimizer)."""
+        self._sf_swap(False)
 
     @contextlib.contextmanager
     def ema_parameters(self):
@@ -697,7 +790,10 @@ class ShardedOptimizerBase:
                 raise ValueError("zero_amd: grads must match their param's dtype and shape (and "
                                  "be contiguous outside the flat arena)")
             seen[i] = weakref.ref(g)
-        with torch.no_grad():
+        # (Schedule-Free AdamW: raises in eval mode; the groups' host scalars advance for the
+        # launches and stay advanced only if they are all enqueued)
+        scalars = sfadam_step(self._groups) if self._kind == "sfadam" else contextlib.nullcontext()
+        with scalars, torch.no_grad():
             self.engine.step(grads, self._hparams_of)
         if not had_vmax and self.engine.vmax is not None:
             self._expose_state()
@@ -769,6 +865,7 @@ class ShardedOptimizerBase:
         flat state, plus the split master's residual / fp32 master and ZeRO-1's carry
         (zero_amd/checkpoint.py)."""
         self._check_not_swapped("state_dict()")
+        self._check_train_mode("state_dict()")
         torch.cuda.synchronize(self.params[0].device)  # the state of every enqueued step
         sd = Optimizer.state_dict(self.optimizer)
         index = {id(p): k for k, p in enumerate(ckpt.inner_params(self.optimizer))}
@@ -790,6 +887,7 @@ class ShardedOptimizerBase:
         owned parameters): hyper-parameters through torch's loader, state copied into the flat
         buffers.  Parameters are the model's (load them with the model's own state dict)."""
         self._check_not_swapped("load_state_dict()")
+        self._check_train_mode("load_state_dict()")
         ckpt.check_header(state_dict, self._ckpt_header())
         if self._ema_decay is None:
             ckpt.check_ema_load(state_dict.get("state", {}))

@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from .checkpoint import step_of
-from .kernels import adam_hparams, lamb_hparams, lion_hparams, sgd_hparams, sr_keys
+from .kernels import (adam_hparams, lamb_hparams, lion_hparams, sfadam_hparams, sgd_hparams,
+                      sr_keys)
 
 # master="none": bf16 parameters without any master — the fused update reads the bf16 parameter,
 # runs the fp32 rule and stores it back rounded stochastically ("Master-free bf16
@@ -49,14 +50,51 @@ def check_params(params):
 BF16_STATE_MIN_ONE_MINUS_BETA = 2.0 ** -8
 
 
-KINDS = ("adam", "sgd", "lion", "adafactor", "muon", "lamb", "normuon", "adamini", "apollo")
+KINDS = ("adam", "sgd", "lion", "adafactor", "muon", "lamb", "normuon", "adamini", "apollo",
+         "sfadam")
 # torch.optim.Muon and zero_amd.optim.NorMuon: one engine path, one set of refusals
 MUON_KINDS = ("muon", "normuon")
 # what the messages call the optimizer of a kind that an option does not support
 KIND_NAMES = {"sgd": "torch.optim.SGD", "lion": "zero_amd.optim.Lion",
               "adafactor": "torch.optim.Adafactor", "muon": "torch.optim.Muon",
               "lamb": "zero_amd.optim.LAMB", "normuon": "zero_amd.optim.NorMuon",
-              "adamini": "zero_amd.optim.AdamMini", "apollo": "zero_amd.optim.Apollo"}
+              "adamini": "zero_amd.optim.AdamMini", "apollo": "zero_amd.optim.Apollo",
+              "sfadam": "zero_amd.optim.ScheduleFreeAdamW"}
+
+
+def check_sfadam(*, arena: str = "flat", layout: str = "reference", carry: bool = False,
+                 zero3_reference: bool = False, skip_nonfinite: bool = False, state_dtype=None,
+                 state_rounding=None, master: str = "split", ema_decay=None,
+                 param_update_norms: bool = False, amsgrad: bool = False) -> None:
+    """What zero_amd.optim.ScheduleFreeAdamW cannot be combined with, as ValueError.  The rule is
+    elementwise on Adam's streams, so it runs wherever Lion does: the flat arena (overlap and the
+    ZeRO-1 carry included) and ZeRO-3's update mode, on fp32 state over an fp32 or split master
+    ("Fused Schedule-Free AdamW"; §8)."""
+    name = KIND_NAMES["sfadam"]
+
+    def no(what: str, why: str):
+        raise ValueError(f"zero_amd: {name} is not supported with {what} ({why})")
+
+    if arena == "buckets":
+        no("arena='buckets'", "the bucket arena; use the flat arena")
+    if layout != "reference" and (layout != "flat" or carry):
+        no(f"layout={layout!r}", "it runs on the bucket arena, arena='buckets'")
+    if zero3_reference:
+        no("ZeRO-3 reference mode", "the fused update and the swap are update mode's")
+    if skip_nonfinite:
+        no("skip_nonfinite", "the host's weight_sum would advance over a skipped step")
+    if state_dtype is not None and state_dtype != torch.float32:
+        no(f"state_dtype={state_dtype}", "z and exp_avg_sq are fp32")
+    if state_rounding is not None:
+        no("state_rounding", "z and exp_avg_sq are fp32")
+    if master == "none":
+        no("master='none'", "y is kept on an fp32 or split master")
+    if ema_decay is not None:
+        no("ema_decay", "x already is the average")
+    if param_update_norms:
+        no("param_update_norms", "the norms are summed inside the fused Adam update")
+    if amsgrad:
+        no("amsgrad", "the rule has no max_exp_avg_sq")
 
 
 def check_lamb(*, carry: bool = False, arena: str = "flat", overlap: bool = False,
@@ -448,7 +486,8 @@ def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = 
         momentum = False                  # flat.ApolloState): nothing per element
     # (Muon: ``m`` alone, always: the momentum buffer)
     # (Adam-mini: ``m`` alone, exp_avg; the block second moment is flat.AdamMiniState's arena)
-    names = ["m", "v"][:2 if kind in ("adam", "lamb")
+    # (Schedule-Free AdamW: ``m`` is z, ``v`` exp_avg_sq)
+    names = ["m", "v"][:2 if kind in ("adam", "lamb", "sfadam")
                        else 1 if kind in ("lion", "adamini") + MUON_KINDS else int(bool(momentum))]
     names += ["carry"] * bool(carry) + ["master"] * bool(fp32_master)
     lay = {name: (k * L, torch.float32) for k, name in enumerate(names)}
@@ -471,7 +510,7 @@ class UpdateCore:
 
         if kind not in KINDS:
             raise ValueError("UpdateCore: kind must be 'adam', 'sgd', 'lion', 'adafactor', 'muon', "
-                             f"'lamb', 'normuon', 'adamini' or 'apollo' (got {kind!r})")
+                             f"'lamb', 'normuon', 'adamini', 'apollo' or 'sfadam' (got {kind!r})")
         # the update: torch.optim.Adam's, torch.optim.SGD's (`momentum`: some group has a
         # momentum, so the shard holds a momentum buffer; none of them: no optimizer state at all)
         # or zero_amd.optim.Lion's (one moment, exp_avg, always); zero_amd.optim.LAMB's has Adam's
@@ -533,6 +572,8 @@ class UpdateCore:
         elif self.kind in MUON_KINDS:  # torch's Muon state: the buffer alone (NorMuon: the engine
             # adds the row second moment, flat.NorMuonState)
             views = {"momentum_buffer": cut(self.m)}
+        elif self.kind == "sfadam":  # (the m array holds z, the base iterate)
+            views = {"z": cut(self.m), "exp_avg_sq": cut(self.v)}
         else:
             views = {"exp_avg": cut(self.m), "exp_avg_sq": cut(self.v)}
         if self.master is not None:
@@ -604,10 +645,12 @@ class UpdateCore:
                 view.copy_(src.reshape(view.shape))
             elif name == "master_param":
                 view.copy_(param.detach().reshape(view.shape))
-            elif name not in ("ema_param", "seed"):  # (Apollo's seed: the optimizer's own)
+            elif name not in ("ema_param", "z", "seed"):  # (Apollo's seed: the optimizer's own)
                 view.zero_()
-        if "ema_param" in views and entry.get("ema_param") is None:
-            view = views["ema_param"]
+        for fresh in ("ema_param", "z"):  # (Schedule-Free AdamW's z starts at the master too)
+            if fresh not in views or entry.get(fresh) is not None:
+                continue
+            view = views[fresh]
             if "master_param" in views:
                 view.copy_(views["master_param"])
             elif "master_residual" in views:
@@ -628,6 +671,8 @@ class UpdateCore:
         steps = np.asarray(steps, np.int64)
         if self.kind == "lion":  # no bias correction: only the rounding keys depend on the step
             return steps if self.state_rounding == "stochastic" else np.zeros_like(steps)
+        if self.kind == "sfadam":  # every scalar is the group's (its count k, c, lr_t)
+            return np.zeros_like(steps)
         return (steps == 1).astype(np.int64) if self.kind == "sgd" else steps
 
     def make_hp(self, hpd: dict, key: int, cmul: int = 0):
@@ -648,6 +693,11 @@ class UpdateCore:
             if self.state_rounding == "stochastic":  # the launch's keys travel with its struct
                 hp.sr_keys = sr_keys(self.state_seed, int(key))
             return hp
+        if self.kind == "sfadam":  # (c and a change every step: they live here, not in a set)
+            return sfadam_hparams(hpd["lr_t"], hpd["beta1"], hpd["beta2"], hpd["eps"],
+                                  hpd["weight_decay"], hpd["step"], hpd["c"],
+                                  maximize=hpd["maximize"], grad_div=float(self.ws),
+                                  carry_mul=carry_mul)
         if self.kind == "lamb":
             hp = lamb_hparams(hpd["beta1"], hpd["beta2"], hpd["eps"], hpd["weight_decay"], int(key),
                               bias_correction=hpd["bias_correction"], maximize=hpd["maximize"],
@@ -708,6 +758,8 @@ class UpdateCore:
         if self.kind == "lion":
             sr = (self.m.data_ptr(), hp.sr_keys) if self.state_rounding == "stochastic" else None
             aset.run(hp, stream, coef=coef, guard=guard, sr=sr)
+        elif self.kind == "sfadam":
+            aset.run(hp, stream, coef=coef, guard=guard)
         elif self.kind == "lamb":  # pass L1; launch_apply is L2
             if stats is None or guard:
                 raise ValueError("zero_amd: LAMB: a launch without its partials, or a guarded one")

@@ -143,6 +143,8 @@ class FlatEngine(ShardEngine):
                 p.data = self.P[s:s + int(self.numel[i])].view(p.shape)
             if self.ema is not None:  # the EMA starts at the master: the own window of P, widened
                 self.ema.copy_(self.own_window())
+            if kind == "sfadam":  # Schedule-Free AdamW's z starts at the master, likewise
+                self.m.copy_(self.own_window())
         # bf16 gradient exchange for fp32 parameters: G is converted into Gc
         # (bf16, same layout) before the reduces, which then move and sum 2 B per element; Adam
         # reads the bf16 sum (its fp32 master is the fp32 parameter itself)
@@ -393,6 +395,18 @@ class FlatEngine(ShardEngine):
             self._bcast_round(rd, cs)
         self.ev_bc[self.K - 1].record(cs)
         stream.wait_event(self.ev_bc[self.K - 1])
+
+    def swap_params(self, to_eval: bool, weight_of: dict, stream) -> None:
+        """Schedule-Free AdamW's ``eval()`` / ``train()``: the swap kernel over the owned rows of
+        the param groups in ``weight_of`` (group -> lerp weight), round by round through the
+        rounds' static sets, then every owner's window to all ranks."""
+        for rd in self.rounds:
+            if not len(rd.idx):
+                continue
+            for gi, _, aset in self._static_sets(rd):
+                if gi in weight_of:
+                    aset.swap(weight_of[gi], to_eval, stream)
+        self.broadcast_params(stream)
 
     def slot_view(self, buf: torch.Tensor, i: int) -> torch.Tensor:
         s, n = int(self.slot[i]), int(self.numel[i])

@@ -10,6 +10,8 @@ finite; ``run_sr`` with ``sr_keys`` stores bf16 moments with stochastic rounding
 ``SgdSet``   — the same tables with torch.optim.SGD's update (momentum, Nesterov); ``sgd_hparams``.
 ``LionSet``  — the same tables with zero_amd.optim.Lion's update (one moment, fp32 or bf16);
 ``lion_hparams``.
+``SfAdamSet`` — the same tables with zero_amd.optim.ScheduleFreeAdamW's update (the master is y,
+``m`` is z) and ``swap``, the eval() / train() kernel; ``sfadam_hparams``.
 ``AdamSet.run_lamb_moments`` / ``lamb_finish`` / ``AdamSet.run_lamb_apply`` — zero_amd.optim.LAMB's
 update over an Adam set, two passes (csrc/zs_lamb.hip); ``lamb_hparams``.
 ``AdafactorSet`` — torch.optim.Adafactor's update over a table of matrices (csrc/zs_adafactor.hip):
@@ -39,7 +41,7 @@ import numpy as np
 from . import _lib
 from ._lib import (AdafactorHParams, AdafactorSeg, AdamHParams, AdamMiniHParams, AdamMiniSeg,
                    AdamSeg, ApolloHParams, ApolloSeg, LambHParams, LionHParams, MuonHParams, MuonSeg, NorMuonHParams,
-                   SgdHParams)
+                   SfAdamHParams, SgdHParams)
 
 _PU64 = ctypes.POINTER(ctypes.c_uint64)
 _PI64 = ctypes.POINTER(ctypes.c_int64)
@@ -492,6 +494,51 @@ class LionSet(AdamSet):
                                 "a Lion set runs through LionSet.run")
 
     run_sr = run_psr = run_ema = run_stats = run_lamb_moments = run_lamb_apply = _not_lion
+
+
+def sfadam_hparams(lr_t, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, step=1, c=1.0, *,
+                   maximize=False, grad_div=1.0, carry_mul=0.0) -> SfAdamHParams:
+    """The scalars of one Schedule-Free AdamW step: ``lr_t`` the learning rate after warm-up,
+    ``step`` the group's count after the increment, ``c`` its averaging weight."""
+    hp = SfAdamHParams()
+    _lib.call("zs_sfadam_hparams_init", float(lr_t), float(beta1), float(beta2), float(eps),
+              float(weight_decay), int(step), float(c), int(bool(maximize)), float(grad_div),
+              float(carry_mul), ctypes.byref(hp))
+    return hp
+
+
+class SfAdamSet(AdamSet):
+    """Fused Schedule-Free AdamW over segments in zs_adam_seg order (zs_sfadamset_create): the
+    master holds ``y``, column ``m`` is ``z`` and ``v`` is ``exp_avg_sq`` on every row, fp32;
+    ``vmax`` is 0.  ``set_grads``, ``grad_sqnorm``, ``grad_sqnorm_segs``, ``bytes`` and
+    ``grad_bytes`` as ``AdamSet``."""
+
+    _CREATE = "zs_sfadamset_create"
+
+    def run(self, hp: SfAdamHParams, stream, coef=None, guard=False) -> None:
+        """One step (zs_sfadamset_run); ``coef`` as ``LionSet.run``.  ``guard`` is refused by the
+        library: the rule has no guarded instances."""
+        ptr = None if coef is None else coef if isinstance(coef, int) else coef.data_ptr()
+        _lib.call("zs_sfadamset_run", self._h, ctypes.byref(hp), ptr, int(bool(guard)),
+                  stream_handle(stream))
+
+    def swap(self, weight: float, to_eval: bool, stream) -> None:
+        """The model parameters to ``x`` (``to_eval``, ``weight = 1 - 1/beta1``) or back to ``y``
+        (``weight = 1 - beta1``): zs_sfadamset_swap."""
+        _lib.call("zs_sfadamset_swap", self._h, float(weight), int(bool(to_eval)),
+                  stream_handle(stream))
+
+    def run_clipped(self, hp, coef, stream) -> None:
+        self.run(hp, stream, coef=coef)
+
+    def run_guarded(self, hp, coef, stream) -> None:
+        self.run(hp, stream, coef=coef, guard=True)
+
+    def _not_sfadam(self, *a, **k):
+        raise _lib.ZeroAmdError("zs_sfadamset_run", _lib.ZS_ERR_INVALID,
+                                "a Schedule-Free AdamW set runs through SfAdamSet.run")
+
+    run_sr = run_psr = run_ema = run_stats = run_lamb_moments = run_lamb_apply = _not_sfadam
 
 
 def lamb_hparams(beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=0.0, step=1, *,

@@ -9,6 +9,11 @@ Its own ``step()`` is plain torch and runs on any device; handed to ``zero_amd.z
 ``zero3.ShardedOptimizer`` the update runs in the fused HIP kernels instead ("Fused
 Lion"), which compute what this ``step()`` computes on fp32 CPU tensors, bit for bit.
 
+``ScheduleFreeAdamW`` (Defazio et al. 2024, "The Road Less Scheduled", arXiv:2405.15682): AdamW
+without a learning-rate schedule, the gradient taken at an interpolation of the base iterate and its
+running average; ``eval()`` / ``train()`` swap the parameters between the two; see the class, which
+is this project's definition of the rule.
+
 ``NorMuon`` (Li et al. 2025): Muon's orthogonalised update normalised per output neuron by a
 running row second moment; see the class, which is this project's definition of the rule.
 
@@ -76,6 +81,140 @@ class Lion(Optimizer):
                 u = m.mul(beta1).add_(g, alpha=1 - beta1).sign_()
                 p.add_(u, alpha=-lr)
                 m.mul_(beta2).add_(g, alpha=1 - beta2)
+        return loss
+
+
+def schedule_free_advance(group: dict):
+    """Advance the host scalars of one ``ScheduleFreeAdamW`` param group by a step, in double:
+    ``k`` becomes the step count ``t``, ``lr_max`` and ``weight_sum`` take this step in; returns
+    ``(t, lr_t, c)``, which also stay in the group as ``lr_t`` and ``c`` (a report).  A pure
+    function of the count and the group's ``lr``: every rank forms the same scalars."""
+    t = int(group["k"]) + 1
+    lr = group["lr"]
+    lr = float(lr.item()) if torch.is_tensor(lr) else float(lr)
+    warmup = int(group["warmup_steps"])
+    sched = min(1.0, t / warmup) if warmup > 0 else 1.0
+    lr_t = lr * sched
+    lr_max = max(float(group["lr_max"]), lr_t)
+    w = float(t) ** float(group["r"]) * lr_max ** float(group["weight_lr_power"])
+    weight_sum = float(group["weight_sum"]) + w
+    c = w / weight_sum if weight_sum != 0.0 else 0.0
+    group.update(k=t, lr_max=lr_max, weight_sum=weight_sum, lr_t=lr_t, c=c)
+    return t, lr_t, c
+
+
+class ScheduleFreeAdamW(Optimizer):
+    """``ScheduleFreeAdamW(params, lr=2.5e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, *,
+    warmup_steps=0, r=0.0, weight_lr_power=2.0, maximize=False)``: Defazio et al. 2024, "The Road
+    Less Scheduled" (arXiv:2405.15682) -- AdamW without a learning-rate schedule: the gradient is
+    taken at ``y``, an interpolation of the base iterate ``z`` and the running average ``x`` of it,
+    and ``x`` is what the model is evaluated at.  Adam's state: ``z`` and ``exp_avg_sq``.
+
+    A group keeps ``k`` (steps taken), ``weight_sum``, ``lr_max`` and ``train_mode`` beside its
+    options; ``state[p]`` holds ``z`` (starts as a copy of ``p``), ``exp_avg_sq`` and ``step`` (an
+    fp32 CPU scalar, as torch.optim.Adam keeps it).  In train mode ``p`` holds ``y``.  One step,
+    with ``t = k + 1`` and every scalar formed on the host in double (``schedule_free_advance``),
+    then rounded to fp32 once where a tensor operation takes it::
+
+        sched = min(1, t / warmup_steps) if warmup_steps > 0 else 1;   lr_t = lr * sched
+        lr_max = max(lr_max, lr_t);  w = t**r * lr_max**weight_lr_power;  weight_sum += w
+        c = w / weight_sum  (0 if weight_sum == 0);   bc2 = 1 - beta2**t
+        a = lr_t * (beta1 * (1 - c) - 1)
+
+        v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+        d = sqrt(v / bc2) + eps                        # IEEE division and root
+        n = g / d;   n.add_(y, alpha=weight_decay)     # (only with weight_decay != 0)
+        y.lerp_(z, c);   y.add_(n, alpha=a)
+        z.add_(n, alpha=-lr_t)
+
+    ``eval()``: ``p.lerp_(z, 1 - 1/beta1)`` (y -> x); ``train()``: ``p.lerp_(z, 1 - beta1)``
+    (x -> y); both are idempotent, and ``step()`` in eval mode raises.  On fp32 parameters the
+    pair returns ``y`` to within the roundings of the two lerps, not bit for bit.  Handed to
+    ``zero_amd.zero1`` / ``zero2`` / ``zero3.ShardedOptimizer`` the update and the swap run in the
+    fused HIP kernels instead ("Fused Schedule-Free AdamW"), which compute what this
+    class computes on fp32 CPU tensors, bit for bit.
+    """
+
+    def __init__(self, params, lr: float = 2.5e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, *, warmup_steps: int = 0, r: float = 0.0,
+                 weight_lr_power: float = 2.0, maximize: bool = False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 < betas[0] < 1.0:  # 0 is refused: 1 - 1/beta1 is undefined
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if not 0 <= warmup_steps:
+            raise ValueError(f"Invalid warmup_steps value: {warmup_steps}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      warmup_steps=int(warmup_steps), r=r,
+                                      weight_lr_power=weight_lr_power, maximize=maximize, k=0,
+                                      weight_sum=0.0, lr_max=-1.0, train_mode=True, lr_t=0.0,
+                                      c=0.0))
+
+    def _swap(self, to_eval: bool):
+        for group in self.param_groups:
+            if group["train_mode"] != to_eval:
+                continue
+            beta1 = group["betas"][0]
+            weight = 1 - 1 / beta1 if to_eval else 1 - beta1
+            for p in group["params"]:
+                state = self.state[p]
+                if "z" in state:
+                    p.data.lerp_(state["z"], weight)
+            group["train_mode"] = not to_eval
+
+    @torch.no_grad()
+    def eval(self):
+        """The parameters to ``x``, the average (a group already there stays)."""
+        self._swap(True)
+
+    @torch.no_grad()
+    def train(self):
+        """The parameters back to ``y`` (a group already there stays)."""
+        self._swap(False)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            if not group["train_mode"]:
+                raise RuntimeError("ScheduleFreeAdamW: step() in eval mode (call train() first)")
+        for group in self.param_groups:
+            beta1, beta2 = group["betas"]
+            t, lr_t, c = schedule_free_advance(group)
+            bc2 = 1 - beta2 ** t
+            a = lr_t * (beta1 * (1 - c) - 1)
+            for y in group["params"]:
+                if y.grad is None:
+                    continue
+                if y.grad.is_sparse:
+                    raise RuntimeError("ScheduleFreeAdamW does not support sparse gradients")
+                g = -y.grad if group["maximize"] else y.grad
+                state = self.state[y]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["z"] = y.detach().clone(memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(y, memory_format=torch.preserve_format)
+                z, v = state["z"], state["exp_avg_sq"]
+                state["step"] += 1
+                v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+                # the root through float64: torch's vectorised fp32 CPU sqrt is not correctly
+                # rounded, the kernel's is; the double root rounded to fp32 is (53 >= 2 * 24 + 2)
+                d = v.div(bc2).to(torch.float64).sqrt_().to(v.dtype).add_(group["eps"])
+                n = g.div(d)
+                if group["weight_decay"] != 0:
+                    n.add_(y, alpha=group["weight_decay"])
+                y.lerp_(z, c)
+                y.add_(n, alpha=a)
+                z.add_(n, alpha=-lr_t)
         return loss
 
 

@@ -68,15 +68,15 @@ from . import _lib
 from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_BF16_SR, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
-from ._sharded import group_hparams, optimizer_kind
-from ._update import (GradClip, LambNorms, UpdateCore, UpdateNorms, check_adafactor, check_adamini, check_apollo, check_lamb, check_muon, check_bf16_state_group,
+from ._sharded import group_hparams, optimizer_kind, sfadam_step, sfadam_swap_weight
+from ._update import (GradClip, LambNorms, UpdateCore, UpdateNorms, check_adafactor, check_adamini, check_apollo, check_lamb, check_muon, check_sfadam, check_bf16_state_group,
                       check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group, check_master_free, check_update_norms,
                       check_update_norms_group,
                       check_master_free_group, check_max_grad_norm, check_param_grad_norms, check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
                       owner_range)
 from .comm import STREAM_SYNC, RcclComm, Sync, comm_stream, sync_kind, zs_dtype
 from .engine import ALIGN_ELEMS
-from .kernels import AdamSet, LionSet, SgdSet, convert, stream_handle
+from .kernels import AdamSet, LionSet, SfAdamSet, SgdSet, convert, stream_handle
 from .training_utils.utils import get
 
 try:  # the hooks' per-module install / release in C++ (csrc/zs_host_ext.cpp, built with the library)
@@ -1863,6 +1863,10 @@ class ShardedOptimizer:
             check_lamb(zero3_reference=not update, skip_nonfinite=skip_nonfinite,
                        state_dtype=state_dtype, state_rounding=state_rounding, master=master,
                        ema_decay=ema_decay, param_update_norms=param_update_norms)
+        if optimizer_kind(optimizer) == "sfadam":
+            check_sfadam(zero3_reference=not update, skip_nonfinite=skip_nonfinite,
+                         state_dtype=state_dtype, state_rounding=state_rounding, master=master,
+                         ema_decay=ema_decay, param_update_norms=param_update_norms)
         self.max_grad_norm = max_grad_norm
         self._check_clip()
         self.skip_nonfinite = check_skip_nonfinite(skip_nonfinite, max_grad_norm,
@@ -2041,6 +2045,9 @@ class ShardedOptimizer:
             self._stats = LambNorms(self._core)
         if self._core.ema is not None:  # the EMA starts at the master: the chunks, widened
             self._core.ema.copy_(ar.P)
+        if self._kind == "sfadam":  # Schedule-Free AdamW's z starts at the master, likewise
+            self._core.m.copy_(ar.P)
+        self._sf_sets = None  # the swap's sets, one per param group (made by the first eval())
         self._core.timing_events = self._timing_events
         self.placement = self._core.placement
         gdt = torch.bfloat16 if self._grad_comm else ar.dtype
@@ -2085,6 +2092,46 @@ class ShardedOptimizer:
         if self.__dict__.get("_ema_swapped"):
             raise RuntimeError(f"zero_amd: {what} inside ema_parameters(): the parameters hold the "
                                "EMA, not the weights training continues from")
+
+    def _check_train_mode(self, what: str):
+        if self._kind == "sfadam" and not all(g["train_mode"] for g in self._groups):
+            raise RuntimeError(f"zero_amd: {what} in eval mode: the parameters hold x, not the y "
+                               "training continues from (call train() first)")
+
+    def _sf_swap(self, to_eval: bool):
+        """Schedule-Free AdamW's ``eval()`` / ``train()`` (update mode): the swap kernel over this
+        rank's chunks of the groups not yet in that mode, then the shards are marked changed so
+        that prefetched gathers are dropped.  Nothing for another optimizer."""
+        todo = [gi for gi, g in enumerate(self._groups) if g["train_mode"] == to_eval] \
+            if self._kind == "sfadam" and self.update else []
+        if not todo:
+            return
+        ar = self._arena
+        if self._sf_sets is None:
+            gof = np.asarray(self._group_of)
+            self._sf_sets = {}
+            for gi in sorted(set(self._group_of)):
+                idx = np.nonzero((gof == gi) & (ar.ln > 0))[0]
+                self._sf_sets[gi] = self._new_set(self._adam_rows(idx, grads=False), False)
+        cur = torch.cuda.current_stream(ar.device)
+        for gi in todo:
+            self._sf_sets[gi].swap(sfadam_swap_weight(self._groups[gi], to_eval), to_eval, cur)
+            self._groups[gi]["train_mode"] = not to_eval
+        self.mark_params_changed()
+        if self._sync:
+            torch.cuda.synchronize(ar.device)
+
+    @on_param_device
+    def eval(self):
+        """zero_amd.optim.ScheduleFreeAdamW (update mode): this rank's chunks to ``x``, the average
+        the model is evaluated at (idempotent; ``step()``, ``state_dict()`` and
+        ``load_state_dict()`` raise until ``train()``).  A no-op for every other optimizer."""
+        self._sf_swap(True)
+
+    @on_param_device
+    def train(self):
+        """The chunks back to ``y`` (idempotent; a no-op for every other optimizer)."""
+        self._sf_swap(False)
 
     @contextlib.contextmanager
     def ema_parameters(self):
@@ -2322,14 +2369,17 @@ class ShardedOptimizer:
             param.grad = None
         return done
 
-    def _adam_rows(self, idx, acc: bool = False):
+    def _adam_rows(self, idx, acc: bool = False, grads: bool = True):
         """zs_adam_seg rows (g, master, master_out, p_out, m, v, vmax, carry, n) of the chunks of
-        the params in ``idx``; ``acc``: the gradients are the fp32 accumulation arena's."""
+        the params in ``idx``; ``acc``: the gradients are the fp32 accumulation arena's; without
+        ``grads`` the rows carry g = 0 (the Schedule-Free swap reads no gradient)."""
         ar, red = self._arena, self._reducer
         es = ar.P.element_size()
         so = ar.slot[idx].astype(np.uint64)
         rows = np.zeros((len(idx), 9), np.uint64)
-        if self.world_size > 1:
+        if not grads:
+            pass
+        elif self.world_size > 1:
             G = self._A if acc else self._G
             rows[:, 0] = np.uint64(G.data_ptr()) + so * np.uint64(G.element_size())
         else:
@@ -2354,6 +2404,8 @@ class ShardedOptimizer:
         mk = SgdSet if self._kind == "sgd" else AdamSet
         if self._kind == "lion":  # (never master-free: refused at construction)
             mk, kw["state_rounding"] = LionSet, self.state_rounding
+        if self._kind == "sfadam":
+            mk = SfAdamSet
         if self._master_free:
             return mk(rows, gz, ZS_BF16_SR, wide_grads=acc, state_rounding=self.state_rounding, **kw)
         if self._split:
@@ -2545,11 +2597,16 @@ class ShardedOptimizer:
             with torch.enable_grad():
                 loss = closure()
         self._check_not_swapped("step()")
+        self._check_train_mode("step()")
         self._check_clip()
         step_start = time.perf_counter()
         e0 = torch.cuda.Event(enable_timing=True)
         e0.record(torch.cuda.current_stream(self.params[0].device))
-        with torch.no_grad():
+        # (Schedule-Free AdamW: the groups' host scalars advance, on every rank alike, for the
+        # launches and stay advanced only if they are all enqueued)
+        scalars = sfadam_step(self._groups) if self._kind == "sfadam" and self.update \
+            else contextlib.nullcontext()
+        with scalars, torch.no_grad():
             done = self._step_update() if self.update else self._reduce_reference()
         if done is not None and self.world_size > 1:
             if self.runtime.stream is None:  # single stream: `done` follows the last collective
@@ -2624,6 +2681,7 @@ class ShardedOptimizer:
         master's residual), so each rank saves its own shard.  Reference mode keeps no state
         (zero3.py:150-153), like the reference."""
         self._check_not_swapped("state_dict()")
+        self._check_train_mode("state_dict()")
         torch.cuda.synchronize(self._arena.device)
         sd = Optimizer.state_dict(self.optimizer)
         state = {}
@@ -2645,6 +2703,7 @@ class ShardedOptimizer:
         the next gather is ordered after that copy; a caller that edits the shards at any other
         time between two steps (after an eval forward, say) calls ``mark_params_changed()``."""
         self._check_not_swapped("load_state_dict()")
+        self._check_train_mode("load_state_dict()")
         ckpt.check_header(state_dict, self._ckpt_header())
         if self._ema_decay is None:
             ckpt.check_ema_load(state_dict.get("state", {}))

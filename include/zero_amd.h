@@ -641,6 +641,78 @@ int zs_lionset_run(const zs_adamset* as, const zs_lion_hparams* hp, const float*
                    uint64_t m_base, uint32_t key0, uint32_t key1, uintptr_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Fused Schedule-Free AdamW (Defazio et al. 2024, arXiv:2405.15682), additive in ABI v13.  The  */
+/* update of zero_amd.optim.ScheduleFreeAdamW on the owned shard through the Adam's tables and   */
+/* kernels' shape: the master holds y, field m of a segment is z, v is exp_avg_sq.  Adam's        */
+/* streams and bytes (26 B/element over the split master with bf16 gradients); a second kernel   */
+/* swaps the model parameters between y (training) and x (evaluation).                           */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  /* doubles on the host, rounded to f32 once */
+  float beta2;
+  float one_minus_beta2;
+  float bc2;              /* 1 - beta2^step */
+  float eps;
+  float weight_decay;     /* decoupled, on y */
+  float c;                /* this step's averaging weight w_t / sum of w, in [0, 1] */
+  float a;                /* lr_t * (beta1 * (1 - c) - 1): y's step */
+  float lr_t;             /* the step's learning rate, after warm-up: z's step */
+  float grad_div;         /* divide the reduced sum by this (world size) */
+  float carry_mul;        /* ZeRO-1: sum += carry_mul * carry (ws-1) */
+  int32_t maximize;
+} zs_sfadam_hparams;
+
+/* Fill hp from the scalars of one step of a ScheduleFreeAdamW param group: lr is the step's
+ * learning rate after warm-up (lr_t), step the group's count after the increment, c the averaging
+ * weight the host formed; a, bc2 and the rest are derived in double.  ZS_ERR_INVALID for what the
+ * class refuses (lr < 0, beta1 outside (0, 1) -- 0 included: 1 - 1/beta1 is undefined --, beta2
+ * outside [0, 1), eps < 0, weight_decay < 0), for step < 1, c outside [0, 1], grad_div <= 0 and a
+ * NULL hp. */
+int zs_sfadam_hparams_init(double lr, double beta1, double beta2, double eps, double weight_decay,
+                           int64_t step, double c, int maximize, double grad_div, double carry_mul,
+                           zs_sfadam_hparams* hp);
+/* A zs_adamset whose update is Schedule-Free AdamW's: segs, g_dtype, p_dtype, alignment and the
+ * vector / scalar split exactly as zs_adamset_create, with m = z and v = exp_avg_sq (fp32, updated
+ * in place) set on every non-empty segment and vmax == 0.  ZS_ERR_INVALID: a NULL out or table,
+ * n < 0, a bad g_dtype; p_dtype other than ZS_BF16 or ZS_BF16_SPLIT; a non-empty segment without
+ * master, m or v, or with vmax; a split master without master_out and p_out; a carry with fp32
+ * gradients over the split master, or on some segments only.  zs_adamset_set_grads, the
+ * sum-of-squares passes, zs_adamset_destroy and zs_adamset_stats work on it unchanged; every
+ * zs_adamset_run*, zs_lionset_run, zs_sgdset_run and zs_lambset_* return ZS_ERR_INVALID on it, as
+ * zs_sfadamset_run and zs_sfadamset_swap do on their sets. */
+int zs_sfadamset_create(const zs_adam_seg* segs, int64_t n, int g_dtype, int p_dtype,
+                        zs_adamset** out);
+/* One step over the set, per element (fp32, only the written fma fused; '/' and sqrt IEEE):
+ *   g = (sum [+ carry_mul * carry]) / grad_div;  [carry = g];  [g *= *coef];  [g = -g]
+ *   v = fma((1 - beta2) * g, g, v * beta2);  d = sqrt(v / bc2) + eps
+ *   n = g / d;  [n = fma(weight_decay, y, n)]
+ *   y = fma(c, z - y, y) if c < 0.5 else fma(c - 1, z - y, z);  y = fma(a, n, y)
+ *   z = fma(-lr_t, n, z)
+ * and y is stored as the set's p_dtype stores a master (with its bf16 copy).  A segment without a
+ * gradient reads g = 0 and runs like any other.  coef as zs_lionset_run; guard must be 0: the
+ * argument is reserved, no guarded instances exist (the host's weight sum would advance over a
+ * skipped step).
+ * ZS_ERR_INVALID, nothing launched: a NULL set or hparams; a set not made by zs_sfadamset_create;
+ * guard != 0; coef on a set with the ZeRO-1 carry; in a struct filled by hand a negative
+ * lr_t, eps or weight_decay, beta2 or c outside [0, 1], bc2 outside (0, 1] or grad_div <= 0. */
+int zs_sfadamset_run(const zs_adamset* as, const zs_sfadam_hparams* hp, const float* coef,
+                     int guard, uintptr_t stream);
+/* The model parameters of the set between y and x, per element p <- lerp(p, z, weight) as ATen
+ * rounds it (fma(w, z - p, p) for |w| < 0.5, fma(w - 1, z - p, z) otherwise; w = (float)weight):
+ * to_eval != 0 with weight = 1 - 1/beta1 gives x, to_eval == 0 with weight = 1 - beta1 gives y back.
+ * What is written depends on where a segment's master lives:
+ *   ZS_BF16 with p_out (an fp32 master beside a bf16 copy): only p_out -- to_eval stores bf16(x)
+ *     and the master keeps y; the way back stores bf16(master) again and reads neither z nor
+ *     weight: the round trip is exact;
+ *   ZS_BF16 without p_out (fp32 parameters, their own master): the master in place, both ways;
+ *   ZS_BF16_SPLIT (the bf16 parameter is the master's high half): the master in place, both ways,
+ *     x split into p_out and the residual as the update splits y.
+ * In place, the round trip returns y to within a rounding or two of each lerp, not bit for bit.
+ * ZS_ERR_INVALID, nothing launched: a NULL set, one not made by zs_sfadamset_create, a weight that
+ * is not finite.  An empty set launches nothing. */
+int zs_sfadamset_swap(const zs_adamset* as, double weight, int to_eval, uintptr_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Fused LAMB (You et al. 2020, arXiv:1904.00962), additive in ABI v13.  The update of          */
 /* zero_amd.optim.LAMB on the owned shard, over a set made by zs_adamset_create (fp32 moments,  */
 /* fp32 or split master, no carry, no vmax), in two stream passes with the per-parameter norms  */
