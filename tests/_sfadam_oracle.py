@@ -30,23 +30,29 @@ class SfHP:
     """The scalars of one run, as zs_sfadam_hparams_init forms them."""
 
     def __init__(self, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, step=1, c=1.0, *,
-                 maximize=False, grad_div=1.0):
+                 maximize=False, grad_div=1.0, carry_mul=0.0):
         self.beta2, self.omb2 = F32(beta2), F32(1.0 - beta2)
         self.bc2 = F32(1.0 - float(beta2) ** int(step))
         self.eps, self.wd, self.c = F32(eps), F32(weight_decay), F32(c)
         self.a, self.neg_lr = F32(lr_t * (beta1 * (1.0 - c) - 1.0)), F32(-lr_t)
         self.grad_div, self.inv_div = F32(grad_div), F32(1.0 / float(F32(grad_div)))
         self.div_pow2 = math.frexp(float(F32(grad_div)))[0] == 0.5
+        self.carry_mul = F32(carry_mul)
         self.maximize = bool(maximize)
 
 
-def sfadam_elem(gsum, y, z, v, hp, *, coef=None):
+def sfadam_elem(gsum, y, z, v, hp, *, coef=None, carry=None):
     """One step over fp32 arrays; ``gsum``: fp32, or bf16 codes (uint16), widened.  Returns
-    (y, z, v) as new arrays."""
+    (y, z, v) as new arrays; with ``carry`` (the ZeRO-1 carry: ``hp.carry_mul`` times it joins the
+    sum, and the averaged gradient is the new carry) (y, z, v, carry)."""
+    assert carry is None or coef is None
     gsum = np.asarray(gsum)
     s = bf16_bits_to_f32(gsum) if gsum.dtype == np.uint16 else gsum.astype(F32)
     with np.errstate(all="ignore"):
+        if carry is not None:
+            s = s + hp.carry_mul * np.asarray(carry, F32)
         g = s * hp.inv_div if hp.div_pow2 else s / hp.grad_div
+        new_carry = g
         if coef is not None:
             g = g * F32(coef)
         if hp.maximize:
@@ -57,7 +63,7 @@ def sfadam_elem(gsum, y, z, v, hp, *, coef=None):
             n = fma32(hp.wd, y, n)
         y = fma32(hp.a, n, lerp32(y, z, hp.c))
         z = fma32(hp.neg_lr, n, z)
-    return y, z, v
+    return (y, z, v) if carry is None else (y, z, v, new_carry.copy())
 
 
 def swap(p, z, beta1, to_eval):

@@ -1,10 +1,13 @@
 """``ShardedOptimizer(ScheduleFreeAdamW(...))`` on ZeRO-1/2/3 in lockstep with the class itself on
 fp32 CPU tensors, bit for bit; the split master of bf16 parameters (the parameter joined with its
-residual) follows the class on the widened values."""
+residual) follows the class on the widened values.  ZeRO-1 at world size 2 (the carry) runs
+against tests/_sfadam_oracle.py on gradients that differ per rank."""
+import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
 
+import _sfadam_oracle as so
 from _zero_run import init_pg, module_for, set_grad, spawn_batch
 from test_gpu_lion_optimizer import _host, _same, _z3_set_grad, pg1  # noqa: F401  (pg1: a fixture)
 
@@ -119,3 +122,87 @@ def _ws2_worker(rank, ws, port):
 
 def test_zero2_ws2_equals_ws1(gpu):
     spawn_batch(2, [(_ws2_worker, ())])
+
+
+class _CarryRef:
+    """ZeRO-1 at world size ``ws`` in numpy, over whole flat parameters: tests/_sfadam_oracle.py's
+    element on the summed gradient with ``grad_div = ws`` and ``carry_mul = ws - 1``, the carry (the
+    last averaged gradient, which ZeRO-1's surviving gradients hold) kept from step to step."""
+
+    def __init__(self, init, ws):
+        self.ws = ws
+        self.y = [a.copy() for a in init]
+        self.z = [a.copy() for a in init]  # starts as a copy of the parameter
+        self.v = [np.zeros_like(a) for a in init]
+        self.carry = [np.zeros_like(a) for a in init]
+        self.sched = so.schedule(HP["lr"], 8, warmup_steps=HP["warmup_steps"])
+        self.k = 0
+
+    def step(self, sums):
+        t, lr_t, c = self.sched[self.k]
+        self.k += 1
+        hp = so.SfHP(lr_t, *HP["betas"], 1e-8, HP["weight_decay"], t, c,
+                     grad_div=float(self.ws), carry_mul=float(self.ws - 1))
+        for i, g in enumerate(sums):
+            self.y[i], self.z[i], self.v[i], self.carry[i] = so.sfadam_elem(
+                g, self.y[i], self.z[i], self.v[i], hp, carry=self.carry[i])
+
+    def swap(self, to_eval):
+        self.y = [so.swap(y, z, HP["betas"][0], to_eval) for y, z in zip(self.y, self.z)]
+
+
+def _z1_carry_worker(rank, ws, port):
+    """ZeRO-1 keeps its carry through opt.zero_grad(): integer gradients that differ per rank (their
+    sum is exact whatever the order), 3 steps with the eval() / train() pair after the second;
+    64-element windows, so several rounds."""
+    from _gloo_comm import test_comm
+    from zero_amd.optim import ScheduleFreeAdamW
+
+    torch.cuda.set_device(0)
+    init_pg(rank, ws, port)
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(31)
+    init = [(rng.standard_normal(int(np.prod(s))) * 0.05).astype(np.float32) for s in SHAPES]
+    params = [torch.nn.Parameter(torch.from_numpy(a.copy()).reshape(s).to(dev))
+              for a, s in zip(init, SHAPES)]
+    opt = module_for(1).ShardedOptimizer(ScheduleFreeAdamW(params, **HP), comm=test_comm(),
+                                         bucket_mb=ws * 64 * 4 / (1 << 20))
+    eng = opt.engine
+    assert eng.kind == "sfadam" and eng.K > 1 and eng.carry is not None
+    assert 0 < len(opt.local_param_indices) < len(SHAPES)
+    ref = _CarryRef(init, ws)
+
+    def check(what):
+        for i, p in enumerate(params):
+            _same(_host(p), ref.y[i], f"rank {rank} {what} param {i}")
+            if i not in opt.local_param_indices:
+                continue
+            st = opt.optimizer.state[p]
+            _same(_host(st["z"]), ref.z[i], f"rank {rank} {what} z {i}")
+            _same(_host(st["exp_avg_sq"]), ref.v[i], f"rank {rank} {what} exp_avg_sq {i}")
+            off = int(eng.pieces.stream_off[eng.pieces.param == i][0])
+            _same(_host(eng.carry[off:off + p.numel()]), ref.carry[i], f"rank {rank} {what} carry {i}")
+
+    for t in range(3):
+        local = [[rng.integers(-8, 9, a.size).astype(np.float32) for a in init] for _ in range(ws)]
+        opt.zero_grad()
+        for p, g, s in zip(params, local[rank], SHAPES):
+            set_grad(p, torch.from_numpy(g.copy()).reshape(s).to(dev))
+        opt.step()
+        ref.step([np.sum(np.stack([local[r][i] for r in range(ws)]), axis=0, dtype=np.float32)
+                  for i in range(len(init))])
+        check(f"step {t}")
+        if t >= 1:  # the carry is in the sum: the step on the summed gradient alone gives other bits
+            assert any(np.any(c != 0) for c in ref.carry)
+        if t == 1:
+            for name in ("eval", "train"):
+                getattr(opt, name)()
+                ref.swap(name == "eval")
+                check(name)
+    assert opt.optimizer.param_groups[0]["k"] == 3
+    dist.destroy_process_group()
+
+
+def test_zero1_ws2_keeps_the_carry(gpu):
+    """ZeRO-1 at world size 2, the CARRY instances behind the wrapper, against the numpy oracle."""
+    spawn_batch(2, [(_z1_carry_worker, ())])
