@@ -1,7 +1,7 @@
 // CDNA4 (gfx950) kernels of the ZeRO step and the C entry points that launch them: segment copy
 // (pack / unpack), the fused optimizer update (one vector and one scalar kernel, instantiated over
 // the element rules: Adam, Adam with bf16 moments rounded to nearest or stochastically, Adam over
-// master-free bf16 parameters rounded stochastically, SGD, Lion, Schedule-Free AdamW), the
+// master-free bf16 parameters rounded stochastically, SGD, Lion, Schedule-Free AdamW, AdEMAMix), the
 // Schedule-Free eval / train swap, the gradient sum of squares and clip coefficient, scale,
 // accumulate, convert, the fp8 row quantizer and gather, and the flag kernels.
 //
@@ -208,8 +208,8 @@ __global__ __launch_bounds__(kThreads) void copy_direct_kernel(const DirectSet s
 }
 
 // ----------------------------------------------------------------------------------------------
-// fused optimizer update: one chunk-streaming skeleton, four element rules (Adam, SGD, Lion,
-// Schedule-Free AdamW)
+// fused optimizer update: one chunk-streaming skeleton, five element rules (Adam, SGD, Lion,
+// Schedule-Free AdamW, AdEMAMix)
 // ----------------------------------------------------------------------------------------------
 struct AdamSeg {
   const void* g;
@@ -647,6 +647,50 @@ struct SfAdamRule {
 };
 template <bool>
 using SfAdamRuleOf = SfAdamRule;
+
+// AdEMAMix (Pagliardini, Ablin, Grangier 2024, arXiv:2409.03137) over the same tables: field `m` of
+// a segment is exp_avg (the fast EMA), `v` is exp_avg_sq and `vmax` holds exp_avg_slow, the slow
+// EMA: the three fp32 state streams of Adam's amsgrad instances, so their bytes.  The host forms
+// every scalar of the step (zs_ademamix_hparams_init); alpha and beta3 arrive as the schedulers
+// left them at this step count (a_t, b3_t).
+struct AdEMAMixHP {
+  float beta1, omb1, beta3, omb3, beta2, omb2, inv_bc1, alpha, bc2_sqrt, eps, neg_lr, decay_mul,
+      grad_div, inv_div, carry_mul;
+  int div_pow2, maximize;
+};
+
+struct AdEMAMixRule {
+  using Hyper = AdEMAMixHP;
+  static constexpr bool kM = true, kV = true, kX = true, kGradOffset2 = true;
+  static constexpr bool kPsr = false;
+  static constexpr bool kEma = false;
+  static constexpr bool kStats = false;
+  static constexpr bool kNoStore = false;
+  using Stats = NoStats;
+
+  // One element of zero_amd.optim.AdEMAMix's step, in the rounding order of torch's CPU kernels:
+  // p.mul_(1 - lr*wd); m1.mul_(b1).add_(g, alpha=1-b1) = fma(1-b1, g, m1*b1); m2 likewise with
+  // b3_t; v.mul_(b2).addcmul_(g, g, value=1-b2) = fma((1-b2)*g, g, v*b2); den = sqrt(v)/bc2_sqrt +
+  // eps (IEEE root and division); num = m1.mul(1/bc1).add_(m2, alpha=a_t) = fma(a_t, m2, m1*inv_bc1);
+  // u = num / den; p.add_(u, alpha=-lr) = fma(-lr, u, p).  Only explicit fmaf() fuse; the chains
+  // are independent until u, so the order they are written in below is free.  m1, m2, v
+  // and p equal the class on fp32 CPU tensors bit for bit; against the exact step of the stored
+  // state p stays within 1 ulp(p) + 8 * 2^-24 * lr * (|m1|/bc1 + a_t |m2|) / den.
+  template <bool CARRY, bool CLIP>
+  static __device__ __forceinline__ void elem(float gsum, float& p, float& m1, float& v, float& m2,
+                                              float& carry, const AdEMAMixHP& hp, float coef) {
+#pragma clang fp contract(off)
+    const float g = prep_grad<CARRY, CLIP>(gsum, carry, hp, coef);
+    v = fmaf(hp.omb2 * g, g, v * hp.beta2);
+    const float den = sqrtf(v) / hp.bc2_sqrt + hp.eps;
+    m1 = fmaf(hp.omb1, g, m1 * hp.beta1);
+    m2 = fmaf(hp.omb3, g, m2 * hp.beta3);
+    const float num = fmaf(hp.alpha, m2, m1 * hp.inv_bc1);
+    p = fmaf(hp.neg_lr, num / den, p * hp.decay_mul);
+  }
+};
+template <bool>
+using AdEMAMixRuleOf = AdEMAMixRule;
 
 template <typename GT>
 __device__ __forceinline__ float load_g1(const void* g, int64_t i) {
@@ -2377,6 +2421,8 @@ struct zs_adamset {
   int lion = 0;
   // zs_sfadamset_create: a Schedule-Free AdamW set (the master is y, field m is z, v exp_avg_sq)
   int sfadam = 0;
+  // zs_ademamixset_create: an AdEMAMix set (m is exp_avg, v exp_avg_sq, vmax exp_avg_slow)
+  int ademamix = 0;
   // zs_adamset_create_ex: the element type of m and v, ZS_F32 or ZS_BF16
   int state_dtype = ZS_F32;
   // zs_adamset_set_grads: which input segment each table entry came from (the scalar entries with
@@ -2538,6 +2584,9 @@ using LionSrFamily = UpdateFamily<LionSrRule, SrBf16, false, true>;
 // instances: the host's weight sum would advance over a skipped step, so the entry point refuses
 // the guard until a caller can use it.
 using SfAdamFamily = UpdateFamily<SfAdamRuleOf, float, true>;
+// zs_ademamixset_run: fp32 m, v and slow EMA (with the carry instances; the rule has no flag), no
+// guarded instances
+using AdEMAMixFamily = UpdateFamily<AdEMAMixRuleOf, float, true>;
 template <bool>
 using AdamPsrRuleOf = AdamPsrRule;
 // zs_adamset_run_psr: the master-free instances, by how m and v are stored
@@ -3109,15 +3158,15 @@ int zs_adam_hparams_init(double lr, double beta1, double beta2, double eps, doub
 // bf16 momentum).
 static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n, int g_dtype,
                       int p_dtype, int state_dtype, zs_adamset** out, bool lion = false,
-                      bool sfadam = false) {
+                      bool sfadam = false, bool ademamix = false) {
   ZS_REQUIRE(out != nullptr, "%s: out is NULL", fn);
   *out = nullptr;
   ZS_REQUIRE(n >= 0 && (n == 0 || in), "%s: bad table", fn);
   ZS_REQUIRE(g_dtype == ZS_F32 || g_dtype == ZS_BF16, "%s: bad g_dtype %d", fn, g_dtype);
   const bool psr = p_dtype == ZS_BF16_SR;  // master-free: zs_adamset_run_psr
-  ZS_REQUIRE(p_dtype == ZS_BF16 || p_dtype == ZS_BF16_SPLIT || (psr && !sgd && !lion && !sfadam),
+  ZS_REQUIRE(p_dtype == ZS_BF16 || p_dtype == ZS_BF16_SPLIT || (psr && !sgd && !lion && !sfadam && !ademamix),
              "%s: p_dtype must be ZS_BF16 or ZS_BF16_SPLIT%s (got %d)", fn,
-             sgd || lion || sfadam ? "" : " or ZS_BF16_SR", p_dtype);
+             sgd || lion || sfadam || ademamix ? "" : " or ZS_BF16_SR", p_dtype);
   ZS_REQUIRE(state_dtype == ZS_F32 || (state_dtype == ZS_BF16 && !sgd),
              "%s: state_dtype must be ZS_F32 or ZS_BF16 (got %d)", fn, state_dtype);
   const bool split = p_dtype == ZS_BF16_SPLIT;
@@ -3159,6 +3208,8 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
       ZS_REQUIRE(s.master && s.m && s.v, "%s: seg %lld missing master/m/v", fn, (long long)i);
       ZS_REQUIRE(!sfadam || !s.vmax, "%s: seg %lld: vmax must be 0 in a Schedule-Free AdamW set",
                  fn, (long long)i);
+      ZS_REQUIRE(!ademamix || s.vmax, "%s: seg %lld missing vmax (exp_avg_slow)", fn,
+                 (long long)i);
     }
     ZS_REQUIRE(!split || (s.master_out && s.p_out),
                "%s: seg %lld: a split master needs master_out (residual) and p_out", fn,
@@ -3274,6 +3325,7 @@ static int set_create(const char* fn, bool sgd, const zs_adam_seg* in, int64_t n
   as->has_mom = mom_state > 0 ? 1 : 0;
   as->lion = lion ? 1 : 0;
   as->sfadam = sfadam ? 1 : 0;
+  as->ademamix = ademamix ? 1 : 0;
   as->state_dtype = state_dtype;
   as->in_g = std::move(in_g);
   as->in_n = std::move(in_n);
@@ -3352,6 +3404,8 @@ int zs_sgdset_run(const zs_adamset* as, const zs_sgd_hparams* h, const float* co
   ZS_REQUIRE(!as->lion, "zs_sgdset_run: the set was made by zs_lionset_create (use zs_lionset_run)");
   ZS_REQUIRE(!as->sfadam,
              "zs_sgdset_run: the set was made by zs_sfadamset_create (use zs_sfadamset_run)");
+  ZS_REQUIRE(!as->ademamix,
+             "zs_sgdset_run: the set was made by zs_ademamixset_create (use zs_ademamixset_run)");
   ZS_REQUIRE(as->sgd, "zs_sgdset_run: the set was made by zs_adamset_create (use zs_adamset_run)");
   // a struct filled by hand gets zs_sgd_hparams_init's rules too (-0.0f is lr = 0)
   ZS_REQUIRE(h->neg_lr <= 0.0f, "zs_sgdset_run: negative learning rate");
@@ -3553,6 +3607,82 @@ int zs_sfadamset_swap(const zs_adamset* as, double weight, int to_eval, uintptr_
   return ZS_OK;
 }
 
+int zs_ademamixset_create(const zs_adam_seg* in, int64_t n, int g_dtype, int p_dtype,
+                          zs_adamset** out) {
+  return set_create("zs_ademamixset_create", false, in, n, g_dtype, p_dtype, ZS_F32, out, false,
+                    false, true);
+}
+
+int zs_ademamix_hparams_init(double lr, double beta1, double beta2, double beta3_t, double alpha_t,
+                             double eps, double weight_decay, int64_t step, int maximize,
+                             double grad_div, double carry_mul, zs_ademamix_hparams* hp) {
+  const char* fn = "zs_ademamix_hparams_init";
+  ZS_REQUIRE(hp != nullptr, "%s: hp is NULL", fn);
+  ZS_REQUIRE(grad_div > 0.0, "%s: grad_div must be > 0", fn);
+  ZS_REQUIRE(step >= 1, "%s: step must be >= 1 (got %lld)", fn, (long long)step);
+  // zero_amd.optim.AdEMAMix.__init__'s rules
+  ZS_REQUIRE(lr >= 0.0, "%s: invalid learning rate %g", fn, lr);
+  ZS_REQUIRE(beta1 >= 0.0 && beta1 < 1.0, "%s: invalid beta1 %g", fn, beta1);
+  ZS_REQUIRE(beta2 >= 0.0 && beta2 < 1.0, "%s: invalid beta2 %g", fn, beta2);
+  ZS_REQUIRE(beta3_t >= 0.0 && beta3_t < 1.0, "%s: invalid beta3 %g", fn, beta3_t);
+  ZS_REQUIRE(alpha_t >= 0.0, "%s: invalid alpha %g", fn, alpha_t);
+  ZS_REQUIRE(eps >= 0.0, "%s: invalid epsilon %g", fn, eps);
+  ZS_REQUIRE(weight_decay >= 0.0, "%s: invalid weight_decay %g", fn, weight_decay);
+  hp->beta1 = float(beta1);
+  hp->one_minus_beta1 = float(1.0 - beta1);
+  hp->beta3 = float(beta3_t);
+  hp->one_minus_beta3 = float(1.0 - beta3_t);
+  hp->beta2 = float(beta2);
+  hp->one_minus_beta2 = float(1.0 - beta2);
+  hp->inv_bc1 = float(1.0 / (1.0 - std::pow(beta1, double(step))));
+  hp->alpha = float(alpha_t);
+  hp->bc2_sqrt = float(std::sqrt(1.0 - std::pow(beta2, double(step))));
+  hp->eps = float(eps);
+  hp->neg_lr = float(-lr);
+  hp->decay_mul = float(1.0 - lr * weight_decay);
+  hp->grad_div = float(grad_div);
+  hp->carry_mul = float(carry_mul);
+  hp->maximize = maximize ? 1 : 0;
+  return ZS_OK;
+}
+
+int zs_ademamixset_run(const zs_adamset* as, const zs_ademamix_hparams* h, const float* coef,
+                       uintptr_t stream) {
+  const char* fn = "zs_ademamixset_run";
+  ZS_REQUIRE(as && h, "%s: NULL argument", fn);
+  ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create (use "
+             "zs_adafactorset_run)", fn);
+  ZS_REQUIRE(as->ademamix, "%s: the set was not made by zs_ademamixset_create", fn);
+  // a struct filled by hand gets zs_ademamix_hparams_init's rules too (-0.0f is lr = 0)
+  ZS_REQUIRE(h->neg_lr <= 0.0f, "%s: negative learning rate", fn);
+  ZS_REQUIRE(h->beta1 >= 0.0f && h->beta1 <= 1.0f && h->beta2 >= 0.0f && h->beta2 <= 1.0f &&
+                 h->beta3 >= 0.0f && h->beta3 <= 1.0f,
+             "%s: invalid betas (%g, %g, %g)", fn, double(h->beta1), double(h->beta2),
+             double(h->beta3));
+  ZS_REQUIRE(h->inv_bc1 >= 1.0f && h->bc2_sqrt > 0.0f && h->bc2_sqrt <= 1.0f,
+             "%s: invalid bias corrections (%g, %g)", fn, double(h->inv_bc1), double(h->bc2_sqrt));
+  ZS_REQUIRE(h->alpha >= 0.0f && h->eps >= 0.0f, "%s: invalid alpha or eps", fn);
+  ZS_REQUIRE(h->grad_div > 0.0f, "%s: grad_div must be > 0", fn);
+  ZS_REQUIRE(!coef || !as->has_carry, "%s: a set with the ZeRO-1 carry cannot be clipped", fn);
+  AdEMAMixHP hp;
+  hp.beta1 = h->beta1;
+  hp.omb1 = h->one_minus_beta1;
+  hp.beta3 = h->beta3;
+  hp.omb3 = h->one_minus_beta3;
+  hp.beta2 = h->beta2;
+  hp.omb2 = h->one_minus_beta2;
+  hp.inv_bc1 = h->inv_bc1;
+  hp.alpha = h->alpha;
+  hp.bc2_sqrt = h->bc2_sqrt;
+  hp.eps = h->eps;
+  hp.neg_lr = h->neg_lr;
+  hp.decay_mul = h->decay_mul;
+  hp.carry_mul = h->carry_mul;
+  set_grad_div(&hp, h->grad_div);
+  hp.maximize = h->maximize ? 1 : 0;
+  return run_set<AdEMAMixFamily>(as, false, hp, coef, stream);
+}
+
 // The three Adam entry points (`fn`: the one called, in messages).  need_coef: zs_adamset_run_clipped
 // requires its coefficient; sr: zs_adamset_run_sr's m_base and keys, over a set with bf16 moments.
 struct SrArgs {
@@ -3566,6 +3696,8 @@ static int adam_run(const char* fn, const zs_adamset* as, const zs_adam_hparams*
              "zs_adafactorset_run)", fn);
   ZS_REQUIRE(!as->lion, "%s: the set was made by zs_lionset_create (use zs_lionset_run)", fn);
   ZS_REQUIRE(!as->sfadam, "%s: the set was made by zs_sfadamset_create (use zs_sfadamset_run)", fn);
+  ZS_REQUIRE(!as->ademamix, "%s: the set was made by zs_ademamixset_create (use "
+             "zs_ademamixset_run)", fn);
   ZS_REQUIRE(!guard || !as->sgd, "%s: the guarded update is Adam's (the set was made by "
              "zs_sgdset_create)", fn);
   ZS_REQUIRE(!sr || (!as->sgd && as->state_dtype == ZS_BF16),
@@ -3629,7 +3761,7 @@ int zs_adamset_run_psr(const zs_adamset* as, const zs_adam_hparams* h, const flo
   ZS_REQUIRE(as && h, "%s: NULL argument", fn);
   ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create (use "
              "zs_adafactorset_run)", fn);
-  ZS_REQUIRE(as->p_dtype == ZS_BF16_SR && !as->sgd && !as->lion && !as->sfadam,
+  ZS_REQUIRE(as->p_dtype == ZS_BF16_SR && !as->sgd && !as->lion && !as->sfadam && !as->ademamix,
              "%s: the set was not made with p_dtype ZS_BF16_SR (zs_adamset_create_ex)", fn);
   ZS_REQUIRE(!guard || coef, "%s: the guard tests the clip coefficient, which is NULL", fn);
   ZS_REQUIRE(h->amsgrad == 0, "%s: a ZS_BF16_SR set has no amsgrad", fn);
@@ -3665,6 +3797,8 @@ int zs_adamset_run_ema(const zs_adamset* as, const zs_adam_hparams* h, const flo
              "zs_lionset_create)", fn);
   ZS_REQUIRE(!as->sfadam, "%s: the EMA rides on Adam's update (the set was made by "
              "zs_sfadamset_create)", fn);
+  ZS_REQUIRE(!as->ademamix, "%s: the EMA rides on Adam's update (the set was made by "
+             "zs_ademamixset_create)", fn);
   ZS_REQUIRE(as->state_dtype == ZS_F32, "%s: a set with ZS_BF16 state has no EMA column", fn);
   ZS_REQUIRE(as->p_dtype != ZS_BF16_SR, "%s: a ZS_BF16_SR set has no master to average", fn);
   ZS_REQUIRE(!as->has_carry, "%s: a set with the ZeRO-1 carry has no EMA instances", fn);
@@ -3719,6 +3853,8 @@ int zs_adamset_run_stats(const zs_adamset* as, const zs_adam_hparams* h, const f
              "zs_lionset_create)", fn);
   ZS_REQUIRE(!as->sfadam, "%s: the norms ride on Adam's update (the set was made by "
              "zs_sfadamset_create)", fn);
+  ZS_REQUIRE(!as->ademamix, "%s: the norms ride on Adam's update (the set was made by "
+             "zs_ademamixset_create)", fn);
   ZS_REQUIRE(as->state_dtype == ZS_F32, "%s: a set with ZS_BF16 state has no stats instances", fn);
   ZS_REQUIRE(as->p_dtype != ZS_BF16_SR, "%s: a ZS_BF16_SR set has no master to measure", fn);
   ZS_REQUIRE(!as->has_carry, "%s: a set with the ZeRO-1 carry has no stats instances", fn);
@@ -3776,9 +3912,12 @@ static zs::LambTables lamb_tables(const zs_adamset* as) {
 static int lamb_check(const char* fn, const zs_adamset* as, const zs_lamb_hparams* h) {
   ZS_REQUIRE(as && h, "%s: NULL argument", fn);
   ZS_REQUIRE(as->tag == zs::kAdamSetTag, "%s: the set was made by zs_adafactorset_create", fn);
-  ZS_REQUIRE(!as->sgd && !as->lion && !as->sfadam,
+  ZS_REQUIRE(!as->sgd && !as->lion && !as->sfadam && !as->ademamix,
              "%s: LAMB runs over a set made by zs_adamset_create (this one was made by %s)", fn,
-             as->sgd ? "zs_sgdset_create" : as->lion ? "zs_lionset_create" : "zs_sfadamset_create");
+             as->sgd      ? "zs_sgdset_create"
+             : as->lion   ? "zs_lionset_create"
+             : as->sfadam ? "zs_sfadamset_create"
+                          : "zs_ademamixset_create");
   ZS_REQUIRE(as->state_dtype == ZS_F32, "%s: a set with ZS_BF16 state has no LAMB instances", fn);
   ZS_REQUIRE(as->p_dtype != ZS_BF16_SR, "%s: a ZS_BF16_SR set has no master to measure", fn);
   ZS_REQUIRE(!as->has_carry, "%s: a set with the ZeRO-1 carry has no LAMB instances", fn);

@@ -3,7 +3,7 @@
 Modules mirror the reference: ``zero_amd.zero1`` / ``zero2`` / ``zero3`` each export
 ``ShardedOptimizer``; ``zero3`` also ``Zero3ParamManager`` and ``register_zero3_hooks``;
 ``zero_amd.training_utils`` exports ``get``, ``set_seed`` and ``print_memory_stats``;
-``zero_amd.optim`` holds ``Lion``, ``LAMB``, ``NorMuon``, ``AdamMini``, ``Apollo`` and
+``zero_amd.optim`` holds ``Lion``, ``LAMB``, ``NorMuon``, ``AdamMini``, ``Apollo``, ``AdEMAMix`` and
 ``ScheduleFreeAdamW``, the optimizers torch does not ship.
 Importing the package loads ``libzero_amd.so``; it raises if the library is missing.
 """

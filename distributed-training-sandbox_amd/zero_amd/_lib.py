@@ -47,6 +47,7 @@ EXPORTED = (
     "zs_sgd_hparams_init", "zs_sgdset_create", "zs_sgdset_run",
     "zs_lion_hparams_init", "zs_lionset_create", "zs_lionset_run",
     "zs_sfadam_hparams_init", "zs_sfadamset_create", "zs_sfadamset_run", "zs_sfadamset_swap",
+    "zs_ademamix_hparams_init", "zs_ademamixset_create", "zs_ademamixset_run",
     "zs_lamb_hparams_init", "zs_lambset_run_moments", "zs_lamb_finish", "zs_lambset_bind_params",
     "zs_lambset_run_apply",
     "zs_adafactor_hparams_init", "zs_adafactorset_create", "zs_adafactorset_run",
@@ -115,6 +116,13 @@ class SfAdamHParams(ctypes.Structure):
                 ("weight_decay", ctypes.c_float), ("c", ctypes.c_float), ("a", ctypes.c_float),
                 ("lr_t", ctypes.c_float), ("grad_div", ctypes.c_float),
                 ("carry_mul", ctypes.c_float), ("maximize", ctypes.c_int32)]
+
+
+class AdEMAMixHParams(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_float) for name in (
+        "beta1", "one_minus_beta1", "beta3", "one_minus_beta3", "beta2", "one_minus_beta2",
+        "inv_bc1", "alpha", "bc2_sqrt", "eps", "neg_lr", "decay_mul", "grad_div", "carry_mul")] + \
+        [("maximize", ctypes.c_int32)]
 
 
 class LambHParams(ctypes.Structure):
@@ -295,6 +303,11 @@ _SIGS = {
                              ctypes.POINTER(_P)], ctypes.c_int),
     "zs_sfadamset_run": ([_P, ctypes.POINTER(SfAdamHParams), _P, ctypes.c_int, _U], ctypes.c_int),
     "zs_sfadamset_swap": ([_P, ctypes.c_double, ctypes.c_int, _U], ctypes.c_int),
+    "zs_ademamix_hparams_init": ([ctypes.c_double] * 7 + [_I64, ctypes.c_int, ctypes.c_double,
+                                  ctypes.c_double, ctypes.POINTER(AdEMAMixHParams)], ctypes.c_int),
+    "zs_ademamixset_create": ([ctypes.POINTER(AdamSeg), _I64, ctypes.c_int, ctypes.c_int,
+                               ctypes.POINTER(_P)], ctypes.c_int),
+    "zs_ademamixset_run": ([_P, ctypes.POINTER(AdEMAMixHParams), _P, _U], ctypes.c_int),
     "zs_lamb_hparams_init": ([ctypes.c_double] * 4 + [ctypes.c_int] * 2 +
                              [_I64, ctypes.c_double, ctypes.POINTER(LambHParams)], ctypes.c_int),
     "zs_lambset_run_moments": ([_P, ctypes.POINTER(LambHParams), _P, _P, _U], ctypes.c_int),

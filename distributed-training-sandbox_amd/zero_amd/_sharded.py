@@ -21,7 +21,7 @@ from torch.optim import Optimizer
 
 from . import checkpoint as ckpt
 from ._hooks import on_param_device
-from ._update import (MUON_KINDS, check_adafactor, check_adamini, check_apollo, check_lamb, check_muon, check_sfadam, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
+from ._update import (MUON_KINDS, check_adafactor, check_adamini, check_apollo, check_lamb, check_muon, check_sfadam, check_ademamix, check_bf16_state_group, check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group,
                       check_max_grad_norm, check_param_grad_norms, check_update_norms,
                       check_update_norms_group,
                       check_skip_nonfinite, check_master_free, check_master_free_group,
@@ -141,6 +141,20 @@ def sfadam_group_hparams(group: dict) -> dict:
                 step=int(group["k"]), lr_t=float(group["lr_t"]), c=float(group["c"]))
 
 
+def ademamix_group_hparams(group: dict) -> dict:
+    """Hyper-parameters of one zero_amd.optim.AdEMAMix param group; ``alpha`` and ``beta3`` are
+    the final values, which the update's struct takes through ``ademamix_schedule`` at each
+    parameter's step count."""
+    lr = group["lr"]
+    lr = float(lr.item()) if torch.is_tensor(lr) else float(lr)
+    beta1, beta2, beta3 = group["betas"]
+    return dict(lr=lr, beta1=float(beta1), beta2=float(beta2), beta3=float(beta3),
+                alpha=float(group["alpha"]), eps=float(group["eps"]),
+                weight_decay=float(group.get("weight_decay", 0.0)),
+                alpha_warmup=group.get("alpha_warmup"), beta3_warmup=group.get("beta3_warmup"),
+                maximize=bool(group.get("maximize", False)), amsgrad=False)
+
+
 SFADAM_HOST_SCALARS = ("k", "weight_sum", "lr_max", "lr_t", "c")
 
 
@@ -175,7 +189,9 @@ def sfadam_swap_weight(group: dict, to_eval: bool) -> float:
 
 def group_hparams(kind: str, group: dict, optimizer: Optimizer) -> dict:
     """One param group's hyper-parameters for the ``kind`` ("adam" / "sgd" / "lion" / "adafactor" /
-    "muon" / "lamb" / "normuon" / "adamini" / "apollo" / "sfadam") update."""
+    "muon" / "lamb" / "normuon" / "adamini" / "apollo" / "ademamix" / "sfadam") update."""
+    if kind == "ademamix":
+        return ademamix_group_hparams(group)
     if kind == "sfadam":
         return sfadam_group_hparams(group)
     if kind == "apollo":
@@ -199,9 +215,9 @@ def optimizer_kind(optimizer: Optimizer) -> str:
     """"adam" (torch.optim.Adam / AdamW), "sgd" (torch.optim.SGD), "lion" (zero_amd.optim.Lion),
     "adafactor" (torch.optim.Adafactor), "muon" (torch.optim.Muon), "lamb" (zero_amd.optim.LAMB),
     "normuon" (zero_amd.optim.NorMuon), "adamini" (zero_amd.optim.AdamMini), "apollo"
-    (zero_amd.optim.Apollo) or "sfadam" (zero_amd.optim.ScheduleFreeAdamW); TypeError for anything
-    else."""
-    from .optim import LAMB, AdamMini, Apollo, Lion, NorMuon, ScheduleFreeAdamW
+    (zero_amd.optim.Apollo), "ademamix" (zero_amd.optim.AdEMAMix) or "sfadam"
+    (zero_amd.optim.ScheduleFreeAdamW); TypeError for anything else."""
+    from .optim import LAMB, AdamMini, AdEMAMix, Apollo, Lion, NorMuon, ScheduleFreeAdamW
 
     if isinstance(optimizer, torch.optim.Adam):
         return "adam"
@@ -221,10 +237,12 @@ def optimizer_kind(optimizer: Optimizer) -> str:
         return "adamini"
     if isinstance(optimizer, Apollo):
         return "apollo"
+    if isinstance(optimizer, AdEMAMix):
+        return "ademamix"
     if isinstance(optimizer, ScheduleFreeAdamW):
         return "sfadam"
     raise TypeError("zero_amd ShardedOptimizer wraps torch.optim.Adam / AdamW / SGD / Adafactor / Muon or "
-                    "zero_amd.optim.Lion / LAMB / NorMuon / AdamMini / Apollo / ScheduleFreeAdamW "
+                    "zero_amd.optim.Lion / LAMB / NorMuon / AdamMini / Apollo / AdEMAMix / ScheduleFreeAdamW "
                     f"(got {type(optimizer).__name__})")
 
 
@@ -252,6 +270,12 @@ class ShardedOptimizerBase:
                          state_rounding=state_rounding, master=master, ema_decay=ema_decay,
                          param_update_norms=param_update_norms)
             arena = "flat"  # arena='auto' would time the bucket arena as a candidate
+        if optimizer_kind(optimizer) == "ademamix":  # likewise
+            check_ademamix(arena=arena, layout=layout, carry=self._carry,
+                           skip_nonfinite=skip_nonfinite, state_dtype=state_dtype,
+                           state_rounding=state_rounding, master=master, ema_decay=ema_decay,
+                           param_update_norms=param_update_norms)
+            arena = "flat"
         # the moments' dtype: None / torch.float32, or torch.bfloat16 (opt-in: exp_avg and
         # exp_avg_sq stored in bf16, the arithmetic in fp32 as before).  What it
         # cannot be combined with is refused below, on every rank and before anything collective

@@ -16,8 +16,8 @@ import numpy as np
 import torch
 
 from .checkpoint import step_of
-from .kernels import (adam_hparams, lamb_hparams, lion_hparams, sfadam_hparams, sgd_hparams,
-                      sr_keys)
+from .kernels import (adam_hparams, ademamix_hparams, lamb_hparams, lion_hparams, sfadam_hparams,
+                      sgd_hparams, sr_keys)
 
 # master="none": bf16 parameters without any master — the fused update reads the bf16 parameter,
 # runs the fp32 rule and stores it back rounded stochastically ("Master-free bf16
@@ -51,7 +51,7 @@ BF16_STATE_MIN_ONE_MINUS_BETA = 2.0 ** -8
 
 
 KINDS = ("adam", "sgd", "lion", "adafactor", "muon", "lamb", "normuon", "adamini", "apollo",
-         "sfadam")
+         "ademamix", "sfadam")
 # torch.optim.Muon and zero_amd.optim.NorMuon: one engine path, one set of refusals
 MUON_KINDS = ("muon", "normuon")
 # what the messages call the optimizer of a kind that an option does not support
@@ -59,7 +59,41 @@ KIND_NAMES = {"sgd": "torch.optim.SGD", "lion": "zero_amd.optim.Lion",
               "adafactor": "torch.optim.Adafactor", "muon": "torch.optim.Muon",
               "lamb": "zero_amd.optim.LAMB", "normuon": "zero_amd.optim.NorMuon",
               "adamini": "zero_amd.optim.AdamMini", "apollo": "zero_amd.optim.Apollo",
+              "ademamix": "zero_amd.optim.AdEMAMix",
               "sfadam": "zero_amd.optim.ScheduleFreeAdamW"}
+
+
+def check_ademamix(*, arena: str = "flat", layout: str = "reference", carry: bool = False,
+                   zero3_reference: bool = False, skip_nonfinite: bool = False, state_dtype=None,
+                   state_rounding=None, master: str = "split", ema_decay=None,
+                   param_update_norms: bool = False) -> None:
+    """What zero_amd.optim.AdEMAMix cannot be combined with, as ValueError.  The rule is
+    elementwise on the streams of Adam with amsgrad, so it runs wherever Lion does: the flat arena
+    (overlap and the ZeRO-1 carry included) and ZeRO-3's update mode, on fp32 state over an fp32 or
+    split master ("Fused AdEMAMix"; §8)."""
+    name = KIND_NAMES["ademamix"]
+
+    def no(what: str, why: str):
+        raise ValueError(f"zero_amd: {name} is not supported with {what} ({why})")
+
+    if arena == "buckets":
+        no("arena='buckets'", "the bucket arena; use the flat arena")
+    if layout != "reference" and (layout != "flat" or carry):
+        no(f"layout={layout!r}", "it runs on the bucket arena, arena='buckets'")
+    if zero3_reference:
+        no("ZeRO-3 reference mode", "the fused update is update mode's")
+    if skip_nonfinite:
+        no("skip_nonfinite", "the rule has no guarded instances")
+    if state_dtype is not None and state_dtype != torch.float32:
+        no(f"state_dtype={state_dtype}", "the three state arrays are fp32")
+    if state_rounding is not None:
+        no("state_rounding", "the three state arrays are fp32")
+    if master == "none":
+        no("master='none'", "the rule has no master-free instances")
+    if ema_decay is not None:
+        no("ema_decay", "the EMA is fused into the Adam update")
+    if param_update_norms:
+        no("param_update_norms", "the norms are summed inside the fused Adam update")
 
 
 def check_sfadam(*, arena: str = "flat", layout: str = "reference", carry: bool = False,
@@ -487,8 +521,10 @@ def state_layout(kind: str, L: int, *, split: bool = False, fp32_master: bool = 
     # (Muon: ``m`` alone, always: the momentum buffer)
     # (Adam-mini: ``m`` alone, exp_avg; the block second moment is flat.AdamMiniState's arena)
     # (Schedule-Free AdamW: ``m`` is z, ``v`` exp_avg_sq)
-    names = ["m", "v"][:2 if kind in ("adam", "lamb", "sfadam")
+    # (AdEMAMix: ``m`` exp_avg, ``v`` exp_avg_sq and ``slow``, exp_avg_slow: the rows' vmax column)
+    names = ["m", "v"][:2 if kind in ("adam", "lamb", "sfadam", "ademamix")
                        else 1 if kind in ("lion", "adamini") + MUON_KINDS else int(bool(momentum))]
+    names += ["slow"] * (kind == "ademamix")
     names += ["carry"] * bool(carry) + ["master"] * bool(fp32_master)
     lay = {name: (k * L, torch.float32) for k, name in enumerate(names)}
     total = len(names) * L
@@ -510,7 +546,8 @@ class UpdateCore:
 
         if kind not in KINDS:
             raise ValueError("UpdateCore: kind must be 'adam', 'sgd', 'lion', 'adafactor', 'muon', "
-                             f"'lamb', 'normuon', 'adamini', 'apollo' or 'sfadam' (got {kind!r})")
+                             f"'lamb', 'normuon', 'adamini', 'apollo', 'ademamix' or 'sfadam' "
+                             f"(got {kind!r})")
         # the update: torch.optim.Adam's, torch.optim.SGD's (`momentum`: some group has a
         # momentum, so the shard holds a momentum buffer; none of them: no optimizer state at all)
         # or zero_amd.optim.Lion's (one moment, exp_avg, always); zero_amd.optim.LAMB's has Adam's
@@ -538,6 +575,8 @@ class UpdateCore:
             off, dt = lay.get(name, (0, None))
             setattr(self, name, None if dt is None else self.state[off:].view(dt)[:self.L])
         self.vmax = None
+        if "slow" in lay:  # AdEMAMix: exp_avg_slow streams through the rows' vmax column, always
+            self.vmax = self.state[lay["slow"][0]:][:self.L]
         # ema (ema_decay): an fp32 EMA of the master per element, sharded like m, allocated like
         # vmax, whose column of the rows it takes; every launch then goes through run_ema with the
         # weight of the decay as it is at that step (the owner initialises the array from the
@@ -574,13 +613,16 @@ class UpdateCore:
             views = {"momentum_buffer": cut(self.m)}
         elif self.kind == "sfadam":  # (the m array holds z, the base iterate)
             views = {"z": cut(self.m), "exp_avg_sq": cut(self.v)}
+        elif self.kind == "ademamix":
+            views = {"exp_avg": cut(self.m), "exp_avg_slow": cut(self.vmax),
+                     "exp_avg_sq": cut(self.v)}
         else:
             views = {"exp_avg": cut(self.m), "exp_avg_sq": cut(self.v)}
         if self.master is not None:
             views["master_param"] = cut(self.master)
         if self.lo is not None:  # the fp32 master = the bf16 param's bits << 16 + this residual
             views["master_residual"] = cut(self.lo)
-        if self.vmax is not None:
+        if self.vmax is not None and self.kind != "ademamix":
             views["max_exp_avg_sq"] = cut(self.vmax)
         if self.ema is not None:
             views["ema_param"] = cut(self.ema)
@@ -698,6 +740,14 @@ class UpdateCore:
                                   hpd["weight_decay"], hpd["step"], hpd["c"],
                                   maximize=hpd["maximize"], grad_div=float(self.ws),
                                   carry_mul=carry_mul)
+        if self.kind == "ademamix":  # (a_t and b3_t: the schedulers at the parameter's count)
+            from .optim import ademamix_schedule
+
+            a_t, b3_t = ademamix_schedule(int(key), hpd["alpha"], hpd["beta1"], hpd["beta3"],
+                                          hpd["alpha_warmup"], hpd["beta3_warmup"])
+            return ademamix_hparams(hpd["lr"], hpd["beta1"], hpd["beta2"], b3_t, a_t, hpd["eps"],
+                                    hpd["weight_decay"], int(key), maximize=hpd["maximize"],
+                                    grad_div=float(self.ws), carry_mul=carry_mul)
         if self.kind == "lamb":
             hp = lamb_hparams(hpd["beta1"], hpd["beta2"], hpd["eps"], hpd["weight_decay"], int(key),
                               bias_correction=hpd["bias_correction"], maximize=hpd["maximize"],
@@ -760,6 +810,10 @@ class UpdateCore:
             aset.run(hp, stream, coef=coef, guard=guard, sr=sr)
         elif self.kind == "sfadam":
             aset.run(hp, stream, coef=coef, guard=guard)
+        elif self.kind == "ademamix":
+            if guard:
+                raise ValueError("zero_amd: AdEMAMix: no guarded instances exist")
+            aset.run(hp, stream, coef=coef)
         elif self.kind == "lamb":  # pass L1; launch_apply is L2
             if stats is None or guard:
                 raise ValueError("zero_amd: LAMB: a launch without its partials, or a guarded one")

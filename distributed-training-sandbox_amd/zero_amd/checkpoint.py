@@ -11,7 +11,7 @@ torch's format — ``{"state": {index: {...}}, "param_groups": [...]}`` with ind
 optimizer's parameters in group order — and the tensors are copied into and out of the flat state.
 
 Per-parameter entries: ``step`` (fp32 CPU scalar, torch's convention), ``exp_avg``, ``exp_avg_sq``
-(+ ``max_exp_avg_sq``) and, beyond torch's Adam, what the engine needs to continue bit for bit:
+(+ ``max_exp_avg_sq``; AdEMAMix: + ``exp_avg_slow``) and, beyond torch's Adam, what the engine needs to continue bit for bit:
 ``master_residual`` (int16; bf16 params, split master: master = bf16 param bits << 16 + residual),
 ``master_param`` (fp32 master), ``zero1_carry`` (ZeRO-1's A_{t-1}),
 ``ema_param`` (the fp32 EMA of an optimizer with ``ema_decay``; the decay itself is not saved).  A

@@ -38,7 +38,7 @@ import torch
 from . import _lib
 from .comm import StreamEvent, comm_stream, zs_dtype
 from ._update import KINDS, MASTERS, UpdateCore, check_master_free, check_params
-from .kernels import AdamSet, CopySet, LionSet, SfAdamSet, SgdSet
+from .kernels import AdamSet, AdEMAMixSet, CopySet, LionSet, SfAdamSet, SgdSet
 from .plan import Plan
 
 ALIGN_ELEMS = 64  # every stream piece starts 256 B (f32) / 128 B (bf16) aligned
@@ -304,7 +304,7 @@ class ShardEngine(UpdateCore):
                  update_norms: bool = False):
         if kind not in KINDS:
             raise ValueError("ShardEngine: kind must be 'adam', 'sgd', 'lion', 'adafactor', 'muon', 'normuon', "
-                             f"'adamini', 'apollo', 'lamb' or 'sfadam' (got {kind!r})")
+                             f"'adamini', 'apollo', 'lamb', 'ademamix' or 'sfadam' (got {kind!r})")
         if not params:
             raise ValueError("ShardEngine: no parameters")
         dev, dtype = check_params(params)
@@ -446,6 +446,8 @@ class ShardEngine(UpdateCore):
                            state_rounding=self.state_rounding)
         if self.kind == "sfadam":
             return SfAdamSet(rows, gz, self.p_dtype)
+        if self.kind == "ademamix":
+            return AdEMAMixSet(rows, gz, self.p_dtype)
         if self.master_free:
             return AdamSet(rows, gz, self.p_dtype, state_dtype=zs_dtype(self.state_dtype),
                            wide_grads=gz == _lib.ZS_F32, state_rounding=self.state_rounding)

@@ -12,6 +12,8 @@ finite; ``run_sr`` with ``sr_keys`` stores bf16 moments with stochastic rounding
 ``lion_hparams``.
 ``SfAdamSet`` — the same tables with zero_amd.optim.ScheduleFreeAdamW's update (the master is y,
 ``m`` is z) and ``swap``, the eval() / train() kernel; ``sfadam_hparams``.
+``AdEMAMixSet`` — the same tables with zero_amd.optim.AdEMAMix's update (``m`` is exp_avg, ``v``
+exp_avg_sq, ``vmax`` exp_avg_slow); ``ademamix_hparams``.
 ``AdamSet.run_lamb_moments`` / ``lamb_finish`` / ``AdamSet.run_lamb_apply`` — zero_amd.optim.LAMB's
 update over an Adam set, two passes (csrc/zs_lamb.hip); ``lamb_hparams``.
 ``AdafactorSet`` — torch.optim.Adafactor's update over a table of matrices (csrc/zs_adafactor.hip):
@@ -39,7 +41,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (AdafactorHParams, AdafactorSeg, AdamHParams, AdamMiniHParams, AdamMiniSeg,
+from ._lib import (AdafactorHParams, AdafactorSeg, AdamHParams, AdEMAMixHParams, AdamMiniHParams, AdamMiniSeg,
                    AdamSeg, ApolloHParams, ApolloSeg, LambHParams, LionHParams, MuonHParams, MuonSeg, NorMuonHParams,
                    SfAdamHParams, SgdHParams)
 
@@ -539,6 +541,42 @@ class SfAdamSet(AdamSet):
                                 "a Schedule-Free AdamW set runs through SfAdamSet.run")
 
     run_sr = run_psr = run_ema = run_stats = run_lamb_moments = run_lamb_apply = _not_sfadam
+
+
+def ademamix_hparams(lr, beta1=0.9, beta2=0.999, beta3_t=0.9999, alpha_t=5.0, eps=1e-8,
+                     weight_decay=0.0, step=1, *, maximize=False, grad_div=1.0,
+                     carry_mul=0.0) -> AdEMAMixHParams:
+    """The scalars of one AdEMAMix step at the parameter's count ``step`` (after the increment);
+    ``beta3_t`` and ``alpha_t``: what ``zero_amd.optim.ademamix_schedule`` gives at that count."""
+    hp = AdEMAMixHParams()
+    _lib.call("zs_ademamix_hparams_init", float(lr), float(beta1), float(beta2), float(beta3_t),
+              float(alpha_t), float(eps), float(weight_decay), int(step), int(bool(maximize)),
+              float(grad_div), float(carry_mul), ctypes.byref(hp))
+    return hp
+
+
+class AdEMAMixSet(AdamSet):
+    """Fused AdEMAMix over segments in zs_adam_seg order (zs_ademamixset_create): column ``m`` is
+    ``exp_avg``, ``v`` is ``exp_avg_sq`` and ``vmax`` is ``exp_avg_slow`` on every row, fp32.
+    ``set_grads``, ``grad_sqnorm``, ``grad_sqnorm_segs``, ``bytes`` and ``grad_bytes`` as
+    ``AdamSet``."""
+
+    _CREATE = "zs_ademamixset_create"
+
+    def run(self, hp: AdEMAMixHParams, stream, coef=None) -> None:
+        """One step (zs_ademamixset_run); ``coef`` as ``LionSet.run``."""
+        ptr = None if coef is None else coef if isinstance(coef, int) else coef.data_ptr()
+        _lib.call("zs_ademamixset_run", self._h, ctypes.byref(hp), ptr, stream_handle(stream))
+
+    def run_clipped(self, hp, coef, stream) -> None:
+        self.run(hp, stream, coef=coef)
+
+    def _not_ademamix(self, *a, **k):
+        raise _lib.ZeroAmdError("zs_ademamixset_run", _lib.ZS_ERR_INVALID,
+                                "an AdEMAMix set runs through AdEMAMixSet.run")
+
+    run_guarded = run_sr = run_psr = run_ema = run_stats = run_lamb_moments = run_lamb_apply = \
+        _not_ademamix
 
 
 def lamb_hparams(beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=0.0, step=1, *,

@@ -14,6 +14,11 @@ without a learning-rate schedule, the gradient taken at an interpolation of the 
 running average; ``eval()`` / ``train()`` swap the parameters between the two; see the class, which
 is this project's definition of the rule.
 
+``AdEMAMix`` (Pagliardini, Ablin, Grangier 2024, "The AdEMAMix Optimizer: Better, Faster, Older",
+arXiv:2409.03137): AdamW with a second, very slow EMA of the gradient mixed into the numerator, its
+weight ``alpha`` and decay ``beta3`` warmed up over training (``ademamix_schedule``); see the class,
+which is this project's definition of the rule.
+
 ``NorMuon`` (Li et al. 2025): Muon's orthogonalised update normalised per output neuron by a
 running row second moment; see the class, which is this project's definition of the rule.
 
@@ -24,6 +29,8 @@ rows; see the class, likewise.
 per channel applied to the raw gradient; see the class, likewise.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -215,6 +222,111 @@ class ScheduleFreeAdamW(Optimizer):
                 y.lerp_(z, c)
                 y.add_(n, alpha=a)
                 z.add_(n, alpha=-lr_t)
+        return loss
+
+
+def ademamix_schedule(t: int, alpha: float, beta1: float, beta3: float, alpha_warmup=None,
+                      beta3_warmup=None):
+    """``(a_t, b3_t)`` of ``AdEMAMix`` at step count ``t`` (after the increment), in double: the
+    paper's linear warm-up of ``alpha`` over ``alpha_warmup`` steps and its warm-up of ``beta3``
+    from ``beta1``, linear in the EMA's half-life, over ``beta3_warmup`` steps; both capped at
+    their final values, either constant without its warm-up.  A pure function of the count, so
+    every rank and a restarted run form the same scalars."""
+    a_t = float(alpha) if alpha_warmup is None else min(t * float(alpha) / alpha_warmup,
+                                                        float(alpha))
+    b3_t = float(beta3)
+    if beta3_warmup is not None:
+        s = t / beta3_warmup
+        l1, l3 = math.log(beta1), math.log(beta3)
+        b3_t = min(math.exp(l1 * l3 / ((1 - s) * l3 + s * l1)), float(beta3))
+    return a_t, b3_t
+
+
+class AdEMAMix(Optimizer):
+    """``AdEMAMix(params, lr=1e-3, betas=(0.9, 0.999, 0.9999), alpha=5.0, eps=1e-8,
+    weight_decay=0.0, *, alpha_warmup=None, beta3_warmup=None, maximize=False)``: Pagliardini, Ablin,
+    Grangier 2024 (arXiv:2409.03137) -- AdamW whose numerator adds ``alpha`` times a slow EMA of the
+    gradient (``beta3`` around 0.9999, no bias correction) to the bias-corrected fast one.
+
+    ``state[p]`` holds ``step`` (an fp32 CPU scalar, as torch.optim.Adam keeps it), ``exp_avg``
+    (fast), ``exp_avg_slow`` and ``exp_avg_sq``.  One step, with ``t = step`` after the increment
+    and every scalar formed on the host in double (``a_t``, ``b3_t``: ``ademamix_schedule``), then
+    rounded to fp32 once where a tensor operation takes it::
+
+        p.mul_(1 - lr * weight_decay)
+        m1.mul_(beta1).add_(g, alpha=1 - beta1)
+        m2.mul_(b3_t).add_(g, alpha=1 - b3_t)
+        v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+        den = sqrt(v) / sqrt(1 - beta2**t) + eps                 # IEEE root and division
+        u = m1.mul(1 / (1 - beta1**t)).add_(m2, alpha=a_t) / den
+        p.add_(u, alpha=-lr)
+
+    Handed to ``zero_amd.zero1`` / ``zero2`` / ``zero3.ShardedOptimizer`` the update runs in the
+    fused HIP kernels instead ("Fused AdEMAMix"), which compute what this ``step()``
+    computes on fp32 CPU tensors, bit for bit.
+    """
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999, 0.9999), alpha: float = 5.0,
+                 eps: float = 1e-8, weight_decay: float = 0.0, *, alpha_warmup=None,
+                 beta3_warmup=None, maximize: bool = False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        for k in range(3):
+            if not 0.0 <= betas[k] < 1.0:
+                raise ValueError(f"Invalid beta parameter at index {k}: {betas[k]}")
+        if not 0.0 <= alpha:
+            raise ValueError(f"Invalid alpha value: {alpha}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if alpha_warmup is not None and not 0 < alpha_warmup:
+            raise ValueError(f"Invalid alpha_warmup value: {alpha_warmup}")
+        if beta3_warmup is not None:
+            if not 0 < beta3_warmup:
+                raise ValueError(f"Invalid beta3_warmup value: {beta3_warmup}")
+            if not (0.0 < betas[0] and 0.0 < betas[2]):  # the schedule takes their logarithms
+                raise ValueError("beta3_warmup needs beta1 > 0 and beta3 > 0 (got betas "
+                                 f"{tuple(betas)})")
+        super().__init__(params, dict(lr=lr, betas=betas, alpha=alpha, eps=eps,
+                                      weight_decay=weight_decay, alpha_warmup=alpha_warmup,
+                                      beta3_warmup=beta3_warmup, maximize=maximize))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            lr, wd = group["lr"], group["weight_decay"]
+            beta1, beta2, beta3 = group["betas"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("AdEMAMix does not support sparse gradients")
+                g = -p.grad if group["maximize"] else p.grad
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    for name in ("exp_avg", "exp_avg_slow", "exp_avg_sq"):
+                        state[name] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                m1, m2, v = state["exp_avg"], state["exp_avg_slow"], state["exp_avg_sq"]
+                state["step"] += 1
+                t = int(state["step"])
+                a_t, b3_t = ademamix_schedule(t, group["alpha"], beta1, beta3,
+                                              group["alpha_warmup"], group["beta3_warmup"])
+                p.mul_(1 - lr * wd)
+                m1.mul_(beta1).add_(g, alpha=1 - beta1)
+                m2.mul_(b3_t).add_(g, alpha=1 - b3_t)
+                v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+                # the root through float64: torch's vectorised fp32 CPU sqrt is not correctly
+                # rounded, the kernel's is; the double root rounded to fp32 is (53 >= 2 * 24 + 2)
+                den = v.to(torch.float64).sqrt_().to(v.dtype).div_(math.sqrt(1 - beta2 ** t))
+                den.add_(group["eps"])
+                u = m1.mul(1 / (1 - beta1 ** t)).add_(m2, alpha=a_t).div_(den)
+                p.add_(u, alpha=-lr)
         return loss
 
 

@@ -69,14 +69,14 @@ from ._lib import ZS_BF16, ZS_BF16_SPLIT, ZS_BF16_SR, ZS_F32
 from . import checkpoint as ckpt
 from ._hooks import WeakArgCall, WeakCall, on_param_device
 from ._sharded import group_hparams, optimizer_kind, sfadam_step, sfadam_swap_weight
-from ._update import (GradClip, LambNorms, UpdateCore, UpdateNorms, check_adafactor, check_adamini, check_apollo, check_lamb, check_muon, check_sfadam, check_bf16_state_group,
+from ._update import (GradClip, LambNorms, UpdateCore, UpdateNorms, check_adafactor, check_adamini, check_apollo, check_lamb, check_muon, check_sfadam, check_ademamix, check_bf16_state_group,
                       check_bf16_state_lion_group, check_ema, check_ema_decay, check_ema_group, check_master_free, check_update_norms,
                       check_update_norms_group,
                       check_master_free_group, check_max_grad_norm, check_param_grad_norms, check_params, check_skip_nonfinite, check_state_dtype, check_state_rounding,
                       owner_range)
 from .comm import STREAM_SYNC, RcclComm, Sync, comm_stream, sync_kind, zs_dtype
 from .engine import ALIGN_ELEMS
-from .kernels import AdamSet, LionSet, SfAdamSet, SgdSet, convert, stream_handle
+from .kernels import AdamSet, AdEMAMixSet, LionSet, SfAdamSet, SgdSet, convert, stream_handle
 from .training_utils.utils import get
 
 try:  # the hooks' per-module install / release in C++ (csrc/zs_host_ext.cpp, built with the library)
@@ -1867,6 +1867,10 @@ class ShardedOptimizer:
             check_sfadam(zero3_reference=not update, skip_nonfinite=skip_nonfinite,
                          state_dtype=state_dtype, state_rounding=state_rounding, master=master,
                          ema_decay=ema_decay, param_update_norms=param_update_norms)
+        if optimizer_kind(optimizer) == "ademamix":
+            check_ademamix(zero3_reference=not update, skip_nonfinite=skip_nonfinite,
+                           state_dtype=state_dtype, state_rounding=state_rounding, master=master,
+                           ema_decay=ema_decay, param_update_norms=param_update_norms)
         self.max_grad_norm = max_grad_norm
         self._check_clip()
         self.skip_nonfinite = check_skip_nonfinite(skip_nonfinite, max_grad_norm,
@@ -2406,6 +2410,8 @@ class ShardedOptimizer:
             mk, kw["state_rounding"] = LionSet, self.state_rounding
         if self._kind == "sfadam":
             mk = SfAdamSet
+        if self._kind == "ademamix":
+            mk = AdEMAMixSet
         if self._master_free:
             return mk(rows, gz, ZS_BF16_SR, wide_grads=acc, state_rounding=self.state_rounding, **kw)
         if self._split:

@@ -713,6 +713,67 @@ int zs_sfadamset_run(const zs_adamset* as, const zs_sfadam_hparams* hp, const fl
 int zs_sfadamset_swap(const zs_adamset* as, double weight, int to_eval, uintptr_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Fused AdEMAMix (Pagliardini, Ablin, Grangier 2024, arXiv:2409.03137), additive in ABI v13.    */
+/* The update of zero_amd.optim.AdEMAMix on the owned shard through Adam's tables and kernels'   */
+/* shape: field m of a segment is exp_avg (the fast EMA), v is exp_avg_sq, vmax holds            */
+/* exp_avg_slow.  The streams and bytes of Adam with amsgrad (34 B/element over the split master */
+/* with bf16 gradients).                                                                         */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  /* doubles on the host, rounded to f32 once */
+  float beta1;
+  float one_minus_beta1;
+  float beta3;            /* the slow EMA's decay at this step (after its warm-up) */
+  float one_minus_beta3;
+  float beta2;
+  float one_minus_beta2;
+  float inv_bc1;          /* 1 / (1 - beta1^step) */
+  float alpha;            /* the slow EMA's weight at this step (after its warm-up) */
+  float bc2_sqrt;         /* sqrt(1 - beta2^step) */
+  float eps;
+  float neg_lr;
+  float decay_mul;        /* 1 - lr*weight_decay (decoupled) */
+  float grad_div;         /* divide the reduced sum by this (world size) */
+  float carry_mul;        /* ZeRO-1: sum += carry_mul * carry (ws-1) */
+  int32_t maximize;
+} zs_ademamix_hparams;
+
+/* Fill hp from the scalars of one step of an AdEMAMix param group: step is the parameter's count
+ * after the increment, beta3_t and alpha_t what the class's schedulers give at that count (the
+ * host runs them: zero_amd.optim.ademamix_schedule); everything else is derived in double.
+ * ZS_ERR_INVALID for what the class refuses (lr < 0, a beta outside [0, 1), alpha < 0, eps < 0,
+ * weight_decay < 0), for step < 1, grad_div <= 0 and a NULL hp. */
+int zs_ademamix_hparams_init(double lr, double beta1, double beta2, double beta3_t, double alpha_t,
+                             double eps, double weight_decay, int64_t step, int maximize,
+                             double grad_div, double carry_mul, zs_ademamix_hparams* hp);
+/* A zs_adamset whose update is AdEMAMix's: segs, g_dtype, p_dtype, alignment and the vector /
+ * scalar split exactly as zs_adamset_create, with m = exp_avg, v = exp_avg_sq and vmax =
+ * exp_avg_slow (fp32, updated in place) set on every non-empty segment.  ZS_ERR_INVALID: a NULL
+ * out or table, n < 0, a bad g_dtype; p_dtype other than ZS_BF16 or ZS_BF16_SPLIT; a non-empty
+ * segment without master, m, v or vmax; a split master without master_out and p_out; a carry with
+ * fp32 gradients over the split master, or on some segments only.  zs_adamset_set_grads, the
+ * sum-of-squares passes, zs_adamset_destroy and zs_adamset_stats work on it unchanged; every
+ * zs_adamset_run*, zs_lionset_run, zs_sgdset_run, zs_sfadamset_* and zs_lambset_* return
+ * ZS_ERR_INVALID on it, as zs_ademamixset_run does on their sets. */
+int zs_ademamixset_create(const zs_adam_seg* segs, int64_t n, int g_dtype, int p_dtype,
+                          zs_adamset** out);
+/* One step over the set, per element (fp32, only the written fma fused; '/' and sqrt IEEE):
+ *   g = (sum [+ carry_mul * carry]) / grad_div;  [carry = g];  [g *= *coef];  [g = -g]
+ *   p = p * decay_mul
+ *   m = fma(1 - beta1, g, m * beta1);  vmax = fma(1 - beta3, g, vmax * beta3)
+ *   v = fma((1 - beta2) * g, g, v * beta2);  den = sqrt(v) / bc2_sqrt + eps
+ *   p = fma(neg_lr, fma(alpha, vmax, m * inv_bc1) / den, p)
+ * and p is stored as the set's p_dtype stores a master (with its bf16 copy).  A segment without a
+ * gradient reads g = 0 and runs like any other.  coef as zs_lionset_run; no guarded instances
+ * exist.
+ * ZS_ERR_INVALID, nothing launched: a NULL set or hparams; a set not made by
+ * zs_ademamixset_create; coef on a set with the ZeRO-1 carry; in a struct filled by hand a
+ * positive neg_lr, a beta outside [0, 1], inv_bc1 < 1, bc2_sqrt outside (0, 1], a negative alpha or
+ * eps, or grad_div <= 0. */
+int zs_ademamixset_run(const zs_adamset* as, const zs_ademamix_hparams* hp, const float* coef,
+                       uintptr_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Fused LAMB (You et al. 2020, arXiv:1904.00962), additive in ABI v13.  The update of          */
 /* zero_amd.optim.LAMB on the owned shard, over a set made by zs_adamset_create (fp32 moments,  */
 /* fp32 or split master, no carry, no vmax), in two stream passes with the per-parameter norms  */
